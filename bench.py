@@ -29,7 +29,9 @@ order, issued by plain C calls -- no extra streams, no hardware-queue setting, n
 The batches rotate over ~1 GB of distinct buffers (about four times the 256 MiB Infinity Cache; `--nbuf` overrides), so every
 dispatch streams from and to HBM.  Before the W warm-up steps the same work runs for about 0.5 s so that the clocks have settled.
 
-`value` = units of all ranks / wall time of the K timed steps (barrier + synchronize on both sides, max over ranks).
+`value` = units of all ranks / wall time of the K timed steps (barrier + synchronize on both sides, max over ranks); `ms_per_step` = that
+wall time / K.  `--dump-outputs DIR` writes what the last timed step computed (a fixed, seeded sample of its columns) as .npy files after
+the timed region; the inputs are seeded, so the same arguments give the same files on every build that computes the same thing.
 `roofline`: the timed region IS a sequence of back-to-back dispatches of one kernel on one stream, so its per-dispatch duration is
 measured live with HIP events on that stream around the K steps: achieved = algorithmic bytes per dispatch / that duration, and
 `timed_region_frac` (bytes of the K steps / wall) is the same number up to the host's last synchronize.  rocprofv3's per-dispatch
@@ -519,6 +521,43 @@ def run_extra_config(cfg):
         return {"error": f"{type(e).__name__}: {e}"[:300]}
 
 
+DUMP_BYTES = 60_000_000      # --dump-outputs: at most this many bytes of arrays in all (under 64 MB with the .npy headers)
+DUMP_SEED = 20261015         # ... and the seed of its fixed sample of columns
+
+
+def dump_outputs(out_dir, c, batches, d_out, d_tail, d_img, use_tail):
+    """--dump-outputs: what the timed path handed its caller in the last timed step -- the dB columns (float32, the n/2+1 bins of the
+    reference's m_mem[col][bin]; under --layout tail the columns with their bin n/2 from the tail plane put back) or, for c5, the ARGB
+    image columns (float64, the packed 0xAARRGGBB pixels from row 0 to H-1) -- of a fixed, seeded sample of the (batch, channel row,
+    column) triples the last step wrote, at most DUMP_BYTES in all.  `sample_index` holds the triples.  Same arguments, same
+    inputs, same sample: two builds can be compared file for file."""
+    import numpy as np
+    import torch
+    n, F = c["n"], c["frames"]
+    H = n // 2 + 1
+    rows = c["channels"] if c.get("per_channel") else 1
+    name, col_bytes = ("argb", 8 * H) if c["colour"] else ("db", 4 * H)
+    total = len(batches) * rows * F
+    k = min(total, DUMP_BYTES // (col_bytes + 3 * 8))
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=k, replace=False))
+    b, r, f = np.asarray(batches)[pick // (rows * F)], (pick // F) % rows, pick % F
+    bi, ri, fi = (torch.from_numpy(a.astype(np.int64)).cuda() for a in (b, r, f))
+    if c["colour"]:
+        cols = d_img[bi, :, fi].cpu().numpy().view(np.uint32).astype(np.float64)          # [k][H]: image column f of image b
+    else:
+        o = d_out.reshape(d_out.shape[0], rows, F, d_out.shape[-1])
+        cols = o[bi, ri, fi, :H] if not use_tail else torch.cat([o[bi, ri, fi], d_tail[bi, ri, fi][:, None]], dim=1)
+        cols = cols.cpu().numpy()
+    arrays = {name: cols, "sample_index": np.stack([b, r, f], axis=1).astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for key, a in arrays.items():
+        np.save(os.path.join(out_dir, key + ".npy"), a)
+        files[key] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+    return {"dir": out_dir, "files": files, "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "sample": f"{k} of the {total} (batch, channel row, column) triples of the last timed step, seed {DUMP_SEED}"}
+
+
 def spawn_ranks(n: int, argv) -> int:
     """Start `n` ranks of this script on this node (one per GPU) and return their exit code.  No torch import, no GPU call in this process."""
     import socket
@@ -555,10 +594,17 @@ def main():
     ap.add_argument("--no-power", action="store_true", help="skip the sustained leg that samples socket power and core clock")
     ap.add_argument("--power-seconds", type=float, default=3.0, help="length of the sustained leg (N=1 only; after the timed region)")
     ap.add_argument("--no-single", action="store_true", help="skip the one-batch-per-dispatch leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (rank 0; a fixed, seeded "
+                         "sample of its columns, float32 dB or float64 ARGB, under 64 MB in all)")
     ap.add_argument("--sub-run", action="store_true", help="(internal) this process is a child of another bench.py")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work at all: exercises the N-rank plumbing (barriers, reductions, "
                                                            "JSON) on a machine without GPUs; value is null")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the GPU path (not --dry-run)")
     if args.config is None:
         args.config = "c2" if args.gpus <= 1 else "c4"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -718,6 +764,12 @@ def main():
     wall = t1 - t0
     if ev0 is not None:
         dispatch_us = ev0.elapsed_time(ev1) * 1e3 / (args.steps * dps)     # per-dispatch duration of the timed region itself
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before any side leg writes to the same buffers: strided, every dispatch of a step covers the whole rotation; single, the
+        # dispatches of a step cover batches 0 .. dps-1
+        written = range(nbuf) if strided else range(min(dps, nbuf))
+        dumped = dump_outputs(args.dump_outputs, c, written, d_out, d_tail, d_img, use_tail)
 
     if not args.dry_run and strided and not args.no_single and not c["colour"]:
         # ---- the literal "4096 frames/launch" of the configuration: one dispatch per batch, in order on the same stream, a hipGraph
@@ -913,6 +965,8 @@ def main():
         out["parity"] = parity
     if extra is not None:
         out["extra"] = extra
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if boundary is not None and rank == 0:
         boundary["pcie_inclusive_rate"] = boundary_pcie_rate(jsg, c)
         out["boundary"] = boundary

@@ -51,6 +51,13 @@ def test_bench_does_not_touch_the_hardware_queue_variable():
     assert "setenv(" not in eng.replace("setenv is not thread-safe", "")
 
 
+def test_steps_below_one_and_dump_outputs_without_a_gpu_path_are_refused():
+    for extra in (["--steps", "0"], ["--dump-outputs", "unused_dir"]):
+        r = subprocess.run([sys.executable, "bench.py", "--dry-run"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "error" in r.stderr, extra
+    assert not os.path.exists(os.path.join(ROOT, "unused_dir"))
+
+
 def test_two_ranks_dry_run_over_gloo():
     j = _run(_torchrun(2, ["--dry-run", "--steps", "4", "--warmup", "1"]))
     assert j["n_gpus"] == 2 and j["steps"] == 4 and j["dry_run"] is True and j["ms_per_step"] > 0
@@ -168,6 +175,39 @@ def test_other_configs_emit_a_line(cfg, unit):
 
 
 @pytest.mark.gpu
+def test_dump_outputs_hold_the_last_timed_step_and_repeat_bit_for_bit(tmp_path):
+    """--dump-outputs: two runs with the same arguments write the same files (float32 / float64 .npy, under 64 MB), and the dumped dB
+    columns are those of bench.py's seeded batches (float64 DFT of the float32 windowed frames, the bound of tests/parity_util.py)."""
+    import numpy as np
+    import bench
+    from oracle import jsg_oracle as oracle
+    from parity_util import assert_db_close
+    cmd = [sys.executable, "bench.py", "--config", "c2", "--steps", "3", "--warmup", "1", "--dispatches-per-step", "2", "--nbuf", "8",
+           "--no-cpu-baseline", "--no-calibration", "--no-boundary", "--no-parity", "--no-power", "--no-single", "--no-extra"]
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        j = _run(cmd + ["--dump-outputs", str(d)])
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["dumped_outputs"]["dir"] == str(d)
+        files = sorted(os.listdir(d))
+        assert files == ["db.npy", "sample_index.npy"] and sum(os.path.getsize(d / f) for f in files) <= 64 * 10 ** 6
+        runs.append({f: np.load(d / f) for f in files})
+    for f, a in runs[0].items():
+        assert a.dtype in (np.float32, np.float64) and a.tobytes() == runs[1][f].tobytes(), f
+    db, idx = runs[0]["db.npy"], runs[0]["sample_index.npy"].astype(np.int64)
+    n, hop, F, H = 1024, 512, 4096, 513
+    assert db.shape == (idx.shape[0], H) and idx.shape[1] == 3 and len(np.unique(idx, axis=0)) == len(idx)
+    assert idx[:, 0].max() < 8 and (idx[:, 1] == 0).all() and idx[:, 2].max() < F
+    n_samples = (F * hop + (n - hop) + 3) // 4 * 4
+    base = bench.synth_audio(1, n_samples + 8 * 64, fs=48000.0, seed=1234)       # batch b = base[:, 64 b : 64 b + n_samples]
+    sel = np.linspace(0, len(idx) - 1, 64).astype(np.int64)
+    starts = idx[sel, 0] * 64 + idx[sel, 2] * hop
+    frames = (base[:, starts[:, None] + np.arange(n)[None, :]] * oracle.window(oracle.WIN_HANN, n)[None, None, :]).astype(np.float32)
+    p32 = oracle.mix_channels(oracle.power_spectrum_f64(frames).astype(np.float32), oracle.MIX_ABSMEAN)
+    assert_db_close(db[sel], oracle.to_db(p32), p32.astype(np.float64), "dumped dB columns")
+
+
+@pytest.mark.gpu
 def test_single_mode_one_dispatch_per_batch_still_runs():
     j = _run([sys.executable, "bench.py", "--mode", "single", "--steps", "2", "--warmup", "1", "--dispatches-per-step", "32", "--no-cpu-baseline",
               "--no-boundary", "--no-calibration", "--no-extra"])
@@ -199,7 +239,8 @@ def test_default_config_line_carries_roofline_calibration_boundary_and_the_other
         assert r[f"extra_{cfg}_value"] == j["extra"][cfg]["value"]
     cal = j["calibration"]
     assert 4000.0 < cal["peak_copy_GBps"] < 8000.0 and cal["sizes"]["8.4MB"]["GBps"] < cal["peak_copy_GBps"]
-    assert j["config"]["GPU_MAX_HW_QUEUES"] is None and "jsg_stft_db_launch_strided" in j["config"]["issue"]
+    # bench.py neither sets nor changes the variable: the line reports what the process inherited
+    assert j["config"]["GPU_MAX_HW_QUEUES"] == os.environ.get("GPU_MAX_HW_QUEUES") and "jsg_stft_db_launch_strided" in j["config"]["issue"]
     assert j["parity"]["kernel"] == "Cfg1024" and j["parity"]["fused_image_pixels_differing_from_two_kernel_image"] == 0
     assert 0.0 <= j["parity"]["float32_cpu_fft_frac_bins_rel_power_err_gt_1e-5"] < 0.05      # what a single-precision CPU FFT does on the same frames
     assert j["parity"]["strided_columns_differing_from_single_launches"] == 0

@@ -189,24 +189,30 @@ def test_geometry_fuzz_vs_oracle(jsg, oracle):
 
 
 def test_colormap_tables_against_the_reference_build_itself(jsg):
-    """Not through a fixture: the product's tables against oracle/_ref -- /root/reference/CColorpalette.cpp compiled as it
-    lies (oracle/Makefile target `ref`; the built .so travels to the GPU box) -- called live.  This is the check of the two
-    perceptual schemes at 256 colours that does not lean on tests/golden/colormap_ref.json, from which their embedded table
-    (csrc/jsg_colormap_tables.inc) was generated.  Reference: CColorpalette.cpp:106-339 (Viridis :254-271, Plasma :272-289)."""
+    """The product's tables against the reference's CColorpalette.cpp compiled as it lies (oracle/Makefile target `ref`):
+    its tables are recorded in tests/golden/colormap_ref_tables.json (oracle/gen_golden.py), and where build() has made
+    oracle/_ref the library is also called live.  This is the check of the two perceptual schemes at 256 colours that does
+    not lean on tests/golden/colormap_ref.json, from which their embedded table (csrc/jsg_colormap_tables.inc) was
+    generated.  Reference: CColorpalette.cpp:106-339 (Viridis :254-271, Plasma :272-289)."""
     import ctypes
+    import json
+    sizes = (256, 2, 3, 7, 64, 100, 255, 257, 512, 1000)
+    with open(os.path.join(ROOT, "tests", "golden", "colormap_ref_tables.json")) as fh:
+        recorded = json.load(fh)["lut"]
     so = os.path.join(ROOT, "oracle", "_ref", "libjade_colorpalette_ref.so")
-    if os.path.isdir("/root/reference"):
-        import subprocess
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"])
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref is not built (no /root/reference in this environment)")
-    ref = ctypes.CDLL(so)
-    ref.ref_cp_lut.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    ref = None
+    if os.path.exists(so):
+        ref = ctypes.CDLL(so)
+        ref.ref_cp_lut.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     for scheme in range(7):
-        for n in (256, 2, 3, 7, 64, 100, 255, 257, 512, 1000):
-            want = np.zeros(n, dtype=np.int32)
-            ref.ref_cp_lut(n, scheme, want.ctypes.data)
+        for n in sizes:
+            want = np.array(recorded[f"{scheme}:{n}"], dtype=np.int32)
+            assert want.shape == (n,), (scheme, n)
             assert (jsg.colormap_lut(n, scheme) == want).all(), (scheme, n)
+            if ref is not None:
+                live = np.zeros(n, dtype=np.int32)
+                ref.ref_cp_lut(n, scheme, live.ctypes.data)
+                assert (live == want).all(), (scheme, n)
 
 
 def test_colormap_tables_match_the_survey_hashes(jsg, oracle, golden):
