@@ -221,10 +221,11 @@ JSG_API int jsg_stft_db_launch_batches(const jsg_plan* plan, const jsg_stft_args
  * batches: lane tables loaded once per workgroup instead of once per step of four to sixteen frames, no ramp-up and drain per batch, the next columns in
  * flight while the current ones are transformed -- the rate of back-to-back launches without extra streams, hardware queues or issuing
  * threads (bench.py's default C2 step).  args->blocks_per_cu: workgroups per CU of the grid (0 = the library's choice).
- *   2048 / 4096 points: the plan rule of plan_select looks at the frames of the WHOLE launch; columns are those of single launches
- *   with plan_select pinned to that plan.  All other sizes: bit-identical to single launches.
- * Max / Min mixes have no strided kernel: they are launched batch by batch in stream order.  More than 2^20 workgroup steps go out as
- * several launches.  jsg_stft_db_strided_kernel_name tells the kernel (as jsg_stft_kernel_name, for the total size). */
+ *   1024 / 2048 / 4096 points: the plan rule of plan_select looks at the frames of the WHOLE call and decides once for all of it;
+ *   columns are those of single launches with plan_select pinned to that plan.  512 / 8192 points: bit-identical to single launches.
+ * Max / Min mixes have no strided kernel: they are launched batch by batch in stream order, and the plan rule looks at the frames of
+ * ONE batch (each launch keeps the faster kernel for its real size).  More than 2^20 workgroup steps go out as several launches, all
+ * pinned to the plan of the whole call.  jsg_stft_db_strided_kernel_name tells the kernel every launch of the call takes. */
 JSG_API int jsg_stft_db_launch_strided(const jsg_plan* plan, const jsg_stft_args* args, int n_batches, int64_t in_batch_stride,
                                int64_t out_batch_stride, void* stream);
 JSG_API int jsg_stft_db_strided_kernel_name(const jsg_plan* plan, const jsg_stft_args* args, int n_batches, int64_t in_batch_stride, char* out,
@@ -275,7 +276,8 @@ JSG_API int jsg_colormap_launch(const jsg_colormap_args* args, void* stream);
 
 /* Fused display path: STFT -> palette index -> ARGB without the dB column ever going to memory (reference
  * Spectrogram.cpp:632-648: the colour loop consumes the column the engine has just produced).  The image is bit-identical to
- * jsg_stft_db_launch (same plan_select) followed by jsg_colormap_launch.
+ * jsg_stft_db_launch (same plan_select) followed by jsg_colormap_launch -- except at 1024 points, where the display launches always
+ * take the three-stage arithmetic ("Cfg1024"), whatever plan_select says: the image is that of jsg_stft_db_launch with plan_select = 1.
  *   ONE kernel where a workgroup of the plan holds eight whole columns -- 1024 points, and 4096 points when the launch takes the
  *   one-wavefront-per-frame kernel (automatic rule of jsg_stft_args.plan_select, or plan_select = 2; e.g. a 10-second stereo image
  *   at 96 kHz = 1875 columns): the workgroup parks the palette indices (CColorPalette::getRGBColor's index, CColorpalette.h:34-45)
@@ -300,8 +302,9 @@ JSG_API int jsg_stft_image_needs_scratch(const jsg_plan* plan, const jsg_stft_im
  * share ONE kernel launch whose workgroups walk through the columns of all of them: tables loaded once, the next columns in flight
  * while the current ones are transformed, no idle workgroup slots at the end of every image (C5, 1875 columns = 235 groups of
  * eight on 256 CUs: see DESIGN.md 4.4 for the measured gain).  Pixels: those of n_images jsg_stft_image_launch calls with plan_select pinned to the
- * plan the whole launch takes (the plan rule looks at the total column count).  Otherwise: n_images launches in stream order,
- * which need `index_scratch` like a single one (jsg_stft_image_strided_needs_scratch tells).  colour.index_out must be NULL. */
+ * plan the whole launch takes (the plan rule looks at the total column count; 1024 points: the three-stage arithmetic, as a single
+ * launch).  Otherwise: n_images launches in stream order, which need `index_scratch` like a single one
+ * (jsg_stft_image_strided_needs_scratch tells).  colour.index_out must be NULL. */
 JSG_API int jsg_stft_image_launch_strided(const jsg_plan* plan, const jsg_stft_image_args* args, int n_images, int64_t in_image_stride,
                                   int64_t argb_image_stride, void* stream);
 JSG_API int jsg_stft_image_strided_needs_scratch(const jsg_plan* plan, const jsg_stft_image_args* args, int n_images);

@@ -459,7 +459,8 @@ static int stft_launch_impl(const jsg_plan* plan, const jsg_stft_args* g, const 
     // agree within the float32 bound, not bit for bit (jsg.h: plan_select pins one plan).
     // (the single-kernel display path exists for the one-wavefront-per-frame plans: at 4096 points that is "B")
     const long long rows = bs ? (long long)bs->n * (ka.per_channel ? g->channels : 1) : 1;
-    // (a strided launch is judged by the frames of ALL its rows: the "B" kernels then fill their rounds)
+    // (a strided launch is judged by the frames of ALL its rows: the "B" kernels then fill their rounds.  jsg_stft_db_launch_strided pins
+    // plan_select to the plan of the whole call, strided_plan_select, before it gets here)
     const bool plan_p = wants_plan_pair(plan->n, g, n_cu, io != nullptr, bs ? rows * g->n_frames : -1) && mixop == 0 && !ka.per_channel &&
                         ((ka.c_end - ka.c_begin) & 1) == 0;
     const bool plan_b = !plan_p && !(plan->n == 1024 && io) &&   // (1024 points: the display launches keep the three-stage plans)
@@ -581,10 +582,12 @@ static int colormap_launch_impl(const jsg_colormap_args* g, const unsigned char*
 // the STFT kernel's epilogue maps every bin to its palette index (CColorPalette::getRGBColor) and writes 1 byte per bin
 // into `index_scratch` -- the dB column never goes to memory -- and the colour kernel turns those columns into ARGB
 // image rows through its LDS transpose tiles.  Per column of C5: 4096 B in + 2049 B + 2049 B + 8196 B instead of
-// 4096 + 8196 + 8196 + 8196 B.  The image is bit-identical to jsg_stft_db_launch + jsg_colormap_launch.
+// 4096 + 8196 + 8196 + 8196 B.  The image is bit-identical to jsg_stft_db_launch + jsg_colormap_launch: with the same plan_select at
+// 2048 / 4096 points; at 1024 points the display launches always take the three-stage arithmetic (stft_launch_impl: no Cfg1024B for
+// them), whatever plan_select says, so the image is that of jsg_stft_db_launch with plan_select = 1.
 // Does jsg_stft_image_launch run as ONE kernel for these arguments?  Where the plan's workgroups hold eight whole columns: 1024
 // points, and 4096 points when the launcher's choice for the launch is the one-wavefront-per-frame kernel ("B": automatic rule or
-// plan_select = 2) -- so the image is always that of jsg_stft_db_launch (same plan_select) + jsg_colormap_launch, bit for bit.
+// plan_select = 2).
 static bool image_takes_one_kernel(const jsg_plan* plan, const jsg_stft_image_args* g, int n_images = 1) {
     static const int two_kernels = dev_knob_set("JSG_IMAGE_TWO_KERNELS") ? 1 : 0;
     const jsg_colormap_args& c = g->colour;
@@ -709,6 +712,21 @@ static int strided_checks(const jsg_plan* plan, const jsg_stft_args* g, int n_ba
     return JSG_OK;
 }
 
+// The plan of a strided call (n_batches >= 1), decided ONCE for the whole call: jsg_stft_db_launch_strided pins every launch it issues to it
+// (the several launches of a job longer than 2^20 workgroup steps and a trailing single batch included) and jsg_stft_db_strided_kernel_name
+// reports it, so the two cannot disagree.  Returns the plan_select that pins it: 1 the small-workgroup plan, 2 "B", 3 the pair plan; 0 at
+// 512 / 8192 points (one plan).  Judged by the frames of ALL rows of the call -- except Max / Min, which go out as one launch per batch
+// (no strided instantiation): there the frames of one batch decide, so every launch keeps the faster kernel for its real size.
+static int strided_plan_select(const jsg_plan* plan, const jsg_stft_args* g, int n_batches, int n_cu) {
+    if (plan->n != 1024 && plan->n != 2048 && plan->n != 4096) return 0;
+    const bool one_by_one = g->mix_mode == JSG_MIX_MAX || g->mix_mode == JSG_MIX_MIN;
+    const long long rows = (one_by_one ? 1ll : (long long)n_batches) * (g->mix_mode == JSG_MIX_PER_CHANNEL ? g->channels : 1);
+    int nc = g->channels;
+    if (g->mix_mode == JSG_MIX_LEFT || g->mix_mode == JSG_MIX_RIGHT || g->mix_mode == JSG_MIX_PER_CHANNEL) nc = 1;
+    if (wants_plan_pair(plan->n, g, n_cu, false, rows * g->n_frames)) return 3;
+    return wants_plan_b(plan->n, g, nc, n_cu, rows * g->n_frames) ? 2 : 1;
+}
+
 int jsg_stft_db_launch_strided(const jsg_plan* plan, const jsg_stft_args* g, int n_batches, int64_t in_batch_stride, int64_t out_batch_stride,
                                void* stream) {
     int rc = strided_checks(plan, g, n_batches, in_batch_stride, out_batch_stride, "jsg_stft_db_launch_strided");
@@ -719,6 +737,7 @@ int jsg_stft_db_launch_strided(const jsg_plan* plan, const jsg_stft_args* g, int
     if (hipGetDevice(&dev) != hipSuccess) return jsg_fail(JSG_ERR_NO_DEVICE, "jsg_stft_db_launch_strided: no device");
     const bool one_by_one = g->mix_mode == JSG_MIX_MAX || g->mix_mode == JSG_MIX_MIN;   // (no strided instantiation: rare modes)
     if (g->n_frames < 0 || g->channels <= 0) return jsg_fail(JSG_ERR_INVALID, "jsg_stft_db_launch_strided: bad geometry");
+    const int pin = strided_plan_select(plan, g, n_batches, cu_count_of_device(dev));
     const long long rows_per_batch = g->mix_mode == JSG_MIX_PER_CHANNEL ? g->channels : 1;
     // at most 2^20 workgroup steps per launch (the kernel's group -> row arithmetic): longer jobs go out in several launches
     // (counted with the smallest workgroup step of the plan's kernels: 16 / 8 / 4 / 2 / 1 columns at 512 ... 8192 points)
@@ -728,6 +747,7 @@ int jsg_stft_db_launch_strided(const jsg_plan* plan, const jsg_stft_args* g, int
     for (long long b0 = 0; b0 < n_batches; b0 += per_launch) {
         const int nb = int(std::min<long long>(per_launch, n_batches - b0));
         jsg_stft_args one = *g;
+        if (pin) one.plan_select = pin;
         one.in = g->in + b0 * in_batch_stride;
         one.out_db = g->out_db ? g->out_db + b0 * out_batch_stride : nullptr;
         if (g->out_tail) one.out_tail = g->out_tail + b0 * rows_per_batch * g->ring_width;   // (a dense plane: rows x ring_width)
@@ -741,20 +761,15 @@ int jsg_stft_db_launch_strided(const jsg_plan* plan, const jsg_stft_args* g, int
     return JSG_OK;
 }
 
-// The kernel a strided launch takes, as text (as jsg_stft_kernel_name, judged by the frames of the whole launch).
+// The kernel every launch of a strided call takes, as text (strided_plan_select: the frames of the whole call; Max / Min: of one batch).
 int jsg_stft_db_strided_kernel_name(const jsg_plan* plan, const jsg_stft_args* g, int n_batches, int64_t in_batch_stride, char* out, int out_len) {
     if (!plan || !g || !out || out_len < 24 || n_batches < 1) return jsg_fail(JSG_ERR_INVALID, "jsg_stft_db_strided_kernel_name: bad argument");
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) return jsg_fail(JSG_ERR_NO_DEVICE, "jsg_stft_db_strided_kernel_name: no device");
     if (n_batches == 1) return jsg_stft_kernel_name(plan, g, out, out_len);
-    const int n_cu = cu_count_of_device(dev);
     (void)in_batch_stride;
-    int nc = g->channels;
-    if (g->mix_mode == JSG_MIX_LEFT || g->mix_mode == JSG_MIX_RIGHT || g->mix_mode == JSG_MIX_PER_CHANNEL) nc = 1;
-    const long long rows = (long long)n_batches * (g->mix_mode == JSG_MIX_PER_CHANNEL ? g->channels : 1);
-    const bool pp = wants_plan_pair(plan->n, g, n_cu, false, rows * g->n_frames);
-    const bool b = !pp && wants_plan_b(plan->n, g, nc, n_cu, rows * g->n_frames);
-    std::snprintf(out, size_t(out_len), "Cfg%d%s", plan->n, pp ? "P" : b ? "B" : "");
+    const int pin = strided_plan_select(plan, g, n_batches, cu_count_of_device(dev));
+    std::snprintf(out, size_t(out_len), "Cfg%d%s", plan->n, pin == 3 ? "P" : pin == 2 ? "B" : "");
     return JSG_OK;
 }
 

@@ -339,7 +339,8 @@ def stft_db_strided(plan: Plan, d_in, hop: int, n_frames: int, d_out, *, stream:
 
 
 def stft_db_strided_kernel_name(plan: Plan, d_in, hop: int, n_frames: int, d_out, **kw) -> str:
-    """The kernel a strided launch takes: as stft_kernel_name, judged by the frames of the whole launch."""
+    """The kernel every launch of a strided call takes: as stft_kernel_name, judged by the frames of the whole call (Max / Min, which go
+    out batch by batch: of one batch)."""
     a, k, s_in, _ = _strided_args(plan, d_in, hop, n_frames, d_out, **kw)
     buf = C.create_string_buffer(32)
     check(lib().jsg_stft_db_strided_kernel_name(plan._p, C.byref(a), k, s_in, buf, 32))
@@ -472,7 +473,8 @@ def stft_image(plan: Plan, d_in, hop: int, n_frames: int, d_lut, lo: float, hi: 
     """Fused display path (jsg_stft_image_launch): STFT -> palette index -> ARGB rows of d_argb [n/2+1][Wimg]; no dB column is
     written.  One kernel where the plan's workgroups hold eight whole columns (1024 points; 4096 points when the launch takes
     the "B" kernel), else two kernels through d_index_scratch (uint8 [ring_width][pitch >= n/2+1]; stft_image_needs_scratch()).
-    The image equals stft_db() + colormap() bit for bit."""
+    The image equals stft_db() + colormap() bit for bit, with the same plan_select -- except at 1024 points, where the display launches
+    always take the three-stage arithmetic: the image is that of stft_db(plan_select=1) + colormap() whatever plan_select says."""
     import torch
     a = _stft_image_args(plan, d_in, hop, n_frames, d_lut, lo, hi, d_argb, d_index_scratch, **kw)
     if stream is None:
