@@ -632,6 +632,8 @@ int jsg_set_channels(jsg_engine* e, int channels) {
     GeomEpoch epoch(e);
     JSG_LOCK_CONFIG(e);
     if (channels <= 0) return e->fail(JSG_ERR_INVALID, "channel count must be positive");
+    // (as jsg_set_mix_mode: a Right mix reads channel 1; accepting one channel here would fail every later block in the launcher)
+    if (channels < 2 && e->mix == JSG_MIX_RIGHT) return e->fail(JSG_ERR_INVALID, "JSG_MIX_RIGHT needs two channels");
     e->channels = channels;
     return buildmem(e);
 }

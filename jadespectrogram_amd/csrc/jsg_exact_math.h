@@ -9,8 +9,11 @@
 // routine instead: exponent extraction, a degree-9 polynomial for log2 of the mantissa (|relative error| < 4.2e-9 before rounding) and a
 // split constant for the final scaling -- 16 full-rate vector instructions per value instead of 3.  The dB
 // values, and with them the palette indices (CColorPalette::getRGBColor, CColorpalette.h:32-47), are then bit-identical to the mirror's.
-// Against the reference's double log10 rounded to float: within 2 ulp of the dB value over [1e-11, 1e12] (tests/test_oracle_golden.py).
-// Finite, non-negative inputs only (what |X|^2 produces); no NaN / infinity handling.
+// Against the reference's double log10 rounded to float: within 2 ulp of the dB value for every finite non-negative float input
+// (tests/test_oracle_golden.py on the CPU; tests/test_gpu_db_epilogue.py on all 2^31 - 2^23 such bit patterns on the GPU).
+// Non-finite inputs come out as the reference's 10*log10 gives them: y = p + 1e-11f is returned itself when it is infinite or NaN
+// (a NaN sample upstream must reach the ring as NaN, not as a finite value read off the exponent bits).  Negative inputs are
+// outside the contract (|X|^2 never produces them).
 #pragma once
 
 #if defined(__HIPCC__)
@@ -50,6 +53,7 @@ JSG_EXACT_HD float jsg_exact_fma(float a, float b, float c) {
 JSG_EXACT_HD float jsg_exact_db(float p) {
     const float y = p + 1e-11f;                       // >= 1e-11: a normal float
     const unsigned b = jsg_exact_bits(y);
+    if ((b & 0x7fffffffu) >= 0x7f800000u) return y;   // inf -> inf, NaN -> NaN (10*log10 of either); finite inputs keep their bits
     int e = (int)(b >> 23) - 127;
     unsigned mb = (b & 0x007fffffu) | 0x3f800000u;    // mantissa as a float in [1, 2)
     if (mb > 0x3fb504f3u) {                           // > sqrt(2): halve it, so that m lies in (sqrt(1/2), sqrt(2)]

@@ -510,11 +510,13 @@ def stft_image_strided_needs_scratch(plan: Plan, d_in, hop: int, n_frames: int, 
     return bool(check(lib().jsg_stft_image_strided_needs_scratch(plan._p, C.byref(a), int(d_in.shape[0]))))
 
 
-def db_from_power(d_power, d_out, divisor: float = 1.0, stream: int | None = None):
-    """out = 10*log10(power/divisor + 1e-11f) elementwise on the GPU (finishes a cross-GPU AbsMean)."""
+def db_from_power(d_power, d_out, divisor: float = 1.0, stream: int | None = None, *, exact_log: bool = False):
+    """out = 10*log10(power/divisor + 1e-11f) elementwise on the GPU (finishes a cross-GPU AbsMean).  exact_log: the shared float32
+    logarithm of jsg_stft_args.exact_log (bit-reproducible on a CPU) instead of the hardware unit (jsg_db_from_power_launch_ex)."""
     import torch
     assert d_power.is_cuda and d_power.dtype == torch.float32 and d_power.is_contiguous()
     assert d_out.is_cuda and d_out.dtype == torch.float32 and d_out.is_contiguous() and d_out.numel() == d_power.numel()
     if stream is None:
         stream = torch.cuda.current_stream(d_power.device).cuda_stream
-    check(lib().jsg_db_from_power_launch(d_power.data_ptr(), d_out.data_ptr(), d_power.numel(), divisor, C.c_void_p(stream)))
+    check(lib().jsg_db_from_power_launch_ex(d_power.data_ptr(), d_out.data_ptr(), d_power.numel(), divisor, int(bool(exact_log)),
+                                            C.c_void_p(stream)))

@@ -63,3 +63,24 @@ def mixed_power_f64(oracle, samples, n, hop, feedblocks, win, mode, power_scale=
     """Float64 view of the power the oracle feeds to 10*log10 (mix done like the reference, in float32)."""
     pw = oracle.stft_db_reference(samples, n, hop, feedblocks, win, return_power=True, power_scale=power_scale)
     return oracle.mix_channels(pw.astype(np.float32), mode).astype(np.float64)
+
+
+def assert_ring_matches(got, rec, what=""):
+    """A [rows][H] buffer read from the engine (getMem / peekMem / getMem rows) against the same buffer of the engine model
+    (oracle/engine_model.py records): the NaN columns are the same, and NaN in every bin; unwritten columns hold exactly the
+    -120 dB fill; columns the model computed with the kernel mirror and the exact logarithm are identical bit for bit; every
+    other written column is within assert_db_close of the float64 record."""
+    got = np.asarray(got, dtype=np.float32)
+    exp = rec["mem"]
+    nan_g, nan_m = np.isnan(got), np.isnan(exp)
+    assert (nan_g == nan_m).all(), f"{what}: NaN in rows {sorted(set(np.nonzero(nan_g != nan_m)[0].tolist()))[:12]} differs from the model"
+    nan_rows = nan_m.any(axis=1)
+    assert nan_m[nan_rows].all(), f"{what}: a NaN column of the model is not NaN in every bin"
+    fill = ~rec["written"]
+    assert (got[fill] == np.float32(-120.0)).all() and (exp[fill] == np.float32(-120.0)).all(), f"{what}: unwritten columns must hold -120 dB"
+    exact = rec["exact"] & rec["written"] & ~nan_rows
+    bad = (got[exact].view(np.uint32) != exp[exact].view(np.uint32))
+    assert not bad.any(), f"{what}: {int(bad.sum())} bins of {int(exact.sum())} exact-log columns differ from the mirror"
+    fine = rec["written"] & ~nan_rows
+    if fine.any():
+        assert_db_close(got[fine], rec["ref_db"][fine], rec["p64"][fine], what, peak=rec["peak"][fine][:, None])

@@ -4,7 +4,8 @@ import os
 import numpy as np
 import pytest
 
-from parity_util import assert_db_close, assert_power_close, mixed_power_f64
+from oracle.engine_model import EngineModel, empty_records
+from parity_util import assert_db_close, assert_power_close, assert_ring_matches, mixed_power_f64
 
 pytestmark = pytest.mark.gpu
 
@@ -127,14 +128,15 @@ def test_per_channel_mode_equals_single_channel_engines(jsg, oracle):
 def test_block_by_block_stream_pause_and_getmem(jsg, oracle):
     """processSynchronBlock per block with getMem in between, a pause, and more than one ring wrap."""
     C, n = 2, 1024
-    s = jsg.Spectrogram(C); o = oracle.OracleSpectrogram(C)
+    s = jsg.Spectrogram(C); o = EngineModel(C)   # (the oracle engine plus float64 records; its columns are OracleSpectrogram's bit for bit)
     for e in (s,):
         e.setSamplerate(48000.0); e.setmemoryTime_s(0.25); e.setFFTSize(n); e.setfeed_percent(1)
     o.set_samplerate(48000.0); o.set_memory_time_s(0.25); o.set_fft_size(n); o.set_feed_percent(1)
     W, H = s.getMemorySize(), s.getSpectrumSize()
     assert W == o.memsize_blocks == 23
     x = oracle.synth_audio(C, 40 * n, seed=9)
-    mem_g = np.zeros((W, H), np.float32); mem_o = np.zeros((W, H), np.float32)
+    rec = empty_records(W, H)
+    mem_g = np.full((W, H), -120.0, np.float32); mem_o = rec["mem"]
     assert s.getMem(np.zeros((W + 1, H), np.float32))[0] == -1          # reference: size mismatch -> -1
     for b in range(40):
         if b == 10:
@@ -146,10 +148,11 @@ def test_block_by_block_stream_pause_and_getmem(jsg, oracle):
         o.process_synchron_block(blk)
         if b % 4 == 3 or b == 39:
             nv_g, pos_g = s.getMem(mem_g)
-            nv_o, pos_o = o.get_mem(mem_o)
+            nv_o, pos_o = o.get_mem(mem_o, records=rec)
             assert (nv_g, pos_g) == (nv_o, pos_o), b
             d = np.abs(mem_g.astype(np.float64) - mem_o.astype(np.float64))
-            assert d.max() < 2e-3, (b, d.max())   # coarse here; exact tolerances are checked in test_engine_db_columns
+            assert d.max() < 2e-3, (b, d.max())
+            assert_ring_matches(mem_g, rec, f"block {b}")   # every column within assert_db_close of its float64 record, the fill exact
     # batch == block-by-block, bit for bit
     s2 = jsg.Spectrogram(C)
     s2.setSamplerate(48000.0); s2.setmemoryTime_s(0.25); s2.setFFTSize(n); s2.setfeed_percent(1)
@@ -171,10 +174,10 @@ def test_block_by_block_stream_pause_and_getmem(jsg, oracle):
 def test_seeded_random_engine_scenarios(jsg, oracle, seed):
     """Random walks over the engine's setter / process / pause / getMem surface, mirrored on the oracle engine: the column
     counters and write positions must agree exactly after every getMem (every setter wipes the history like the
-    reference's buildmem), the ring contents within the coarse bound used above (fine tolerances: test_engine_db_columns)."""
+    reference's buildmem), every ring column within assert_db_close of the model's float64 record of it."""
     rng = np.random.default_rng(1000 + seed)
     C = int(rng.integers(1, 5))
-    s = jsg.Spectrogram(C); o = oracle.OracleSpectrogram(C)
+    s = jsg.Spectrogram(C); o = EngineModel(C)
     n = int(rng.choice([512, 1024, 2048]))
     s.setSamplerate(48000.0); o.set_samplerate(48000.0)
     s.setmemoryTime_s(0.2); o.set_memory_time_s(0.2)
@@ -196,7 +199,7 @@ def test_seeded_random_engine_scenarios(jsg, oracle, seed):
         elif ev == "window":
             w = int(rng.integers(0, 6)); s.setWindow(w); o.set_window(w)
         elif ev == "mix":
-            m = int(rng.integers(0, 5 if C > 1 else 4)); s.setMixMode(m); o.mode = m
+            m = int(rng.integers(0, 5 if C > 1 else 4)); s.setMixMode(m); o.set_mix_mode(m)
         elif ev == "fft":
             n = int(rng.choice([512, 1024, 2048, 4096])); s.setFFTSize(n); o.set_fft_size(n)
         elif ev == "memtime":
@@ -204,13 +207,15 @@ def test_seeded_random_engine_scenarios(jsg, oracle, seed):
         if ev == "getmem" or step == 59:
             W, H = s.getMemorySize(), s.getSpectrumSize()
             assert (W, H, s.getFeedSamples()) == (o.memsize_blocks, o.freqsize, o.hop), (seed, step)
-            mg = np.zeros((W, H), np.float32); mo = np.zeros((W, H), np.float32)
-            assert s.getMem(mg) == o.get_mem(mo), (seed, step)
-            # this test is about the state machine: bins within 60 dB of their column's peak to 2e-3 dB, the weak rest
-            # (deep window side lobes, where two float32 FFTs differ visibly) only coarsely
+            rec = empty_records(W, H)
+            mg = np.full((W, H), -120.0, np.float32); mo = rec["mem"]
+            assert s.getMem(mg) == o.get_mem(mo, records=rec), (seed, step)
+            # bins within 60 dB of their column's peak to 2e-3 dB, the weak rest (deep window side lobes, where two float32 FFTs
+            # differ visibly) to 0.5 dB -- and every bin within assert_db_close of the float64 record of its column
             d = np.abs(mg.astype(np.float64) - mo.astype(np.float64))
             strong = mo > (mo.max(axis=1, keepdims=True) - 60.0)
             assert d[strong].max() < 2e-3 and d.max() < 0.5, (seed, step, float(d[strong].max()), float(d.max()))
+            assert_ring_matches(mg, rec, f"seed {seed} step {step}")
     s.close()
 
 
