@@ -42,7 +42,8 @@ extern "C" {
 
 #define JSG_ABI_VERSION 6   /* 3: + kernel-name query, launch pool, image scratch query, sharded set; 4: + strided image batches (round 3);
                                5: + strided dB batches, exact-log mode, producer ring statistics (round 4);
-                               6: + lossless producer call, all-or-nothing sharded push, exact-log display path, tail plane, pair plan (round 5) */
+                               6: + lossless producer call, all-or-nothing sharded push, exact-log display path, tail plane, pair plan (round 5);
+                                  additions to 6: filterbank spectrograms (jsg_filterbank_*, jsg_stft_fb_*; section 2b) */
 
 typedef enum jsg_status {
     JSG_OK = 0,
@@ -308,6 +309,82 @@ JSG_API int jsg_stft_image_needs_scratch(const jsg_plan* plan, const jsg_stft_im
 JSG_API int jsg_stft_image_launch_strided(const jsg_plan* plan, const jsg_stft_image_args* args, int n_images, int64_t in_image_stride,
                                   int64_t argb_image_stride, void* stream);
 JSG_API int jsg_stft_image_strided_needs_scratch(const jsg_plan* plan, const jsg_stft_image_args* args, int n_images);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2b. Filterbank spectrograms: mel and log-frequency rows (no reference counterpart; the reference stores its
+ *     MinFreq / MaxFreq as log(Hz), Spectrogram.h:24-39, and stretches a linear bin range, Spectrogram.cpp:441-463).
+ *
+ *     A bank is sparse and banded: band b has the weights w[b][k] of the bins k = first_bin[b] .. first_bin[b]+n_bins[b]-1,
+ *     stored at weights[offset[b] ..] (CSR).  Band power and value of one column (power P_k = the mixed linear power of
+ *     jsg_stft_args.linear_out = 1, bit for bit):
+ *         acc = +0.0f;  for k ascending over the band:  acc = acc + w[b][k] * P_k
+ *     in float32, every product and every sum rounded separately (no fused multiply-add, no reordering), and
+ *         value = acc (linear_out = 1),  10*log10(acc + 1e-11f) on the hardware unit (exact_log = 0, the STFT epilogue's
+ *         logarithm), or jsg_exact_db of acc (exact_log = 1; jadespectrogram_amd/csrc/jsg_exact_math.h: bit-reproducible on a CPU).
+ *     An empty band (n_bins = 0) has power 0 and reads 10*log10(1e-11f), about -110 dB.
+ * ------------------------------------------------------------------------------------------------ */
+typedef enum jsg_fb_scale { JSG_FB_MEL_SLANEY = 0, JSG_FB_MEL_HTK = 1, JSG_FB_LOG = 2, JSG_FB_LINEAR = 3 } jsg_fb_scale;
+typedef enum jsg_fb_norm { JSG_FB_NORM_NONE = 0, JSG_FB_NORM_SLANEY = 1, JSG_FB_NORM_UNIT_SUM = 2 } jsg_fb_norm;
+#define JSG_FB_MAX_BANDS 8192
+typedef struct jsg_fb_spec {
+    int32_t n;          /* FFT size: a power of two in 512..8192 */
+    float fs;           /* sample rate, Hz (> 0) */
+    int32_t n_bands;    /* 1..JSG_FB_MAX_BANDS (LOG / LINEAR: >= 2) */
+    float fmin, fmax;   /* Hz: 0 <= fmin < fmax <= fs/2 (LOG: fmin > 0) */
+    int32_t scale;      /* jsg_fb_scale */
+    int32_t norm;       /* jsg_fb_norm */
+} jsg_fb_spec;
+/* The bank of a spec, on the host (no GPU).  All arithmetic in double, every weight rounded to float32 once.  Positions are fractional
+ * bins, x = f * n / fs (bin k sits at x = k).  A triangle (lo, c, hi) gives bin k the weight max(0, min((k-lo)/(c-lo), (hi-k)/(hi-c)));
+ * zero weights at either end of a band are trimmed (a band may be empty: n_bins 0, first_bin 0).
+ *   MEL_SLANEY / MEL_HTK (librosa.filters.mel, htk = False / True): B+2 points equally spaced in mel between mel(fmin) and mel(fmax);
+ *       band b = the triangle (p_b, p_b+1, p_b+2).  Slaney: mel = f / (200/3) below 1 kHz, 15 + ln(f/1000) / (ln(6.4)/27) above;
+ *       HTK: mel = 2595 log10(1 + f/700).  centre_hz[b] = p_b+1.
+ *   LOG (display rows): centres c_b = fmin r^b, r = (fmax/fmin)^(1/(B-1)), c_-1 and c_B extend the progression;
+ *       lo_b = min(x(c_b-1), x(c_b) - 1), hi_b = max(x(c_b+1), x(c_b) + 1): a row narrower than a bin is the linear interpolation
+ *       between its two neighbouring bins.  centre_hz[b] = c_b.
+ *   LINEAR: as LOG with c_b = fmin + b (fmax - fmin)/(B-1) (the reference's min / max-frequency zoom, any pixel height).
+ *   NORM_SLANEY: band b times 2 / (hi - lo) in Hz.  NORM_UNIT_SUM: band b divided by its weight sum (a flat spectrum keeps its
+ *       level; the natural choice for LOG / LINEAR).
+ * Outputs: first_bin, n_bins, offset, centre_hz of n_bands entries each, weights of *nnz floats (weights_cap >= *nnz, else
+ * JSG_ERR_SIZE_MISMATCH with *nnz set).  weights == NULL: only *nnz is computed (the other arrays may then be NULL as well).
+ * JSG_ERR_INVALID for a spec outside the ranges above. */
+JSG_API int jsg_filterbank_build(const jsg_fb_spec* s, int32_t* first_bin, int32_t* n_bins, int32_t* offset, float* centre_hz,
+                                 float* weights, int64_t weights_cap, int64_t* nnz);
+
+/* A bank resident on the device that is current at creation (uploaded once, like jsg_plan_create). */
+typedef struct jsg_filterbank jsg_filterbank;
+JSG_API int jsg_filterbank_create(jsg_filterbank** out, const jsg_fb_spec* s);
+/* A caller's dense bank w[n_bands][n/2+1] (host floats); each row keeps the span from its first to its last nonzero weight
+ * (interior zeros are kept).  n: a power of two in 512..8192, 1 <= n_bands <= JSG_FB_MAX_BANDS, finite weights. */
+JSG_API int jsg_filterbank_create_matrix(jsg_filterbank** out, int n, int n_bands, const float* w);
+JSG_API int jsg_filterbank_destroy(jsg_filterbank* fb);
+JSG_API int jsg_filterbank_bands(const jsg_filterbank* fb);
+JSG_API int jsg_filterbank_fft_size(const jsg_filterbank* fb);
+/* The weights as a dense host matrix [n_bands][n/2+1] (zeros outside every band's span). */
+JSG_API int jsg_filterbank_weights(const jsg_filterbank* fb, float* dense);
+
+/* STFT + filterbank: the columns of jsg_stft_db_launch(_strided) with the bank applied.  `args` keeps its meaning, except:
+ *   out_db is a ring of BAND columns: out_db[col*out_pitch + b], b < n_bands, out_pitch >= n_bands (per-channel mode: + c*out_channel_pitch);
+ *   linear_out = 1 writes band power instead of dB; exact_log selects the logarithm (see above); out_tail must be NULL.
+ * Every mix, per-channel included.  The launcher runs the STFT kernel (linear power) into the caller's `scratch` (device floats,
+ * 16-byte aligned; the layout is private to the library) in chunks of as many columns as scratch_floats holds, and after each chunk the
+ * band kernel on it -- all on `stream`, enqueue only (no allocation, no synchronisation; hipGraph capture works).  The STFT plan is
+ * resolved ONCE for the whole call, by the rule of jsg_stft_db_launch_strided (the frames of all rows of the call decide), and every
+ * chunk is pinned to it: the result does not depend on scratch_floats, and jsg_stft_fb_kernel_name reports that plan.  Refused
+ * (JSG_ERR_INVALID): scratch smaller than one workgroup step of the plan (rows x step columns), a bank of another FFT size, a bank or plan
+ * of another device, null pointers, n_frames > ring_width -- and every argument jsg_stft_db_launch(_strided) refuses.  All refusals are
+ * decided for the whole call before its first chunk is enqueued: a refused call enqueues nothing.  A single call is the strided call with
+ * n_batches = 1. */
+JSG_API int jsg_stft_fb_launch(const jsg_plan* plan, const jsg_filterbank* fb, const jsg_stft_args* args, float* scratch, int64_t scratch_floats,
+                               void* stream);
+JSG_API int jsg_stft_fb_launch_strided(const jsg_plan* plan, const jsg_filterbank* fb, const jsg_stft_args* args, int n_batches, int64_t in_batch_stride,
+                                       int64_t out_batch_stride, float* scratch, int64_t scratch_floats, void* stream);
+/* A recommended scratch size (floats) for such a call: the whole call where it fits 64 MiB (one STFT launch and one band launch),
+ * otherwise 64 MiB worth of whole workgroup steps (chunks that stay inside the GPU's 256 MiB Infinity Cache).  < 0: error. */
+JSG_API int64_t jsg_stft_fb_scratch_floats(const jsg_plan* plan, const jsg_filterbank* fb, const jsg_stft_args* args, int n_batches);
+/* The STFT kernel every chunk of such a call takes ("Cfg1024", "Cfg2048B", ...; out_len >= 24). */
+JSG_API int jsg_stft_fb_kernel_name(const jsg_plan* plan, const jsg_filterbank* fb, const jsg_stft_args* args, int n_batches, char* out, int out_len);
 
 /* ------------------------------------------------------------------------------------------------
  * 3. Engine: the state of class Spectrogram (Spectrogram.h:81-169) living on the GPU.

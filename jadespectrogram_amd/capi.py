@@ -25,6 +25,9 @@ MIX_SUM = 101
 WIN_RECT, WIN_HANN, WIN_HAMMING, WIN_BLACKMANHARRIS, WIN_FLATTOP, WIN_HANNPOISSON = range(6)
 FEED_100, FEED_50, FEED_25, FEED_10 = range(4)
 CM_MONO, CM_BW, CM_HOT, CM_RAINBOW, CM_VIRIDIS, CM_PLASMA, CM_JADE = range(7)
+FB_MEL_SLANEY, FB_MEL_HTK, FB_LOG, FB_LINEAR = range(4)
+FB_NORM_NONE, FB_NORM_SLANEY, FB_NORM_UNIT_SUM = range(3)
+FB_MAX_BANDS = 8192
 
 
 class JsgError(RuntimeError):
@@ -40,6 +43,11 @@ class StftArgs(C.Structure):
                 ("out_channel_pitch", C.c_int64), ("ring_width", C.c_int32), ("ring_pos", C.c_int32),
                 ("linear_out", C.c_int32), ("blocks_per_cu", C.c_int32), ("in_samples", C.c_int64),
                 ("plan_select", C.c_int32), ("exact_log", C.c_int32), ("reserved0", C.c_int32), ("out_tail", C.c_void_p)]
+
+
+class FbSpec(C.Structure):
+    _fields_ = [("n", C.c_int32), ("fs", C.c_float), ("n_bands", C.c_int32), ("fmin", C.c_float), ("fmax", C.c_float),
+                ("scale", C.c_int32), ("norm", C.c_int32)]
 
 
 class ColormapArgs(C.Structure):
@@ -84,6 +92,17 @@ SIGNATURES = {
     "jsg_stft_image_strided_needs_scratch": (C.c_int, [_P, C.POINTER(StftImageArgs), C.c_int]),
     "jsg_db_from_power_launch": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P]),
     "jsg_db_from_power_launch_ex": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_int, _P]),
+    "jsg_filterbank_build": (C.c_int, [C.POINTER(FbSpec), _P, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "jsg_filterbank_create": (C.c_int, [C.POINTER(_P), C.POINTER(FbSpec)]),
+    "jsg_filterbank_create_matrix": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, _P]),
+    "jsg_filterbank_destroy": (C.c_int, [_P]),
+    "jsg_filterbank_bands": (C.c_int, [_P]),
+    "jsg_filterbank_fft_size": (C.c_int, [_P]),
+    "jsg_filterbank_weights": (C.c_int, [_P, _P]),
+    "jsg_stft_fb_launch": (C.c_int, [_P, _P, C.POINTER(StftArgs), _P, C.c_int64, _P]),
+    "jsg_stft_fb_launch_strided": (C.c_int, [_P, _P, C.POINTER(StftArgs), C.c_int, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
+    "jsg_stft_fb_scratch_floats": (C.c_int64, [_P, _P, C.POINTER(StftArgs), C.c_int]),
+    "jsg_stft_fb_kernel_name": (C.c_int, [_P, _P, C.POINTER(StftArgs), C.c_int, C.c_char_p, C.c_int]),
     "jsg_create": (C.c_int, [C.POINTER(_P), C.c_int]),
     "jsg_create_on_device": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int]),
     "jsg_get_device": (C.c_int, [_P]),

@@ -34,7 +34,7 @@ static bool b_plan_fills_its_rounds(long long n_frames, int frames_per_workgroup
 }
 // compute units of the current device (256 on an MI355X in SPX mode, fewer when it is partitioned: CPX / DPX): read once per
 // device from the runtime.  The "one workgroup per CU" grids and the round rule above are sized with it.
-static int cu_count_of_device(int dev) {
+int cu_count_of_device(int dev) {
     static std::atomic<int> cached[64];
     if (dev >= 0 && dev < 64) {
         const int c = cached[dev].load(std::memory_order_acquire);
@@ -289,6 +289,8 @@ int jsg_plan_destroy(jsg_plan* plan) {
 int jsg_plan_fft_size(const jsg_plan* plan) { return plan ? plan->n : JSG_ERR_INVALID; }
 
 }   // extern "C"
+
+int jsg::plan_device(const jsg_plan* plan) { return plan->device; }
 
 namespace {
 struct IndexOut {   // fused display path: where and how the palette indices of the columns are written ...
@@ -717,7 +719,7 @@ static int strided_checks(const jsg_plan* plan, const jsg_stft_args* g, int n_ba
 // reports it, so the two cannot disagree.  Returns the plan_select that pins it: 1 the small-workgroup plan, 2 "B", 3 the pair plan; 0 at
 // 512 / 8192 points (one plan).  Judged by the frames of ALL rows of the call -- except Max / Min, which go out as one launch per batch
 // (no strided instantiation): there the frames of one batch decide, so every launch keeps the faster kernel for its real size.
-static int strided_plan_select(const jsg_plan* plan, const jsg_stft_args* g, int n_batches, int n_cu) {
+int strided_plan_select(const jsg_plan* plan, const jsg_stft_args* g, int n_batches, int n_cu) {
     if (plan->n != 1024 && plan->n != 2048 && plan->n != 4096) return 0;
     const bool one_by_one = g->mix_mode == JSG_MIX_MAX || g->mix_mode == JSG_MIX_MIN;
     const long long rows = (one_by_one ? 1ll : (long long)n_batches) * (g->mix_mode == JSG_MIX_PER_CHANNEL ? g->channels : 1);

@@ -357,13 +357,14 @@ def stft_kernel_name(plan: Plan, d_in, hop: int, n_frames: int, d_out, **kw) -> 
 
 def _stft_args(plan: Plan, d_in, hop: int, n_frames: int, d_out, *, feedblocks: int | None = None, mix_mode: int = 0,
                first_frame: int = 0, ring_pos: int = 0, linear_out: bool = False, blocks_per_cu: int = 0, plan_select: int = 0,
-               exact_log: bool = False, d_tail=None):
+               exact_log: bool = False, d_tail=None, col_height: int | None = None):
     """d_tail (jsg_stft_args.out_tail): float32 CUDA tensor of rows x W floats (rows = 1, or channels in per-channel mode, times the batches
-    of a strided launch), contiguous -- bin n/2 of every column goes there and a column of d_out is then n/2 floats."""
+    of a strided launch), contiguous -- bin n/2 of every column goes there and a column of d_out is then n/2 floats.
+    col_height: floats a column of d_out needs (default: the bins of the plan; the band count of a filterbank launch)."""
     import torch
     assert d_in.is_cuda and d_in.dtype == torch.float32 and d_in.dim() == 2 and d_in.stride(1) == 1
     assert d_out.is_cuda and d_out.dtype == torch.float32 and d_out.stride(-1) == 1
-    H = plan.n // 2 + 1 - (1 if d_tail is not None else 0)
+    H = (plan.n // 2 + 1 - (1 if d_tail is not None else 0)) if col_height is None else int(col_height)
     if d_out.shape[-1] < H:
         raise JsgError(capi.JSG_ERR_INVALID, f"output rows hold {d_out.shape[-1]} floats, a column needs {H}")
     if mix_mode == capi.MIX_PER_CHANNEL and (d_out.dim() != 3 or d_out.shape[0] != d_in.shape[0]):
@@ -520,3 +521,180 @@ def db_from_power(d_power, d_out, divisor: float = 1.0, stream: int | None = Non
         stream = torch.cuda.current_stream(d_power.device).cuda_stream
     check(lib().jsg_db_from_power_launch_ex(d_power.data_ptr(), d_out.data_ptr(), d_power.numel(), divisor, int(bool(exact_log)),
                                             C.c_void_p(stream)))
+
+
+# --------------------------------------------------------------------------------------------------
+# filterbank spectrograms: mel and log-frequency rows (include/jsg.h, section 2b)
+# --------------------------------------------------------------------------------------------------
+class Filterbank:
+    """A sparse, banded filterbank over the n/2+1 bins of an n-point FFT (CSR: band b = weights[offset[b] : offset[b] + n_bins[b]]
+    over the bins first_bin[b] ..).  Built on the host by jsg_filterbank_build (no GPU needed) or taken from a dense matrix; uploaded to
+    a device once, the first time a launch on that device needs it.
+
+        Filterbank(n, fs, n_bands, fmin, fmax, scale=capi.FB_MEL_SLANEY, norm=None)
+            norm None: NORM_SLANEY for the mel scales (librosa's default), NORM_UNIT_SUM for LOG / LINEAR.
+        Filterbank.from_matrix(W)       W [n_bands][n/2+1]: every row keeps the span from its first to its last nonzero
+    """
+
+    def __init__(self, n: int, fs: float, n_bands: int, fmin: float = 0.0, fmax: float | None = None, scale: int = capi.FB_MEL_SLANEY,
+                 norm: int | None = None):
+        if fmax is None:
+            fmax = fs / 2.0
+        if norm is None:
+            norm = capi.FB_NORM_SLANEY if scale in (capi.FB_MEL_SLANEY, capi.FB_MEL_HTK) else capi.FB_NORM_UNIT_SUM
+        self.spec = capi.FbSpec(int(n), float(fs), int(n_bands), float(fmin), float(fmax), int(scale), int(norm))
+        nnz = C.c_int64()
+        check(lib().jsg_filterbank_build(C.byref(self.spec), None, None, None, None, None, 0, C.byref(nnz)))
+        B = int(n_bands)
+        self.first_bin = np.zeros(B, np.int32)
+        self.n_bins = np.zeros(B, np.int32)
+        self.offset = np.zeros(B, np.int32)
+        self.centres_hz = np.zeros(B, np.float32)
+        self.weights = np.zeros(max(1, nnz.value), np.float32)
+        check(lib().jsg_filterbank_build(C.byref(self.spec), self.first_bin.ctypes.data, self.n_bins.ctypes.data, self.offset.ctypes.data,
+                                         self.centres_hz.ctypes.data, self.weights.ctypes.data, self.weights.size, C.byref(nnz)))
+        self.weights = self.weights[:nnz.value]
+        self.n, self.n_bands, self._dense = int(n), B, None
+        self._handles = {}
+
+    @classmethod
+    def from_matrix(cls, W) -> "Filterbank":
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        assert W.ndim == 2 and W.shape[1] >= 257
+        self = cls.__new__(cls)
+        self.n, self.n_bands = 2 * (W.shape[1] - 1), W.shape[0]
+        self.spec, self._dense, self._handles = None, W, {}
+        first, count, off, w = [], [], [], []
+        for row in W:
+            nz = np.flatnonzero(row)
+            a, e = (int(nz[0]), int(nz[-1]) + 1) if nz.size else (0, 0)
+            first.append(a)
+            count.append(e - a)
+            off.append(sum(len(x) for x in w))
+            w.append(row[a:e])
+        self.first_bin, self.n_bins, self.offset = (np.array(v, np.int32) for v in (first, count, off))
+        self.weights = np.concatenate(w).astype(np.float32) if w else np.zeros(0, np.float32)
+        self.centres_hz = None
+        return self
+
+    def matrix(self) -> np.ndarray:
+        """The bank as a dense [n_bands][n/2+1] float32 matrix (zeros outside every band's span)."""
+        out = np.zeros((self.n_bands, self.n // 2 + 1), np.float32)
+        for b in range(self.n_bands):
+            out[b, self.first_bin[b]:self.first_bin[b] + self.n_bins[b]] = self.weights[self.offset[b]:self.offset[b] + self.n_bins[b]]
+        return out
+
+    def handle(self, device: int | None = None) -> C.c_void_p:
+        """The jsg_filterbank on `device` (default: the current one), created on first use."""
+        import torch
+        dev = torch.cuda.current_device() if device is None else int(device)
+        h = self._handles.get(dev)
+        if h is None:
+            h = C.c_void_p()
+            with torch.cuda.device(dev):
+                if self.spec is not None:
+                    check(lib().jsg_filterbank_create(C.byref(h), C.byref(self.spec)))
+                else:
+                    check(lib().jsg_filterbank_create_matrix(C.byref(h), self.n, self.n_bands, self._dense.ctypes.data))
+            self._handles[dev] = h
+        return h
+
+    def device_weights(self, device: int | None = None) -> np.ndarray:
+        """jsg_filterbank_weights of the device object: the bank as the library holds it."""
+        out = np.zeros((self.n_bands, self.n // 2 + 1), np.float32)
+        check(lib().jsg_filterbank_weights(self.handle(device), out.ctypes.data))
+        return out
+
+    def close(self):
+        for h in getattr(self, "_handles", {}).values():
+            lib().jsg_filterbank_destroy(h)
+        self._handles = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _fb_args(plan: Plan, fb: Filterbank, d_in, hop: int, n_frames: int, d_out, strided: bool, **kw):
+    if strided:
+        assert d_in.dim() == 3 and d_in.stride(2) == 1 and d_out.shape[0] == d_in.shape[0] and d_out.stride(-1) == 1
+        a = _stft_args(plan, d_in[0], hop, n_frames, d_out[0], col_height=fb.n_bands, **kw)
+        return a, int(d_in.shape[0]), int(d_in.stride(0)), int(d_out.stride(0))
+    return _stft_args(plan, d_in, hop, n_frames, d_out, col_height=fb.n_bands, **kw), 1, 0, 0
+
+
+def stft_fb_scratch_floats(plan: Plan, fb: Filterbank, d_in, hop: int, n_frames: int, d_out, *, strided: bool = False, **kw) -> int:
+    """jsg_stft_fb_scratch_floats: the scratch size (floats) the library recommends for this call."""
+    a, k, _, _ = _fb_args(plan, fb, d_in, hop, n_frames, d_out, strided, **kw)
+    return int(check(lib().jsg_stft_fb_scratch_floats(plan._p, fb.handle(d_in.device.index), C.byref(a), k)))
+
+
+def _fb_launch(plan, fb, d_in, hop, n_frames, d_out, strided, d_scratch, stream, kw):
+    import torch
+    a, k, s_in, s_out = _fb_args(plan, fb, d_in, hop, n_frames, d_out, strided, **kw)
+    h = fb.handle(d_in.device.index)
+    temporary = d_scratch is None
+    if temporary:
+        n_sc = int(check(lib().jsg_stft_fb_scratch_floats(plan._p, h, C.byref(a), k)))
+        d_scratch = torch.empty(n_sc, dtype=torch.float32, device=d_in.device)
+    assert d_scratch.is_cuda and d_scratch.dtype == torch.float32 and d_scratch.is_contiguous()
+    if stream is None:
+        stream = torch.cuda.current_stream(d_in.device).cuda_stream
+    elif temporary:   # the caching allocator must not hand the block out again before the launch on the caller's stream is done
+        d_scratch.record_stream(torch.cuda.ExternalStream(stream, device=d_in.device))
+    check(lib().jsg_stft_fb_launch_strided(plan._p, h, C.byref(a), k, s_in, s_out, d_scratch.data_ptr(), d_scratch.numel(), C.c_void_p(stream)))
+
+
+def stft_fb_db(plan: Plan, fb: Filterbank, d_in, hop: int, n_frames: int, d_out, *, d_scratch=None, stream: int | None = None, **kw):
+    """jsg_stft_fb_launch: the columns of stft_db with the filterbank applied.  d_out [W][pitch >= n_bands] (per-channel mode:
+    [C][W][pitch]); d_scratch: float32 CUDA tensor (None: one of the recommended size is allocated with torch for this call).
+    Keywords as stft_db (linear_out: band power instead of dB; exact_log: the bit-reproducible logarithm)."""
+    _fb_launch(plan, fb, d_in, hop, n_frames, d_out, False, d_scratch, stream, kw)
+
+
+def stft_fb_db_strided(plan: Plan, fb: Filterbank, d_in, hop: int, n_frames: int, d_out, *, d_scratch=None, stream: int | None = None, **kw):
+    """jsg_stft_fb_launch_strided: d_in [k][channels][samples] -> d_out [k][W][pitch] (per-channel: [k][C][W][pitch]), one call."""
+    _fb_launch(plan, fb, d_in, hop, n_frames, d_out, True, d_scratch, stream, kw)
+
+
+def stft_fb_kernel_name(plan: Plan, fb: Filterbank, d_in, hop: int, n_frames: int, d_out, *, strided: bool = False, **kw) -> str:
+    """The STFT kernel every chunk of this filterbank call takes (decided once for the whole call)."""
+    a, k, _, _ = _fb_args(plan, fb, d_in, hop, n_frames, d_out, strided, **kw)
+    buf = C.create_string_buffer(32)
+    check(lib().jsg_stft_fb_kernel_name(plan._p, fb.handle(d_in.device.index), C.byref(a), k, buf, 32))
+    return buf.value.decode()
+
+
+_mel_cache: dict = {}
+_window_table = window      # (mel_spectrogram_db takes a `window` argument)
+
+
+def mel_spectrogram_db(x, fs: float, n_fft: int, hop: int, n_mels: int, fmin: float = 0.0, fmax: float | None = None,
+                       window: int = capi.WIN_HANN, mix_mode: int = capi.MIX_ABSMEAN, exact_log: bool = False):
+    """Mel spectrogram in dB of a torch CUDA tensor x ([samples] or [channels][samples], float32): Slaney mels with Slaney
+    normalisation (librosa.feature.melspectrogram's bank), frames at t * hop (no padding), 10*log10(band power + 1e-11).
+    hop must divide n_fft (the kernels' regular framing, hop * feedblocks = n_fft; other hops are refused with JSG_ERR_INVALID).
+    Returns a new tensor [frames][n_mels] on x.device.  Plan and Filterbank are cached per geometry."""
+    import torch
+    if hop <= 0 or hop > n_fft or n_fft % hop:
+        raise JsgError(capi.JSG_ERR_INVALID, f"mel_spectrogram_db: hop {hop} must divide n_fft {n_fft} (frames at t * hop)")
+    if x.dim() == 1:
+        x = x[None, :]
+    x = x.contiguous().float()
+    assert x.is_cuda
+    frames = 1 + (x.shape[1] - n_fft) // hop
+    if frames < 1:
+        raise JsgError(capi.JSG_ERR_INVALID, f"mel_spectrogram_db: {x.shape[1]} samples hold no frame of {n_fft}")
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    key = (dev, int(n_fft), int(window), float(fs), int(n_mels), float(fmin), None if fmax is None else float(fmax))
+    if key not in _mel_cache:
+        with torch.cuda.device(dev):
+            _mel_cache[key] = (Plan(n_fft, _window_table(window, n_fft)),
+                               Filterbank(n_fft, fs, n_mels, fmin, fmax, scale=capi.FB_MEL_SLANEY, norm=capi.FB_NORM_SLANEY))
+    plan, fb = _mel_cache[key]
+    out = torch.empty((frames, n_mels), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(dev):
+        stft_fb_db(plan, fb, x, hop, frames, out, feedblocks=n_fft // hop, mix_mode=mix_mode, exact_log=exact_log)
+    return out
