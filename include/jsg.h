@@ -43,7 +43,9 @@ extern "C" {
 #define JSG_ABI_VERSION 6   /* 3: + kernel-name query, launch pool, image scratch query, sharded set; 4: + strided image batches (round 3);
                                5: + strided dB batches, exact-log mode, producer ring statistics (round 4);
                                6: + lossless producer call, all-or-nothing sharded push, exact-log display path, tail plane, pair plan (round 5);
-                                  additions to 6: filterbank spectrograms (jsg_filterbank_*, jsg_stft_fb_*; section 2b) */
+                                  additions to 6: filterbank spectrograms (jsg_filterbank_*, jsg_stft_fb_*; section 2b),
+                                  display frequency axes (jsg_freq_axis_*, jsg_colormap_axis_launch, jsg_display_set_freq_axis,
+                                  jsg_display_height, jsg_display_axis_centres; section 2c) */
 
 typedef enum jsg_status {
     JSG_OK = 0,
@@ -387,6 +389,52 @@ JSG_API int64_t jsg_stft_fb_scratch_floats(const jsg_plan* plan, const jsg_filte
 JSG_API int jsg_stft_fb_kernel_name(const jsg_plan* plan, const jsg_filterbank* fb, const jsg_stft_args* args, int n_batches, char* out, int out_len);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2c. Frequency axis of the colour loop: `height` image rows on a linear, log or mel axis, drawn from the dB columns the ring
+ *     already holds (the reference draws one row per bin and zooms by blitting a sub-rectangle, Spectrogram.cpp:441-459).
+ *
+ *     Row table (jsg_freq_axis_build, host, double arithmetic; row r = 0 is the BOTTOM row, H = height):
+ *         w(f) = f (LINEAR), ln f (LOG), Slaney mel (MEL: the formula of the MEL_SLANEY filterbank), du = (w(fmax) - w(fmin)) / (H-1)
+ *         centre_hz[r] = w^-1(w(fmin) + r du)
+ *         b_j = w^-1(w(fmin) + (j - 1/2) du) * n / fs,  j = 0..H  (each bound computed once: row r = [b_r, b_r+1), the rows
+ *               partition the bin axis)
+ *         the bins of row r are the integers k in [0, n/2] with b_r <= k < b_r+1:
+ *           at least one: first_bin[r] = the first of them, n_bins[r] = their count (interp_t[r] = 0);
+ *           none:         n_bins[r] = 0, x = centre_hz[r] n / fs (double centre), k = min(floor(x), n/2-1),
+ *                         first_bin[r] = k, interp_t[r] = (float)(x - k).
+ *     LINEAR over [0, fs/2] with H = n/2+1 is the identity: row r holds exactly bin r.
+ *
+ *     Pixel of dB column c, row r (float32, bit for bit):
+ *         n_bins >= 1: v = max(db[c][first .. first+n_bins-1]); NaN if any of those values is NaN
+ *         n_bins == 0: a = db[c][k], b = db[c][k+1], v = a + t (b - a), the subtraction, the product and the sum rounded
+ *                      separately (no fused multiply-add)
+ *         pixel(x, H-1-r) = lut[index(v)] | 0xFF000000 and index_out = index(v), index() as in jsg_colormap_launch (NaN: index 0).
+ *     The maximum keeps a narrow tone visible in a row that spans many bins (a mean of dB would hide it).
+ * ------------------------------------------------------------------------------------------------ */
+typedef enum jsg_axis_scale { JSG_AXIS_BINS = 0, JSG_AXIS_LINEAR = 1, JSG_AXIS_LOG = 2, JSG_AXIS_MEL = 3 } jsg_axis_scale;
+#define JSG_AXIS_MAX_HEIGHT 16384
+typedef struct jsg_axis_spec {
+    int32_t n;          /* FFT size: a power of two in 512..8192 */
+    float fs;           /* sample rate, Hz (> 0) */
+    int32_t scale;      /* LINEAR / LOG / MEL (BINS is the engine's default and is refused here) */
+    int32_t height;     /* image rows, 2..JSG_AXIS_MAX_HEIGHT */
+    float fmin, fmax;   /* Hz: 0 <= fmin < fmax <= fs/2 (LOG: fmin > 0) */
+} jsg_axis_spec;
+/* The row table of a spec, on the host (no GPU): first_bin, n_bins, interp_t, centre_hz of `height` entries each.
+ * JSG_ERR_INVALID for a spec outside the ranges above. */
+JSG_API int jsg_freq_axis_build(const jsg_axis_spec* s, int32_t* first_bin, int32_t* n_bins, float* interp_t, float* centre_hz);
+
+/* The row table resident on the device that is current at creation (uploaded once, with the row tiles the kernel is launched over). */
+typedef struct jsg_freq_axis jsg_freq_axis;
+JSG_API int jsg_freq_axis_create(jsg_freq_axis** out, const jsg_axis_spec* s);
+JSG_API int jsg_freq_axis_destroy(jsg_freq_axis* ax);
+JSG_API int jsg_freq_axis_height(const jsg_freq_axis* ax);
+/* jsg_colormap_launch with the rows of `ax`: args->height must be n/2+1 of the axis's FFT size (the bins of a dB column); the image
+ * has jsg_freq_axis_height(ax) rows.  Every other argument keeps its meaning (ring wrap, x_first / x_wrap, argb_out and / or
+ * index_out, any n_colors).  Enqueue only (hipGraph capture works).  Refused: everything jsg_colormap_launch refuses, an axis of
+ * another device or of another FFT size. */
+JSG_API int jsg_colormap_axis_launch(const jsg_colormap_args* args, const jsg_freq_axis* ax, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 3. Engine: the state of class Spectrogram (Spectrogram.h:81-169) living on the GPU.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct jsg_engine jsg_engine;
@@ -500,6 +548,20 @@ JSG_API int jsg_display_update(jsg_engine* e, float min_color, float max_color, 
  * jsg_display_update for the whole image. */
 JSG_API int jsg_display_update_tile(jsg_engine* e, float min_color, float max_color, uint32_t* tile, int64_t tile_pitch,
                             int max_cols, int* new_vals, int* pos);
+
+/* Frequency axis of the display image (section 2c).  scale JSG_AXIS_BINS (the default): one row per bin, height n/2+1, the other
+ * arguments are ignored.  LINEAR / LOG / MEL: `height` rows over [fmin, fmax] Hz, checked against the engine's current sample rate
+ * and FFT size (JSG_ERR_INVALID keeps the old axis).  An accepted call forces a full recolour: jsg_display_update_tile returns 1
+ * until jsg_display_update has run, and the whole history is drawn on the new axis.  The engine keeps the requested range; after
+ * jsg_set_samplerate / jsg_set_fft_size the next tick rebuilds the rows with paint()'s clamps (Spectrogram.cpp:444-452: fmin >= fs/2
+ * -> 0.9 fs/2, fmax >= fs/2 -> fs/2, fmin >= fmax -> 0.9 fmax) and recolours everything; the requested range comes back with a
+ * sample rate that admits it. */
+JSG_API int jsg_display_set_freq_axis(jsg_engine* e, int scale, int height, float fmin, float fmax);
+/* Image rows that the next jsg_display_update / _tile writes (the `argb` buffer has this many rows). */
+JSG_API int jsg_display_height(const jsg_engine* e);
+/* Centre frequency (Hz) of every image row, bottom row first, for tick labels: n >= jsg_display_height (else JSG_ERR_SIZE_MISMATCH);
+ * BINS: k fs / n.  Returns the row count. */
+JSG_API int jsg_display_axis_centres(jsg_engine* e, float* centre_hz, int n);
 
 /* The frequency window of SpectrogramComponent::paint (Spectrogram.cpp:441-459): which image rows show
  * [min_freq, max_freq] Hz.  Pure host arithmetic (same clamps and roundings); outputs displayStartPixel,

@@ -28,6 +28,8 @@ CM_MONO, CM_BW, CM_HOT, CM_RAINBOW, CM_VIRIDIS, CM_PLASMA, CM_JADE = range(7)
 FB_MEL_SLANEY, FB_MEL_HTK, FB_LOG, FB_LINEAR = range(4)
 FB_NORM_NONE, FB_NORM_SLANEY, FB_NORM_UNIT_SUM = range(3)
 FB_MAX_BANDS = 8192
+AXIS_BINS, AXIS_LINEAR, AXIS_LOG, AXIS_MEL = range(4)
+AXIS_MAX_HEIGHT = 16384
 
 
 class JsgError(RuntimeError):
@@ -48,6 +50,11 @@ class StftArgs(C.Structure):
 class FbSpec(C.Structure):
     _fields_ = [("n", C.c_int32), ("fs", C.c_float), ("n_bands", C.c_int32), ("fmin", C.c_float), ("fmax", C.c_float),
                 ("scale", C.c_int32), ("norm", C.c_int32)]
+
+
+class AxisSpec(C.Structure):
+    _fields_ = [("n", C.c_int32), ("fs", C.c_float), ("scale", C.c_int32), ("height", C.c_int32), ("fmin", C.c_float),
+                ("fmax", C.c_float)]
 
 
 class ColormapArgs(C.Structure):
@@ -103,6 +110,11 @@ SIGNATURES = {
     "jsg_stft_fb_launch_strided": (C.c_int, [_P, _P, C.POINTER(StftArgs), C.c_int, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
     "jsg_stft_fb_scratch_floats": (C.c_int64, [_P, _P, C.POINTER(StftArgs), C.c_int]),
     "jsg_stft_fb_kernel_name": (C.c_int, [_P, _P, C.POINTER(StftArgs), C.c_int, C.c_char_p, C.c_int]),
+    "jsg_freq_axis_build": (C.c_int, [C.POINTER(AxisSpec), _P, _P, _P, _P]),
+    "jsg_freq_axis_create": (C.c_int, [C.POINTER(_P), C.POINTER(AxisSpec)]),
+    "jsg_freq_axis_destroy": (C.c_int, [_P]),
+    "jsg_freq_axis_height": (C.c_int, [_P]),
+    "jsg_colormap_axis_launch": (C.c_int, [C.POINTER(ColormapArgs), _P, _P]),
     "jsg_create": (C.c_int, [C.POINTER(_P), C.c_int]),
     "jsg_create_on_device": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int]),
     "jsg_get_device": (C.c_int, [_P]),
@@ -150,6 +162,9 @@ SIGNATURES = {
     "jsg_display_update": (C.c_int, [_P, C.c_float, C.c_float, _P, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "jsg_display_update_tile": (C.c_int, [_P, C.c_float, C.c_float, _P, C.c_int64, C.c_int, C.POINTER(C.c_int),
                                           C.POINTER(C.c_int)]),
+    "jsg_display_set_freq_axis": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float]),
+    "jsg_display_height": (C.c_int, [_P]),
+    "jsg_display_axis_centres": (C.c_int, [_P, _P, C.c_int]),
     "jsg_display_freq_rows": (C.c_int, [C.c_float, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }

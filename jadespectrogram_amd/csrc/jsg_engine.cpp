@@ -164,6 +164,15 @@ struct jsg_engine {
     int64_t host_pitch = 0;
     bool host_fixed_valid = false;
     int host_cursor_pos = 0, host_cursor_w = 0;
+    // frequency axis of the image (jsg_display_set_freq_axis; readers' state like d_img).  The requested range is kept; `axis` holds its
+    // rows for (axis_fs, axis_n) and is rebuilt with paint()'s clamps by the first reader after a sample-rate or FFT-size change.
+    // JSG_AXIS_BINS: no axis, one row per bin (jsg_colormap_launch).
+    int axis_scale = JSG_AXIS_BINS, axis_height = 0;
+    float axis_fmin = 0.f, axis_fmax = 0.f;
+    jsg_freq_axis* axis = nullptr;
+    float axis_fs = 0.f;
+    int axis_n = 0;
+    std::atomic<int> a_axis_h{0};   // rows of the axis image, 0 for BINS (jsg_display_height)
 
     int fail(int code, const std::string& what) {
         {
@@ -586,6 +595,7 @@ int jsg_destroy(jsg_engine* e) {
     if (e->d_in) (void)hipFree(e->d_in);
     if (e->d_lut) (void)hipFree(e->d_lut);
     if (e->d_img) (void)hipFree(e->d_img);
+    if (e->axis) jsg_freq_axis_destroy(e->axis);
     if (e->q.mem) (void)hipHostFree(e->q.mem);
     if (e->h_mem) (void)hipHostFree(e->h_mem);
     if (e->d_snap) (void)hipFree(e->d_snap);
@@ -987,6 +997,87 @@ int jsg_display_invalidate(jsg_engine* e) {
 
 namespace {
 
+// (rd_mu held) a new row table replaces the old one once the read-out stream no longer uses it; the next tick recolours everything
+int install_axis(jsg_engine* e, jsg_freq_axis* ax) {
+    const hipError_t err = hipStreamSynchronize(e->rstream);
+    if (err != hipSuccess) {
+        jsg_freq_axis_destroy(ax);
+        return e->fail_hip(err, "hipStreamSynchronize");
+    }
+    if (e->axis) jsg_freq_axis_destroy(e->axis);
+    e->axis = ax;
+    e->axis_fs = e->fs;
+    e->axis_n = e->n;
+    e->recompute_all = true;
+    return JSG_OK;
+}
+
+// (rd_mu held) the row table of the requested axis for the current sample rate and FFT size, clamped as paint() clamps its
+// frequency window (Spectrogram.cpp:444-452)
+int axis_current(jsg_engine* e) {
+    if (e->axis_scale == JSG_AXIS_BINS || (e->axis && e->axis_fs == e->fs && e->axis_n == e->n)) return JSG_OK;
+    const double half = 0.5 * double(e->fs);
+    double fmin = e->axis_fmin, fmax = e->axis_fmax;
+    if (fmin >= half) fmin = 0.9 * half;
+    if (fmax >= half) fmax = half;
+    if (fmin >= fmax) fmin = 0.9 * fmax;
+    const jsg_axis_spec s{e->n, e->fs, e->axis_scale, e->axis_height, float(fmin), float(fmax)};
+    jsg_freq_axis* ax = nullptr;
+    const int rc = jsg_freq_axis_create(&ax, &s);
+    if (rc != JSG_OK) return e->fail_tls(rc);
+    return install_axis(e, ax);
+}
+
+}  // namespace
+
+int jsg_display_set_freq_axis(jsg_engine* e, int scale, int height, float fmin, float fmax) {
+    JSG_LOCK_CONFIG(e);
+    if (scale == JSG_AXIS_BINS) {
+        if (e->axis) {
+            JSG_HIP(e, hipStreamSynchronize(e->rstream));
+            jsg_freq_axis_destroy(e->axis);
+            e->axis = nullptr;
+        }
+        e->axis_scale = JSG_AXIS_BINS;
+        e->a_axis_h.store(0);
+        e->recompute_all = true;
+        return JSG_OK;
+    }
+    const jsg_axis_spec s{e->n, e->fs, scale, height, fmin, fmax};   // checked against the current rate and size, unclamped
+    jsg_freq_axis* ax = nullptr;
+    int rc = jsg_freq_axis_create(&ax, &s);
+    if (rc != JSG_OK) return e->fail_tls(rc);   // the old axis stays
+    rc = install_axis(e, ax);
+    if (rc != JSG_OK) return rc;
+    e->axis_scale = scale;
+    e->axis_height = height;
+    e->axis_fmin = fmin;
+    e->axis_fmax = fmax;
+    e->a_axis_h.store(height);
+    return JSG_OK;
+}
+
+int jsg_display_height(const jsg_engine* e) {
+    if (!e) return jsg_fail(JSG_ERR_INVALID, "null engine");
+    const int h = e->a_axis_h.load();
+    return h > 0 ? h : e->a_H.load();
+}
+
+int jsg_display_axis_centres(jsg_engine* e, float* centre_hz, int n) {
+    JSG_LOCK_CONFIG(e);
+    if (!centre_hz) return e->fail(JSG_ERR_INVALID, "null centre array");
+    const int rc = axis_current(e);
+    if (rc != JSG_OK) return rc;
+    const int H = e->axis ? e->axis->height : e->H;
+    if (n < H) return e->fail(JSG_ERR_SIZE_MISMATCH, "centre array shorter than the image height");
+    if (e->axis) std::copy(e->axis->centre_hz.begin(), e->axis->centre_hz.end(), centre_hz);
+    else
+        for (int k = 0; k < H; ++k) centre_hz[k] = float(double(k) * double(e->fs) / double(e->n));
+    return H;
+}
+
+namespace {
+
 struct Tick {   // what a display tick decided under the state lock
     int W = 0, H = 0, pos = 0, n_cols = 0, col_first = 0;
     long long nec = 0;
@@ -998,24 +1089,27 @@ struct Tick {   // what a display tick decided under the state lock
 int display_enqueue(jsg_engine* e, float min_color, float max_color, bool tile_mode, int max_cols, Tick* t, int* need_full) {
     hipError_t herr = hipSetDevice(e->device);
     if (herr != hipSuccess) return e->fail_hip(herr, "hipSetDevice");
-    if (!tile_mode && (e->W != e->img_w || e->H != e->img_h)) {   // Spectrogram.cpp:595-605; geometry is stable under rd_mu,
-        JSG_HIP(e, hipStreamSynchronize(e->rstream));             // and the image belongs to the readers: no state lock here
+    int arc = axis_current(e);   // after a sample-rate / FFT-size change: the rows for the new geometry, and a full recolour
+    if (arc != JSG_OK) return arc;
+    const int img_rows = e->axis ? e->axis->height : e->H;
+    if (!tile_mode && (e->W != e->img_w || img_rows != e->img_h)) {   // Spectrogram.cpp:595-605; geometry is stable under rd_mu,
+        JSG_HIP(e, hipStreamSynchronize(e->rstream));                 // and the image belongs to the readers: no state lock here
         if (e->d_img) (void)hipFree(e->d_img);
         e->d_img = nullptr;
         e->img_pitch = round_up(e->W, 32);
-        JSG_HIP(e, hipMalloc(reinterpret_cast<void**>(&e->d_img), size_t(e->img_pitch) * e->H * 4));
+        JSG_HIP(e, hipMalloc(reinterpret_cast<void**>(&e->d_img), size_t(e->img_pitch) * img_rows * 4));
         e->img_w = e->W;
-        e->img_h = e->H;
+        e->img_h = img_rows;
         e->recompute_all = true;
     }
     std::lock_guard<std::mutex> lk(e->mu);
     if (e->mix == JSG_MIX_PER_CHANNEL) return e->fail(JSG_ERR_UNSUPPORTED, "display needs a mixed (single) spectrogram");
     const int W = e->W, H = e->H;
     t->W = W;
-    t->H = H;
+    t->H = img_rows;
     const long long nec = e->new_entry;                   // getMem, Spectrogram.cpp:607-608
     if (tile_mode) {
-        if (e->recompute_all || W != e->img_w || H != e->img_h || nec > W || nec > max_cols) {
+        if (e->recompute_all || W != e->img_w || img_rows != e->img_h || nec > W || nec > max_cols) {
             t->nec = std::min<long long>(nec, 2000000000ll);
             t->pos = e->mem_counter;
             *need_full = 1;
@@ -1052,7 +1146,7 @@ int display_enqueue(jsg_engine* e, float min_color, float max_color, bool tile_m
         a.x_first = t->col_first;
         int rc = reader_begin(e);
         if (rc != JSG_OK) return rc;
-        rc = jsg_colormap_launch(&a, e->rstream);
+        rc = e->axis ? jsg_colormap_axis_launch(&a, e->axis, e->rstream) : jsg_colormap_launch(&a, e->rstream);
         if (rc != JSG_OK) return e->fail_tls(rc);
         rc = reader_end(e);                               // the ring is free again once the colour kernel has run
         if (rc != JSG_OK) return rc;

@@ -25,16 +25,13 @@ struct Csr {
     std::vector<float> centre, w;
 };
 
-// Slaney: linear below 1 kHz (200/3 Hz per mel), logarithmic above (27 mels per factor 6.4)
-const double kSpMelHz = 200.0 / 3.0, kSpBreakHz = 1000.0, kSpBreakMel = 15.0;
-inline double sp_logstep() { return std::log(6.4) / 27.0; }
 inline double hz_to_mel(double f, bool htk) {
     if (htk) return 2595.0 * std::log10(1.0 + f / 700.0);
-    return f < kSpBreakHz ? f / kSpMelHz : kSpBreakMel + std::log(f / kSpBreakHz) / sp_logstep();
+    return slaney_hz_to_mel(f);
 }
 inline double mel_to_hz(double m, bool htk) {
     if (htk) return 700.0 * (std::pow(10.0, m / 2595.0) - 1.0);
-    return m < kSpBreakMel ? kSpMelHz * m : kSpBreakHz * std::exp(sp_logstep() * (m - kSpBreakMel));
+    return slaney_mel_to_hz(m);
 }
 
 bool pow2_in_range(int n) { return n >= 512 && n <= 8192 && (n & (n - 1)) == 0; }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -17,6 +18,14 @@ int jsg_fail_hip(hipError_t err, const char* where);
 // jsg_kernels.hip: compute units of a device (read once per device), the device a plan was created on
 int cu_count_of_device(int dev);
 int plan_device(const jsg_plan* plan);
+// jsg_display_axis.hip: load the code object of the axis kernel (jsg_freq_axis_create, on the thread that configures)
+void touch_axis_module();
+
+// Slaney's mel scale (librosa.filters.mel, htk = False): linear below 1 kHz (200/3 Hz per mel), logarithmic above (27 mels per
+// factor 6.4).  Shared by the MEL_SLANEY filterbank and the MEL display axis.
+inline double slaney_logstep() { return std::log(6.4) / 27.0; }
+inline double slaney_hz_to_mel(double f) { return f < 1000.0 ? f / (200.0 / 3.0) : 15.0 + std::log(f / 1000.0) / slaney_logstep(); }
+inline double slaney_mel_to_hz(double m) { return m < 15.0 ? (200.0 / 3.0) * m : 1000.0 * std::exp(slaney_logstep() * (m - 15.0)); }
 
 }  // namespace jsg
 
@@ -35,4 +44,20 @@ struct jsg_filterbank {
     const float* d_w = nullptr;
     std::vector<int> first, count, offset;   // host copy (jsg_filterbank_weights)
     std::vector<float> w;
+};
+
+// A display frequency axis on the device (jsg_display_axis_host.cpp creates it, jsg_display_axis.hip launches over it): the row table of
+// jsg_freq_axis_build and the row tiles of the launch, one allocation.  A tile is (first row, rows, first bin, bins): at most
+// kAxisTileRows consecutive rows whose bins -- those of a reduced row, k and k+1 of an interpolated one -- lie in [first bin,
+// first bin + bins).  A tile spans at most kAxisSpan bins unless it is one reduced row (the kernel then walks its span in steps).
+constexpr int kAxisTileRows = 64;
+constexpr int kAxisSpan = 128;
+struct jsg_freq_axis {
+    int n = 0;
+    int height = 0;
+    int device = -1;
+    int n_tiles = 0;
+    int* d_rows = nullptr;        // first_bin[height], n_bins[height], interp_t[height] (float bits), then tiles[4 * n_tiles]
+    const int* d_tiles = nullptr;
+    std::vector<float> centre_hz; // host copy (jsg_display_axis_centres)
 };

@@ -182,6 +182,20 @@ public:
     int updateTile(float minColor, float maxColor, uint32_t* tile, int64_t pitchPixels, int maxCols, int& newVals, int& pos) {
         return jsg_display_update_tile(m_spec.engine(), minColor, maxColor, tile, pitchPixels, maxCols, &newVals, &pos);
     }
+    // Image rows on a frequency axis: JSG_AXIS_LINEAR / LOG / MEL, `height` rows (the window's pixel height) over [minFreq, maxFreq] Hz;
+    // JSG_AXIS_BINS (the default) is one row per bin.  Returns JSG_ERR_INVALID and keeps the old axis for a range the current sample rate
+    // or FFT size does not admit.  The image that update() / updateTile() write then has height() rows; paint() blits all of them.
+    int setFrequencyAxis(int scale, int height = 0, float minFreq = 0.f, float maxFreq = 0.f) {
+        return jsg_display_set_freq_axis(m_spec.engine(), scale, height, minFreq, maxFreq);
+    }
+    int height() { return jsg_display_height(m_spec.engine()); }
+    // centre frequency of every image row, bottom row first (tick labels of the frequency meter)
+    std::vector<float> centres() {
+        std::vector<float> c(size_t(std::max(0, height())));
+        const int n = jsg_display_axis_centres(m_spec.engine(), c.data(), int(c.size()));
+        c.resize(size_t(std::max(0, n)));
+        return c;
+    }
     // the rows paint() blits for [minFreq, maxFreq] (reference Spectrogram.cpp:441-459)
     static void freqRows(float fs, int height, float minFreq, float maxFreq, int& startPixel, int& endPixel,
                          int& heightInterval, int& hStart) {

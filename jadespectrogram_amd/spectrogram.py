@@ -186,9 +186,25 @@ class SpectrogramDisplay:
     def invalidate(self):
         self.spec._c(lib().jsg_display_invalidate(self.spec._h))
 
+    def setFrequencyAxis(self, scale: int, height: int = 0, fmin: float = 0.0, fmax: float = 0.0):
+        """Image rows on a LINEAR / LOG / MEL axis over [fmin, fmax] Hz (capi.AXIS_BINS: one row per bin, the default).  Forces a full
+        recolour; the image then has height() rows."""
+        self.spec._c(lib().jsg_display_set_freq_axis(self.spec._h, int(scale), int(height), float(fmin), float(fmax)))
+
+    def height(self) -> int:
+        """Rows of the image the next timerCallback / timerCallbackTile writes."""
+        return self.spec._c(lib().jsg_display_height(self.spec._h))
+
+    def centres(self) -> np.ndarray:
+        """Centre frequency (Hz) of every image row, bottom row first."""
+        out = np.zeros(self.height(), np.float32)
+        self.spec._c(lib().jsg_display_axis_centres(self.spec._h, out.ctypes.data, out.size))
+        return out
+
     def timerCallback(self, img: np.ndarray, min_color=-50.0, max_color=50.0):
-        """img: [H][W] uint32 ARGB, updated in place.  Returns (newVals, pos)."""
+        """img: [height()][W] uint32 ARGB, updated in place.  Returns (newVals, pos)."""
         assert img.dtype == np.uint32 and img.ndim == 2 and img.strides[1] == 4
+        assert img.shape[0] >= self.height(), "the image needs height() rows (the frequency axis sets them)"
         nv, pos = C.c_int(), C.c_int()
         self.spec._c(lib().jsg_display_update(self.spec._h, min_color, max_color, img.ctypes.data, img.strides[0] // 4,
                                               C.byref(nv), C.byref(pos)))
@@ -196,9 +212,10 @@ class SpectrogramDisplay:
 
 
     def timerCallbackTile(self, tile: np.ndarray, min_color=-50.0, max_color=50.0):
-        """Incremental tick: only the new columns, as a [H][max_cols] tile (oldest first).  Returns
+        """Incremental tick: only the new columns, as a [height()][max_cols] tile (oldest first).  Returns
         (need_full, newVals, pos); need_full=True means call timerCallback() for the whole image instead."""
         assert tile.dtype == np.uint32 and tile.ndim == 2 and tile.strides[1] == 4
+        assert tile.shape[0] >= self.height(), "the tile needs height() rows (the frequency axis sets them)"
         nv, pos = C.c_int(), C.c_int()
         rc = self.spec._c(lib().jsg_display_update_tile(self.spec._h, min_color, max_color, tile.ctypes.data,
                                                         tile.strides[0] // 4, tile.shape[1], C.byref(nv), C.byref(pos)))
@@ -399,6 +416,23 @@ def colormap(d_db, d_lut, lo: float, hi: float, *, d_argb=None, d_index=None, co
              x_first: int = 0, height: int | None = None, stream: int | None = None):
     """Enqueue the colour loop: d_db [W][pitch] float32 CUDA -> d_argb [H][Wimg] int32/uint32 and/or d_index uint8."""
     import torch
+    a = _colormap_args(d_db, d_lut, lo, hi, d_argb, d_index, col_first, n_cols, x_first, height)
+    if stream is None:
+        stream = torch.cuda.current_stream(d_db.device).cuda_stream
+    check(lib().jsg_colormap_launch(C.byref(a), C.c_void_p(stream)))
+
+
+def colormap_axis(d_db, d_lut, lo: float, hi: float, axis: "FreqAxis", *, d_argb=None, d_index=None, col_first: int = 0,
+                  n_cols: int | None = None, x_first: int = 0, stream: int | None = None):
+    """colormap() over the rows of a FreqAxis: d_db [W][pitch >= n/2+1] float32 CUDA -> d_argb / d_index of axis.height rows."""
+    import torch
+    a = _colormap_args(d_db, d_lut, lo, hi, d_argb, d_index, col_first, n_cols, x_first, axis.n // 2 + 1)
+    if stream is None:
+        stream = torch.cuda.current_stream(d_db.device).cuda_stream
+    check(lib().jsg_colormap_axis_launch(C.byref(a), axis.handle(d_db.device.index), C.c_void_p(stream)))
+
+
+def _colormap_args(d_db, d_lut, lo, hi, d_argb, d_index, col_first, n_cols, x_first, height) -> capi.ColormapArgs:
     a = capi.ColormapArgs()
     a.db = d_db.data_ptr()
     a.db_pitch = d_db.stride(0)
@@ -418,9 +452,7 @@ def colormap(d_db, d_lut, lo: float, hi: float, *, d_argb=None, d_index=None, co
         a.index_out = d_index.data_ptr()
         a.index_pitch = d_index.stride(0)
         a.x_wrap = d_index.shape[1]
-    if stream is None:
-        stream = torch.cuda.current_stream(d_db.device).cuda_stream
-    check(lib().jsg_colormap_launch(C.byref(a), C.c_void_p(stream)))
+    return a
 
 
 def _stft_image_args(plan: Plan, d_in, hop: int, n_frames: int, d_lut, lo: float, hi: float, d_argb, d_index_scratch, *,
@@ -608,6 +640,54 @@ class Filterbank:
     def close(self):
         for h in getattr(self, "_handles", {}).values():
             lib().jsg_filterbank_destroy(h)
+        self._handles = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# --------------------------------------------------------------------------------------------------
+# display frequency axes: linear / log / mel image rows (include/jsg.h, section 2c)
+# --------------------------------------------------------------------------------------------------
+class FreqAxis:
+    """`height` image rows over [fmin, fmax] Hz of an n-point FFT at fs, on a LINEAR, LOG or MEL axis (row 0 = bottom row).  The row
+    table is built on the host by jsg_freq_axis_build (no GPU needed); uploaded to a device once, the first time it is used there.
+    The defaults (LINEAR over [0, fs/2]) are valid for every scale but LOG, which needs fmin > 0."""
+
+    def __init__(self, n: int, fs: float, height: int, fmin: float = 0.0, fmax: float | None = None, scale: int = capi.AXIS_LINEAR):
+        if fmax is None:
+            fmax = fs / 2.0
+        self.spec = capi.AxisSpec(int(n), float(fs), int(scale), int(height), float(fmin), float(fmax))
+        self.n, self.height = int(n), int(height)
+        H = max(0, self.height)
+        self.first_bin, self.n_bins = np.zeros(H, np.int32), np.zeros(H, np.int32)
+        self.interp_t, self.centres_hz = np.zeros(H, np.float32), np.zeros(H, np.float32)
+        check(lib().jsg_freq_axis_build(C.byref(self.spec), self.first_bin.ctypes.data, self.n_bins.ctypes.data,
+                                        self.interp_t.ctypes.data, self.centres_hz.ctypes.data))
+        self._handles = {}
+
+    def rows(self):
+        """(first_bin, n_bins, interp_t, centre_hz): the row table, height entries each."""
+        return self.first_bin, self.n_bins, self.interp_t, self.centres_hz
+
+    def handle(self, device: int | None = None) -> C.c_void_p:
+        """The jsg_freq_axis on `device` (default: the current one), created on first use."""
+        import torch
+        dev = torch.cuda.current_device() if device is None else int(device)
+        h = self._handles.get(dev)
+        if h is None:
+            h = C.c_void_p()
+            with torch.cuda.device(dev):
+                check(lib().jsg_freq_axis_create(C.byref(h), C.byref(self.spec)))
+            self._handles[dev] = h
+        return h
+
+    def close(self):
+        for h in getattr(self, "_handles", {}).values():
+            lib().jsg_freq_axis_destroy(h)
         self._handles = {}
 
     def __del__(self):

@@ -2,7 +2,8 @@
 """Per-kernel resource usage of the built STFT units (VGPRs, SGPRs, spills, scratch, LDS) from the code objects' metadata, plus
 instruction-mix counts from the disassembly.  CPU only (llvm-objcopy / clang-offload-bundler / llvm-readelf / llvm-objdump).
 
-    python tools/kernel_regs.py [--isa PATTERN] [obj ...]      (default objects: jadespectrogram_amd/build/jsg_stft_{a,b}.o; jsg_filterbank.o holds the band kernel)
+    python tools/kernel_regs.py [--isa PATTERN] [obj ...]      (default objects: jadespectrogram_amd/build/jsg_stft_{a,b}.o; jsg_filterbank.o holds the band kernel,
+                                                               jsg_display_axis.o the display-axis colour kernel)
 """
 import os
 import re
@@ -59,7 +60,7 @@ def main():
             for blk in re.split(r"\n\s+- \.agpr_count", notes)[1:]:
                 g = lambda k: (re.search(rf"\.{k}:\s+(\S+)", blk) or [None, "?"])[1]
                 name = g("name")
-                if "stft_db_kernel" not in name and "fb_band_kernel" not in name:
+                if not any(k in name for k in ("stft_db_kernel", "fb_band_kernel", "colormap_axis_kernel")):
                     continue
                 mx = mix.get(name, {})
                 valu = sum(c for o, c in mx.items() if o.startswith("v_"))
