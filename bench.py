@@ -24,7 +24,7 @@ order, issued by plain C calls -- no extra streams, no hardware-queue setting, n
   c5 (configs[4]: stereo 96 kHz, 4096 points, 87.5 % overlap -> ARGB): one step = 3 dispatches of jsg_stft_image_launch_strided,
       each a whole rotation of ~44 independent 1875-column images.
   `--mode single` times one dispatch per batch instead (the literal "4096 frames/launch" of configs[1]; also what the
-  `one_batch_per_launch` block of every default line reports, from a short in-order run).
+  `one_batch_per_launch` block of every `--full` line reports, from a short in-order run).
 
 The batches rotate over ~1 GB of distinct buffers (about four times the 256 MiB Infinity Cache; `--nbuf` overrides), so every
 dispatch streams from and to HBM.  Before the W warm-up steps the same work runs for about 0.5 s so that the clocks have settled.
@@ -36,13 +36,25 @@ the timed region; the inputs are seeded, so the same arguments give the same fil
 measured live with HIP events on that stream around the K steps: achieved = algorithmic bytes per dispatch / that duration, and
 `timed_region_frac` (bytes of the K steps / wall) is the same number up to the host's last synchronize.  rocprofv3's per-dispatch
 average of the same command is committed under profiles/ (tools/profile_bench.sh) and quoted beside it when it was recorded with
-the same kernel sources.  `calibration` = what a tuned float4 copy (jsg_calib_copy_launch) reaches on this box: the measured roof.
-`power` = the same steps kept running for --power-seconds (after the timed region, N = 1) with the card's socket power and core clock
-sampled from its hwmon files: every kernel of this path runs the socket into its 1400 W cap, the core clock gives.
+the same kernel sources.
+
+Plain and full runs
+-------------------
+A plain run (no `--full`) does only what the headline needs: it sets up, settles the clocks, runs the W warm-up and K timed steps,
+writes --dump-outputs if asked and prints the line, with `roofline` from the timed region's own HIP events.  `--full` adds every
+leg that costs runs of its own, each switched off singly by its --no-* option (at N = 1 only, but for the one-batch-per-dispatch leg):
+  `calibration` = what a tuned float4 copy (jsg_calib_copy_launch) reaches on this box: the measured roof.
+  `power` = the same steps kept running for --power-seconds (after the timed region) with the card's socket power and core clock
+      sampled from its hwmon files: every kernel of this path runs the socket into its 1400 W cap, the core clock gives.
+  `parity` = the timed kernel against the float64 DFT and the oracle's palette, and the strided dispatch against single launches.
+  roofline.one_batch_per_dispatch and roofline.other_column_layout: the same batches one launch per batch, and in the other column layout.
+  `boundary` = jsg_process_block latency under a reading consumer, and the PCIe-inclusive rate of jsg_process_blocks.
+  `cpu_baseline` = the oracle's C port of the CPU path timed on this host.
+  `extra` = the c4, c3 and c5 results of the default c2 line (and as scalars roofline.extra_<cfg>_frac / _value), from child processes
+      that run BEFORE this process touches the GPU.
 
 Every rank works on its own batches (weak scaling; the path shards by channel / stream, there is no data-path collective); RCCL
-carries only the barriers and the max-over-ranks time.  At N = 1 the default line also carries the c4, c3 and c5 results (`extra`, and as
-scalars roofline.extra_<cfg>_frac / _value), from child processes that run BEFORE this process touches the GPU.
+carries only the barriers and the max-over-ranks time.
 """
 from __future__ import annotations
 
@@ -505,7 +517,7 @@ def calibrate_copy(lib, torch, stream):
 def run_extra_config(cfg):
     """c3 / c5 as a child process (started before this process touches the GPU): their headline numbers for the driver's line."""
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--no-boundary",
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", "8", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-boundary",
                             "--no-extra", "--no-calibration", "--power-seconds", "2", "--sub-run"], capture_output=True, text=True, timeout=400)
         j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         return {"metric": j["metric"], "value": j["value"], "unit": j["unit"], "ms_per_step": j["ms_per_step"], "step": j["config"]["step"],
@@ -586,14 +598,18 @@ def main():
                     help="dB column layout of the timed dispatches: reference (= auto) = the reference's m_mem[col][bin]: bin n/2 inline, n/2+1 contiguous "
                          "floats per column (pitch rounded up to 32 floats); tail = jsg_stft_args.out_tail: columns of exactly n/2 floats + a dense "
                          "plane of bin n/2 (same values; the c2 line reports it as a side leg, roofline.frac_tail_plane)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the CPU baseline, the c4 / c3 / c5 child runs, the boundary, parity, power and "
+                         "copy-roof blocks, the one-batch-per-dispatch and other-column-layout legs.  Without it a run sets up, warms up, times "
+                         "the steps, writes --dump-outputs and prints the line; the --no-* options below switch single legs off under --full")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the `parity` block (the profile scripts: its few launches would mix into the tracer's averages)")
     ap.add_argument("--no-boundary", action="store_true", help="skip the `boundary` block (jsg_process_block latency, PCIe-inclusive rate)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the c3 / c5 child runs of the default line")
+    ap.add_argument("--no-extra", action="store_true", help="skip the c4 / c3 / c5 child runs of the default line")
     ap.add_argument("--no-calibration", action="store_true", help="skip the copy-roof calibration")
     ap.add_argument("--no-power", action="store_true", help="skip the sustained leg that samples socket power and core clock")
     ap.add_argument("--power-seconds", type=float, default=3.0, help="length of the sustained leg (N=1 only; after the timed region)")
-    ap.add_argument("--no-single", action="store_true", help="skip the one-batch-per-dispatch leg")
+    ap.add_argument("--no-single", action="store_true", help="skip the one-batch-per-dispatch and other-column-layout legs")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (rank 0; a fixed, seeded "
                          "sample of its columns, float32 dB or float64 ARGB, under 64 MB in all)")
@@ -605,6 +621,8 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.dry_run:
         ap.error("--dump-outputs needs the GPU path (not --dry-run)")
+    if not args.full:   # a plain run does what its headline needs and nothing else: every side leg is off
+        args.no_cpu_baseline = args.no_parity = args.no_boundary = args.no_extra = args.no_calibration = args.no_power = args.no_single = True
     if args.config is None:
         args.config = "c2" if args.gpus <= 1 else "c4"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:

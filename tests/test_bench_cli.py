@@ -7,12 +7,15 @@ import os
 import socket
 import subprocess
 import sys
+import time
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "config"}
+
+SIDE_BLOCKS = ("cpu_baseline", "extra", "boundary", "power", "calibration", "parity")      # what only --full runs
 
 
 def _free_port():
@@ -56,6 +59,12 @@ def test_steps_below_one_and_dump_outputs_without_a_gpu_path_are_refused():
         r = subprocess.run([sys.executable, "bench.py", "--dry-run"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=120)
         assert r.returncode == 2 and "error" in r.stderr, extra
     assert not os.path.exists(os.path.join(ROOT, "unused_dir"))
+
+
+def test_full_is_an_option_of_the_dry_run_too():
+    for extra in ([], ["--full"]):
+        j = _run([sys.executable, "bench.py", "--dry-run", "--steps", "2", "--warmup", "1"] + extra)
+        assert REQUIRED <= set(j) and j["steps"] == 2 and j["dry_run"] is True and not set(SIDE_BLOCKS) & set(j), extra
 
 
 def test_two_ranks_dry_run_over_gloo():
@@ -142,9 +151,24 @@ def test_plain_gpus_2_self_started_runs_the_kernels_on_the_one_gpu():
 
 
 @pytest.mark.gpu
+def test_plain_run_does_only_what_its_headline_needs():
+    """Without --full: set-up, warm-up, the timed steps and the line, whose roofline comes from the timed region's own events -- none of the
+    legs that take runs of their own, and at most 30 s of the whole process outside the warm-up and timed steps."""
+    t0 = time.perf_counter()
+    j = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--dispatches-per-step", "2"])
+    outside_s = time.perf_counter() - t0 - (j["steps"] + j["warmup"]) * j["ms_per_step"] * 1e-3
+    assert REQUIRED <= set(j) and j["n_gpus"] == 1 and j["value"] > 1e7 and not set(SIDE_BLOCKS) & set(j)
+    r = j["roofline"]
+    assert r["avg_dispatch_us"] > 0 and 0.0 < r["frac"] < 1.0 and "Cfg1024" in r["kernel"]
+    assert not [k for k in r if k.startswith(("one_batch", "other_column", "extra_", "frac_tail", "frac_one"))] and r["frac_of_measured_copy_roof"] is None
+    assert abs(j["ms_per_step"] * j["steps"] * 1e-3 * j["value"] - 3 * 2 * 64 * 4096) < 1.0
+    assert outside_s < 30.0, outside_s
+
+
+@pytest.mark.gpu
 def test_c4_shard_line_on_one_gpu():
-    j = _run([sys.executable, "bench.py", "--config", "c4", "--steps", "2", "--warmup", "1", "--dispatches-per-step", "2", "--no-cpu-baseline", "--no-calibration",
-              "--no-boundary"])
+    j = _run([sys.executable, "bench.py", "--config", "c4", "--steps", "2", "--warmup", "1", "--dispatches-per-step", "2", "--full", "--no-cpu-baseline",
+              "--no-calibration", "--no-boundary"])
     k = j["config"]["batches_per_dispatch"]
     assert j["unit"] == "frames/s" and j["value"] > 1e7 and k >= 8 and j["config"]["column_layout"].startswith("reference")
     assert j["roofline"]["algorithmic_bytes_per_dispatch"] == k * 8 * 4096 * 4100 and 0.05 < j["roofline"]["frac"] < 1.0
@@ -157,7 +181,8 @@ def test_c4_shard_line_on_one_gpu():
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg,unit", [("c3", "frames/s"), ("c5", "columns/s")])
 def test_other_configs_emit_a_line(cfg, unit):
-    j = _run([sys.executable, "bench.py", "--config", cfg, "--steps", "2", "--warmup", "1", "--dispatches-per-step", "2", "--no-cpu-baseline", "--no-calibration"])
+    j = _run([sys.executable, "bench.py", "--config", cfg, "--steps", "2", "--warmup", "1", "--dispatches-per-step", "2", "--full", "--no-cpu-baseline",
+              "--no-calibration"])
     k = j["config"]["batches_per_dispatch"]
     assert j["unit"] == unit and j["value"] > 0 and k >= 8
     assert j["parity"]["max_rel_power_err_bins_within_20dB_of_peak"] < 1e-5
@@ -216,11 +241,11 @@ def test_single_mode_one_dispatch_per_batch_still_runs():
 
 @pytest.mark.gpu
 def test_default_config_line_carries_roofline_calibration_boundary_and_the_other_configs():
-    """The driver's line (configs[1]) with few dispatches per step: the objects the contract asks for are there and consistent --
+    """The driver's line (configs[1]) under --full, with few dispatches per step: the objects of a full line are there and consistent --
     roofline measured live on the timed region (fraction, per-dispatch duration, the whole-region figure beside it, traffic with its
     staleness flag, the one-batch-per-dispatch figure), the measured copy roof, parity of the kernel that is timed, the boundary block
     (producer latency under a reading consumer, PCIe-inclusive rate), and the c3 / c5 results from their child processes."""
-    j = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--dispatches-per-step", "2", "--no-cpu-baseline"], timeout=1200)
+    j = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--dispatches-per-step", "2", "--full", "--no-cpu-baseline"], timeout=1200)
     assert REQUIRED <= set(j) and j["n_gpus"] == 1 and j["value"] > 1e7 and j["scaling"] == "weak" and j["dtype"] == "f32"
     r = j["roofline"]
     assert r["bound"] == "hbm" and r["peak"] == 8000.0 and 0.0 < r["frac"] < 1.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9

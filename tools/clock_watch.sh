@@ -4,7 +4,7 @@
 # rocm-smi only reads sysfs here (no settings are changed; an ordinary user cannot change them anyway).
 out=${1:-gpurun_out/clock}
 mkdir -p "$out"
-B="--no-extra --no-boundary --no-calibration --no-parity --no-cpu-baseline --no-single"
+B="--full --no-extra --no-boundary --no-calibration --no-parity --no-cpu-baseline --no-single"
 rocm-smi --showclocks --showpower > "$out/idle.txt" 2>&1
 for cfg in c2 c3 c5; do
   python bench.py --config $cfg --steps 400 --warmup 20 $B > "$out/bench_$cfg.json" 2> "$out/bench_$cfg.err" &

@@ -9,7 +9,7 @@ import json, subprocess, sys, os
 tag, cfg, nbs = sys.argv[1], sys.argv[2], [int(v) for v in sys.argv[3:]]
 rows = []
 for nb in nbs:
-    out = subprocess.run([sys.executable, "bench.py", "--config", cfg, "--nbuf", str(nb), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-boundary",
+    out = subprocess.run([sys.executable, "bench.py", "--config", cfg, "--nbuf", str(nb), "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-boundary",
                           "--no-extra", "--no-calibration", "--no-parity", "--dispatches-per-step", str(max(1, 1024 // nb))],
                          capture_output=True, text=True).stdout.strip().splitlines()[-1]
     l = json.loads(out)
