@@ -45,7 +45,8 @@ extern "C" {
                                6: + lossless producer call, all-or-nothing sharded push, exact-log display path, tail plane, pair plan (round 5);
                                   additions to 6: filterbank spectrograms (jsg_filterbank_*, jsg_stft_fb_*; section 2b),
                                   display frequency axes (jsg_freq_axis_*, jsg_colormap_axis_launch, jsg_display_set_freq_axis,
-                                  jsg_display_height, jsg_display_axis_centres; section 2c) */
+                                  jsg_display_height, jsg_display_axis_centres; section 2c),
+                                  complex STFT and inverse STFT with any hop (jsg_cstft_*, jsg_istft_*; section 2d) */
 
 typedef enum jsg_status {
     JSG_OK = 0,
@@ -433,6 +434,67 @@ JSG_API int jsg_freq_axis_height(const jsg_freq_axis* ax);
  * index_out, any n_colors).  Enqueue only (hipGraph capture works).  Refused: everything jsg_colormap_launch refuses, an axis of
  * another device or of another FFT size. */
 JSG_API int jsg_colormap_axis_launch(const jsg_colormap_args* args, const jsg_freq_axis* ax, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2d. Complex STFT and inverse STFT with any hop (no reference counterpart: the reference keeps only power).
+ *
+ *     Forward: frame j of row r reads n samples at in[r*in_pitch + j*hop + m], m < n, any hop in 1..n, and writes the n/2+1 bins
+ *         X[r][j][k] = sum_{m<n} w[m] x[r][j*hop+m] exp(-2 pi i k m / n)        (numpy.fft.rfft(w * frame); no scaling)
+ *     as interleaved float pairs (re, im) at out[2 * (r*out_row_pitch + j*out_frame_pitch + k)] (pitches in complex elements).
+ *     Inverse (torch.istft's definition, frames at j*hop, no centring):
+ *         y[r][t] = (sum_j w[t - j*hop] irfft(X[r][j])[t - j*hop]) / (sum_j w[t - j*hop]^2),   t < (n_frames-1)*hop + n,
+ *     irfft dividing by n and ignoring the imaginary parts of bins 0 and n/2.  Each sample sums its frames in ascending j (no atomics,
+ *     bit for bit the same whatever the chunking); the envelope is summed in double from w^2 (computed on the host, uploaded with the
+ *     plan) and its reciprocal rounded to float32 once; y = 0 where the envelope is <= 1e-11 (only at the edges of a call that passes
+ *     the NOLA check).
+ * ------------------------------------------------------------------------------------------------ */
+/* A plan: window, twiddle tables (double on the host, rounded to float once) and w^2, resident on the device that is current at
+ * creation.  n: a power of two in 512..8192 (else JSG_ERR_UNSUPPORTED); a non-finite window is refused (JSG_ERR_INVALID). */
+typedef struct jsg_cstft jsg_cstft;
+JSG_API int jsg_cstft_create(jsg_cstft** out, int n, const float* window);
+JSG_API int jsg_cstft_destroy(jsg_cstft* plan);
+JSG_API int jsg_cstft_fft_size(const jsg_cstft* plan);
+
+typedef struct jsg_cstft_args {
+    const float* in;            /* device floats, rows of samples */
+    int64_t in_pitch;           /* floats between rows (>= 0) */
+    int32_t rows;               /* 1..65535, independent (no channel mix); all in one launch */
+    int32_t hop;                /* 1..n */
+    int64_t n_frames;           /* frames per row (0: nothing is enqueued) */
+    int64_t in_samples;         /* floats of every row that may be read: a launch whose last frame would read past them is refused
+                                   (and rows > 1 need in_pitch >= in_samples).  0: not checked */
+    float* out;                 /* device complex bins, 8-byte aligned */
+    int64_t out_frame_pitch;    /* complex elements between frames (>= n/2+1) */
+    int64_t out_row_pitch;      /* complex elements between rows (rows > 1: >= (n_frames-1)*out_frame_pitch + n/2+1) */
+} jsg_cstft_args;
+/* Enqueue only: no allocation, no synchronisation; hipGraph capture works.  Refused (JSG_ERR_INVALID, nothing enqueued, jsg_last_error
+ * set): null pointers, a plan of another device, hop outside 1..n, pitches smaller than above, a read past in_samples. */
+JSG_API int jsg_cstft_launch(const jsg_cstft* plan, const jsg_cstft_args* args, void* stream);
+
+/* NOLA on the host: *min_envelope = the smallest interior envelope, min over rho < hop of sum_{m = rho mod hop} w[m]^2 (double, then
+ * rounded to float).  JSG_ERR_INVALID when it is <= 1e-11 (*min_envelope is still set); jsg_istft_launch refuses such a hop. */
+JSG_API int jsg_istft_nola(int n, int hop, const float* window, float* min_envelope);
+
+typedef struct jsg_istft_args {
+    const float* in;            /* device complex bins (float pairs), 8-byte aligned */
+    int64_t in_frame_pitch;     /* complex elements between frames (>= n/2+1) */
+    int64_t in_row_pitch;       /* complex elements between rows (rows > 1: >= (n_frames-1)*in_frame_pitch + n/2+1) */
+    int32_t rows;               /* 1..65535 */
+    int32_t hop;                /* 1..n, passing jsg_istft_nola */
+    int64_t n_frames;           /* 1..2^31-1 */
+    float* out;                 /* device floats: y[r][t] at out[r*out_pitch + t], t < out_samples */
+    int64_t out_pitch;          /* rows > 1: >= out_samples */
+    int64_t out_samples;        /* 1..(n_frames-1)*hop + n */
+} jsg_istft_args;
+/* `scratch`: device floats, 16-byte aligned, layout private to the library.  The call runs in chunks of as many frames as scratch
+ * holds; a chunk recomputes the floor((n-1)/hop) frames before it that overlap its first sample, so the output is bit-identical for
+ * every accepted scratch size.  Refused (JSG_ERR_INVALID): everything jsg_cstft_launch refuses for its arguments, a hop that fails
+ * NOLA, out_samples outside the range above, scratch smaller than rows * n * min(F, floor((n-1)/hop) + 1) floats (F = the frames
+ * that reach out_samples).  All refusals are decided before anything is enqueued.  Enqueue only; hipGraph capture works. */
+JSG_API int jsg_istft_launch(const jsg_cstft* plan, const jsg_istft_args* args, float* scratch, int64_t scratch_floats, void* stream);
+/* A recommended scratch size (floats): the whole call where it fits 64 MiB, otherwise 64 MiB worth of frames (at least the minimum
+ * above).  < 0: the call would be refused. */
+JSG_API int64_t jsg_istft_scratch_floats(const jsg_cstft* plan, const jsg_istft_args* args);
 
 /* ------------------------------------------------------------------------------------------------
  * 3. Engine: the state of class Spectrogram (Spectrogram.h:81-169) living on the GPU.

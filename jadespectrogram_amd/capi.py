@@ -65,6 +65,16 @@ class ColormapArgs(C.Structure):
                 ("index_out", C.c_void_p), ("index_pitch", C.c_int64)]
 
 
+class CstftArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("in_pitch", C.c_int64), ("rows", C.c_int32), ("hop", C.c_int32), ("n_frames", C.c_int64),
+                ("in_samples", C.c_int64), ("out", C.c_void_p), ("out_frame_pitch", C.c_int64), ("out_row_pitch", C.c_int64)]
+
+
+class IstftArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("in_frame_pitch", C.c_int64), ("in_row_pitch", C.c_int64), ("rows", C.c_int32),
+                ("hop", C.c_int32), ("n_frames", C.c_int64), ("out", C.c_void_p), ("out_pitch", C.c_int64), ("out_samples", C.c_int64)]
+
+
 class StftImageArgs(C.Structure):
     _fields_ = [("stft", StftArgs), ("colour", ColormapArgs), ("index_scratch", C.c_void_p), ("index_scratch_pitch", C.c_int64)]
 
@@ -115,6 +125,13 @@ SIGNATURES = {
     "jsg_freq_axis_destroy": (C.c_int, [_P]),
     "jsg_freq_axis_height": (C.c_int, [_P]),
     "jsg_colormap_axis_launch": (C.c_int, [C.POINTER(ColormapArgs), _P, _P]),
+    "jsg_cstft_create": (C.c_int, [C.POINTER(_P), C.c_int, _P]),
+    "jsg_cstft_destroy": (C.c_int, [_P]),
+    "jsg_cstft_fft_size": (C.c_int, [_P]),
+    "jsg_cstft_launch": (C.c_int, [_P, C.POINTER(CstftArgs), _P]),
+    "jsg_istft_nola": (C.c_int, [C.c_int, C.c_int, _P, C.POINTER(C.c_float)]),
+    "jsg_istft_launch": (C.c_int, [_P, C.POINTER(IstftArgs), _P, C.c_int64, _P]),
+    "jsg_istft_scratch_floats": (C.c_int64, [_P, C.POINTER(IstftArgs)]),
     "jsg_create": (C.c_int, [C.POINTER(_P), C.c_int]),
     "jsg_create_on_device": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int]),
     "jsg_get_device": (C.c_int, [_P]),

@@ -778,3 +778,210 @@ def mel_spectrogram_db(x, fs: float, n_fft: int, hop: int, n_mels: int, fmin: fl
     with torch.cuda.device(dev):
         stft_fb_db(plan, fb, x, hop, frames, out, feedblocks=n_fft // hop, mix_mode=mix_mode, exact_log=exact_log)
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# complex STFT and inverse STFT with any hop (include/jsg.h, section 2d)
+# --------------------------------------------------------------------------------------------------
+class CStftPlan:
+    """jsg_cstft: window, twiddle tables and w^2 for one FFT size, resident on the current device."""
+
+    def __init__(self, n: int, window_table: np.ndarray):
+        import torch
+        w = np.ascontiguousarray(window_table, dtype=np.float32)
+        assert w.size == n
+        self.window = w
+        self._p = C.c_void_p()
+        check(lib().jsg_cstft_create(C.byref(self._p), int(n), w.ctypes.data))
+        self.n = int(n)
+        self.device = torch.cuda.current_device()
+
+    def close(self):
+        if getattr(self, "_p", None) is not None and self._p:
+            lib().jsg_cstft_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _rows3(t, what: str):
+    """[rows][frames][bins] view of a 2- or 3-dimensional tensor (a 2-dimensional one is one row)."""
+    if t.dim() == 2:
+        t = t[None]
+    assert t.dim() == 3, f"{what}: expected [rows][frames][bins]"
+    return t
+
+
+def _cstft_args(plan: CStftPlan, d_in, hop: int, n_frames: int, d_out, in_samples: int | None) -> capi.CstftArgs:
+    import torch
+    x = d_in[None] if d_in.dim() == 1 else d_in
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1, "d_in: float32 CUDA [rows][samples]"
+    o = _rows3(d_out, "d_out")
+    assert o.is_cuda and o.dtype == torch.complex64 and o.stride(2) == 1 and o.shape[0] == x.shape[0], "d_out: complex64 CUDA [rows][frames][bins]"
+    return capi.CstftArgs(x.data_ptr(), x.stride(0), x.shape[0], int(hop), int(n_frames),
+                          x.shape[1] if in_samples is None else int(in_samples), o.data_ptr(), o.stride(1), o.stride(0))
+
+
+def cstft(plan: CStftPlan, d_in, hop: int, n_frames: int, d_out, *, in_samples: int | None = None, stream: int | None = None):
+    """jsg_cstft_launch: d_in float32 [rows][samples] (frame j of a row at j * hop, any hop 1..n) -> d_out complex64 [rows][frames][>= n/2+1],
+    the bins of numpy.fft.rfft(window * frame).  in_samples: the readable length of a row (default d_in.shape[-1]; 0: not checked)."""
+    import torch
+    a = _cstft_args(plan, d_in, hop, n_frames, d_out, in_samples)
+    if stream is None:
+        stream = torch.cuda.current_stream(d_in.device).cuda_stream
+    check(lib().jsg_cstft_launch(plan._p, C.byref(a), C.c_void_p(stream)))
+
+
+def _istft_args(plan: CStftPlan, d_X, hop: int, n_frames: int, d_out, out_samples: int | None) -> capi.IstftArgs:
+    import torch
+    X = _rows3(d_X, "d_X")
+    assert X.is_cuda and X.dtype == torch.complex64 and X.stride(2) == 1, "d_X: complex64 CUDA [rows][frames][>= n/2+1]"
+    y = d_out[None] if d_out.dim() == 1 else d_out
+    assert y.is_cuda and y.dtype == torch.float32 and y.dim() == 2 and y.stride(1) == 1 and y.shape[0] == X.shape[0], "d_out: float32 CUDA [rows][samples]"
+    T = int(y.shape[1]) if out_samples is None else int(out_samples)
+    return capi.IstftArgs(X.data_ptr(), X.stride(1), X.stride(0), X.shape[0], int(hop), int(n_frames), y.data_ptr(), y.stride(0), T)
+
+
+def istft_scratch_floats(plan: CStftPlan, d_X, hop: int, n_frames: int, d_out, out_samples: int | None = None) -> int:
+    """jsg_istft_scratch_floats: the scratch size (floats) the library recommends for this call."""
+    a = _istft_args(plan, d_X, hop, n_frames, d_out, out_samples)
+    return int(check(lib().jsg_istft_scratch_floats(plan._p, C.byref(a))))
+
+
+def istft_launch(plan: CStftPlan, d_X, hop: int, n_frames: int, d_out, out_samples: int | None = None, *, d_scratch=None,
+                 stream: int | None = None):
+    """jsg_istft_launch: d_X complex64 [rows][frames][>= n/2+1] -> d_out float32 [rows][>= out_samples], torch.istft's overlap-add
+    (frames at j * hop, no centring; 0 where the envelope is <= 1e-11).  d_scratch: float32 CUDA tensor (None: one of the recommended
+    size is allocated with torch for this call); any accepted size gives the same bits."""
+    import torch
+    a = _istft_args(plan, d_X, hop, n_frames, d_out, out_samples)
+    temporary = d_scratch is None
+    if temporary:
+        d_scratch = torch.empty(int(check(lib().jsg_istft_scratch_floats(plan._p, C.byref(a)))), dtype=torch.float32, device=d_out.device)
+    assert d_scratch.is_cuda and d_scratch.dtype == torch.float32 and d_scratch.is_contiguous()
+    if stream is None:
+        stream = torch.cuda.current_stream(d_out.device).cuda_stream
+    elif temporary:   # the caching allocator must not hand the block out again before the launch on the caller's stream is done
+        d_scratch.record_stream(torch.cuda.ExternalStream(stream, device=d_out.device))
+    check(lib().jsg_istft_launch(plan._p, C.byref(a), d_scratch.data_ptr(), d_scratch.numel(), C.c_void_p(stream)))
+
+
+def istft_nola(n: int, hop: int, window_table) -> tuple[bool, float]:
+    """jsg_istft_nola: (passes, smallest interior envelope min_rho sum_{m = rho mod hop} w[m]^2)."""
+    w = np.ascontiguousarray(window_table, dtype=np.float32)
+    assert w.size == n
+    v = C.c_float()
+    rc = lib().jsg_istft_nola(int(n), int(hop), w.ctypes.data, C.byref(v))
+    if rc == capi.JSG_ERR_INVALID and np.isfinite(v.value) and 1 <= hop <= n:
+        return False, float(v.value)
+    check(rc)
+    return True, float(v.value)
+
+
+_cstft_cache: dict = {}
+
+
+def _stft_window(window, n_fft: int, win_length: int) -> np.ndarray:
+    """torch.stft's window: None = rectangular, a tensor / array, or a jsg_window id; a shorter one is zero-padded to the centre."""
+    if window is None:
+        w = np.ones(win_length, np.float32)
+    elif isinstance(window, (int, np.integer)):
+        w = _window_table(int(window), win_length)
+    else:
+        w = (window.detach().cpu().numpy() if hasattr(window, "detach") else np.asarray(window)).astype(np.float32).ravel()
+    if w.size != win_length:
+        raise JsgError(capi.JSG_ERR_INVALID, f"window has {w.size} samples, win_length is {win_length}")
+    if win_length > n_fft:
+        raise JsgError(capi.JSG_ERR_INVALID, f"win_length {win_length} > n_fft {n_fft}")
+    out = np.zeros(n_fft, np.float32)
+    left = (n_fft - win_length) // 2
+    out[left:left + win_length] = w
+    return out
+
+
+def _cstft_plan(dev: int, n_fft: int, w: np.ndarray) -> CStftPlan:
+    import torch
+    key = (dev, int(n_fft), w.tobytes())
+    if key not in _cstft_cache:
+        with torch.cuda.device(dev):
+            _cstft_cache[key] = CStftPlan(n_fft, w)
+    return _cstft_cache[key]
+
+
+def stft(x, n_fft: int, hop_length: int | None = None, win_length: int | None = None, window=None, center: bool = True,
+         pad_mode: str = "reflect"):
+    """torch.stft(..., return_complex=True, onesided=True, normalized=False) on the GPU: x float32 CUDA [..., samples] ->
+    complex64 [..., n_fft//2+1, frames] (the transposed view of the library's frame-major buffer).  Any hop in 1..n_fft."""
+    import torch
+    import torch.nn.functional as Fn
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    wl = n_fft if win_length is None else int(win_length)
+    w = _stft_window(window, n_fft, wl)
+    assert x.is_cuda, "stft: x must be a CUDA tensor"
+    batch = tuple(x.shape[:-1])
+    xr = x.reshape(-1, x.shape[-1]).float()
+    if center:
+        xr = Fn.pad(xr[:, None, :], (n_fft // 2, n_fft // 2), mode=pad_mode)[:, 0]
+    xr = xr.contiguous()
+    L = int(xr.shape[1])
+    if L < n_fft:
+        raise JsgError(capi.JSG_ERR_INVALID, f"stft: {L} samples hold no frame of {n_fft}")
+    frames = 1 + (L - n_fft) // hop
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    plan = _cstft_plan(dev, n_fft, w)
+    out = torch.empty((xr.shape[0], frames, n_fft // 2 + 1), dtype=torch.complex64, device=x.device)
+    with torch.cuda.device(dev):
+        cstft(plan, xr, hop, frames, out)
+    return out.reshape(*batch, frames, n_fft // 2 + 1).transpose(-1, -2)
+
+
+def _envelope(w: np.ndarray, hop: int, frames: int) -> np.ndarray:
+    """sum_j w[t - j hop]^2 in float64 for t < (frames-1) hop + n."""
+    n = w.size
+    w2 = w.astype(np.float64) ** 2
+    P = -(-n // hop)
+    pieces = np.zeros((P, hop))
+    pieces.ravel()[:n] = w2
+    E = np.zeros((frames + P, hop))
+    for p in range(P):
+        E[p:p + frames] += pieces[p]
+    return E.ravel()[:(frames - 1) * hop + n]
+
+
+def istft(X, n_fft: int, hop_length: int | None = None, win_length: int | None = None, window=None, center: bool = True,
+          length: int | None = None):
+    """torch.istft on the GPU: X complex CUDA [..., n_fft//2+1, frames] -> float32 [..., samples].  Raises JsgError where torch raises:
+    the window envelope is <= 1e-11 somewhere inside the returned span."""
+    import torch
+    import torch.nn.functional as Fn
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    wl = n_fft if win_length is None else int(win_length)
+    w = _stft_window(window, n_fft, wl)
+    assert X.is_cuda and X.is_complex(), "istft: X must be a complex CUDA tensor"
+    if X.shape[-2] != n_fft // 2 + 1:
+        raise JsgError(capi.JSG_ERR_INVALID, f"istft: {X.shape[-2]} bins, expected n_fft//2+1 = {n_fft // 2 + 1}")
+    batch = tuple(X.shape[:-2])
+    frames = int(X.shape[-1])
+    Xf = X.to(torch.complex64).transpose(-1, -2).reshape(-1, frames, n_fft // 2 + 1)
+    if Xf.stride(2) != 1:
+        Xf = Xf.contiguous()
+    T = (frames - 1) * hop + n_fft
+    start = n_fft // 2 if center else 0
+    end = (T - n_fft // 2 if center else T) if length is None else start + int(length)
+    stop = min(end, T)
+    env = _envelope(w, hop, frames)[start:stop]
+    if env.size and not (np.abs(env) > 1e-11).all():
+        raise JsgError(capi.JSG_ERR_INVALID, f"istft: window overlap-add envelope <= 1e-11 at sample {start + int(np.argmin(np.abs(env)))}")
+    dev = X.device.index if X.device.index is not None else torch.cuda.current_device()
+    plan = _cstft_plan(dev, n_fft, w)
+    y = torch.empty((Xf.shape[0], max(stop, 1)), dtype=torch.float32, device=X.device)
+    with torch.cuda.device(dev):
+        istft_launch(plan, Xf, hop, frames, y, max(stop, 1))
+    y = y[:, start:stop]
+    if end > stop:
+        y = Fn.pad(y, (0, end - stop))
+    return y.contiguous().reshape(*batch, -1)
