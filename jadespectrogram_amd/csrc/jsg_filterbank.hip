@@ -1,6 +1,6 @@
 // libjsg.so, filterbank spectrograms: the band kernel and the launcher of jsg_stft_fb_launch(_strided) (include/jsg.h, section 2b).
 //
-//   launcher     resolves the STFT plan ONCE for the whole call (strided_plan_select, the rule of jsg_stft_db_launch_strided) and pins
+//   launcher     resolves the STFT plan ONCE for the whole call (strided_call_variant, the rule of jsg_stft_db_launch_strided) and pins
 //                every chunk to it; runs the existing STFT kernels with linear_out = 1 into the caller's scratch, a chunk of columns at a
 //                time, and the band kernel after every chunk -- all on one stream, enqueue only.
 //   fb_band_kernel  power columns -> band columns.  A persistent grid of 256-thread workgroups over tiles of T power columns: the tile
@@ -134,22 +134,10 @@ using namespace jsg;
 
 namespace {
 
-// the workgroup step (columns per row) of the kernel a pinned plan_select takes at this size (Cfg*::TPB)
-int plan_step(int n, int pin) {
-    switch (n) {
-        case 512: return Cfg512::TPB;
-        case 1024: return pin == 2 ? Cfg1024B::TPB : Cfg1024::TPB;
-        case 2048: return pin == 3 ? Cfg2048P::TPB : pin == 2 ? Cfg2048B::TPB : Cfg2048::TPB;
-        case 4096: return pin == 2 ? Cfg4096B::TPB : Cfg4096::TPB;
-        default: return Cfg8192::TPB;
-    }
-}
-
 struct FbCall {
-    int pin = 0;            // plan_select of every STFT chunk (0: 512 / 8192 points, one plan)
-    long long rows = 1;     // rows per batch
-    long long pitch = 0;    // floats per power column in scratch
-    long long step = 1;     // minimum chunk: columns per row
+    const VariantRow* stft = nullptr;   // the STFT variant of every chunk: its plan_select pins them, its workgroup step is the minimum chunk
+    long long rows = 1;                 // rows per batch
+    long long pitch = 0;                // floats per power column in scratch
 };
 
 int fb_resolve(const jsg_plan* plan, const jsg_filterbank* fb, const jsg_stft_args* g, int n_batches, FbCall& c, const char* who) {
@@ -163,10 +151,9 @@ int fb_resolve(const jsg_plan* plan, const jsg_filterbank* fb, const jsg_stft_ar
     if (dev != plan_device(plan) || dev != fb->device)
         return jsg_fail(JSG_ERR_INVALID, (w + ": the plan or the filterbank was created on another device").c_str());
     if (g->channels <= 0 || g->n_frames < 0) return jsg_fail(JSG_ERR_INVALID, (w + ": bad geometry").c_str());
-    c.pin = strided_plan_select(plan, g, n_batches, cu_count_of_device(dev));
+    c.stft = &strided_call_variant(plan, g, n_batches, cu_count_of_device(dev));
     c.rows = g->mix_mode == JSG_MIX_PER_CHANNEL ? g->channels : 1;
     c.pitch = fb_pw_pitch(n);
-    c.step = plan_step(n, c.pin);
     return JSG_OK;
 }
 
@@ -193,36 +180,21 @@ int jsg_stft_fb_launch_strided(const jsg_plan* plan, const jsg_filterbank* fb, c
     }
     if ((reinterpret_cast<uintptr_t>(scratch) & 15) != 0) return jsg_fail(JSG_ERR_INVALID, "jsg_stft_fb_launch: scratch must be 16-byte aligned");
     // columns per row the scratch holds (at most 2^28 columns per chunk: the band kernel counts them in 32 bits)
+    const long long step = c.stft->step;
     const long long cap = scratch_floats > 0 ? std::min(scratch_floats / (c.rows * c.pitch), (1ll << 28) / c.rows) : 0;
-    if (cap < c.step) return jsg_fail(JSG_ERR_INVALID, "jsg_stft_fb_launch: scratch holds less than one workgroup step of columns");
+    if (cap < step) return jsg_fail(JSG_ERR_INVALID, "jsg_stft_fb_launch: scratch holds less than one workgroup step of columns");
     if (g->n_frames == 0) return JSG_OK;
-    // Every refusal the STFT launcher (stft_launch_impl, strided_checks) could raise for one of the chunks, decided here for the WHOLE call
-    // before the first chunk is enqueued: a refused call enqueues nothing (all or nothing, whatever the chunking)
-    if (g->channels > 65535) return jsg_fail(JSG_ERR_UNSUPPORTED, "jsg_stft_fb_launch: more than 65535 channels");
-    if (g->hop <= 0 || g->feedblocks <= 0) return jsg_fail(JSG_ERR_INVALID, "jsg_stft_fb_launch: bad geometry (hop, feedblocks)");
-    switch (g->mix_mode) {
-        case JSG_MIX_ABSMEAN: case JSG_MIX_MAX: case JSG_MIX_MIN: case JSG_MIX_LEFT: case JSG_MIX_PER_CHANNEL: case JSG_MIX_SUM: break;
-        case JSG_MIX_RIGHT:
-            if (g->channels < 2) return jsg_fail(JSG_ERR_INVALID, "jsg_stft_fb_launch: JSG_MIX_RIGHT needs at least two channels");
-            break;
-        default: return jsg_fail(JSG_ERR_INVALID, "jsg_stft_fb_launch: unknown mix mode");
-    }
-    if (g->n_frames >= (1ll << 31) || g->first_frame + g->n_frames >= (1ll << 31))
-        return jsg_fail(JSG_ERR_UNSUPPORTED, "jsg_stft_fb_launch: frame index does not fit 31 bits");
-    if (g->in_samples != 0) {   // the caller told us how long the channel rows are (every batch: in + b * in_batch_stride)
-        const long long j = g->first_frame + g->n_frames - 1;
-        const long long start = ((long long)g->hop * g->feedblocks == n) ? j * g->hop : (j / g->feedblocks) * n + (j % g->feedblocks) * g->hop;
-        if (g->in_samples < 0 || start + n > g->in_samples)
-            return jsg_fail(JSG_ERR_INVALID, "jsg_stft_fb_launch: the last frame would read past the end of the input rows");
-        if (g->channels > 1 && g->in_pitch < g->in_samples) return jsg_fail(JSG_ERR_INVALID, "jsg_stft_fb_launch: in_pitch < in_samples");
-    }
+    // Every refusal the STFT launcher could raise for one of the chunks (the per-launch ones: check_stft_args; every batch reads in +
+    // b * in_batch_stride), decided here for the WHOLE call before the first chunk is enqueued: a refused call enqueues nothing
+    rc = check_stft_args(n, g, who);
+    if (rc != JSG_OK) return rc;
     int dev = -1;
     (void)hipGetDevice(&dev);
     const int n_cu = cu_count_of_device(dev);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
 
     jsg_stft_args st = *g;                   // the STFT chunks: linear power into scratch, pinned to the plan of the whole call
-    if (c.pin) st.plan_select = c.pin;
+    if (c.stft->plan_select) st.plan_select = c.stft->plan_select;
     st.linear_out = 1;
     st.exact_log = 0;
     st.out_db = scratch;
@@ -267,7 +239,7 @@ int jsg_stft_fb_launch_strided(const jsg_plan* plan, const jsg_filterbank* fb, c
         }
         return JSG_OK;
     }
-    const long long m = cap / c.step * c.step;   // chunks of whole workgroup steps of one batch
+    const long long m = cap / step * step;   // chunks of whole workgroup steps of one batch
     for (long long b = 0; b < n_batches; ++b)
         for (long long f0 = 0; f0 < g->n_frames; f0 += m) {
             rc = chunk(b, 1, f0, std::min(m, g->n_frames - f0));
@@ -287,8 +259,9 @@ int64_t jsg_stft_fb_scratch_floats(const jsg_plan* plan, const jsg_filterbank* f
     const long long per_col = c.rows * c.pitch;
     const long long budget = (64ll << 20) / 4;
     const long long whole = std::max<long long>(1, g->n_frames) * n_batches * per_col;
-    if (whole <= budget) return std::max(whole, c.step * per_col);
-    return std::max(1ll, budget / (c.step * per_col)) * c.step * per_col;
+    const long long step = c.stft->step;
+    if (whole <= budget) return std::max(whole, step * per_col);
+    return std::max(1ll, budget / (step * per_col)) * step * per_col;
 }
 
 int jsg_stft_fb_kernel_name(const jsg_plan* plan, const jsg_filterbank* fb, const jsg_stft_args* g, int n_batches, char* out, int out_len) {
@@ -296,7 +269,7 @@ int jsg_stft_fb_kernel_name(const jsg_plan* plan, const jsg_filterbank* fb, cons
     FbCall c;
     const int rc = fb_resolve(plan, fb, g, n_batches, c, "jsg_stft_fb_kernel_name");
     if (rc != JSG_OK) return rc;
-    std::snprintf(out, size_t(out_len), "Cfg%d%s", jsg_plan_fft_size(plan), c.pin == 3 ? "P" : c.pin == 2 ? "B" : "");
+    std::snprintf(out, size_t(out_len), "%s", c.stft->name);
     return JSG_OK;
 }
 

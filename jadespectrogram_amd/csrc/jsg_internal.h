@@ -18,6 +18,8 @@ int jsg_fail_hip(hipError_t err, const char* where);
 // jsg_kernels.hip: compute units of a device (read once per device), the device a plan was created on
 int cu_count_of_device(int dev);
 int plan_device(const jsg_plan* plan);
+// jsg_kernels.hip: the refusals of jsg_stft_args that the STFT launcher and the filterbank launcher share (message prefix `who`)
+int check_stft_args(int n, const jsg_stft_args* g, const char* who);
 // jsg_display_axis.hip: load the code object of the axis kernel (jsg_freq_axis_create, on the thread that configures)
 void touch_axis_module();
 
@@ -28,10 +30,6 @@ inline double slaney_hz_to_mel(double f) { return f < 1000.0 ? f / (200.0 / 3.0)
 inline double slaney_mel_to_hz(double m) { return m < 15.0 ? (200.0 / 3.0) * m : 1000.0 * std::exp(slaney_logstep() * (m - 15.0)); }
 
 }  // namespace jsg
-
-// jsg_kernels.hip: the plan_select that pins every launch of a strided call (n_batches >= 1) to the plan of the whole call;
-// jsg_filterbank.hip pins its STFT chunks with it (defined inside the C-ABI block of jsg_kernels.hip; hidden like every internal symbol)
-extern "C" int strided_plan_select(const jsg_plan* plan, const jsg_stft_args* g, int n_batches, int n_cu);
 
 // A filterbank on the device (jsg_filterbank_host.cpp creates it, jsg_filterbank.hip applies it): the CSR of jsg_filterbank_build,
 // band descriptors as three int arrays of n_bands entries (first bin, bin count, weight offset) followed by the weights, one allocation

@@ -6,8 +6,8 @@
 //                    Replaces Spectrogram.cpp:50-119 + :137-145 + spectrum::power (call site :144) of the reference.
 //   colormap_kernel  (here) dB ring columns -> ARGB image rows (transpose through LDS so both sides are coalesced),
 //                    CColorPalette::getRGBColor inlined.  Replaces Spectrogram.cpp:632-648 / :673-680 / :693-700.
-//   launcher         stft_launch_impl: which kernel a launch takes (wants_plan_b: launch fill, channel count, CU count of the device),
-//                    grid and loop counts; jsg_stft_db_launch_batches: the library's launch pool (caller's stream + three).
+//   launcher         resolve_variant: which kernel variant a launch takes (the table kVariants; launch fill, channel count, CU count of the
+//                    device); stft_launch_impl: grid and loop counts; jsg_stft_db_launch_batches: the library's launch pool (caller's stream + three).
 //
 // The index algebra, the twiddle tables and the LDS layouts are modelled and checked in tools/fft_model.py.
 #include "jsg_stft_kernel.h"
@@ -26,6 +26,11 @@ static constexpr int dev_knob_int(const char*) { return 0; }
 static constexpr bool dev_knob_set(const char*) { return false; }
 static constexpr bool dev_knob_is(const char*, char) { return false; }
 #endif
+
+static bool chunked_traversal() {   // JSG_TRAVERSAL=c: one contiguous chunk of steps per workgroup instead of the grid-stride traversal
+    static const bool chunked = dev_knob_is("JSG_TRAVERSAL", 'c');
+    return chunked;
+}
 
 static bool b_plan_fills_its_rounds(long long n_frames, int frames_per_workgroup, int n_cu) {
     const long long want = (n_frames + frames_per_workgroup - 1) / frames_per_workgroup;
@@ -177,13 +182,21 @@ __global__ __launch_bounds__(256) void calib_copy_kernel(const float* __restrict
 
 using namespace jsg;
 
+// ---- the variants: one row each, from JSG_STFT_VARIANTS (jsg_stft_kernel.h) ----
+namespace {
+#define JSG_VARIANT_ROW(V, C, U, name, step, tables, pin, one_per_cu) \
+    {C::N, name, step, int(Tables::tables), pin, one_per_cu, &launch_##V, &ensure_attrs_##V, &fill_tables<C>},
+const VariantRow kVariants[] = {JSG_STFT_VARIANTS(JSG_VARIANT_ROW)};
+#undef JSG_VARIANT_ROW
+const VariantRow& row_of(Variant v) { return kVariants[int(v)]; }
+}  // namespace
+
 struct jsg_plan {
     int n = 0;
     int device = -1;
-    float2* d_tab = nullptr;
+    float2* d_tab = nullptr;              // the lane-table sets of the plan's variants, one allocation
     size_t tab_elems = 0;
-    float2* d_tab_b = nullptr;   // 1024 / 2048 / 4096 points: lane tables of the second plan (Cfg1024B / Cfg2048B / Cfg4096B), behind d_tab in the same allocation
-    float2* d_tab_p = nullptr;   // 2048 points: lane tables of the pair plan (Cfg2048P), behind those
+    size_t set_at[kTableSets] = {0, 0, 0};   // where each set starts in d_tab (Tables)
 };
 
 extern "C" {
@@ -201,49 +214,25 @@ int jsg_plan_create(jsg_plan** out, int n, const float* window, float power_scal
     if (!out || !window) return jsg_fail(JSG_ERR_INVALID, "jsg_plan_create: null argument");
     *out = nullptr;
     if (!(power_scale > 0.f)) return jsg_fail(JSG_ERR_INVALID, "jsg_plan_create: power_scale must be > 0");
-    std::vector<float2> t;
-    size_t tab_b_at = 0, tab_p_at = 0;
+    // the lane-table sets of the variants of this size (the launcher picks per launch), first, "B", pair, each further set 256-byte
+    // aligned: filled by the first row of the size that reads the set
+    std::vector<float2> t, one;
+    size_t set_at[kTableSets] = {0, 0, 0};
     const double amp = std::sqrt(double(power_scale));   // |FFT(a w x)|^2 = a^2 |FFT(w x)|^2
-    switch (n) {
-        case 512: fill_tables<Cfg512>(t, window, amp); break;
-        case 1024: {   // the three-stage plan and, behind it, the two-stage one (Cfg1024B)
-            fill_tables<Cfg1024>(t, window, amp);
-            std::vector<float2> tb;
-            fill_tables<Cfg1024B>(tb, window, amp);
-            t.resize((t.size() + 31) / 32 * 32, make_float2(0.f, 0.f));
-            tab_b_at = t.size();
-            t.insert(t.end(), tb.begin(), tb.end());
-            break;
-        }
-        case 2048: {   // both 2048-point plans (the launcher picks per launch); the second table set starts 256-byte aligned
-            fill_tables<Cfg2048>(t, window, amp);
-            std::vector<float2> tb;
-            fill_tables<Cfg2048B>(tb, window, amp);
-            t.resize((t.size() + 31) / 32 * 32, make_float2(0.f, 0.f));
-            tab_b_at = t.size();
-            t.insert(t.end(), tb.begin(), tb.end());
-            fill_tables<Cfg2048P>(tb, window, amp);   // ... and the pair plan's
-            t.resize((t.size() + 31) / 32 * 32, make_float2(0.f, 0.f));
-            tab_p_at = t.size();
-            t.insert(t.end(), tb.begin(), tb.end());
-            break;
-        }
-        case 4096: {   // likewise the two 4096-point plans
-            fill_tables<Cfg4096>(t, window, amp);
-            std::vector<float2> tb;
-            fill_tables<Cfg4096B>(tb, window, amp);
-            t.resize((t.size() + 31) / 32 * 32, make_float2(0.f, 0.f));
-            tab_b_at = t.size();
-            t.insert(t.end(), tb.begin(), tb.end());
-            break;
-        }
-        case 8192: fill_tables<Cfg8192>(t, window, amp); break;
-        default:
-            return jsg_fail(JSG_ERR_UNSUPPORTED, "jsg_plan_create: FFT size must be 512, 1024, 2048, 4096 or 8192");
-    }
+    for (int set = 0; set < kTableSets; ++set)
+        for (const VariantRow& r : kVariants)
+            if (r.n == n && r.tables == set) {
+                r.fill(one, window, amp);
+                t.resize((t.size() + 31) / 32 * 32, make_float2(0.f, 0.f));
+                set_at[set] = t.size();
+                t.insert(t.end(), one.begin(), one.end());
+                break;
+            }
+    if (t.empty()) return jsg_fail(JSG_ERR_UNSUPPORTED, "jsg_plan_create: FFT size must be 512, 1024, 2048, 4096 or 8192");
     jsg_plan* p = new (std::nothrow) jsg_plan();
     if (!p) return jsg_fail(JSG_ERR_NOMEM, "jsg_plan_create: out of host memory");
     p->n = n;
+    std::copy(set_at, set_at + kTableSets, p->set_at);
     p->tab_elems = t.size();
     if (hipGetDevice(&p->device) != hipSuccess) {
         delete p;
@@ -258,13 +247,8 @@ int jsg_plan_create(jsg_plan** out, int n, const float* window, float power_scal
         (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&colormap_kernel));
     }
     hipError_t err = hipSuccess;
-    switch (n) {
-        case 512: err = ensure_attrs_Cfg512(); break;
-        case 1024: err = ensure_attrs_Cfg1024(); if (err == hipSuccess) err = ensure_attrs_Cfg1024I(); if (err == hipSuccess) err = ensure_attrs_Cfg1024B(); break;
-        case 2048: err = ensure_attrs_Cfg2048(); if (err == hipSuccess) err = ensure_attrs_Cfg2048B(); if (err == hipSuccess) err = ensure_attrs_Cfg2048P(); break;
-        case 4096: err = ensure_attrs_Cfg4096(); if (err == hipSuccess) err = ensure_attrs_Cfg4096B(); break;
-        case 8192: err = ensure_attrs_Cfg8192(); break;
-    }
+    for (const VariantRow& r : kVariants)
+        if (r.n == n && err == hipSuccess) err = r.ensure_attrs();
     if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&p->d_tab), t.size() * sizeof(float2));
     if (err == hipSuccess) err = hipMemcpy(p->d_tab, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice);
     if (err != hipSuccess) {
@@ -272,8 +256,6 @@ int jsg_plan_create(jsg_plan** out, int n, const float* window, float power_scal
         delete p;
         return jsg_fail_hip(err, "jsg_plan_create");
     }
-    if (tab_b_at) p->d_tab_b = p->d_tab + tab_b_at;
-    if (tab_p_at) p->d_tab_p = p->d_tab + tab_p_at;
     pool_prepare_for_device(p->device);
     *out = p;
     return JSG_OK;
@@ -309,42 +291,102 @@ struct IndexOut {   // fused display path: where and how the palette indices of 
 };
 }  // namespace
 
-// 2048 points: does this launch take the pair plan (Cfg2048P: a channel PAIR as one complex transform)?  Sum-type mixes (AbsMean, Sum)
-// over an EVEN number of channels, float columns (not the display launches), and -- like the "B" kernels, it runs one 8-wave workgroup
-// per CU, here of eight columns -- launches that fill their rounds.  plan_select = 3 pins it where it applies (else: as 0).
-constexpr bool kPairPlanByDefault = false;  // opt-in only (plan_select = 3): measured 20 % BEHIND Cfg2048B on the C3 dispatch (537 vs 446 us)
-static bool wants_plan_pair(int n, const jsg_stft_args* g, int n_cu, bool display, long long frames_of_launch = -1) {
-    if (n != 2048 || display) return false;
-    if (g->mix_mode != JSG_MIX_ABSMEAN && g->mix_mode != JSG_MIX_SUM) return false;
-    if (g->channels < 2 || (g->channels & 1)) return false;
-    if (g->plan_select == 3) return true;
-    if (g->plan_select != 0 || !kPairPlanByDefault) return false;
-    static const int forced2048 = dev_knob_int("JSG_2048_PLAN");   // variant builds only: 4 = pair plan, 2 / 3 = not
-    if (forced2048) return forced2048 == 4;
-    return b_plan_fills_its_rounds(frames_of_launch >= 0 ? frames_of_launch : g->n_frames, Cfg2048P::TPB, n_cu);
+// 1024 points (round 6): the two-stage plan Cfg1024B is taken automatically from four channels per column on.  What the interleaved A/B
+// decided (tools/plan1024b_ab.py): one channel per column (C2, the C4 shard) it is 3-7 % BEHIND the three-stage plan (two
+// waves per SIMD instead of five; its core clock under the 1400 W cap is 2.0-2.1 instead of 1.6 GHz and it is still slower), two channels
+// mixed +1.5 %, four +3.3 %, eight +4.1..+4.8 %.
+constexpr int k1024B_min_channels = 4;
+
+namespace {
+// What the kernel of a launch -- or of every launch of a strided call -- has to produce, as far as the choice of the variant goes
+struct CallShape {
+    enum Out { kFloat, kIndex, kArgb } out = kFloat;   // dB / power columns, palette indices (fused display path), ARGB images (one kernel)
+    long long rows = 1;         // kFloat: the frames of this many rows are judged together (batches, times channels in per-channel mode)
+    int n_images = 1;           // kArgb: images of the launch
+    bool multi_batch = false;   // kFloat: ONE launch over several batches (the strided instantiations; the runs form serves some)
+};
+}  // namespace
+
+// THE choice of the kernel: the variant that a launch of this shape takes on a device of n_cu CUs.  The launcher, both kernel-name queries,
+// the strided calls (the plan they pin), the display path and the filterbank all ask here.
+//  - 2048 points, plan_select = 3: the pair plan (Cfg2048P: a channel PAIR as one complex transform) for float columns of the sum-type mixes
+//    (AbsMean, Sum) over an EVEN number of channels; where it does not apply, 3 acts as 0.  Opt-in only: measured 20 % BEHIND Cfg2048B on
+//    the C3 dispatch (537 vs 446 us).
+//  - 1024 / 2048 / 4096 points: the "B" plan (two-stage / one wavefront per frame, one 8-wave workgroup per CU) where plan_select = 2 pins it,
+//    else automatically where enough channels are mixed into one column (k*B_min_channels) and the launch fills its rounds (kB_min_round_fill);
+//    plan_select = 1 pins the other plan.  At 1024 points only for float columns of the sum-type and one-channel mixes: the display launches
+//    keep the three-stage arithmetic, and any plan_select but 0 and 2 pins the three-stage plan.  The choice depends on the launch geometry
+//    only; sub-launches of one stream that fall on different sides of the rule agree within the float32 bound, not bit for bit (jsg.h).
+//    The frames judged: those of all rows of the shape (a strided call: except Max / Min, which go out one launch per batch); of an ARGB
+//    launch, the whole groups of all its images.
+//  - "runs" (round 6): one launch over several batches of one-channel columns of the 1024-point three-stage plan at exactly 50 % overlap --
+//    a wavefront transforms kRunLen consecutive columns and keeps the overlapped half of the raw frame in registers (see stft_db_kernel).
+static Variant resolve_variant(const jsg_plan* plan, const jsg_stft_args* g, const CallShape& sh, int n_cu) {
+    const int n = plan->n, mm = g->mix_mode, sel = g->plan_select;
+    const bool maxmin = mm == JSG_MIX_MAX || mm == JSG_MIX_MIN;
+    const int nc = (mm == JSG_MIX_LEFT || mm == JSG_MIX_RIGHT || mm == JSG_MIX_PER_CHANNEL) ? 1 : g->channels;   // channels per column
+    if (n == 512) return Variant::k512;
+    if (n == 8192) return Variant::k8192;
+    if (n == 1024 && sh.out == CallShape::kArgb) return Variant::k1024I;   // (the display path's eight-column workgroups)
+    if (n == 2048 && sel == 3 && sh.out == CallShape::kFloat && (mm == JSG_MIX_ABSMEAN || mm == JSG_MIX_SUM) && g->channels >= 2 &&
+        (g->channels & 1) == 0)
+        return Variant::k2048P;
+    const Variant b_plan = n == 1024 ? Variant::k1024B : n == 2048 ? Variant::k2048B : Variant::k4096B;
+    const int step = row_of(b_plan).step;
+    const long long frames = sh.out == CallShape::kArgb ? (g->n_frames + step - 1) / step * step * sh.n_images : sh.rows * g->n_frames;
+    bool b;
+    if (n == 1024) {
+        b = sh.out == CallShape::kFloat && !maxmin &&
+            (sel == 2 || (sel == 0 && nc >= k1024B_min_channels && b_plan_fills_its_rounds(frames, step, n_cu)));
+    } else {
+        static const int forced2048 = dev_knob_int("JSG_2048_PLAN");   // variant builds only (JSG_DEV_KNOBS): 2 = "B" | 3
+        static const int forced4096 = dev_knob_int("JSG_4096_PLAN");
+        const int forced = sel == 1 ? 3 : sel == 2 ? 2 : n == 2048 ? forced2048 : forced4096;
+        b = forced == 2 || (forced != 3 && nc >= (n == 2048 ? k2048B_min_channels : k4096B_min_channels) &&
+                            b_plan_fills_its_rounds(frames, step, n_cu));
+    }
+    if (b) return b_plan;
+    if (n == 2048) return Variant::k2048;
+    if (n == 4096) return Variant::k4096;
+    static const bool no_runs = dev_knob_set("JSG_NO_RUNS");   // (variant builds only)
+    const bool runs = sh.multi_batch && nc == 1 && !maxmin && (long long)g->hop * g->feedblocks == n && 2 * g->hop == n &&
+                      !chunked_traversal() && !no_runs;
+    return runs ? Variant::k1024Runs : Variant::k1024;
 }
 
-// 1024 points (round 6): the two-stage plan Cfg1024B -- float columns, sum-type and one-channel mixes.  plan_select = 2 pins it where it
-// applies, 1 pins the three-stage plan.  Automatic rule = what the interleaved A/B decided (tools/plan1024b_ab.py):
-// one channel per column (C2, the C4 shard) it is 3-7 % BEHIND the three-stage plan (two waves per SIMD instead of five; its core clock under
-// the 1400 W cap is 2.0-2.1 instead of 1.6 GHz and it is still slower), two channels mixed +1.5 %, four +3.3 %, eight +4.1..+4.8 %: taken
-// from four channels per column on, for launches that fill their rounds of one workgroup per CU.
-constexpr int k1024B_min_channels = 4;
-// 1024 / 2048 / 4096 points: does this launch take the "B" kernel?  (nc: channels combined into one column)
-static bool wants_plan_b(int n, const jsg_stft_args* g, int nc, int n_cu, long long frames_of_launch = -1) {   // (-1: g->n_frames)
-    if (n == 1024) {
-        if (g->mix_mode == JSG_MIX_MAX || g->mix_mode == JSG_MIX_MIN) return false;
-        if (g->plan_select == 2) return true;
-        if (g->plan_select != 0 || nc < k1024B_min_channels) return false;
-        return b_plan_fills_its_rounds(frames_of_launch >= 0 ? frames_of_launch : g->n_frames, Cfg1024B::TPB, n_cu);
+// The variant every launch of a strided call (n_batches >= 1) is pinned to, decided ONCE for the whole call: jsg_stft_db_launch_strided
+// pins every launch it issues to its plan_select (the several launches of a job longer than 2^20 workgroup steps and a trailing single batch
+// included), jsg_stft_db_strided_kernel_name reports it and the filterbank pins and sizes its chunks with it, so none of them can disagree.
+// Judged by the frames of ALL rows of the call -- except Max / Min, which go out as one launch per batch (no strided instantiation): there
+// the frames of one batch decide, so every launch keeps the faster kernel for its real size.
+const VariantRow& jsg::strided_call_variant(const jsg_plan* plan, const jsg_stft_args* g, int n_batches, int n_cu) {
+    const bool one_by_one = g->mix_mode == JSG_MIX_MAX || g->mix_mode == JSG_MIX_MIN;
+    CallShape sh;
+    sh.rows = (one_by_one ? 1ll : (long long)n_batches) * (g->mix_mode == JSG_MIX_PER_CHANNEL ? g->channels : 1);
+    return row_of(resolve_variant(plan, g, sh, n_cu));
+}
+
+// The refusals of jsg_stft_args that every STFT launch makes (stft_launch_impl) and that the filterbank launcher makes for its whole call
+// before the first chunk, so that a refused call enqueues nothing.  `who` prefixes the message.
+int jsg::check_stft_args(int n, const jsg_stft_args* g, const char* who) {
+    auto fail = [who](int code, const char* what) { return jsg_fail(code, (std::string(who) + ": " + what).c_str()); };
+    if (g->hop <= 0 || g->feedblocks <= 0) return fail(JSG_ERR_INVALID, "bad geometry (hop, feedblocks)");
+    if (g->channels > 65535) return fail(JSG_ERR_UNSUPPORTED, "more than 65535 channels");
+    if (g->in_samples != 0) {   // the caller told us how long the channel rows are: refuse to read past them
+        const long long j = g->first_frame + g->n_frames - 1;
+        const long long start = ((long long)g->hop * g->feedblocks == n) ? j * g->hop : (j / g->feedblocks) * n + (j % g->feedblocks) * g->hop;
+        if (g->in_samples < 0 || start + n > g->in_samples) return fail(JSG_ERR_INVALID, "the last frame would read past the end of the input rows");
+        if (g->channels > 1 && g->in_pitch < g->in_samples) return fail(JSG_ERR_INVALID, "in_pitch < in_samples");
     }
-    if (n != 2048 && n != 4096) return false;
-    static const int forced2048 = dev_knob_int("JSG_2048_PLAN");   // variant builds only (JSG_DEV_KNOBS): 2 = "B" | 3
-    static const int forced4096 = dev_knob_int("JSG_4096_PLAN");
-    const int forced = g->plan_select == 1 ? 3 : g->plan_select == 2 ? 2 : (n == 2048 ? (forced2048 == 4 ? 0 : forced2048) : forced4096);
-    const int tpb_b = n == 2048 ? Cfg2048B::TPB : Cfg4096B::TPB;
-    return forced == 2 || (forced != 3 && nc >= (n == 2048 ? k2048B_min_channels : k4096B_min_channels) &&
-                           b_plan_fills_its_rounds(frames_of_launch >= 0 ? frames_of_launch : g->n_frames, tpb_b, n_cu));
+    if (g->n_frames >= (1ll << 31) || g->first_frame + g->n_frames >= (1ll << 31)) return fail(JSG_ERR_UNSUPPORTED, "frame index does not fit 31 bits");
+    switch (g->mix_mode) {
+        case JSG_MIX_ABSMEAN: case JSG_MIX_MAX: case JSG_MIX_MIN: case JSG_MIX_LEFT: case JSG_MIX_PER_CHANNEL: case JSG_MIX_SUM: return JSG_OK;
+        case JSG_MIX_RIGHT:
+            // reference Spectrogram.cpp:97-105 reads m_power[1] whenever m_channels > 0; with one channel that is out of bounds there, so it
+            // is rejected here
+            return g->channels < 2 ? fail(JSG_ERR_INVALID, "JSG_MIX_RIGHT needs at least two channels") : JSG_OK;
+        default: return fail(JSG_ERR_INVALID, "unknown mix mode");
+    }
 }
 
 namespace {
@@ -358,9 +400,8 @@ static int stft_launch_impl(const jsg_plan* plan, const jsg_stft_args* g, const 
     if (!plan || !g) return jsg_fail(JSG_ERR_INVALID, "jsg_stft_db_launch: null argument");
     if (g->n_frames == 0) return JSG_OK;
     const int H = plan->n / 2 + 1;
-    if (!g->in || (!io && !g->out_db) || g->channels <= 0 || g->hop <= 0 || g->feedblocks <= 0 || g->n_frames < 0 ||
-        g->first_frame < 0 || g->ring_width <= 0 || g->ring_pos < 0 || g->ring_pos >= g->ring_width ||
-        (!io && g->out_pitch < H - (g->out_tail ? 1 : 0)))   // (with a tail plane a column is n/2 floats)
+    if (!g->in || (!io && !g->out_db) || g->channels <= 0 || g->n_frames < 0 || g->first_frame < 0 || g->ring_width <= 0 ||
+        g->ring_pos < 0 || g->ring_pos >= g->ring_width || (!io && g->out_pitch < H - (g->out_tail ? 1 : 0)))   // (with a tail plane a column is n/2 floats)
         return jsg_fail(JSG_ERR_INVALID, "jsg_stft_db_launch: bad geometry");
     if (io && g->out_tail) return jsg_fail(JSG_ERR_INVALID, "jsg_stft_image_launch: out_tail belongs to the dB launches");
     if (io && !io->argb && (!io->idx || io->pitch < H || io->n_colors <= 0 || io->n_colors > 256 || g->linear_out))
@@ -374,16 +415,8 @@ static int stft_launch_impl(const jsg_plan* plan, const jsg_stft_args* g, const 
     if (hipGetDevice(&dev) != hipSuccess || dev != plan->device)
         return jsg_fail(JSG_ERR_INVALID, "jsg_stft_db_launch: the plan was created on another device");
     const int n_cu = cu_count_of_device(dev);
-    if (g->channels > 65535) return jsg_fail(JSG_ERR_UNSUPPORTED, "jsg_stft_db_launch: more than 65535 channels");
-    if (g->in_samples != 0) {   // the caller told us how long the channel rows are: refuse to read past them
-        const long long j = g->first_frame + g->n_frames - 1;
-        const long long start = ((long long)g->hop * g->feedblocks == plan->n)
-                                    ? j * g->hop : (j / g->feedblocks) * plan->n + (j % g->feedblocks) * g->hop;
-        if (g->in_samples < 0 || start + plan->n > g->in_samples || (g->channels > 1 && g->in_pitch < g->in_samples))
-            return jsg_fail(JSG_ERR_INVALID, "jsg_stft_db_launch: the last frame would read past the end of the input rows");
-    }
-    if (g->n_frames >= (1ll << 31) || g->first_frame + g->n_frames >= (1ll << 31))
-        return jsg_fail(JSG_ERR_UNSUPPORTED, "jsg_stft_db_launch: frame index does not fit 31 bits");
+    const int rc = check_stft_args(plan->n, g, "jsg_stft_db_launch");
+    if (rc != JSG_OK) return rc;
     StftKArgs ka{};
     ka.in = g->in;
     ka.in_pitch = g->in_pitch;
@@ -399,7 +432,6 @@ static int stft_launch_impl(const jsg_plan* plan, const jsg_stft_args* g, const 
     ka.ring_pos = g->ring_pos;
     ka.tail = io ? nullptr : g->out_tail;
     ka.exact_log = g->exact_log ? 1 : 0;
-    ka.tab = plan->d_tab;
     if (io) {
         ka.argb = io->argb;
         ka.argb_pitch = io->argb_pitch;
@@ -419,8 +451,7 @@ static int stft_launch_impl(const jsg_plan* plan, const jsg_stft_args* g, const 
     }
     static const int xcd_remap = dev_knob_set("JSG_NO_XCD_REMAP") ? 0 : 1;   // (variant builds only, as every dev_knob_*)
     ka.xcd_remap = xcd_remap;
-    static const int chunked = dev_knob_is("JSG_TRAVERSAL", 'c') ? 1 : 0;
-    ka.chunked = chunked;
+    ka.chunked = chunked_traversal() ? 1 : 0;
     ka.per_channel = 0;
     ka.c_begin = 0;
     ka.c_end = g->channels;
@@ -428,7 +459,7 @@ static int stft_launch_impl(const jsg_plan* plan, const jsg_stft_args* g, const 
     ka.divisor = 1.0f;
     ka.exact_div = 0;
     int mixop = 0;
-    switch (g->mix_mode) {
+    switch (g->mix_mode) {   // (check_stft_args has refused the unknown modes and a one-channel Right)
         case JSG_MIX_ABSMEAN:
             // m_powerfinal[kk] /= m_channels (Spectrogram.cpp:74).  For a power-of-two channel count the division
             // is an exact scaling and is done as one multiply; otherwise the kernel performs the IEEE division.
@@ -439,49 +470,24 @@ static int stft_launch_impl(const jsg_plan* plan, const jsg_stft_args* g, const 
         case JSG_MIX_MAX: mixop = 1; break;
         case JSG_MIX_MIN: mixop = 2; break;
         case JSG_MIX_LEFT: ka.c_end = 1; break;
-        case JSG_MIX_RIGHT:
-            // reference Spectrogram.cpp:97-105 reads m_power[1] whenever m_channels > 0; with one channel that is
-            // out of bounds there, so it is rejected here
-            if (g->channels < 2) return jsg_fail(JSG_ERR_INVALID, "JSG_MIX_RIGHT needs at least two channels");
-            ka.c_begin = 1;
-            ka.c_end = 2;
-            break;
+        case JSG_MIX_RIGHT: ka.c_begin = 1; ka.c_end = 2; break;
         case JSG_MIX_PER_CHANNEL: ka.per_channel = 1; break;
-        case JSG_MIX_SUM: break;
-        default: return jsg_fail(JSG_ERR_INVALID, "jsg_stft_db_launch: unknown mix mode");
+        default: break;   // JSG_MIX_SUM
     }
     ka.linear = g->linear_out ? 1 : 0;
     // one channel per column and nothing to scale: the specialised instantiation (see stft_db_kernel)
     if (mixop == 0 && (ka.per_channel || ka.c_end - ka.c_begin == 1) && ka.scale == 1.0f && !ka.exact_div) mixop = 3;
     if (io && (ka.per_channel || (mixop != 0 && mixop != 3)))
         return jsg_fail(JSG_ERR_UNSUPPORTED, "jsg_stft_image_launch: AbsMean / Sum / Left / Right mixes only");
-    // 2048 / 4096 points: the "B" plan (two-stage / one wavefront per frame) where several channels are mixed into one column and the
-    // launch fills its rounds, else the other one (see Cfg2048B, Cfg4096B, kB_min_round_fill).  The choice depends on the launch
-    // geometry (channels per column, frames, CU count) only; sub-launches of one stream that fall on different sides of the rule
-    // agree within the float32 bound, not bit for bit (jsg.h: plan_select pins one plan).
-    // (the single-kernel display path exists for the one-wavefront-per-frame plans: at 4096 points that is "B")
     const long long rows = bs ? (long long)bs->n * (ka.per_channel ? g->channels : 1) : 1;
-    // (a strided launch is judged by the frames of ALL its rows: the "B" kernels then fill their rounds.  jsg_stft_db_launch_strided pins
-    // plan_select to the plan of the whole call, strided_plan_select, before it gets here)
-    const bool plan_p = wants_plan_pair(plan->n, g, n_cu, io != nullptr, bs ? rows * g->n_frames : -1) && mixop == 0 && !ka.per_channel &&
-                        ((ka.c_end - ka.c_begin) & 1) == 0;
-    const bool plan_b = !plan_p && !(plan->n == 1024 && io) &&   // (1024 points: the display launches keep the three-stage plans)
-                        ((io && io->argb && plan->n == 4096) ||
-                         wants_plan_b(plan->n, g, ka.per_channel ? 1 : ka.c_end - ka.c_begin, n_cu, bs ? rows * g->n_frames : -1));
-    if (plan_b) ka.tab = plan->d_tab_b;
-    if (plan_p) ka.tab = plan->d_tab_p;
-    // "runs" (STREAM == 2, round 6): strided one-channel dB launches of the 1024-point three-stage plan at exactly 50 % overlap -- a wavefront
-    // transforms kRunLen consecutive columns and keeps the overlapped half of the raw frame in registers (see stft_db_kernel)
-    static const bool no_runs = dev_knob_set("JSG_NO_RUNS");   // (variant builds only)
-    const bool runs = bs && plan->n == 1024 && !plan_b && !io && mixop == 3 && ka.regular && 2 * g->hop == plan->n && !ka.chunked && !no_runs;
-    int tpb = 0;
-    switch (plan->n) {
-        case 512: tpb = Cfg512::TPB; break;
-        case 1024: tpb = (io && io->argb) ? Cfg1024I::TPB : plan_b ? Cfg1024B::TPB : runs ? Cfg1024::TPB * jsg::kRunLen : Cfg1024::TPB; break;   // (the display path's eight-column workgroups)
-        case 2048: tpb = plan_p ? Cfg2048P::TPB : plan_b ? Cfg2048B::TPB : Cfg2048::TPB; break;
-        case 4096: tpb = plan_b ? Cfg4096B::TPB : Cfg4096::TPB; break;
-        case 8192: tpb = Cfg8192::TPB; break;
-    }
+    CallShape sh;
+    sh.out = !io ? CallShape::kFloat : io->argb ? CallShape::kArgb : CallShape::kIndex;
+    sh.rows = rows;
+    sh.n_images = io ? io->n_images : 1;
+    sh.multi_batch = bs != nullptr;
+    const VariantRow& v = row_of(resolve_variant(plan, g, sh, n_cu));
+    ka.tab = plan->d_tab + plan->set_at[v.tables];
+    const int tpb = v.step;
     long long want = (g->n_frames + tpb - 1) / tpb;   // workgroup iterations ("groups" of tpb frames) of the launch
     if (io && io->argb) {   // single-kernel display path: the groups are numbered through the images of the launch
         const long long gpi = want;
@@ -505,8 +511,7 @@ static int stft_launch_impl(const jsg_plan* plan, const jsg_stft_args* g, const 
         ka.in_image_stride = bs->in_stride;
         ka.out_batch_stride = bs->out_stride;
     }
-    const int ny = (ka.per_channel && !bs) ? g->channels : 1;
-    if (ny > 65535) return jsg_fail(JSG_ERR_UNSUPPORTED, "jsg_stft_db_launch: more than 65535 channels in per-channel mode");
+    const int ny = (ka.per_channel && !bs) ? g->channels : 1;   // (<= 65535: check_stft_args)
     static const int blocks_per_cu_env = std::max(0, dev_knob_int("JSG_STFT_BLOCKS_PER_CU"));
     // workgroups per CU of the grid; the rest of the frames is looped over.  The "B" plans hold one workgroup per CU: a grid of
     // exactly that many keeps the tables and the prefetch pipeline alive across a workgroup's frames (16 384 mono 4096-point
@@ -525,7 +530,7 @@ static int stft_launch_impl(const jsg_plan* plan, const jsg_stft_args* g, const 
         else if (plan->n == 1024) bpc_default = ncol == 1 ? 32 : 16;
         else if (plan->n == 2048) bpc_default = 16;
     }
-    const int bpc = g->blocks_per_cu > 0 ? g->blocks_per_cu : (blocks_per_cu_env > 0 ? blocks_per_cu_env : ((plan_b || plan_p) ? 1 : bpc_default));
+    const int bpc = g->blocks_per_cu > 0 ? g->blocks_per_cu : (blocks_per_cu_env > 0 ? blocks_per_cu_env : (v.one_per_cu ? 1 : bpc_default));
     long long max_blocks = (long long)n_cu * bpc / ny;     // resident workgroups; the rest is looped over
     if (max_blocks < 64) max_blocks = 64;
     static const int max_blocks_env = dev_knob_int("JSG_STFT_MAX_BLOCKS");
@@ -535,28 +540,8 @@ static int stft_launch_impl(const jsg_plan* plan, const jsg_stft_args* g, const 
     // 0.54 against 0.58 of 8 TB/s at 8 per CU)
     ka.iters = int((want + max_blocks - 1) / max_blocks);
     const int nblk = int((want + ka.iters - 1) / ka.iters);
-    const dim3 grid(nblk, ny);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipError_t err = hipSuccess;
-    if (bs) {
-        switch (plan->n) {
-            case 512: err = launch_strided_Cfg512(ka, mixop, grid, s); break;
-            case 1024: err = plan_b ? launch_strided_Cfg1024B(ka, mixop, grid, s) : runs ? launch_runs_Cfg1024(ka, mixop, grid, s) : launch_strided_Cfg1024(ka, mixop, grid, s); break;
-            case 2048: err = plan_p ? launch_strided_Cfg2048P(ka, mixop, grid, s) : plan_b ? launch_strided_Cfg2048B(ka, mixop, grid, s) : launch_strided_Cfg2048(ka, mixop, grid, s); break;
-            case 4096: err = plan_b ? launch_strided_Cfg4096B(ka, mixop, grid, s) : launch_strided_Cfg4096(ka, mixop, grid, s); break;
-            case 8192: err = launch_strided_Cfg8192(ka, mixop, grid, s); break;
-        }
-        if (err != hipSuccess) return jsg_fail_hip(err, "jsg_stft_db_launch_strided");
-        return JSG_OK;
-    }
-    switch (plan->n) {
-        case 512: err = launch_Cfg512(ka, mixop, grid, s); break;
-        case 1024: err = (io && io->argb) ? launch_Cfg1024I(ka, mixop, grid, s) : plan_b ? launch_Cfg1024B(ka, mixop, grid, s) : launch_Cfg1024(ka, mixop, grid, s); break;
-        case 2048: err = plan_p ? launch_Cfg2048P(ka, mixop, grid, s) : plan_b ? launch_Cfg2048B(ka, mixop, grid, s) : launch_Cfg2048(ka, mixop, grid, s); break;
-        case 4096: err = plan_b ? launch_Cfg4096B(ka, mixop, grid, s) : launch_Cfg4096(ka, mixop, grid, s); break;
-        case 8192: err = launch_Cfg8192(ka, mixop, grid, s); break;
-    }
-    if (err != hipSuccess) return jsg_fail_hip(err, "jsg_stft_db_launch");
+    const hipError_t err = v.launch(ka, mixop, bs != nullptr, dim3(nblk, ny), reinterpret_cast<hipStream_t>(stream));
+    if (err != hipSuccess) return jsg_fail_hip(err, bs ? "jsg_stft_db_launch_strided" : "jsg_stft_db_launch");
     return JSG_OK;
 }
 
@@ -565,16 +550,12 @@ extern "C" {
 int jsg_stft_db_launch(const jsg_plan* plan, const jsg_stft_args* g, void* stream) { return stft_launch_impl(plan, g, nullptr, stream); }
 
 // Which kernel configuration jsg_stft_db_launch runs for these arguments on the current device (benchmarks and tests name the
-// kernel they time / check with it; the rule itself: wants_plan_b).
+// kernel they time / check with it; the rule itself: resolve_variant).
 int jsg_stft_kernel_name(const jsg_plan* plan, const jsg_stft_args* g, char* out, int out_len) {
     if (!plan || !g || !out || out_len < 24) return jsg_fail(JSG_ERR_INVALID, "jsg_stft_kernel_name: bad argument");
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) return jsg_fail(JSG_ERR_NO_DEVICE, "jsg_stft_kernel_name: no device");
-    int nc = g->channels;
-    if (g->mix_mode == JSG_MIX_LEFT || g->mix_mode == JSG_MIX_RIGHT || g->mix_mode == JSG_MIX_PER_CHANNEL) nc = 1;
-    const bool pp = wants_plan_pair(plan->n, g, cu_count_of_device(dev), false);
-    const bool b = !pp && wants_plan_b(plan->n, g, nc, cu_count_of_device(dev));
-    std::snprintf(out, size_t(out_len), "Cfg%d%s", plan->n, pp ? "P" : b ? "B" : "");
+    std::snprintf(out, size_t(out_len), "%s", row_of(resolve_variant(plan, g, CallShape{}, cu_count_of_device(dev))).name);
     return JSG_OK;
 }
 
@@ -585,11 +566,10 @@ static int colormap_launch_impl(const jsg_colormap_args* g, const unsigned char*
 // into `index_scratch` -- the dB column never goes to memory -- and the colour kernel turns those columns into ARGB
 // image rows through its LDS transpose tiles.  Per column of C5: 4096 B in + 2049 B + 2049 B + 8196 B instead of
 // 4096 + 8196 + 8196 + 8196 B.  The image is bit-identical to jsg_stft_db_launch + jsg_colormap_launch: with the same plan_select at
-// 2048 / 4096 points; at 1024 points the display launches always take the three-stage arithmetic (stft_launch_impl: no Cfg1024B for
+// 2048 / 4096 points; at 1024 points the display launches always take the three-stage arithmetic (resolve_variant: no Cfg1024B for
 // them), whatever plan_select says, so the image is that of jsg_stft_db_launch with plan_select = 1.
-// Does jsg_stft_image_launch run as ONE kernel for these arguments?  Where the plan's workgroups hold eight whole columns: 1024
-// points, and 4096 points when the launcher's choice for the launch is the one-wavefront-per-frame kernel ("B": automatic rule or
-// plan_select = 2).
+// Does jsg_stft_image_launch run as ONE kernel for these arguments?  Where the variant of the launch has workgroups of eight whole
+// columns: Cfg1024I at 1024 points, Cfg4096B at 4096 points where the rule picks it for the launch (automatically or by plan_select = 2).
 static bool image_takes_one_kernel(const jsg_plan* plan, const jsg_stft_image_args* g, int n_images = 1) {
     static const int two_kernels = dev_knob_set("JSG_IMAGE_TWO_KERNELS") ? 1 : 0;
     const jsg_colormap_args& c = g->colour;
@@ -599,14 +579,17 @@ static bool image_takes_one_kernel(const jsg_plan* plan, const jsg_stft_image_ar
         return false;
     const int mm = g->stft.mix_mode;
     if (mm == JSG_MIX_PER_CHANNEL || mm == JSG_MIX_MAX || mm == JSG_MIX_MIN) return false;
+    int n_cu = 0;   // (1024 points: every launch, no fill rule to judge -- and no device query on the launch path)
     if (plan->n == 4096) {
         int dev = -1;
         if (hipGetDevice(&dev) != hipSuccess) return false;
-        const int nc = (mm == JSG_MIX_LEFT || mm == JSG_MIX_RIGHT) ? 1 : g->stft.channels;
-        const long long gpi = (g->stft.n_frames + Cfg4096B::TPB - 1) / Cfg4096B::TPB;
-        return wants_plan_b(4096, &g->stft, nc, cu_count_of_device(dev), gpi * Cfg4096B::TPB * n_images);   // (the fill of the whole launch)
+        n_cu = cu_count_of_device(dev);
     }
-    return true;
+    CallShape sh;
+    sh.out = CallShape::kArgb;
+    sh.n_images = n_images;
+    const Variant v = resolve_variant(plan, &g->stft, sh, n_cu);
+    return v == Variant::k1024I || v == Variant::k4096B;
 }
 
 int jsg_stft_image_needs_scratch(const jsg_plan* plan, const jsg_stft_image_args* g) {
@@ -714,21 +697,6 @@ static int strided_checks(const jsg_plan* plan, const jsg_stft_args* g, int n_ba
     return JSG_OK;
 }
 
-// The plan of a strided call (n_batches >= 1), decided ONCE for the whole call: jsg_stft_db_launch_strided pins every launch it issues to it
-// (the several launches of a job longer than 2^20 workgroup steps and a trailing single batch included) and jsg_stft_db_strided_kernel_name
-// reports it, so the two cannot disagree.  Returns the plan_select that pins it: 1 the small-workgroup plan, 2 "B", 3 the pair plan; 0 at
-// 512 / 8192 points (one plan).  Judged by the frames of ALL rows of the call -- except Max / Min, which go out as one launch per batch
-// (no strided instantiation): there the frames of one batch decide, so every launch keeps the faster kernel for its real size.
-int strided_plan_select(const jsg_plan* plan, const jsg_stft_args* g, int n_batches, int n_cu) {
-    if (plan->n != 1024 && plan->n != 2048 && plan->n != 4096) return 0;
-    const bool one_by_one = g->mix_mode == JSG_MIX_MAX || g->mix_mode == JSG_MIX_MIN;
-    const long long rows = (one_by_one ? 1ll : (long long)n_batches) * (g->mix_mode == JSG_MIX_PER_CHANNEL ? g->channels : 1);
-    int nc = g->channels;
-    if (g->mix_mode == JSG_MIX_LEFT || g->mix_mode == JSG_MIX_RIGHT || g->mix_mode == JSG_MIX_PER_CHANNEL) nc = 1;
-    if (wants_plan_pair(plan->n, g, n_cu, false, rows * g->n_frames)) return 3;
-    return wants_plan_b(plan->n, g, nc, n_cu, rows * g->n_frames) ? 2 : 1;
-}
-
 int jsg_stft_db_launch_strided(const jsg_plan* plan, const jsg_stft_args* g, int n_batches, int64_t in_batch_stride, int64_t out_batch_stride,
                                void* stream) {
     int rc = strided_checks(plan, g, n_batches, in_batch_stride, out_batch_stride, "jsg_stft_db_launch_strided");
@@ -739,11 +707,13 @@ int jsg_stft_db_launch_strided(const jsg_plan* plan, const jsg_stft_args* g, int
     if (hipGetDevice(&dev) != hipSuccess) return jsg_fail(JSG_ERR_NO_DEVICE, "jsg_stft_db_launch_strided: no device");
     const bool one_by_one = g->mix_mode == JSG_MIX_MAX || g->mix_mode == JSG_MIX_MIN;   // (no strided instantiation: rare modes)
     if (g->n_frames < 0 || g->channels <= 0) return jsg_fail(JSG_ERR_INVALID, "jsg_stft_db_launch_strided: bad geometry");
-    const int pin = strided_plan_select(plan, g, n_batches, cu_count_of_device(dev));
+    const int pin = strided_call_variant(plan, g, n_batches, cu_count_of_device(dev)).plan_select;
     const long long rows_per_batch = g->mix_mode == JSG_MIX_PER_CHANNEL ? g->channels : 1;
     // at most 2^20 workgroup steps per launch (the kernel's group -> row arithmetic): longer jobs go out in several launches
-    // (counted with the smallest workgroup step of the plan's kernels: 16 / 8 / 4 / 2 / 1 columns at 512 ... 8192 points)
-    const int tpb_min = plan->n == 512 ? Cfg512::TPB : plan->n == 1024 ? Cfg1024::TPB : plan->n == 2048 ? Cfg2048::TPB : plan->n == 4096 ? Cfg4096::TPB : Cfg8192::TPB;
+    // (counted with the smallest workgroup step among the variants of the plan's size: 16 / 4 / 4 / 2 / 1 columns at 512 ... 8192 points)
+    int tpb_min = 1 << 30;
+    for (const VariantRow& r : kVariants)
+        if (r.n == plan->n) tpb_min = std::min(tpb_min, r.step);
     const long long steps_per_batch = rows_per_batch * ((g->n_frames + tpb_min - 1) / tpb_min);
     const long long per_launch = one_by_one ? 1 : std::max(1ll, (1ll << 20) / std::max(1ll, steps_per_batch));
     for (long long b0 = 0; b0 < n_batches; b0 += per_launch) {
@@ -763,15 +733,14 @@ int jsg_stft_db_launch_strided(const jsg_plan* plan, const jsg_stft_args* g, int
     return JSG_OK;
 }
 
-// The kernel every launch of a strided call takes, as text (strided_plan_select: the frames of the whole call; Max / Min: of one batch).
+// The kernel every launch of a strided call takes, as text (strided_call_variant: the frames of the whole call; Max / Min: of one batch).
 int jsg_stft_db_strided_kernel_name(const jsg_plan* plan, const jsg_stft_args* g, int n_batches, int64_t in_batch_stride, char* out, int out_len) {
     if (!plan || !g || !out || out_len < 24 || n_batches < 1) return jsg_fail(JSG_ERR_INVALID, "jsg_stft_db_strided_kernel_name: bad argument");
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) return jsg_fail(JSG_ERR_NO_DEVICE, "jsg_stft_db_strided_kernel_name: no device");
     if (n_batches == 1) return jsg_stft_kernel_name(plan, g, out, out_len);
     (void)in_batch_stride;
-    const int pin = strided_plan_select(plan, g, n_batches, cu_count_of_device(dev));
-    std::snprintf(out, size_t(out_len), "Cfg%d%s", plan->n, pin == 3 ? "P" : pin == 2 ? "B" : "");
+    std::snprintf(out, size_t(out_len), "%s", strided_call_variant(plan, g, n_batches, cu_count_of_device(dev)).name);
     return JSG_OK;
 }
 
@@ -893,11 +862,9 @@ int jsg_stft_db_launch_batches(const jsg_plan* plan, const jsg_stft_args* args, 
         const int rc = pool_ensure(p);
         if (rc != JSG_OK) return rc;
     }
-    // launches of the one-workgroup-per-CU kernels (2048 / 4096 "B") fill the GPU by themselves: two streams are enough to hide
+    // launches of the one-workgroup-per-CU kernels ("B", the pair plan) fill the GPU by themselves: two streams are enough to hide
     // the ramp-up and drain (measured at C3, round 2), four make them queue behind each other
-    int nc0 = args[0].channels;
-    if (args[0].mix_mode == JSG_MIX_LEFT || args[0].mix_mode == JSG_MIX_RIGHT || args[0].mix_mode == JSG_MIX_PER_CHANNEL) nc0 = 1;
-    const int want_s = wants_plan_b(plan->n, &args[0], nc0, cu_count_of_device(dev)) ? 2 : kPoolStreams;
+    const int want_s = row_of(resolve_variant(plan, &args[0], CallShape{}, cu_count_of_device(dev))).one_per_cu ? 2 : kPoolStreams;
     const int n_s = count < want_s ? count : want_s;     // working streams: sv[0] = the caller's, sv[1..] = the library's
     // fork: the library's streams start behind everything already enqueued on the caller's stream
     err = hipEventRecord(p.fork, user);

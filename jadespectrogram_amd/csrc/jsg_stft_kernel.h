@@ -506,7 +506,7 @@ using Cfg1024I = Cfg<1024, 8, 8, 8, 64, 72, 9, 72, 2, 8, 1, 6>;
 // frames instead of two of 8 + 8 per frame, the lane tables read once per four frames, 2 x 80 + 212 packed instructions of butterflies per four
 // frames... (tools/kernel_regs.py and the PMC figures in DESIGN.md section 6).  A 4 x 4 transposition across the quarter-waves
 // (v_permlane32_swap + v_permlane16_swap) turns the registers into runs of 64 consecutive bins of ONE frame before the column stores.
-// dB / power columns only (sum-type and one-channel mixes); opt-in or automatic: see wants_plan_1024b in jsg_kernels.hip.
+// dB / power columns only (sum-type and one-channel mixes); opt-in or automatic: see resolve_variant in jsg_kernels.hip.
 using Cfg1024B = Cfg<1024, 16, 32, 1, 16, 34, 0, 0, 0, 8, 1, 1>;
 // factorised stage-2 / post tables (Cfg::TWF): 11.3 instead of 21.2 KB of tables, so that THREE 4-wave workgroups fit a CU (12 waves
 // instead of 8): stereo launches -9..-13 %, mono -1..-5 %
@@ -519,7 +519,7 @@ using Cfg2048 = Cfg<2048, 16, 8, 8, 64, 72, 65, 16, 2, 4, 1, 3, 1, 1, 1>;   // (
 // once per CU and loops over its frames.  For launches that fill the GPU in whole rounds of 256 workgroups it is ahead of the
 // three-stage plan, the more channels are mixed into a column the more (8 ch -10..-13 %, 4 ch -3..-8 %, 1-2 ch level);
 // for anything smaller the 4-frame workgroups of the three-stage plan use more CUs (tools/abbench --cfg x2048 / mid).
-// The launcher picks by channel count and by how well the launch fills its rounds (stft_launch_impl).
+// The launcher picks by channel count and by how well the launch fills its rounds (resolve_variant).
 using Cfg2048B = Cfg<2048, 32, 32, 1, 32, 34, 0, 0, 0, 8, 1, 1>;
 // The pair plan (round 5): the same two radix-32 stages and the same single exchange per 1024-point sub-transform, but a
 // wavefront transforms the channel pair (c, c + 1) of ONE column as z = x_c + i x_(c+1): half-wave 0 the even samples, half-wave 1 the odd
@@ -1928,49 +1928,37 @@ constexpr bool image_only = std::is_same<C, Cfg1024I>::value;
 template <class C>
 constexpr bool db_only = C::L == 16;
 
-// every instantiation of a plan that can be launched: (MIXOP, OUTK, STREAM) x the two logarithms
-template <class C, int XLOG>
-hipError_t ensure_lds_attrs_of_plan_x() {
-    if constexpr (db_only<C>) {
-        hipError_t e = ensure_lds_attr<C, 0, 0, 0, XLOG>();
-        if (e == hipSuccess) e = ensure_lds_attr<C, 3, 0, 0, XLOG>();
-        if (e == hipSuccess) e = ensure_lds_attr<C, 0, 0, 1, XLOG>();
-        if (e == hipSuccess) e = ensure_lds_attr<C, 3, 0, 1, XLOG>();
-        return e;
-    } else
-    if constexpr (C::PAIR) {   // the pair plan exists for the sum-type mixes and float columns only
-        hipError_t e = ensure_lds_attr<C, 0, 0, 0, XLOG>();
-        if (e == hipSuccess) e = ensure_lds_attr<C, 0, 0, 1, XLOG>();
-        return e;
-    } else
-    if constexpr (image_only<C>) {
-        hipError_t e = ensure_lds_attr<C, 0, 2, 0, XLOG>();
-        if (e == hipSuccess) e = ensure_lds_attr<C, 3, 2, 0, XLOG>();
-        return e;
-    } else {
-    hipError_t e = ensure_lds_attr<C, 0, 0, 0, XLOG>();
-    if (e == hipSuccess) e = ensure_lds_attr<C, 1, 0, 0, XLOG>();
-    if (e == hipSuccess) e = ensure_lds_attr<C, 2, 0, 0, XLOG>();
-    if (e == hipSuccess) e = ensure_lds_attr<C, 3, 0, 0, XLOG>();
-    if (e == hipSuccess) e = ensure_lds_attr<C, 0, 1, 0, XLOG>();
-    if (e == hipSuccess) e = ensure_lds_attr<C, 3, 1, 0, XLOG>();
-    if (e == hipSuccess) e = ensure_lds_attr<C, 0, 0, 1, XLOG>();
-    if (e == hipSuccess) e = ensure_lds_attr<C, 3, 0, 1, XLOG>();
-    if constexpr (image_ok<C>) {
-        if (e == hipSuccess) e = ensure_lds_attr<C, 0, 2, 0, XLOG>();
-        if (e == hipSuccess) e = ensure_lds_attr<C, 3, 2, 0, XLOG>();
-    }
-    return e;
-    }
-}
-template <class C>
-hipError_t ensure_lds_attrs_of_plan() {
-    hipError_t e = ensure_lds_attrs_of_plan_x<C, 0>();
-    if (e == hipSuccess) e = ensure_lds_attrs_of_plan_x<C, 1>();
-    return e;
+// THE instantiation rule: which stft_db_kernel<C, MIXOP, OUTK, STREAM, *> exist (both logarithms of each).  The LDS attribute set-up and the
+// launch dispatch below both follow it, so the set of kernels is written down here only.  MIXOP 0 sum-type, 1 Max, 2 Min, 3 one channel per
+// column; OUTK 0 float columns, 1 palette indices (fused display path), 2 ARGB rows (single-kernel display path); STREAM 0 one batch,
+// 1 strided multi-batch launches, 2 "runs" (consecutive columns per wavefront, the overlapped half of a frame kept in registers).
+template <class C, int MIXOP, int OUTK, int STREAM>
+constexpr bool stft_instantiated() {
+    constexpr bool sum_or_one = MIXOP == 0 || MIXOP == 3;   // the mixed (AbsMean / Sum) and the one-channel kernels
+    if (image_only<C>) return OUTK == 2 && STREAM == 0 && sum_or_one;
+    if (C::PAIR) return OUTK == 0 && STREAM <= 1 && MIXOP == 0;   // the pair plan: sum-type mixes and float columns only
+    if (db_only<C>) return OUTK == 0 && STREAM <= 1 && sum_or_one;
+    if (STREAM == 2) return std::is_same<C, Cfg1024>::value && OUTK == 0 && MIXOP == 3;   // runs: one-channel columns of the 1024-point plan
+    if (STREAM == 1) return OUTK == 0 && sum_or_one;
+    if (OUTK == 2) return image_ok<C> && sum_or_one;
+    return OUTK == 0 || sum_or_one;
 }
 
-template <class C, int MIXOP, int OUTK = 0, int STREAM = 0>
+// the LDS attributes of every instantiation of plan C (K runs through MIXOP x OUTK x STREAM x XLOG)
+template <class C, int K = 0>
+hipError_t ensure_lds_attrs() {
+    if constexpr (K == 4 * 3 * 3 * 2) return hipSuccess;
+    else {
+        constexpr int MIXOP = K % 4, OUTK = K / 4 % 3, STREAM = K / 12 % 3, XLOG = K / 36;
+        if constexpr (stft_instantiated<C, MIXOP, OUTK, STREAM>()) {
+            const hipError_t e = ensure_lds_attr<C, MIXOP, OUTK, STREAM, XLOG>();
+            if (e != hipSuccess) return e;
+        }
+        return ensure_lds_attrs<C, K + 1>();
+    }
+}
+
+template <class C, int MIXOP, int OUTK, int STREAM>
 hipError_t launch_stft_mix(const StftKArgs& ka, dim3 grid, hipStream_t s) {
     const bool xlog = ka.exact_log && !ka.linear;   // (linear power has no logarithm: one instantiation serves both)
     hipError_t err = xlog ? ensure_lds_attr<C, MIXOP, OUTK, STREAM, 1>() : ensure_lds_attr<C, MIXOP, OUTK, STREAM, 0>();
@@ -1986,78 +1974,80 @@ hipError_t launch_stft_mix(const StftKArgs& ka, dim3 grid, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <class C>
-hipError_t launch_stft(const StftKArgs& ka, int mixop, dim3 grid, hipStream_t s) {
-    if constexpr (db_only<C>) {
-        if (ka.argb || ka.idx || (mixop != 0 && mixop != 3)) return hipErrorInvalidValue;
-        return mixop == 3 ? launch_stft_mix<C, 3>(ka, grid, s) : launch_stft_mix<C, 0>(ka, grid, s);
-    } else
-    if constexpr (C::PAIR) {
-        if (ka.argb || ka.idx || mixop != 0) return hipErrorInvalidValue;
-        return launch_stft_mix<C, 0>(ka, grid, s);
-    } else {
-    if (ka.argb) {  // single-kernel display path
-        if constexpr (image_ok<C>) {
-            if (mixop == 3) return launch_stft_mix<C, 3, 2>(ka, grid, s);
-            if (mixop == 0) return launch_stft_mix<C, 0, 2>(ka, grid, s);
-        }
-        return hipErrorInvalidValue;
-    }
-    if constexpr (image_only<C>) return hipErrorInvalidValue;
+// launches the instantiation of plan C for (mixop, what ka writes: ARGB rows / palette indices / float columns, stream); hipErrorInvalidValue
+// where the rule above has none
+template <class C, int K = 0>
+hipError_t launch_stft(const StftKArgs& ka, int mixop, int stream, dim3 grid, hipStream_t s) {
+    if constexpr (K == 4 * 3 * 3) return hipErrorInvalidValue;
     else {
-    if (ka.idx) {   // fused display path: the mixed (AbsMean / Sum) and the one-channel instantiations only
-        if (mixop == 3) return launch_stft_mix<C, 3, 1>(ka, grid, s);
-        if (mixop == 0) return launch_stft_mix<C, 0, 1>(ka, grid, s);
-        return hipErrorInvalidValue;
-    }
-    switch (mixop) {
-        case 1: return launch_stft_mix<C, 1>(ka, grid, s);
-        case 2: return launch_stft_mix<C, 2>(ka, grid, s);
-        case 3: return launch_stft_mix<C, 3>(ka, grid, s);
-        default: return launch_stft_mix<C, 0>(ka, grid, s);
-    }
-    }
+        constexpr int MIXOP = K % 4, OUTK = K / 4 % 3, STREAM = K / 12;
+        if constexpr (stft_instantiated<C, MIXOP, OUTK, STREAM>())
+            if (mixop == MIXOP && (ka.argb ? 2 : ka.idx ? 1 : 0) == OUTK && stream == STREAM) return launch_stft_mix<C, MIXOP, OUTK, STREAM>(ka, grid, s);
+        return launch_stft<C, K + 1>(ka, mixop, stream, grid, s);
     }
 }
 
-// strided multi-batch launches (STREAM == 1): the sum-mixed and the one-channel instantiations
-template <class C, int STREAM>
-hipError_t launch_stft_strided(const StftKArgs& ka, int mixop, dim3 grid, hipStream_t s) {
-    if constexpr (image_only<C>) return hipErrorInvalidValue;
-    else {
-        if (ka.argb || ka.idx) return hipErrorInvalidValue;
-        if constexpr (C::PAIR) return mixop == 0 ? launch_stft_mix<C, 0, 0, STREAM>(ka, grid, s) : hipErrorInvalidValue;
-        else
-        if (mixop == 3) return launch_stft_mix<C, 3, 0, STREAM>(ka, grid, s);
-        if constexpr (STREAM == 2) return hipErrorInvalidValue;   // (runs: the one-channel kernels only)
-        else
-        if (mixop == 0) return launch_stft_mix<C, 0, 0, STREAM>(ka, grid, s);
-        return hipErrorInvalidValue;
-    }
-}
-
-
 // ------------------------------------------------------------------------------------------------------------
-// Per-plan entry points.  The kernels of a plan are instantiated in exactly one translation unit (jsg_stft_a.hip or
-// jsg_stft_b.hip: JSG_STFT_PLANS below); jsg_kernels.hip reaches them through these plain functions only, so no kernel is
-// ever compiled twice and hipFuncSetAttribute always addresses the one copy that is launched.
+// The launchable variants.  One row each: the enumerator, the plan whose kernels it launches, the translation unit that compiles them
+// (jsg_stft_a.hip or jsg_stft_b.hip: the two groups want different machine schedulers), the name the *_kernel_name queries report, the columns
+// per workgroup step, the lane-table set of the plan it reads, the plan_select that pins it (0: none does) and whether its grid holds one
+// workgroup per CU.  jsg_kernels.hip builds its variant table (kVariants) from this list; the enumerator, the two entry points of a variant
+// and their definitions in its unit come from it too.  jsg_kernels.hip reaches the kernels through the entry points only, so no kernel is ever
+// compiled twice and hipFuncSetAttribute always addresses the one copy that is launched.
+// k1024I: the eight-column display form of the 1024-point plan; k1024Runs: its "runs" form (strided launches only, STREAM == 2).
 // ------------------------------------------------------------------------------------------------------------
-#define JSG_FOR_EACH_PLAN(X) X(Cfg512) X(Cfg1024) X(Cfg1024I) X(Cfg1024B) X(Cfg2048) X(Cfg2048B) X(Cfg2048P) X(Cfg4096) X(Cfg4096B) X(Cfg8192)
-#define JSG_DECLARE_PLAN(C)                                                                   \
-    hipError_t launch_##C(const StftKArgs& ka, int mixop, dim3 grid, hipStream_t s);          \
-    hipError_t launch_strided_##C(const StftKArgs& ka, int mixop, dim3 grid, hipStream_t s);  \
-    hipError_t ensure_attrs_##C();
-JSG_FOR_EACH_PLAN(JSG_DECLARE_PLAN)
-#undef JSG_DECLARE_PLAN
-#define JSG_DEFINE_PLAN(C)                                                                                                  \
-    hipError_t launch_##C(const StftKArgs& ka, int mixop, dim3 grid, hipStream_t s) { return launch_stft<C>(ka, mixop, grid, s); } \
-    hipError_t launch_strided_##C(const StftKArgs& ka, int mixop, dim3 grid, hipStream_t s) { return launch_stft_strided<C, 1>(ka, mixop, grid, s); } \
-    hipError_t ensure_attrs_##C() { return ensure_lds_attrs_of_plan<C>(); }
+//                       variant    plan      unit  name        columns per step        tables pin one WG per CU
+#define JSG_STFT_VARIANTS(X)                                                                                  \
+    X(k512,      Cfg512,   A, "Cfg512",   Cfg512::TPB,            First, 0, false)                            \
+    X(k1024,     Cfg1024,  A, "Cfg1024",  Cfg1024::TPB,           First, 1, false)                            \
+    X(k1024I,    Cfg1024I, A, "Cfg1024I", Cfg1024I::TPB,          First, 0, false)                            \
+    X(k1024B,    Cfg1024B, A, "Cfg1024B", Cfg1024B::TPB,          B,     2, true)                             \
+    X(k1024Runs, Cfg1024,  A, "Cfg1024",  Cfg1024::TPB * kRunLen, First, 1, false)                            \
+    X(k2048,     Cfg2048,  A, "Cfg2048",  Cfg2048::TPB,           First, 1, false)                            \
+    X(k2048B,    Cfg2048B, A, "Cfg2048B", Cfg2048B::TPB,          B,     2, true)                             \
+    X(k2048P,    Cfg2048P, A, "Cfg2048P", Cfg2048P::TPB,          Pair,  3, true)                             \
+    X(k4096,     Cfg4096,  B, "Cfg4096",  Cfg4096::TPB,           First, 1, false)                            \
+    X(k4096B,    Cfg4096B, B, "Cfg4096B", Cfg4096B::TPB,          B,     2, true)                             \
+    X(k8192,     Cfg8192,  A, "Cfg8192",  Cfg8192::TPB,           First, 0, false)
+
+#define JSG_VARIANT_ENUMERATOR(V, ...) V,
+enum class Variant : int { JSG_STFT_VARIANTS(JSG_VARIANT_ENUMERATOR) };
+#undef JSG_VARIANT_ENUMERATOR
+
+// entry points of a variant: launch (strided: a multi-batch launch, STREAM 1; the runs form: STREAM 2), and the LDS attributes of its plan's kernels
+#define JSG_VARIANT_ENTRY_POINTS(V, C, ...)                                                        \
+    hipError_t launch_##V(const StftKArgs& ka, int mixop, bool strided, dim3 grid, hipStream_t s); \
+    hipError_t ensure_attrs_##V();
+JSG_STFT_VARIANTS(JSG_VARIANT_ENTRY_POINTS)
+#undef JSG_VARIANT_ENTRY_POINTS
+// a row of the variant table (jsg_kernels.hip: kVariants)
+enum class Tables : int { First, B, Pair };   // the lane-table sets of a plan, in the order they sit in its allocation
+constexpr int kTableSets = 3;
+struct VariantRow {
+    int n;                  // FFT size
+    const char* name;       // as the *_kernel_name queries report it
+    int step;               // columns per workgroup step
+    int tables;             // the lane-table set of the plan it reads (Tables)
+    int plan_select;        // the plan_select that pins it (0: none does)
+    bool one_per_cu;        // its grid holds one workgroup per CU
+    hipError_t (*launch)(const StftKArgs& ka, int mixop, bool strided, dim3 grid, hipStream_t s);
+    hipError_t (*ensure_attrs)();
+    void (*fill)(std::vector<float2>& t, const float* window, double amp);
+};
+// jsg_kernels.hip: the variant every launch of a strided call (n_batches >= 1) is pinned to -- the filterbank pins, steps and names its chunks by it
+const VariantRow& strided_call_variant(const jsg_plan* plan, const jsg_stft_args* g, int n_batches, int n_cu);
+
+// jsg_stft_a.hip / jsg_stft_b.hip: JSG_STFT_VARIANTS(JSG_DEFINE_VARIANT) defines the entry points of the variants whose unit column names the
+// unit (it defines JSG_IN_UNIT_A and JSG_IN_UNIT_B: one passes its argument through, the other drops it)
+#define JSG_DEFINE_VARIANT(V, C, U, ...)                                                                                 \
+    JSG_IN_UNIT_##U(                                                                                                      \
+        hipError_t launch_##V(const StftKArgs& ka, int mixop, bool strided, dim3 grid, hipStream_t s) {                   \
+            return launch_stft<C>(ka, mixop, Variant::V == Variant::k1024Runs ? 2 : strided ? 1 : 0, grid, s);              \
+        }                                                                                                                 \
+        hipError_t ensure_attrs_##V() { return ensure_lds_attrs<C>(); })
 // Loads the unit's code object onto the current device (the runtime loads lazily, 2.5 ms on first use: done when a plan is
 // created, not inside the audio thread's first jsg_process_block).
 hipError_t touch_module_a();
 hipError_t touch_module_b();
-// STREAM == 2 ("runs": consecutive columns per wavefront, the overlapped half of a frame kept in registers) exists for the 1024-point plan
-hipError_t launch_runs_Cfg1024(const StftKArgs& ka, int mixop, dim3 grid, hipStream_t s);
 
 }  // namespace jsg

@@ -1,5 +1,5 @@
 """Plan routing where the launcher's automatic rule flips.  1024, 2048 and 4096 points have two kernels each, which round differently in
-the last bits; the launcher picks one per launch (csrc/jsg_kernels.hip: wants_plan_b, wants_plan_pair) from the channels per column, the
+the last bits; the launcher picks one per launch (csrc/jsg_kernels.hip: resolve_variant) from the channels per column, the
 mix, the frame count and the CU count of the device.  Several entry points promise bit-identity relative to a PINNED plan (include/jsg.h:
 strided dB launches, the fused display path, jsg_stft_db_strided_kernel_name); these tests check those promises on both sides of the rule,
 and check the kernels the benchmark times against a float64 DFT directly.
@@ -298,7 +298,7 @@ def test_timed_strided_dispatch_every_bin_against_float64(jsg, oracle, torch_cud
     """The strided dispatch of bench.py's C2 line (64 mono batches of 4096 columns, hop 512) and of one GPU's C4 shard (8 batches x 8
     channels, one column per channel), a different seeded bench.synth_audio input per batch: every bin of every column of every batch
     against the float64 DFT, one batch at a time, and the dB columns of >= 512 columns spread over all batches.  Both geometries take the
-    "runs" kernel -- csrc/jsg_kernels.hip, stft_launch_impl: `runs` = a strided launch at 1024 points, not the "B" plan, no display, one
+    "runs" kernel -- csrc/jsg_kernels.hip, resolve_variant: k1024Runs = a strided launch at 1024 points, not the "B" plan, no display, one
     channel per column (mixop 3), regular frames with 2 * hop == n -- which no query reports; the conditions are asserted here."""
     torch = torch_cuda
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
