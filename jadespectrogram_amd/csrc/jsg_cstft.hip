@@ -23,6 +23,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -263,8 +264,7 @@ using namespace jsg;
 // (n doubles), one allocation; the window is kept on the host for the NOLA check.
 struct jsg_cstft {
     int n = 0;
-    int device = -1;
-    void* d_mem = nullptr;
+    DeviceBlob blob;
     const float* d_win = nullptr;
     const cs_v2* d_tw = nullptr;
     const double* d_w2 = nullptr;
@@ -287,12 +287,10 @@ double nola_min(int n, int hop, const float* w) {
     return mn;
 }
 
-bool cs_pow2_in_range(int n) { return n >= 512 && n <= 8192 && (n & (n - 1)) == 0; }
-
 int cs_check_device(const jsg_cstft* p, const char* who) {
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return jsg_fail(JSG_ERR_NO_DEVICE, (std::string(who) + ": no HIP device").c_str());
-    if (dev != p->device) return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": the plan was created on another device").c_str());
+    const DeviceBlob::Where at = p->blob.where();
+    if (at == DeviceBlob::kNoDevice) return jsg_fail_who(JSG_ERR_NO_DEVICE, who, "no HIP device");
+    if (at != DeviceBlob::kHere) return jsg_fail_who(JSG_ERR_INVALID, who, "the plan was created on another device");
     return JSG_OK;
 }
 
@@ -333,25 +331,25 @@ struct IstftPlanOfCall {
 };
 
 int istft_check(const jsg_cstft* p, const jsg_istft_args* g, const char* who, IstftPlanOfCall* c) {
-    if (!p || !g) return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": null argument").c_str());
+    if (!p || !g) return jsg_fail_who(JSG_ERR_INVALID, who, "null argument");
     const int n = p->n, N = n / 2;
-    if (!g->in || !g->out) return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": null data pointer").c_str());
-    if (g->hop < 1 || g->hop > n) return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": hop must be in 1..n").c_str());
-    if (g->rows < 1 || g->rows > 65535) return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": rows must be in 1..65535").c_str());
+    if (!g->in || !g->out) return jsg_fail_who(JSG_ERR_INVALID, who, "null data pointer");
+    if (g->hop < 1 || g->hop > n) return jsg_fail_who(JSG_ERR_INVALID, who, "hop must be in 1..n");
+    if (g->rows < 1 || g->rows > 65535) return jsg_fail_who(JSG_ERR_INVALID, who, "rows must be in 1..65535");
     if (g->n_frames < 1 || g->n_frames >= (1ll << 31))
-        return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": n_frames must be in 1..2^31-1").c_str());
+        return jsg_fail_who(JSG_ERR_INVALID, who, "n_frames must be in 1..2^31-1");
     const long long span = (g->n_frames - 1) * (long long)g->hop + n;
     if (g->out_samples < 1 || g->out_samples > span)
-        return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": out_samples must be in 1..(n_frames-1)*hop+n").c_str());
-    if (g->in_frame_pitch < N + 1) return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": in_frame_pitch smaller than n/2+1").c_str());
+        return jsg_fail_who(JSG_ERR_INVALID, who, "out_samples must be in 1..(n_frames-1)*hop+n");
+    if (g->in_frame_pitch < N + 1) return jsg_fail_who(JSG_ERR_INVALID, who, "in_frame_pitch smaller than n/2+1");
     if (g->rows > 1 && g->in_row_pitch < (g->n_frames - 1) * g->in_frame_pitch + N + 1)
-        return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": in_row_pitch smaller than one row of frames").c_str());
+        return jsg_fail_who(JSG_ERR_INVALID, who, "in_row_pitch smaller than one row of frames");
     if (g->rows > 1 && g->out_pitch < g->out_samples)
-        return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": out_pitch smaller than out_samples").c_str());
+        return jsg_fail_who(JSG_ERR_INVALID, who, "out_pitch smaller than out_samples");
     if ((reinterpret_cast<uintptr_t>(g->in) & 7) != 0)
-        return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": in must be 8-byte aligned (complex float pairs)").c_str());
+        return jsg_fail_who(JSG_ERR_INVALID, who, "in must be 8-byte aligned (complex float pairs)");
     if (nola_min(n, g->hop, p->win.data()) <= kNolaEps)
-        return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": the window fails the NOLA condition at this hop (envelope <= 1e-11)").c_str());
+        return jsg_fail_who(JSG_ERR_INVALID, who, "the window fails the NOLA condition at this hop (envelope <= 1e-11)");
     c->F = std::min(g->n_frames, (g->out_samples - 1) / g->hop + 1);
     c->K = (n - 1) / g->hop;
     return JSG_OK;
@@ -364,7 +362,7 @@ extern "C" {
 int jsg_cstft_create(jsg_cstft** out, int n, const float* window) {
     if (!out || !window) return jsg_fail(JSG_ERR_INVALID, "jsg_cstft_create: null argument");
     *out = nullptr;
-    if (!cs_pow2_in_range(n)) return jsg_fail(JSG_ERR_UNSUPPORTED, "jsg_cstft_create: FFT size must be 512, 1024, 2048, 4096 or 8192");
+    if (!fft_size_supported(n)) return jsg_fail(JSG_ERR_UNSUPPORTED, "jsg_cstft_create: FFT size must be 512, 1024, 2048, 4096 or 8192");
     for (int m = 0; m < n; ++m)
         if (!std::isfinite(window[m])) return jsg_fail(JSG_ERR_INVALID, "jsg_cstft_create: the window must be finite");
     const int N = n / 2;
@@ -383,34 +381,23 @@ int jsg_cstft_create(jsg_cstft** out, int n, const float* window) {
         tw[2 * m] = float(std::cos(ang));
         tw[2 * m + 1] = float(std::sin(ang));
     }
-    jsg_cstft* p = new (std::nothrow) jsg_cstft();
-    if (!p) return jsg_fail(JSG_ERR_NOMEM, "jsg_cstft_create: out of host memory");
+    static const char* who = "jsg_cstft_create";
+    std::unique_ptr<jsg_cstft> p(new (std::nothrow) jsg_cstft());
+    if (!p) return jsg_fail_who(JSG_ERR_NOMEM, who, "out of host memory");
     p->n = n;
-    if (hipGetDevice(&p->device) != hipSuccess) {
-        delete p;
-        return jsg_fail(JSG_ERR_NO_DEVICE, "jsg_cstft_create: no HIP device (the engine has no CPU fallback)");
-    }
-    hipError_t err = hipMalloc(&p->d_mem, blob.size());
-    if (err == hipSuccess) err = hipMemcpy(p->d_mem, blob.data(), blob.size(), hipMemcpyHostToDevice);
-    if (err != hipSuccess) {
-        if (p->d_mem) (void)hipFree(p->d_mem);
-        delete p;
-        return jsg_fail_hip(err, "jsg_cstft_create");
-    }
-    unsigned char* d = static_cast<unsigned char*>(p->d_mem);
+    const int rc = p->blob.upload(blob.data(), blob.size(), who);
+    if (rc != JSG_OK) return rc;
+    const unsigned char* d = static_cast<const unsigned char*>(p->blob.data());
     p->d_win = reinterpret_cast<const float*>(d);
     p->d_tw = reinterpret_cast<const cs_v2*>(d + size_t(n) * 4);
     p->d_w2 = reinterpret_cast<const double*>(d + size_t(n) * 4 + size_t(N) * 8);
     p->win.assign(window, window + n);
-    hipFuncAttributes fa;   // load the unit's code object now, not inside the first launch
-    (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&istft_ola_kernel));
-    *out = p;
+    (void)preload_code_object(reinterpret_cast<const void*>(&istft_ola_kernel));
+    *out = p.release();
     return JSG_OK;
 }
 
 int jsg_cstft_destroy(jsg_cstft* plan) {
-    if (!plan) return JSG_OK;
-    if (plan->d_mem) (void)hipFree(plan->d_mem);
     delete plan;
     return JSG_OK;
 }
@@ -449,11 +436,11 @@ int jsg_cstft_launch(const jsg_cstft* plan, const jsg_cstft_args* g, void* strea
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipError_t err;
     switch (n) {
-        case 512: err = fwd_launch<256>(k, g->rows, g->n_frames, plan->device, s); break;
-        case 1024: err = fwd_launch<512>(k, g->rows, g->n_frames, plan->device, s); break;
-        case 2048: err = fwd_launch<1024>(k, g->rows, g->n_frames, plan->device, s); break;
-        case 4096: err = fwd_launch<2048>(k, g->rows, g->n_frames, plan->device, s); break;
-        default: err = fwd_launch<4096>(k, g->rows, g->n_frames, plan->device, s); break;
+        case 512: err = fwd_launch<256>(k, g->rows, g->n_frames, plan->blob.device(), s); break;
+        case 1024: err = fwd_launch<512>(k, g->rows, g->n_frames, plan->blob.device(), s); break;
+        case 2048: err = fwd_launch<1024>(k, g->rows, g->n_frames, plan->blob.device(), s); break;
+        case 4096: err = fwd_launch<2048>(k, g->rows, g->n_frames, plan->blob.device(), s); break;
+        default: err = fwd_launch<4096>(k, g->rows, g->n_frames, plan->blob.device(), s); break;
     }
     if (err != hipSuccess) return jsg_fail_hip(err, "jsg_cstft_launch");
     return JSG_OK;
@@ -461,7 +448,7 @@ int jsg_cstft_launch(const jsg_cstft* plan, const jsg_cstft_args* g, void* strea
 
 int jsg_istft_nola(int n, int hop, const float* window, float* min_envelope) {
     if (!window || !min_envelope) return jsg_fail(JSG_ERR_INVALID, "jsg_istft_nola: null argument");
-    if (!cs_pow2_in_range(n)) return jsg_fail(JSG_ERR_UNSUPPORTED, "jsg_istft_nola: FFT size must be 512, 1024, 2048, 4096 or 8192");
+    if (!fft_size_supported(n)) return jsg_fail(JSG_ERR_UNSUPPORTED, "jsg_istft_nola: FFT size must be 512, 1024, 2048, 4096 or 8192");
     if (hop < 1 || hop > n) return jsg_fail(JSG_ERR_INVALID, "jsg_istft_nola: hop must be in 1..n");
     for (int m = 0; m < n; ++m)
         if (!std::isfinite(window[m])) return jsg_fail(JSG_ERR_INVALID, "jsg_istft_nola: the window must be finite");
@@ -509,7 +496,7 @@ int jsg_istft_launch(const jsg_cstft* plan, const jsg_istft_args* g, float* scra
         k.frames_per_row = fpr;
         k.first_frame = base;
         k.n_frames = b - base;
-        hipError_t err = c2r_dispatch(n, k, g->rows, plan->device, s);
+        hipError_t err = c2r_dispatch(n, k, g->rows, plan->blob.device(), s);
         if (err != hipSuccess) return jsg_fail_hip(err, "jsg_istft_launch");
         CsOlaArgs o{};
         o.scratch = scratch;

@@ -129,10 +129,7 @@ __global__ __launch_bounds__(256) void colormap_axis_kernel(const AxisKArgs a) {
 }
 
 // load the unit's code object now (jsg_freq_axis_create), not inside the first display tick
-void touch_axis_module() {
-    hipFuncAttributes fa;
-    (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&colormap_axis_kernel));
-}
+void touch_axis_module() { (void)preload_code_object(reinterpret_cast<const void*>(&colormap_axis_kernel)); }
 
 }  // namespace jsg
 
@@ -155,9 +152,9 @@ int jsg_colormap_axis_launch(const jsg_colormap_args* g, const jsg_freq_axis* ax
     if (g->height != ax->n / 2 + 1)
         return jsg_fail(JSG_ERR_INVALID, "jsg_colormap_axis_launch: the axis was built for another FFT size (height must be n/2+1)");
     if (g->db_pitch < g->height) return jsg_fail(JSG_ERR_INVALID, "jsg_colormap_axis_launch: db_pitch smaller than n/2+1");
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return jsg_fail(JSG_ERR_NO_DEVICE, "jsg_colormap_axis_launch: no device");
-    if (dev != ax->device) return jsg_fail(JSG_ERR_INVALID, "jsg_colormap_axis_launch: the axis was created on another device");
+    const DeviceBlob::Where at = ax->blob.where();
+    if (at == DeviceBlob::kNoDevice) return jsg_fail(JSG_ERR_NO_DEVICE, "jsg_colormap_axis_launch: no device");
+    if (at != DeviceBlob::kHere) return jsg_fail(JSG_ERR_INVALID, "jsg_colormap_axis_launch: the axis was created on another device");
     AxisKArgs ka{};
     ka.db = g->db;
     ka.db_pitch = g->db_pitch;

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -22,11 +23,9 @@ struct Rows {
     std::vector<float> t, centre;
 };
 
-bool pow2_in_range(int n) { return n >= 512 && n <= 8192 && (n & (n - 1)) == 0; }
-
 int check_spec(const jsg_axis_spec* s) {
     if (!s) return jsg_fail(JSG_ERR_INVALID, "jsg_freq_axis: null spec");
-    if (!pow2_in_range(s->n)) return jsg_fail(JSG_ERR_INVALID, "jsg_freq_axis: n must be a power of two in 512..8192");
+    if (!fft_size_supported(s->n)) return jsg_fail(JSG_ERR_INVALID, "jsg_freq_axis: n must be a power of two in 512..8192");
     if (!(s->fs > 0.f) || !std::isfinite(s->fs)) return jsg_fail(JSG_ERR_INVALID, "jsg_freq_axis: fs must be > 0");
     if (s->scale != JSG_AXIS_LINEAR && s->scale != JSG_AXIS_LOG && s->scale != JSG_AXIS_MEL)
         return jsg_fail(JSG_ERR_INVALID, "jsg_freq_axis: scale must be LINEAR, LOG or MEL");
@@ -121,39 +120,29 @@ int jsg_freq_axis_create(jsg_freq_axis** out, const jsg_axis_spec* s) {
     Rows r;
     build_rows(s, r);
     const std::vector<int> tiles = build_tiles(r);
-    jsg_freq_axis* ax = new (std::nothrow) jsg_freq_axis();
-    if (!ax) return jsg_fail(JSG_ERR_NOMEM, "jsg_freq_axis_create: out of host memory");
+    static const char* who = "jsg_freq_axis_create";
+    std::unique_ptr<jsg_freq_axis> ax(new (std::nothrow) jsg_freq_axis());
+    if (!ax) return jsg_fail_who(JSG_ERR_NOMEM, who, "out of host memory");
     ax->n = s->n;
     ax->height = s->height;
     ax->n_tiles = int(tiles.size() / 4);
-    hipError_t err = hipGetDevice(&ax->device);
-    if (err != hipSuccess) {
-        delete ax;
-        return jsg_fail(JSG_ERR_NO_DEVICE, "jsg_freq_axis_create: no HIP device (the engine has no CPU fallback)");
-    }
     const size_t H = size_t(s->height);
     std::vector<int> blob(3 * H + tiles.size());
     std::memcpy(blob.data(), r.first.data(), H * 4);
     std::memcpy(blob.data() + H, r.count.data(), H * 4);
     std::memcpy(blob.data() + 2 * H, r.t.data(), H * 4);
     std::memcpy(blob.data() + 3 * H, tiles.data(), tiles.size() * 4);
-    err = hipMalloc(reinterpret_cast<void**>(&ax->d_rows), blob.size() * 4);
-    if (err == hipSuccess) err = hipMemcpy(ax->d_rows, blob.data(), blob.size() * 4, hipMemcpyHostToDevice);
-    if (err != hipSuccess) {
-        if (ax->d_rows) (void)hipFree(ax->d_rows);
-        delete ax;
-        return jsg_fail_hip(err, "jsg_freq_axis_create");
-    }
+    rc = ax->blob.upload(blob.data(), blob.size() * 4, who);
+    if (rc != JSG_OK) return rc;
+    ax->d_rows = static_cast<const int*>(ax->blob.data());
     ax->d_tiles = ax->d_rows + 3 * H;
     touch_axis_module();
     ax->centre_hz = std::move(r.centre);
-    *out = ax;
+    *out = ax.release();
     return JSG_OK;
 }
 
 int jsg_freq_axis_destroy(jsg_freq_axis* ax) {
-    if (!ax) return JSG_OK;
-    if (ax->d_rows) (void)hipFree(ax->d_rows);
     delete ax;
     return JSG_OK;
 }

@@ -141,16 +141,16 @@ struct FbCall {
 };
 
 int fb_resolve(const jsg_plan* plan, const jsg_filterbank* fb, const jsg_stft_args* g, int n_batches, FbCall& c, const char* who) {
-    const std::string w(who);
-    if (!plan || !fb || !g) return jsg_fail(JSG_ERR_INVALID, (w + ": null argument").c_str());
-    if (n_batches < 1) return jsg_fail(JSG_ERR_INVALID, (w + ": n_batches must be >= 1").c_str());
+    if (!plan || !fb || !g) return jsg_fail_who(JSG_ERR_INVALID, who, "null argument");
+    if (n_batches < 1) return jsg_fail_who(JSG_ERR_INVALID, who, "n_batches must be >= 1");
     const int n = jsg_plan_fft_size(plan);
-    if (fb->n != n) return jsg_fail(JSG_ERR_INVALID, (w + ": the filterbank was built for another FFT size than the plan's").c_str());
+    if (fb->n != n) return jsg_fail_who(JSG_ERR_INVALID, who, "the filterbank was built for another FFT size than the plan's");
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return jsg_fail(JSG_ERR_NO_DEVICE, (w + ": no device").c_str());
-    if (dev != plan_device(plan) || dev != fb->device)
-        return jsg_fail(JSG_ERR_INVALID, (w + ": the plan or the filterbank was created on another device").c_str());
-    if (g->channels <= 0 || g->n_frames < 0) return jsg_fail(JSG_ERR_INVALID, (w + ": bad geometry").c_str());
+    const DeviceBlob::Where at = fb->blob.where(&dev);
+    if (at == DeviceBlob::kNoDevice) return jsg_fail_who(JSG_ERR_NO_DEVICE, who, "no device");
+    if (at != DeviceBlob::kHere || dev != plan_device(plan))
+        return jsg_fail_who(JSG_ERR_INVALID, who, "the plan or the filterbank was created on another device");
+    if (g->channels <= 0 || g->n_frames < 0) return jsg_fail_who(JSG_ERR_INVALID, who, "bad geometry");
     c.stft = &strided_call_variant(plan, g, n_batches, cu_count_of_device(dev));
     c.rows = g->mix_mode == JSG_MIX_PER_CHANNEL ? g->channels : 1;
     c.pitch = fb_pw_pitch(n);

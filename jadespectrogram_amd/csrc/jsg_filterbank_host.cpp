@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -34,11 +35,9 @@ inline double mel_to_hz(double m, bool htk) {
     return slaney_mel_to_hz(m);
 }
 
-bool pow2_in_range(int n) { return n >= 512 && n <= 8192 && (n & (n - 1)) == 0; }
-
 int check_spec(const jsg_fb_spec* s) {
     if (!s) return jsg_fail(JSG_ERR_INVALID, "jsg_filterbank: null spec");
-    if (!pow2_in_range(s->n)) return jsg_fail(JSG_ERR_INVALID, "jsg_filterbank: n must be a power of two in 512..8192");
+    if (!fft_size_supported(s->n)) return jsg_fail(JSG_ERR_INVALID, "jsg_filterbank: n must be a power of two in 512..8192");
     if (!(s->fs > 0.f) || !std::isfinite(s->fs)) return jsg_fail(JSG_ERR_INVALID, "jsg_filterbank: fs must be > 0");
     if (s->n_bands < 1 || s->n_bands > JSG_FB_MAX_BANDS) return jsg_fail(JSG_ERR_INVALID, "jsg_filterbank: n_bands must be in 1..8192");
     if (!(s->fmin >= 0.f)) return jsg_fail(JSG_ERR_INVALID, "jsg_filterbank: fmin must be >= 0");
@@ -105,36 +104,28 @@ void build_csr(const jsg_fb_spec* s, Csr& m) {
 }
 
 int upload(jsg_filterbank** out, int n, Csr& m) {
+    static const char* who = "jsg_filterbank_create";
     *out = nullptr;
-    jsg_filterbank* fb = new (std::nothrow) jsg_filterbank();
-    if (!fb) return jsg_fail(JSG_ERR_NOMEM, "jsg_filterbank_create: out of host memory");
+    std::unique_ptr<jsg_filterbank> fb(new (std::nothrow) jsg_filterbank());
+    if (!fb) return jsg_fail_who(JSG_ERR_NOMEM, who, "out of host memory");
     fb->n = n;
     fb->n_bands = int(m.first.size());
     fb->nnz = (long long)m.w.size();
-    hipError_t err = hipGetDevice(&fb->device);
-    if (err != hipSuccess) {
-        delete fb;
-        return jsg_fail(JSG_ERR_NO_DEVICE, "jsg_filterbank_create: no HIP device (the engine has no CPU fallback)");
-    }
     const size_t B = size_t(fb->n_bands);
     std::vector<int> blob(3 * B + m.w.size());
     std::memcpy(blob.data(), m.first.data(), B * 4);
     std::memcpy(blob.data() + B, m.count.data(), B * 4);
     std::memcpy(blob.data() + 2 * B, m.offset.data(), B * 4);
     if (!m.w.empty()) std::memcpy(blob.data() + 3 * B, m.w.data(), m.w.size() * 4);
-    err = hipMalloc(reinterpret_cast<void**>(&fb->d_desc), blob.size() * 4);
-    if (err == hipSuccess) err = hipMemcpy(fb->d_desc, blob.data(), blob.size() * 4, hipMemcpyHostToDevice);
-    if (err != hipSuccess) {
-        if (fb->d_desc) (void)hipFree(fb->d_desc);
-        delete fb;
-        return jsg_fail_hip(err, "jsg_filterbank_create");
-    }
+    const int rc = fb->blob.upload(blob.data(), blob.size() * 4, who);
+    if (rc != JSG_OK) return rc;
+    fb->d_desc = static_cast<const int*>(fb->blob.data());
     fb->d_w = reinterpret_cast<const float*>(fb->d_desc + 3 * B);
     fb->first = std::move(m.first);
     fb->count = std::move(m.count);
     fb->offset = std::move(m.offset);
     fb->w = std::move(m.w);
-    *out = fb;
+    *out = fb.release();
     return JSG_OK;
 }
 
@@ -175,7 +166,7 @@ int jsg_filterbank_create(jsg_filterbank** out, const jsg_fb_spec* s) {
 int jsg_filterbank_create_matrix(jsg_filterbank** out, int n, int n_bands, const float* w) {
     if (!out || !w) return jsg_fail(JSG_ERR_INVALID, "jsg_filterbank_create_matrix: null argument");
     *out = nullptr;
-    if (!pow2_in_range(n) || n_bands < 1 || n_bands > JSG_FB_MAX_BANDS)
+    if (!fft_size_supported(n) || n_bands < 1 || n_bands > JSG_FB_MAX_BANDS)
         return jsg_fail(JSG_ERR_INVALID, "jsg_filterbank_create_matrix: n must be a power of two in 512..8192, n_bands in 1..8192");
     const int H = n / 2 + 1;
     Csr m;
@@ -196,8 +187,6 @@ int jsg_filterbank_create_matrix(jsg_filterbank** out, int n, int n_bands, const
 }
 
 int jsg_filterbank_destroy(jsg_filterbank* fb) {
-    if (!fb) return JSG_OK;
-    if (fb->d_desc) (void)hipFree(fb->d_desc);
     delete fb;
     return JSG_OK;
 }

@@ -14,13 +14,66 @@ namespace jsg {
 std::string& tls_error();
 int jsg_fail(int code, const char* what);
 int jsg_fail_hip(hipError_t err, const char* where);
+// jsg_fail with the text "<who>: <what>" (checks that several entry points share)
+inline int jsg_fail_who(int code, const char* who, const char* what) { return jsg_fail(code, (std::string(who) + ": " + what).c_str()); }
+
+// the transform sizes of every plan and table object: 512, 1024, 2048, 4096, 8192
+inline bool fft_size_supported(int n) { return n >= 512 && n <= 8192 && (n & (n - 1)) == 0; }
+
+// Loads the code object that holds `kernel` onto the current device now, on the thread that configures, not inside the first launch
+// (the runtime loads lazily; querying any kernel of a translation unit loads all of them).
+inline hipError_t preload_code_object(const void* kernel) {
+    hipFuncAttributes fa;
+    return hipFuncGetAttributes(&fa, kernel);
+}
+
+// A table built on the host, uploaded once to the device that is current at creation and used by launches on that device: what
+// jsg_plan, jsg_filterbank, jsg_freq_axis and jsg_cstft own.  The objects keep typed pointers into data().
+struct DeviceBlob {
+    enum Where { kHere, kNoDevice, kElsewhere };
+
+    DeviceBlob() = default;
+    DeviceBlob(const DeviceBlob&) = delete;
+    DeviceBlob& operator=(const DeviceBlob&) = delete;
+    ~DeviceBlob() {
+        if (d_) (void)hipFree(d_);
+    }
+
+    // records the current device; upload() does it itself unless the caller has (jsg_plan_create: device, kernel attributes, then tables)
+    int bind(const char* who) {
+        if (hipGetDevice(&device_) == hipSuccess) return JSG_OK;
+        return jsg_fail_who(JSG_ERR_NO_DEVICE, who, "no HIP device (the engine has no CPU fallback)");
+    }
+    int upload(const void* host, size_t bytes, const char* who) {
+        if (device_ < 0) {
+            const int rc = bind(who);
+            if (rc != JSG_OK) return rc;
+        }
+        hipError_t err = hipMalloc(&d_, bytes);
+        if (err == hipSuccess) err = hipMemcpy(d_, host, bytes, hipMemcpyHostToDevice);
+        return err == hipSuccess ? JSG_OK : jsg_fail_hip(err, who);
+    }
+    void* data() const { return d_; }
+    int device() const { return device_; }
+    // launch time: is the current device (stored to *current where the caller goes on to use it) the blob's?
+    Where where(int* current = nullptr) const {
+        int dev = -1;
+        if (hipGetDevice(&dev) != hipSuccess) return kNoDevice;
+        if (current) *current = dev;
+        return dev == device_ ? kHere : kElsewhere;
+    }
+
+private:
+    void* d_ = nullptr;
+    int device_ = -1;
+};
 
 // jsg_kernels.hip: compute units of a device (read once per device), the device a plan was created on
 int cu_count_of_device(int dev);
 int plan_device(const jsg_plan* plan);
 // jsg_kernels.hip: the refusals of jsg_stft_args that the STFT launcher and the filterbank launcher share (message prefix `who`)
 int check_stft_args(int n, const jsg_stft_args* g, const char* who);
-// jsg_display_axis.hip: load the code object of the axis kernel (jsg_freq_axis_create, on the thread that configures)
+// jsg_display_axis.hip: preload_code_object of the axis kernel (jsg_freq_axis_create)
 void touch_axis_module();
 
 // Slaney's mel scale (librosa.filters.mel, htk = False): linear below 1 kHz (200/3 Hz per mel), logarithmic above (27 mels per
@@ -36,9 +89,9 @@ inline double slaney_mel_to_hz(double m) { return m < 15.0 ? (200.0 / 3.0) * m :
 struct jsg_filterbank {
     int n = 0;
     int n_bands = 0;
-    int device = -1;
     long long nnz = 0;
-    int* d_desc = nullptr;      // first_bin[n_bands], n_bins[n_bands], offset[n_bands], then nnz floats of weights
+    jsg::DeviceBlob blob;       // first_bin[n_bands], n_bins[n_bands], offset[n_bands], then nnz floats of weights
+    const int* d_desc = nullptr;
     const float* d_w = nullptr;
     std::vector<int> first, count, offset;   // host copy (jsg_filterbank_weights)
     std::vector<float> w;
@@ -53,9 +106,9 @@ constexpr int kAxisSpan = 128;
 struct jsg_freq_axis {
     int n = 0;
     int height = 0;
-    int device = -1;
     int n_tiles = 0;
-    int* d_rows = nullptr;        // first_bin[height], n_bins[height], interp_t[height] (float bits), then tiles[4 * n_tiles]
+    jsg::DeviceBlob blob;         // first_bin[height], n_bins[height], interp_t[height] (float bits), then tiles[4 * n_tiles]
+    const int* d_rows = nullptr;
     const int* d_tiles = nullptr;
     std::vector<float> centre_hz; // host copy (jsg_display_axis_centres)
 };

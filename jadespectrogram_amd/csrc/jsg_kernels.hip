@@ -10,6 +10,8 @@
 //                    device); stft_launch_impl: grid and loop counts; jsg_stft_db_launch_batches: the library's launch pool (caller's stream + three).
 //
 // The index algebra, the twiddle tables and the LDS layouts are modelled and checked in tools/fft_model.py.
+#include <memory>
+
 #include "jsg_stft_kernel.h"
 
 namespace jsg {
@@ -193,9 +195,8 @@ const VariantRow& row_of(Variant v) { return kVariants[int(v)]; }
 
 struct jsg_plan {
     int n = 0;
-    int device = -1;
-    float2* d_tab = nullptr;              // the lane-table sets of the plan's variants, one allocation
-    size_t tab_elems = 0;
+    DeviceBlob blob;                      // the lane-table sets of the plan's variants, one allocation
+    const float2* d_tab = nullptr;
     size_t set_at[kTableSets] = {0, 0, 0};   // where each set starts in d_tab (Tables)
 };
 
@@ -229,41 +230,31 @@ int jsg_plan_create(jsg_plan** out, int n, const float* window, float power_scal
                 break;
             }
     if (t.empty()) return jsg_fail(JSG_ERR_UNSUPPORTED, "jsg_plan_create: FFT size must be 512, 1024, 2048, 4096 or 8192");
-    jsg_plan* p = new (std::nothrow) jsg_plan();
-    if (!p) return jsg_fail(JSG_ERR_NOMEM, "jsg_plan_create: out of host memory");
+    static const char* who = "jsg_plan_create";
+    std::unique_ptr<jsg_plan> p(new (std::nothrow) jsg_plan());
+    if (!p) return jsg_fail_who(JSG_ERR_NOMEM, who, "out of host memory");
     p->n = n;
     std::copy(set_at, set_at + kTableSets, p->set_at);
-    p->tab_elems = t.size();
-    if (hipGetDevice(&p->device) != hipSuccess) {
-        delete p;
-        return jsg_fail(JSG_ERR_NO_DEVICE, "jsg_plan_create: no HIP device (the engine has no CPU fallback)");
-    }
+    int rc = p->blob.bind(who);
+    if (rc != JSG_OK) return rc;
     // Force the (lazily loaded) code object onto the device now, on the thread that configures, not inside the audio
     // thread's first jsg_process_block: querying any kernel of the module loads all of them (measured: 2.5 ms otherwise).
-    {
-        hipFuncAttributes fa;
-        (void)touch_module_a();
-        (void)touch_module_b();
-        (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&colormap_kernel));
-    }
+    (void)touch_module_a();
+    (void)touch_module_b();
+    (void)preload_code_object(reinterpret_cast<const void*>(&colormap_kernel));
     hipError_t err = hipSuccess;
     for (const VariantRow& r : kVariants)
         if (r.n == n && err == hipSuccess) err = r.ensure_attrs();
-    if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&p->d_tab), t.size() * sizeof(float2));
-    if (err == hipSuccess) err = hipMemcpy(p->d_tab, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (err != hipSuccess) {
-        if (p->d_tab) (void)hipFree(p->d_tab);
-        delete p;
-        return jsg_fail_hip(err, "jsg_plan_create");
-    }
-    pool_prepare_for_device(p->device);
-    *out = p;
+    if (err != hipSuccess) return jsg_fail_hip(err, who);
+    rc = p->blob.upload(t.data(), t.size() * sizeof(float2), who);
+    if (rc != JSG_OK) return rc;
+    p->d_tab = static_cast<const float2*>(p->blob.data());
+    pool_prepare_for_device(p->blob.device());
+    *out = p.release();
     return JSG_OK;
 }
 
 int jsg_plan_destroy(jsg_plan* plan) {
-    if (!plan) return JSG_OK;
-    if (plan->d_tab) (void)hipFree(plan->d_tab);
     delete plan;
     return JSG_OK;
 }
@@ -272,7 +263,7 @@ int jsg_plan_fft_size(const jsg_plan* plan) { return plan ? plan->n : JSG_ERR_IN
 
 }   // extern "C"
 
-int jsg::plan_device(const jsg_plan* plan) { return plan->device; }
+int jsg::plan_device(const jsg_plan* plan) { return plan->blob.device(); }
 
 namespace {
 struct IndexOut {   // fused display path: where and how the palette indices of the columns are written ...
@@ -369,23 +360,22 @@ const VariantRow& jsg::strided_call_variant(const jsg_plan* plan, const jsg_stft
 // The refusals of jsg_stft_args that every STFT launch makes (stft_launch_impl) and that the filterbank launcher makes for its whole call
 // before the first chunk, so that a refused call enqueues nothing.  `who` prefixes the message.
 int jsg::check_stft_args(int n, const jsg_stft_args* g, const char* who) {
-    auto fail = [who](int code, const char* what) { return jsg_fail(code, (std::string(who) + ": " + what).c_str()); };
-    if (g->hop <= 0 || g->feedblocks <= 0) return fail(JSG_ERR_INVALID, "bad geometry (hop, feedblocks)");
-    if (g->channels > 65535) return fail(JSG_ERR_UNSUPPORTED, "more than 65535 channels");
+    if (g->hop <= 0 || g->feedblocks <= 0) return jsg_fail_who(JSG_ERR_INVALID, who, "bad geometry (hop, feedblocks)");
+    if (g->channels > 65535) return jsg_fail_who(JSG_ERR_UNSUPPORTED, who, "more than 65535 channels");
     if (g->in_samples != 0) {   // the caller told us how long the channel rows are: refuse to read past them
         const long long j = g->first_frame + g->n_frames - 1;
         const long long start = ((long long)g->hop * g->feedblocks == n) ? j * g->hop : (j / g->feedblocks) * n + (j % g->feedblocks) * g->hop;
-        if (g->in_samples < 0 || start + n > g->in_samples) return fail(JSG_ERR_INVALID, "the last frame would read past the end of the input rows");
-        if (g->channels > 1 && g->in_pitch < g->in_samples) return fail(JSG_ERR_INVALID, "in_pitch < in_samples");
+        if (g->in_samples < 0 || start + n > g->in_samples) return jsg_fail_who(JSG_ERR_INVALID, who, "the last frame would read past the end of the input rows");
+        if (g->channels > 1 && g->in_pitch < g->in_samples) return jsg_fail_who(JSG_ERR_INVALID, who, "in_pitch < in_samples");
     }
-    if (g->n_frames >= (1ll << 31) || g->first_frame + g->n_frames >= (1ll << 31)) return fail(JSG_ERR_UNSUPPORTED, "frame index does not fit 31 bits");
+    if (g->n_frames >= (1ll << 31) || g->first_frame + g->n_frames >= (1ll << 31)) return jsg_fail_who(JSG_ERR_UNSUPPORTED, who, "frame index does not fit 31 bits");
     switch (g->mix_mode) {
         case JSG_MIX_ABSMEAN: case JSG_MIX_MAX: case JSG_MIX_MIN: case JSG_MIX_LEFT: case JSG_MIX_PER_CHANNEL: case JSG_MIX_SUM: return JSG_OK;
         case JSG_MIX_RIGHT:
             // reference Spectrogram.cpp:97-105 reads m_power[1] whenever m_channels > 0; with one channel that is out of bounds there, so it
             // is rejected here
-            return g->channels < 2 ? fail(JSG_ERR_INVALID, "JSG_MIX_RIGHT needs at least two channels") : JSG_OK;
-        default: return fail(JSG_ERR_INVALID, "unknown mix mode");
+            return g->channels < 2 ? jsg_fail_who(JSG_ERR_INVALID, who, "JSG_MIX_RIGHT needs at least two channels") : JSG_OK;
+        default: return jsg_fail_who(JSG_ERR_INVALID, who, "unknown mix mode");
     }
 }
 
@@ -412,7 +402,7 @@ static int stft_launch_impl(const jsg_plan* plan, const jsg_stft_args* g, const 
     if (g->n_frames > g->ring_width)
         return jsg_fail(JSG_ERR_INVALID, "jsg_stft_db_launch: more frames than ring columns in one launch (columns would race)");
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != plan->device)
+    if (plan->blob.where(&dev) != DeviceBlob::kHere)
         return jsg_fail(JSG_ERR_INVALID, "jsg_stft_db_launch: the plan was created on another device");
     const int n_cu = cu_count_of_device(dev);
     const int rc = check_stft_args(plan->n, g, "jsg_stft_db_launch");
@@ -679,20 +669,20 @@ int jsg_stft_image_launch_strided(const jsg_plan* plan, const jsg_stft_image_arg
 // The workgroups of the launch walk through the columns of all batches: tables loaded once per workgroup, no ramp-up and drain per
 // batch, no dependence on extra streams, hardware queues or issuing threads.
 static int strided_checks(const jsg_plan* plan, const jsg_stft_args* g, int n_batches, int64_t in_batch_stride, int64_t out_batch_stride, const char* who) {
-    if (!plan || !g) return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": null argument").c_str());
-    if (n_batches < 0) return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": negative batch count").c_str());
-    if (in_batch_stride < 0 || out_batch_stride < 0) return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": negative stride").c_str());
+    if (!plan || !g) return jsg_fail_who(JSG_ERR_INVALID, who, "null argument");
+    if (n_batches < 0) return jsg_fail_who(JSG_ERR_INVALID, who, "negative batch count");
+    if (in_batch_stride < 0 || out_batch_stride < 0) return jsg_fail_who(JSG_ERR_INVALID, who, "negative stride");
     if (n_batches > 1 && g->n_frames > 0) {
-        if (g->channels <= 0 || g->ring_width <= 0 || g->out_pitch <= 0) return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": bad geometry").c_str());
+        if (g->channels <= 0 || g->ring_width <= 0 || g->out_pitch <= 0) return jsg_fail_who(JSG_ERR_INVALID, who, "bad geometry");
         const long long ring_extent = (g->mix_mode == JSG_MIX_PER_CHANNEL ? (long long)(g->channels - 1) * g->out_channel_pitch : 0ll) +
                                       (long long)(g->ring_width - 1) * g->out_pitch + plan->n / 2 + (g->out_tail ? 0 : 1);
         if (out_batch_stride < ring_extent)
-            return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": the rings of consecutive batches would overlap (out_batch_stride too small)").c_str());
+            return jsg_fail_who(JSG_ERR_INVALID, who, "the rings of consecutive batches would overlap (out_batch_stride too small)");
         // the caller told us how long the channel rows are: consecutive batches may share samples (stride < row length: a long stream
         // cut along time), but a batch must not reach past what the stride + in_samples describe for the LAST batch -- checked per
         // batch by the launcher -- and a stride of 0 means "the same input for every batch"
         if (g->in_samples != 0 && in_batch_stride != 0 && g->channels > 1 && g->in_pitch < g->in_samples)
-            return jsg_fail(JSG_ERR_INVALID, (std::string(who) + ": in_pitch < in_samples").c_str());
+            return jsg_fail_who(JSG_ERR_INVALID, who, "in_pitch < in_samples");
     }
     return JSG_OK;
 }

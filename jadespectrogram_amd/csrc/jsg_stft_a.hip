@@ -10,8 +10,5 @@ namespace jsg {
 #define JSG_IN_UNIT_A(...) __VA_ARGS__
 #define JSG_IN_UNIT_B(...)
 JSG_STFT_VARIANTS(JSG_DEFINE_VARIANT)
-hipError_t touch_module_a() {
-    hipFuncAttributes fa;
-    return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&stft_db_kernel<Cfg1024, 3>));
-}
+hipError_t touch_module_a() { return preload_code_object(reinterpret_cast<const void*>(&stft_db_kernel<Cfg1024, 3>)); }
 }  // namespace jsg

@@ -8,8 +8,5 @@ namespace jsg {
 #define JSG_IN_UNIT_A(...)
 #define JSG_IN_UNIT_B(...) __VA_ARGS__
 JSG_STFT_VARIANTS(JSG_DEFINE_VARIANT)
-hipError_t touch_module_b() {
-    hipFuncAttributes fa;
-    return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&stft_db_kernel<Cfg4096, 3>));
-}
+hipError_t touch_module_b() { return preload_code_object(reinterpret_cast<const void*>(&stft_db_kernel<Cfg4096, 3>)); }
 }  // namespace jsg

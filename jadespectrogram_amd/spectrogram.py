@@ -255,17 +255,13 @@ class CColorPalette:
 # --------------------------------------------------------------------------------------------------
 # stateless device ops on torch tensors
 # --------------------------------------------------------------------------------------------------
-class Plan:
-    def __init__(self, n: int, window_table: np.ndarray, power_scale: float = 1.0):
-        w = np.ascontiguousarray(window_table, dtype=np.float32)
-        assert w.size == n
-        self._p = C.c_void_p()
-        check(lib().jsg_plan_create(C.byref(self._p), int(n), w.ctypes.data, power_scale))
-        self.n = int(n)
+class _NativeHandle:
+    """One native object behind `_p`, freed by the library call that `_destroy` names."""
+    _destroy: str
 
     def close(self):
         if getattr(self, "_p", None) is not None and self._p:
-            lib().jsg_plan_destroy(self._p)
+            getattr(lib(), self._destroy)(self._p)
             self._p = C.c_void_p()
 
     def __del__(self):
@@ -273,6 +269,46 @@ class Plan:
             self.close()
         except Exception:
             pass
+
+
+class _PerDeviceHandles:
+    """A description on the host and the native objects made from it in `_handles`, one per device: `_create(h)` makes the one of the
+    current device, the library call that `_destroy` names frees one."""
+    _destroy: str
+
+    def handle(self, device: int | None = None) -> C.c_void_p:
+        """The jsg_filterbank / jsg_freq_axis on `device` (default: the current one), created on first use."""
+        import torch
+        dev = torch.cuda.current_device() if device is None else int(device)
+        h = self._handles.get(dev)
+        if h is None:
+            h = C.c_void_p()
+            with torch.cuda.device(dev):
+                self._create(h)
+            self._handles[dev] = h
+        return h
+
+    def close(self):
+        for h in getattr(self, "_handles", {}).values():
+            getattr(lib(), self._destroy)(h)
+        self._handles = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Plan(_NativeHandle):
+    _destroy = "jsg_plan_destroy"
+
+    def __init__(self, n: int, window_table: np.ndarray, power_scale: float = 1.0):
+        w = np.ascontiguousarray(window_table, dtype=np.float32)
+        assert w.size == n
+        self._p = C.c_void_p()
+        check(lib().jsg_plan_create(C.byref(self._p), int(n), w.ctypes.data, power_scale))
+        self.n = int(n)
 
 
 class StftLaunch:
@@ -558,7 +594,7 @@ def db_from_power(d_power, d_out, divisor: float = 1.0, stream: int | None = Non
 # --------------------------------------------------------------------------------------------------
 # filterbank spectrograms: mel and log-frequency rows (include/jsg.h, section 2b)
 # --------------------------------------------------------------------------------------------------
-class Filterbank:
+class Filterbank(_PerDeviceHandles):
     """A sparse, banded filterbank over the n/2+1 bins of an n-point FFT (CSR: band b = weights[offset[b] : offset[b] + n_bins[b]]
     over the bins first_bin[b] ..).  Built on the host by jsg_filterbank_build (no GPU needed) or taken from a dense matrix; uploaded to
     a device once, the first time a launch on that device needs it.
@@ -567,6 +603,7 @@ class Filterbank:
             norm None: NORM_SLANEY for the mel scales (librosa's default), NORM_UNIT_SUM for LOG / LINEAR.
         Filterbank.from_matrix(W)       W [n_bands][n/2+1]: every row keeps the span from its first to its last nonzero
     """
+    _destroy = "jsg_filterbank_destroy"
 
     def __init__(self, n: int, fs: float, n_bands: int, fmin: float = 0.0, fmax: float | None = None, scale: int = capi.FB_MEL_SLANEY,
                  norm: int | None = None):
@@ -616,20 +653,11 @@ class Filterbank:
             out[b, self.first_bin[b]:self.first_bin[b] + self.n_bins[b]] = self.weights[self.offset[b]:self.offset[b] + self.n_bins[b]]
         return out
 
-    def handle(self, device: int | None = None) -> C.c_void_p:
-        """The jsg_filterbank on `device` (default: the current one), created on first use."""
-        import torch
-        dev = torch.cuda.current_device() if device is None else int(device)
-        h = self._handles.get(dev)
-        if h is None:
-            h = C.c_void_p()
-            with torch.cuda.device(dev):
-                if self.spec is not None:
-                    check(lib().jsg_filterbank_create(C.byref(h), C.byref(self.spec)))
-                else:
-                    check(lib().jsg_filterbank_create_matrix(C.byref(h), self.n, self.n_bands, self._dense.ctypes.data))
-            self._handles[dev] = h
-        return h
+    def _create(self, h):
+        if self.spec is not None:
+            check(lib().jsg_filterbank_create(C.byref(h), C.byref(self.spec)))
+        else:
+            check(lib().jsg_filterbank_create_matrix(C.byref(h), self.n, self.n_bands, self._dense.ctypes.data))
 
     def device_weights(self, device: int | None = None) -> np.ndarray:
         """jsg_filterbank_weights of the device object: the bank as the library holds it."""
@@ -637,25 +665,15 @@ class Filterbank:
         check(lib().jsg_filterbank_weights(self.handle(device), out.ctypes.data))
         return out
 
-    def close(self):
-        for h in getattr(self, "_handles", {}).values():
-            lib().jsg_filterbank_destroy(h)
-        self._handles = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # --------------------------------------------------------------------------------------------------
 # display frequency axes: linear / log / mel image rows (include/jsg.h, section 2c)
 # --------------------------------------------------------------------------------------------------
-class FreqAxis:
+class FreqAxis(_PerDeviceHandles):
     """`height` image rows over [fmin, fmax] Hz of an n-point FFT at fs, on a LINEAR, LOG or MEL axis (row 0 = bottom row).  The row
     table is built on the host by jsg_freq_axis_build (no GPU needed); uploaded to a device once, the first time it is used there.
     The defaults (LINEAR over [0, fs/2]) are valid for every scale but LOG, which needs fmin > 0."""
+    _destroy = "jsg_freq_axis_destroy"
 
     def __init__(self, n: int, fs: float, height: int, fmin: float = 0.0, fmax: float | None = None, scale: int = capi.AXIS_LINEAR):
         if fmax is None:
@@ -673,28 +691,8 @@ class FreqAxis:
         """(first_bin, n_bins, interp_t, centre_hz): the row table, height entries each."""
         return self.first_bin, self.n_bins, self.interp_t, self.centres_hz
 
-    def handle(self, device: int | None = None) -> C.c_void_p:
-        """The jsg_freq_axis on `device` (default: the current one), created on first use."""
-        import torch
-        dev = torch.cuda.current_device() if device is None else int(device)
-        h = self._handles.get(dev)
-        if h is None:
-            h = C.c_void_p()
-            with torch.cuda.device(dev):
-                check(lib().jsg_freq_axis_create(C.byref(h), C.byref(self.spec)))
-            self._handles[dev] = h
-        return h
-
-    def close(self):
-        for h in getattr(self, "_handles", {}).values():
-            lib().jsg_freq_axis_destroy(h)
-        self._handles = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _create(self, h):
+        check(lib().jsg_freq_axis_create(C.byref(h), C.byref(self.spec)))
 
 
 def _fb_args(plan: Plan, fb: Filterbank, d_in, hop: int, n_frames: int, d_out, strided: bool, **kw):
@@ -783,8 +781,9 @@ def mel_spectrogram_db(x, fs: float, n_fft: int, hop: int, n_mels: int, fmin: fl
 # --------------------------------------------------------------------------------------------------
 # complex STFT and inverse STFT with any hop (include/jsg.h, section 2d)
 # --------------------------------------------------------------------------------------------------
-class CStftPlan:
+class CStftPlan(_NativeHandle):
     """jsg_cstft: window, twiddle tables and w^2 for one FFT size, resident on the current device."""
+    _destroy = "jsg_cstft_destroy"
 
     def __init__(self, n: int, window_table: np.ndarray):
         import torch
@@ -795,17 +794,6 @@ class CStftPlan:
         check(lib().jsg_cstft_create(C.byref(self._p), int(n), w.ctypes.data))
         self.n = int(n)
         self.device = torch.cuda.current_device()
-
-    def close(self):
-        if getattr(self, "_p", None) is not None and self._p:
-            lib().jsg_cstft_destroy(self._p)
-            self._p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _rows3(t, what: str):
