@@ -46,7 +46,8 @@ extern "C" {
                                   additions to 6: filterbank spectrograms (jsg_filterbank_*, jsg_stft_fb_*; section 2b),
                                   display frequency axes (jsg_freq_axis_*, jsg_colormap_axis_launch, jsg_display_set_freq_axis,
                                   jsg_display_height, jsg_display_axis_centres; section 2c),
-                                  complex STFT and inverse STFT with any hop (jsg_cstft_*, jsg_istft_*; section 2d) */
+                                  complex STFT and inverse STFT with any hop (jsg_cstft_*, jsg_istft_*; section 2d); additive since: the
+                                 phase vocoder (jsg_pvoc_*; section 2e) */
 
 typedef enum jsg_status {
     JSG_OK = 0,
@@ -495,6 +496,52 @@ JSG_API int jsg_istft_launch(const jsg_cstft* plan, const jsg_istft_args* args, 
 /* A recommended scratch size (floats): the whole call where it fits 64 MiB, otherwise 64 MiB worth of frames (at least the minimum
  * above).  < 0: the call would be refused. */
 JSG_API int64_t jsg_istft_scratch_floats(const jsg_cstft* plan, const jsg_istft_args* args);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2e. Phase vocoder (time stretch between jsg_cstft_launch and jsg_istft_launch; torchaudio.functional.phase_vocoder's formula).
+ *
+ *     Input X[r][j][k], complex64, frame-major with the pitches of section 2d: T frames of K = n/2+1 bins, taken with hop `hop` and
+ *     FFT size n.  Output frame i sits at time t_i = (double)i * rate (one IEEE multiply); there are T_out = #{i >= 0 : t_i < T} of
+ *     them (jsg_pvoc_frames).  With j = floor(t_i), alpha = (float)(t_i - j), a0 = X[j], a1 = X[j+1] (frames at index >= T are zero):
+ *         mag_i = alpha |a1| + (1 - alpha) |a0|                                   (float32)
+ *         d_i   = wrap(arg a1 - arg a0 - A_k) + A_k,  A_k = 2 pi hop k / n,  wrap(x) = x - 2 pi round(x / 2 pi)
+ *         phi_0 = arg X[0],  phi_i = phi_(i-1) + d_(i-1)
+ *         Y[r][i][k] = mag_i (cos phi_i, sin phi_i)
+ *     The phase arithmetic is exact by construction.  Only phi mod 2 pi matters, so the library works in turns: the advance is
+ *     frac(hop k / n), taken from the integer (hop k) mod n in double; (arg a1 - arg a0) is a float32 difference times the float32
+ *     1 / (2 pi), widened to double; the advance is subtracted, round() of the result is subtracted, the advance is added back; the
+ *     increment becomes fixed point with llrint(u * 2^32) and is accumulated in uint32_t with its natural wrap-around (2^32 units are
+ *     one turn); phi_0 is converted the same way.  sincosf receives (float)(int32_t)acc * (2 pi / 2^32).  Integer addition is
+ *     associative, so every chunk length, grid, row count and pitch gives the same bits, and a large hop * k causes no drift
+ *     however long the input.  atan2f and sincosf are the device library's, so there is no bit-exact CPU mirror: the contract is a
+ *     tolerance against a float64 evaluation of the formulas above.
+ * ------------------------------------------------------------------------------------------------ */
+/* T_out for T = n_frames_in (1..2^31-1) and a finite rate > 0.  JSG_ERR_INVALID for other arguments or a T_out above 2^31-1. */
+JSG_API int64_t jsg_pvoc_frames(int64_t n_frames_in, double rate);
+
+typedef struct jsg_pvoc_args {
+    const float* in;            /* device complex bins (float pairs), 8-byte aligned */
+    int64_t in_frame_pitch;     /* complex elements between frames (>= n/2+1) */
+    int64_t in_row_pitch;       /* complex elements between rows (rows > 1: >= (n_frames_in-1)*in_frame_pitch + n/2+1) */
+    int32_t rows;               /* 1..65535 */
+    int32_t n;                  /* FFT size of the frames: any even number in 2..65536 (no transform is done here) */
+    int32_t hop;                /* analysis hop, 1..n */
+    int64_t n_frames_in;        /* T, 1..2^31-1 */
+    double rate;                /* finite, > 0; > 1 shortens */
+    float* out;                 /* device complex bins, 8-byte aligned, not overlapping `in` */
+    int64_t out_frame_pitch;    /* >= n/2+1; elements between the bins of two frames are not written */
+    int64_t out_row_pitch;      /* rows > 1: >= (n_frames_out-1)*out_frame_pitch + n/2+1 */
+    int64_t n_frames_out;       /* must equal jsg_pvoc_frames(n_frames_in, rate) */
+    int32_t chunk_frames;       /* output frames per chunk: 0 = the library's choice, else 1..65536; the result does not depend on it */
+} jsg_pvoc_args;
+/* Bytes of scratch the call needs (4 bytes per row, chunk and bin, rounded up to 16).  < 0: the call would be refused.  Needs no device. */
+JSG_API int64_t jsg_pvoc_scratch_bytes(const jsg_pvoc_args* args);
+/* Enqueue only (three kernels: chunk sums, their prefixes, the output): no allocation, no synchronisation; hipGraph capture works.
+ * `scratch`: device memory, 16-byte aligned, layout private to the library.  Refused (JSG_ERR_INVALID, nothing enqueued,
+ * jsg_last_error set): null pointers, in or out not 8-byte aligned, n, hop, rows, n_frames_in or chunk_frames outside their ranges,
+ * a rate that is not finite or <= 0, a T_out above 2^31-1, n_frames_out != T_out, pitches smaller than above, out overlapping in,
+ * scratch that is null, not 16-byte aligned or smaller than jsg_pvoc_scratch_bytes.  JSG_ERR_NO_DEVICE without a HIP device. */
+JSG_API int jsg_pvoc_launch(const jsg_pvoc_args* args, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 3. Engine: the state of class Spectrogram (Spectrogram.h:81-169) living on the GPU.

@@ -75,6 +75,12 @@ class IstftArgs(C.Structure):
                 ("hop", C.c_int32), ("n_frames", C.c_int64), ("out", C.c_void_p), ("out_pitch", C.c_int64), ("out_samples", C.c_int64)]
 
 
+class PvocArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("in_frame_pitch", C.c_int64), ("in_row_pitch", C.c_int64), ("rows", C.c_int32), ("n", C.c_int32),
+                ("hop", C.c_int32), ("n_frames_in", C.c_int64), ("rate", C.c_double), ("out", C.c_void_p), ("out_frame_pitch", C.c_int64),
+                ("out_row_pitch", C.c_int64), ("n_frames_out", C.c_int64), ("chunk_frames", C.c_int32)]
+
+
 class StftImageArgs(C.Structure):
     _fields_ = [("stft", StftArgs), ("colour", ColormapArgs), ("index_scratch", C.c_void_p), ("index_scratch_pitch", C.c_int64)]
 
@@ -132,6 +138,9 @@ SIGNATURES = {
     "jsg_istft_nola": (C.c_int, [C.c_int, C.c_int, _P, C.POINTER(C.c_float)]),
     "jsg_istft_launch": (C.c_int, [_P, C.POINTER(IstftArgs), _P, C.c_int64, _P]),
     "jsg_istft_scratch_floats": (C.c_int64, [_P, C.POINTER(IstftArgs)]),
+    "jsg_pvoc_frames": (C.c_int64, [C.c_int64, C.c_double]),
+    "jsg_pvoc_scratch_bytes": (C.c_int64, [C.POINTER(PvocArgs)]),
+    "jsg_pvoc_launch": (C.c_int, [C.POINTER(PvocArgs), _P, C.c_int64, _P]),
     "jsg_create": (C.c_int, [C.POINTER(_P), C.c_int]),
     "jsg_create_on_device": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int]),
     "jsg_get_device": (C.c_int, [_P]),

@@ -973,3 +973,71 @@ def istft(X, n_fft: int, hop_length: int | None = None, win_length: int | None =
     if end > stop:
         y = Fn.pad(y, (0, end - stop))
     return y.contiguous().reshape(*batch, -1)
+
+
+# --------------------------------------------------------------------------------------------------
+# phase vocoder and time stretch (include/jsg.h, section 2e)
+# --------------------------------------------------------------------------------------------------
+def pvoc_frames(n_frames: int, rate: float) -> int:
+    """jsg_pvoc_frames: the number of output frames i >= 0 with float(i) * rate < n_frames."""
+    return int(check(lib().jsg_pvoc_frames(int(n_frames), float(rate))))
+
+
+def _pvoc_args(d_X, rate: float, hop: int, n: int, d_out, chunk_frames: int) -> capi.PvocArgs:
+    import torch
+    X, Y = _rows3(d_X, "d_X"), _rows3(d_out, "d_out")
+    assert X.is_cuda and X.dtype == torch.complex64 and X.stride(2) == 1, "d_X: complex64 CUDA [rows][frames][>= n/2+1]"
+    assert Y.is_cuda and Y.dtype == torch.complex64 and Y.stride(2) == 1 and Y.shape[0] == X.shape[0], "d_out: complex64 CUDA [rows][frames][>= n/2+1]"
+    return capi.PvocArgs(X.data_ptr(), X.stride(1), X.stride(0), X.shape[0], int(n), int(hop), X.shape[1], float(rate),
+                         Y.data_ptr(), Y.stride(1), Y.stride(0), Y.shape[1], int(chunk_frames))
+
+
+def phase_vocoder_launch(d_X, rate: float, hop: int, n: int, d_out, *, chunk_frames: int = 0, d_scratch=None, stream: int | None = None):
+    """jsg_pvoc_launch: d_X complex64 [rows][T][>= n/2+1] (frames taken with `hop` at FFT size n) -> d_out complex64
+    [rows][pvoc_frames(T, rate)][>= n/2+1], torchaudio.functional.phase_vocoder's formula with the phase summed exactly.  chunk_frames
+    (0: the library's choice) never changes the result.  d_scratch: a contiguous CUDA tensor of at least jsg_pvoc_scratch_bytes bytes
+    (None: one is allocated with torch for this call)."""
+    import torch
+    a = _pvoc_args(d_X, rate, hop, n, d_out, chunk_frames)
+    temporary = d_scratch is None
+    if temporary:
+        d_scratch = torch.empty(int(check(lib().jsg_pvoc_scratch_bytes(C.byref(a)))) // 4, dtype=torch.int32, device=d_out.device)
+    assert d_scratch.is_cuda and d_scratch.is_contiguous()
+    if stream is None:
+        stream = torch.cuda.current_stream(d_out.device).cuda_stream
+    elif temporary:   # the caching allocator must not hand the block out again before the launch on the caller's stream is done
+        d_scratch.record_stream(torch.cuda.ExternalStream(stream, device=d_out.device))
+    check(lib().jsg_pvoc_launch(C.byref(a), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), C.c_void_p(stream)))
+
+
+def phase_vocoder(X, rate: float, hop_length: int, n_fft: int | None = None):
+    """torchaudio.functional.phase_vocoder on the GPU: X complex CUDA [..., bins, frames] -> complex64 [..., bins, pvoc_frames(frames,
+    rate)] (the transposed view of the library's frame-major buffer, as stft returns).  n_fft defaults to 2 * (bins - 1)."""
+    import torch
+    assert X.is_cuda and X.is_complex(), "phase_vocoder: X must be a complex CUDA tensor"
+    bins, frames = int(X.shape[-2]), int(X.shape[-1])
+    n = 2 * (bins - 1) if n_fft is None else int(n_fft)
+    if bins != n // 2 + 1:
+        raise JsgError(capi.JSG_ERR_INVALID, f"phase_vocoder: {bins} bins, expected n_fft//2+1 = {n // 2 + 1}")
+    batch = tuple(X.shape[:-2])
+    Xf = X.to(torch.complex64).transpose(-1, -2).reshape(-1, frames, bins)
+    if Xf.stride(2) != 1:
+        Xf = Xf.contiguous()
+    out = torch.empty((Xf.shape[0], pvoc_frames(frames, rate), bins), dtype=torch.complex64, device=X.device)
+    dev = X.device.index if X.device.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(dev):
+        phase_vocoder_launch(Xf, rate, hop_length, n, out)
+    return out.reshape(*batch, out.shape[1], bins).transpose(-1, -2)
+
+
+def time_stretch(x, rate: float, n_fft: int = 2048, hop_length: int | None = None, win_length: int | None = None, window=None,
+                 center: bool = True, length: int | None = None):
+    """Time stretch without a change of pitch (rate > 1 shortens): x float32 CUDA [..., L] -> float32 [..., length or round(L / rate)].
+    Exactly istft(phase_vocoder(stft(x, ...), rate, hop), ..., length=length or round(L / rate)) with the same n_fft, hop, win_length,
+    window and center on both sides.  window = None means a Hann window here, unlike stft and istft: a rectangular window at hop
+    n_fft / 4 is a poor default for resynthesis."""
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    w = capi.WIN_HANN if window is None else window
+    X = stft(x, n_fft, hop, win_length, w, center)
+    Y = phase_vocoder(X, rate, hop, n_fft)
+    return istft(Y, n_fft, hop, win_length, w, center, length=length or int(round(x.shape[-1] / rate)))
