@@ -53,8 +53,27 @@ def colormap_range(n_colors: int, lo: float, hi: float):
 # --------------------------------------------------------------------------------------------------
 # class Spectrogram
 # --------------------------------------------------------------------------------------------------
-class Spectrogram:
+class _NativeHandle:
+    """One native object behind the attribute that `_handle` names, freed by the library call that `_destroy` names."""
+    _destroy: str
+    _handle = "_p"
+
+    def close(self):
+        p = getattr(self, self._handle, None)
+        if p:
+            getattr(lib(), self._destroy)(p)
+            setattr(self, self._handle, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Spectrogram(_NativeHandle):
     """Drop-in mirror of the reference's `Spectrogram` (engine half).  The channel count is explicit."""
+    _destroy, _handle = "jsg_destroy", "_h"
 
     ChannelMixMode = type("ChannelMixMode", (), dict(AbsMean=0, Max=1, Min=2, Left=3, Right=4, PerChannel=100))
     Windows = type("Windows", (), dict(Rect=0, Hann=1, Hamming=2, BlackmanHarris=3, FlatTop=4, HannPoisson=5))
@@ -63,17 +82,6 @@ class Spectrogram:
     def __init__(self, channels: int = 2):
         self._h = C.c_void_p()
         check(lib().jsg_create(C.byref(self._h), int(channels)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            lib().jsg_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _c(self, rc):
         return check(rc, self._h)
@@ -255,22 +263,6 @@ class CColorPalette:
 # --------------------------------------------------------------------------------------------------
 # stateless device ops on torch tensors
 # --------------------------------------------------------------------------------------------------
-class _NativeHandle:
-    """One native object behind `_p`, freed by the library call that `_destroy` names."""
-    _destroy: str
-
-    def close(self):
-        if getattr(self, "_p", None) is not None and self._p:
-            getattr(lib(), self._destroy)(self._p)
-            self._p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 class _PerDeviceHandles:
     """A description on the host and the native objects made from it in `_handles`, one per device: `_create(h)` makes the one of the
     current device, the library call that `_destroy` names frees one."""
@@ -311,6 +303,42 @@ class Plan(_NativeHandle):
         self.n = int(n)
 
 
+def _stream_handle(stream, tensor) -> C.c_void_p:
+    """The caller's stream, or torch's current stream on the device of `tensor`, as the library takes it."""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream(tensor.device).cuda_stream
+    return C.c_void_p(stream)
+
+
+def _device_index(tensor) -> int:
+    """The index of the tensor's device (a bare "cuda" device: the current one)."""
+    if tensor.device.index is not None:
+        return tensor.device.index
+    import torch
+    return torch.cuda.current_device()
+
+
+def _scratch_and_stream(d_scratch, stream, tensor, count, dtype, any_dtype: bool = False):
+    """(scratch, stream handle) of a launch that works through scratch memory, on the device of `tensor`.  d_scratch None: count()
+    elements of `dtype` are allocated with torch for this call."""
+    import torch
+    temporary = d_scratch is None
+    if temporary:
+        d_scratch = torch.empty(int(count()), dtype=dtype, device=tensor.device)
+    assert d_scratch.is_cuda and d_scratch.is_contiguous() and (any_dtype or d_scratch.dtype == dtype)
+    if temporary and stream is not None:   # the caching allocator must not hand the block out again before the launch on the caller's stream is done
+        d_scratch.record_stream(torch.cuda.ExternalStream(stream, device=tensor.device))
+    return d_scratch, _stream_handle(stream, tensor)
+
+
+def _kernel_name(query, *args) -> str:
+    """The text a jsg_*_kernel_name query writes for `args`."""
+    buf = C.create_string_buffer(32)
+    check(query(*args, buf, 32))
+    return buf.value.decode()
+
+
 class StftLaunch:
     """A prepared launch: the argument block is filled once, `launch(stream)` is then a single FFI call
     (the per-call Python work of stft_db() is ~2 us, comparable to a short kernel)."""
@@ -334,19 +362,15 @@ def stft_db(plan: Plan, d_in, hop: int, n_frames: int, d_out, *, feedblocks: int
     """Enqueue one fused STFT->dB launch.  d_in: torch CUDA float32 [C][samples]; d_out: [W][pitch] (or
     [C][W][pitch] with mix_mode PER_CHANNEL).  Frame j starts at sample (j//feedblocks)*n + (j%feedblocks)*hop.
     d_tail: see _stft_args (jsg_stft_args.out_tail: bin n/2 in a dense plane, columns of n/2 floats)."""
-    import torch
     a = _stft_args(plan, d_in, hop, n_frames, d_out, feedblocks=feedblocks, mix_mode=mix_mode, first_frame=first_frame,
                    ring_pos=ring_pos, linear_out=linear_out, blocks_per_cu=blocks_per_cu, plan_select=plan_select, exact_log=exact_log, d_tail=d_tail)
-    if stream is None:
-        stream = torch.cuda.current_stream(d_in.device).cuda_stream
-    check(lib().jsg_stft_db_launch(plan._p, C.byref(a), C.c_void_p(stream)))
+    check(lib().jsg_stft_db_launch(plan._p, C.byref(a), _stream_handle(stream, d_in)))
 
 
 def columns_from_tail_layout(d_db, d_tail, d_dst, *, n: int | None = None, stream: int | None = None):
     """jsg_columns_from_tail_layout_launch: d_db [W][pitch >= n/2] + d_tail [W] (the tail-plane layout of stft_db(..., d_tail=)) -> d_dst [W][>= n/2+1],
     the reference's dense column shape (what getMem hands out).  `n` = the FFT size (a Plan's .n); without it the rows of d_db must be
     exactly n/2 floats wide (the shape stft_db's tail layout is normally given) -- the height is never guessed from padded rows."""
-    import torch
     assert d_db.is_cuda and d_tail.is_cuda and d_dst.is_cuda and d_db.dim() == 2 and d_dst.dim() == 2 and d_db.stride(1) == 1 and d_dst.stride(1) == 1
     W = d_db.shape[0]
     assert d_tail.numel() == W and d_tail.is_contiguous() and d_dst.shape[0] == W
@@ -357,22 +381,18 @@ def columns_from_tail_layout(d_db, d_tail, d_dst, *, n: int | None = None, strea
     H = n // 2 + 1
     if d_db.shape[1] < H - 1 or d_dst.shape[1] < H:
         raise JsgError(capi.JSG_ERR_INVALID, f"columns_from_tail_layout: n = {n} needs source rows of >= {H - 1} and destination rows of >= {H} floats")
-    if stream is None:
-        stream = torch.cuda.current_stream(d_db.device).cuda_stream
-    check(lib().jsg_columns_from_tail_layout_launch(d_db.data_ptr(), d_db.stride(0), d_tail.data_ptr(), W, H, d_dst.data_ptr(), d_dst.stride(0), C.c_void_p(stream)))
+    check(lib().jsg_columns_from_tail_layout_launch(d_db.data_ptr(), d_db.stride(0), d_tail.data_ptr(), W, H, d_dst.data_ptr(), d_dst.stride(0),
+                                                    _stream_handle(stream, d_db)))
 
 
 def stft_db_batches(plan: Plan, batches, hop: int, n_frames: int, *, stream: int | None = None, **kw):
     """jsg_stft_db_launch_batches: `batches` = [(d_in, d_out), ...] independent launches of the same geometry, stream-ordered with
     respect to `stream` like one launch but overlapped on the library's own working streams (include/jsg.h)."""
-    import torch
     arr = (capi.StftArgs * len(batches))()
     for i, (d_in, d_out) in enumerate(batches):
         a = _stft_args(plan, d_in, hop, n_frames, d_out, **kw)
         C.memmove(C.byref(arr, i * C.sizeof(capi.StftArgs)), C.byref(a), C.sizeof(capi.StftArgs))
-    if stream is None:
-        stream = torch.cuda.current_stream(batches[0][0].device).cuda_stream
-    check(lib().jsg_stft_db_launch_batches(plan._p, arr, len(batches), C.c_void_p(stream)))
+    check(lib().jsg_stft_db_launch_batches(plan._p, arr, len(batches), _stream_handle(stream, batches[0][0])))
 
 
 def _strided_args(plan: Plan, d_in, hop: int, n_frames: int, d_out, **kw):
@@ -384,28 +404,47 @@ def _strided_args(plan: Plan, d_in, hop: int, n_frames: int, d_out, **kw):
 
 def stft_db_strided(plan: Plan, d_in, hop: int, n_frames: int, d_out, *, stream: int | None = None, **kw):
     """jsg_stft_db_launch_strided: k independent batches of one geometry in ONE kernel launch on one stream (include/jsg.h)."""
-    import torch
     a, k, s_in, s_out = _strided_args(plan, d_in, hop, n_frames, d_out, **kw)
-    if stream is None:
-        stream = torch.cuda.current_stream(d_in.device).cuda_stream
-    check(lib().jsg_stft_db_launch_strided(plan._p, C.byref(a), k, s_in, s_out, C.c_void_p(stream)))
+    check(lib().jsg_stft_db_launch_strided(plan._p, C.byref(a), k, s_in, s_out, _stream_handle(stream, d_in)))
 
 
 def stft_db_strided_kernel_name(plan: Plan, d_in, hop: int, n_frames: int, d_out, **kw) -> str:
     """The kernel every launch of a strided call takes: as stft_kernel_name, judged by the frames of the whole call (Max / Min, which go
     out batch by batch: of one batch)."""
     a, k, s_in, _ = _strided_args(plan, d_in, hop, n_frames, d_out, **kw)
-    buf = C.create_string_buffer(32)
-    check(lib().jsg_stft_db_strided_kernel_name(plan._p, C.byref(a), k, s_in, buf, 32))
-    return buf.value.decode()
+    return _kernel_name(lib().jsg_stft_db_strided_kernel_name, plan._p, C.byref(a), k, s_in)
 
 
 def stft_kernel_name(plan: Plan, d_in, hop: int, n_frames: int, d_out, **kw) -> str:
     """The kernel configuration jsg_stft_db_launch picks for this launch ("Cfg1024", "Cfg2048B", ...)."""
     a = _stft_args(plan, d_in, hop, n_frames, d_out, **kw)
-    buf = C.create_string_buffer(32)
-    check(lib().jsg_stft_kernel_name(plan._p, C.byref(a), buf, 32))
-    return buf.value.decode()
+    return _kernel_name(lib().jsg_stft_kernel_name, plan._p, C.byref(a))
+
+
+def _stft_input_args(plan: Plan, d_in, hop, n_frames, ring_width, feedblocks, mix_mode, first_frame, ring_pos, linear_out, blocks_per_cu,
+                     plan_select, exact_log) -> capi.StftArgs:
+    """jsg_stft_args without its output pointers and pitches: the input rows, the framing, the ring geometry and the kernel switches."""
+    import torch
+    assert d_in.is_cuda and d_in.dtype == torch.float32 and d_in.dim() == 2 and d_in.stride(1) == 1
+    channels, samples = d_in.shape
+    a = capi.StftArgs()
+    a.in_ = d_in.data_ptr()
+    a.in_pitch = d_in.stride(0) if channels > 1 else samples
+    a.in_samples = samples            # the launcher refuses frames that would read past the rows
+    a.channels = channels
+    a.hop = hop
+    a.feedblocks = feedblocks if feedblocks is not None else max(1, plan.n // hop)
+    a.mix_mode = mix_mode
+    a.first_frame = first_frame
+    a.n_frames = n_frames
+    a.ring_width = ring_width
+    a.ring_pos = ring_pos
+    a.linear_out = bool(linear_out)
+    a.blocks_per_cu = int(blocks_per_cu)
+    a.exact_log = bool(exact_log)          # dB by the shared float32 routine (bit-reproducible on a CPU) instead of v_log_f32
+    a.plan_select = int(plan_select)       # 0 automatic, 1 small-workgroup kernel, 2 "B" kernel (2048 / 4096 points), 3 pair plan (2048 points, even channel
+                                           # counts, sum-type mixes); 1024 points: 2 = the two-stage kernel Cfg1024B (include/jsg.h)
+    return a
 
 
 def _stft_args(plan: Plan, d_in, hop: int, n_frames: int, d_out, *, feedblocks: int | None = None, mix_mode: int = 0,
@@ -414,36 +453,20 @@ def _stft_args(plan: Plan, d_in, hop: int, n_frames: int, d_out, *, feedblocks: 
     """d_tail (jsg_stft_args.out_tail): float32 CUDA tensor of rows x W floats (rows = 1, or channels in per-channel mode, times the batches
     of a strided launch), contiguous -- bin n/2 of every column goes there and a column of d_out is then n/2 floats.
     col_height: floats a column of d_out needs (default: the bins of the plan; the band count of a filterbank launch)."""
-    import torch
-    assert d_in.is_cuda and d_in.dtype == torch.float32 and d_in.dim() == 2 and d_in.stride(1) == 1
-    assert d_out.is_cuda and d_out.dtype == torch.float32 and d_out.stride(-1) == 1
+    a = _stft_input_args(plan, d_in, hop, n_frames, d_out.shape[-2], feedblocks, mix_mode, first_frame, ring_pos, linear_out, blocks_per_cu,
+                         plan_select, exact_log)
+    float32 = d_in.dtype               # (checked just above)
+    assert d_out.is_cuda and d_out.dtype == float32 and d_out.stride(-1) == 1
     H = (plan.n // 2 + 1 - (1 if d_tail is not None else 0)) if col_height is None else int(col_height)
     if d_out.shape[-1] < H:
         raise JsgError(capi.JSG_ERR_INVALID, f"output rows hold {d_out.shape[-1]} floats, a column needs {H}")
-    if mix_mode == capi.MIX_PER_CHANNEL and (d_out.dim() != 3 or d_out.shape[0] != d_in.shape[0]):
+    if mix_mode == capi.MIX_PER_CHANNEL and (d_out.dim() != 3 or d_out.shape[0] != a.channels):
         raise JsgError(capi.JSG_ERR_INVALID, "per-channel mode needs an output of [channels][W][pitch]")
-    a = capi.StftArgs()
-    a.in_ = d_in.data_ptr()
-    a.in_pitch = d_in.stride(0) if d_in.shape[0] > 1 else d_in.shape[1]
-    a.in_samples = d_in.shape[1]      # the launcher refuses frames that would read past the rows
-    a.channels = d_in.shape[0]
-    a.hop = hop
-    a.feedblocks = feedblocks if feedblocks is not None else max(1, plan.n // hop)
-    a.mix_mode = mix_mode
-    a.first_frame = first_frame
-    a.n_frames = n_frames
     a.out_db = d_out.data_ptr()
     a.out_pitch = d_out.stride(-2)
     a.out_channel_pitch = d_out.stride(0) if d_out.dim() == 3 else 0
-    a.ring_width = d_out.shape[-2]
-    a.ring_pos = ring_pos
-    a.linear_out = int(bool(linear_out))
-    a.blocks_per_cu = int(blocks_per_cu)
-    a.exact_log = int(bool(exact_log))     # dB by the shared float32 routine (bit-reproducible on a CPU) instead of v_log_f32
-    a.plan_select = int(plan_select)       # 0 automatic, 1 small-workgroup kernel, 2 "B" kernel (2048 / 4096 points), 3 pair plan (2048 points, even channel
-                                           # counts, sum-type mixes); 1024 points: 2 = the two-stage kernel Cfg1024B (include/jsg.h)
     if d_tail is not None:
-        assert d_tail.is_cuda and d_tail.dtype == torch.float32 and d_tail.is_contiguous() and d_tail.shape[-1] == d_out.shape[-2]
+        assert d_tail.is_cuda and d_tail.dtype == float32 and d_tail.is_contiguous() and d_tail.shape[-1] == a.ring_width
         a.out_tail = d_tail.data_ptr()
     return a
 
@@ -451,35 +474,29 @@ def _stft_args(plan: Plan, d_in, hop: int, n_frames: int, d_out, *, feedblocks: 
 def colormap(d_db, d_lut, lo: float, hi: float, *, d_argb=None, d_index=None, col_first: int = 0, n_cols: int | None = None,
              x_first: int = 0, height: int | None = None, stream: int | None = None):
     """Enqueue the colour loop: d_db [W][pitch] float32 CUDA -> d_argb [H][Wimg] int32/uint32 and/or d_index uint8."""
-    import torch
     a = _colormap_args(d_db, d_lut, lo, hi, d_argb, d_index, col_first, n_cols, x_first, height)
-    if stream is None:
-        stream = torch.cuda.current_stream(d_db.device).cuda_stream
-    check(lib().jsg_colormap_launch(C.byref(a), C.c_void_p(stream)))
+    check(lib().jsg_colormap_launch(C.byref(a), _stream_handle(stream, d_db)))
 
 
 def colormap_axis(d_db, d_lut, lo: float, hi: float, axis: "FreqAxis", *, d_argb=None, d_index=None, col_first: int = 0,
                   n_cols: int | None = None, x_first: int = 0, stream: int | None = None):
     """colormap() over the rows of a FreqAxis: d_db [W][pitch >= n/2+1] float32 CUDA -> d_argb / d_index of axis.height rows."""
-    import torch
     a = _colormap_args(d_db, d_lut, lo, hi, d_argb, d_index, col_first, n_cols, x_first, axis.n // 2 + 1)
-    if stream is None:
-        stream = torch.cuda.current_stream(d_db.device).cuda_stream
-    check(lib().jsg_colormap_axis_launch(C.byref(a), axis.handle(d_db.device.index), C.c_void_p(stream)))
+    check(lib().jsg_colormap_axis_launch(C.byref(a), axis.handle(d_db.device.index), _stream_handle(stream, d_db)))
 
 
-def _colormap_args(d_db, d_lut, lo, hi, d_argb, d_index, col_first, n_cols, x_first, height) -> capi.ColormapArgs:
+def _colour_args(ring_width, height, col_first, n_cols, x_first, d_lut, lo, hi, d_argb, d_index) -> capi.ColormapArgs:
+    """jsg_colormap_args without its dB ring: the columns, the palette with its range, and the image(s) they go to."""
     a = capi.ColormapArgs()
-    a.db = d_db.data_ptr()
-    a.db_pitch = d_db.stride(0)
-    a.ring_width = d_db.shape[0]
-    a.height = height if height is not None else d_db.shape[1]
+    a.ring_width = ring_width
+    a.height = height
     a.col_first = col_first
-    a.n_cols = n_cols if n_cols is not None else d_db.shape[0]
+    a.n_cols = n_cols
     a.x_first = x_first
     a.lut = d_lut.data_ptr()
     a.n_colors = d_lut.numel()
-    a.vmin, a.vmax, a.access_mult = (float(v) for v in colormap_range(a.n_colors, lo, hi))
+    F = capi.ColormapArgs       # the library writes the range straight into the block
+    check(lib().jsg_colormap_range(a.n_colors, lo, hi, C.byref(a, F.vmin.offset), C.byref(a, F.vmax.offset), C.byref(a, F.access_mult.offset)))
     if d_argb is not None:
         a.argb_out = d_argb.data_ptr()
         a.argb_pitch = d_argb.stride(0)
@@ -491,46 +508,26 @@ def _colormap_args(d_db, d_lut, lo, hi, d_argb, d_index, col_first, n_cols, x_fi
     return a
 
 
+def _colormap_args(d_db, d_lut, lo, hi, d_argb, d_index, col_first, n_cols, x_first, height) -> capi.ColormapArgs:
+    a = _colour_args(d_db.shape[0], height if height is not None else d_db.shape[1], col_first, n_cols if n_cols is not None else d_db.shape[0],
+                     x_first, d_lut, lo, hi, d_argb, d_index)
+    a.db = d_db.data_ptr()
+    a.db_pitch = d_db.stride(0)
+    return a
+
+
 def _stft_image_args(plan: Plan, d_in, hop: int, n_frames: int, d_lut, lo: float, hi: float, d_argb, d_index_scratch, *,
                      feedblocks: int | None = None, mix_mode: int = 0, first_frame: int = 0, ring_pos: int = 0,
                      ring_width: int | None = None, x_first: int | None = None, plan_select: int = 0, exact_log: bool = False,
                      blocks_per_cu: int = 0):
-    import torch
     assert d_argb.is_cuda and d_argb.element_size() == 4 and d_argb.dim() == 2 and d_argb.stride(1) == 1
     if d_index_scratch is not None:
+        import torch
         assert d_index_scratch.is_cuda and d_index_scratch.dtype == torch.uint8 and d_index_scratch.dim() == 2 and d_index_scratch.stride(1) == 1
     W = ring_width if ring_width is not None else (d_index_scratch.shape[0] if d_index_scratch is not None else n_frames)
     a = capi.StftImageArgs()
-    H = plan.n // 2 + 1
-    st = capi.StftArgs()
-    st.in_ = d_in.data_ptr()
-    st.in_pitch = d_in.stride(0) if d_in.shape[0] > 1 else d_in.shape[1]
-    st.in_samples = d_in.shape[1]
-    st.channels = d_in.shape[0]
-    st.hop = hop
-    st.feedblocks = feedblocks if feedblocks is not None else max(1, plan.n // hop)
-    st.mix_mode = mix_mode
-    st.first_frame = first_frame
-    st.n_frames = n_frames
-    st.ring_width = W
-    st.ring_pos = ring_pos
-    st.plan_select = int(plan_select)
-    st.exact_log = int(bool(exact_log))
-    st.blocks_per_cu = int(blocks_per_cu)
-    a.stft = st
-    c = capi.ColormapArgs()
-    c.ring_width = W
-    c.height = H
-    c.col_first = ring_pos
-    c.n_cols = n_frames
-    c.x_first = ring_pos if x_first is None else x_first
-    c.x_wrap = d_argb.shape[1]
-    c.lut = d_lut.data_ptr()
-    c.n_colors = d_lut.numel()
-    c.vmin, c.vmax, c.access_mult = (float(v) for v in colormap_range(c.n_colors, lo, hi))
-    c.argb_out = d_argb.data_ptr()
-    c.argb_pitch = d_argb.stride(0)
-    a.colour = c
+    a.stft = _stft_input_args(plan, d_in, hop, n_frames, W, feedblocks, mix_mode, first_frame, ring_pos, False, blocks_per_cu, plan_select, exact_log)
+    a.colour = _colour_args(W, plan.n // 2 + 1, ring_pos, n_frames, ring_pos if x_first is None else x_first, d_lut, lo, hi, d_argb, None)
     if d_index_scratch is not None:
         a.index_scratch = d_index_scratch.data_ptr()
         a.index_scratch_pitch = d_index_scratch.stride(0)
@@ -544,11 +541,8 @@ def stft_image(plan: Plan, d_in, hop: int, n_frames: int, d_lut, lo: float, hi: 
     the "B" kernel), else two kernels through d_index_scratch (uint8 [ring_width][pitch >= n/2+1]; stft_image_needs_scratch()).
     The image equals stft_db() + colormap() bit for bit, with the same plan_select -- except at 1024 points, where the display launches
     always take the three-stage arithmetic: the image is that of stft_db(plan_select=1) + colormap() whatever plan_select says."""
-    import torch
     a = _stft_image_args(plan, d_in, hop, n_frames, d_lut, lo, hi, d_argb, d_index_scratch, **kw)
-    if stream is None:
-        stream = torch.cuda.current_stream(d_in.device).cuda_stream
-    check(lib().jsg_stft_image_launch(plan._p, C.byref(a), C.c_void_p(stream)))
+    check(lib().jsg_stft_image_launch(plan._p, C.byref(a), _stream_handle(stream, d_in)))
 
 
 def stft_image_needs_scratch(plan: Plan, d_in, hop: int, n_frames: int, d_lut, lo: float, hi: float, d_argb, d_index_scratch=None, **kw) -> bool:
@@ -562,15 +556,12 @@ def stft_image_strided(plan: Plan, d_in, hop: int, n_frames: int, d_lut, lo: flo
     """`k` images of one geometry from one call (jsg_stft_image_launch_strided): d_in float32 [k][channels][samples], d_argb
     int32 / uint32 [k][n/2+1][Wimg].  One kernel launch for all of them where the single-kernel form applies to the total size
     (stft_image_strided_needs_scratch() tells), else k launches in stream order."""
-    import torch
     assert d_in.dim() == 3 and d_argb.dim() == 3 and d_in.shape[0] == d_argb.shape[0] and d_in.stride(2) == 1 and d_argb.stride(2) == 1
     assert d_argb.shape[1] >= plan.n // 2 + 1, "image rows: one per bin"
     assert d_in.shape[0] == 1 or d_in.stride(0) == 0 or d_in.stride(0) >= (d_in.shape[1] - 1) * d_in.stride(1) + d_in.shape[2], "images overlap in the input"
     a = _stft_image_args(plan, d_in[0], hop, n_frames, d_lut, lo, hi, d_argb[0], d_index_scratch, **kw)
-    if stream is None:
-        stream = torch.cuda.current_stream(d_in.device).cuda_stream
     check(lib().jsg_stft_image_launch_strided(plan._p, C.byref(a), int(d_in.shape[0]), int(d_in.stride(0)), int(d_argb.stride(0)),
-                                              C.c_void_p(stream)))
+                                              _stream_handle(stream, d_in)))
 
 
 def stft_image_strided_needs_scratch(plan: Plan, d_in, hop: int, n_frames: int, d_lut, lo: float, hi: float, d_argb, d_index_scratch=None,
@@ -585,10 +576,8 @@ def db_from_power(d_power, d_out, divisor: float = 1.0, stream: int | None = Non
     import torch
     assert d_power.is_cuda and d_power.dtype == torch.float32 and d_power.is_contiguous()
     assert d_out.is_cuda and d_out.dtype == torch.float32 and d_out.is_contiguous() and d_out.numel() == d_power.numel()
-    if stream is None:
-        stream = torch.cuda.current_stream(d_power.device).cuda_stream
     check(lib().jsg_db_from_power_launch_ex(d_power.data_ptr(), d_out.data_ptr(), d_power.numel(), divisor, int(bool(exact_log)),
-                                            C.c_void_p(stream)))
+                                            _stream_handle(stream, d_power)))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -697,9 +686,7 @@ class FreqAxis(_PerDeviceHandles):
 
 def _fb_args(plan: Plan, fb: Filterbank, d_in, hop: int, n_frames: int, d_out, strided: bool, **kw):
     if strided:
-        assert d_in.dim() == 3 and d_in.stride(2) == 1 and d_out.shape[0] == d_in.shape[0] and d_out.stride(-1) == 1
-        a = _stft_args(plan, d_in[0], hop, n_frames, d_out[0], col_height=fb.n_bands, **kw)
-        return a, int(d_in.shape[0]), int(d_in.stride(0)), int(d_out.stride(0))
+        return _strided_args(plan, d_in, hop, n_frames, d_out, col_height=fb.n_bands, **kw)
     return _stft_args(plan, d_in, hop, n_frames, d_out, col_height=fb.n_bands, **kw), 1, 0, 0
 
 
@@ -713,16 +700,9 @@ def _fb_launch(plan, fb, d_in, hop, n_frames, d_out, strided, d_scratch, stream,
     import torch
     a, k, s_in, s_out = _fb_args(plan, fb, d_in, hop, n_frames, d_out, strided, **kw)
     h = fb.handle(d_in.device.index)
-    temporary = d_scratch is None
-    if temporary:
-        n_sc = int(check(lib().jsg_stft_fb_scratch_floats(plan._p, h, C.byref(a), k)))
-        d_scratch = torch.empty(n_sc, dtype=torch.float32, device=d_in.device)
-    assert d_scratch.is_cuda and d_scratch.dtype == torch.float32 and d_scratch.is_contiguous()
-    if stream is None:
-        stream = torch.cuda.current_stream(d_in.device).cuda_stream
-    elif temporary:   # the caching allocator must not hand the block out again before the launch on the caller's stream is done
-        d_scratch.record_stream(torch.cuda.ExternalStream(stream, device=d_in.device))
-    check(lib().jsg_stft_fb_launch_strided(plan._p, h, C.byref(a), k, s_in, s_out, d_scratch.data_ptr(), d_scratch.numel(), C.c_void_p(stream)))
+    d_scratch, stream = _scratch_and_stream(d_scratch, stream, d_in, lambda: check(lib().jsg_stft_fb_scratch_floats(plan._p, h, C.byref(a), k)),
+                                            torch.float32)
+    check(lib().jsg_stft_fb_launch_strided(plan._p, h, C.byref(a), k, s_in, s_out, d_scratch.data_ptr(), d_scratch.numel(), stream))
 
 
 def stft_fb_db(plan: Plan, fb: Filterbank, d_in, hop: int, n_frames: int, d_out, *, d_scratch=None, stream: int | None = None, **kw):
@@ -740,9 +720,7 @@ def stft_fb_db_strided(plan: Plan, fb: Filterbank, d_in, hop: int, n_frames: int
 def stft_fb_kernel_name(plan: Plan, fb: Filterbank, d_in, hop: int, n_frames: int, d_out, *, strided: bool = False, **kw) -> str:
     """The STFT kernel every chunk of this filterbank call takes (decided once for the whole call)."""
     a, k, _, _ = _fb_args(plan, fb, d_in, hop, n_frames, d_out, strided, **kw)
-    buf = C.create_string_buffer(32)
-    check(lib().jsg_stft_fb_kernel_name(plan._p, fb.handle(d_in.device.index), C.byref(a), k, buf, 32))
-    return buf.value.decode()
+    return _kernel_name(lib().jsg_stft_fb_kernel_name, plan._p, fb.handle(d_in.device.index), C.byref(a), k)
 
 
 _mel_cache: dict = {}
@@ -765,7 +743,7 @@ def mel_spectrogram_db(x, fs: float, n_fft: int, hop: int, n_mels: int, fmin: fl
     frames = 1 + (x.shape[1] - n_fft) // hop
     if frames < 1:
         raise JsgError(capi.JSG_ERR_INVALID, f"mel_spectrogram_db: {x.shape[1]} samples hold no frame of {n_fft}")
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    dev = _device_index(x)
     key = (dev, int(n_fft), int(window), float(fs), int(n_mels), float(fmin), None if fmax is None else float(fmax))
     if key not in _mel_cache:
         with torch.cuda.device(dev):
@@ -804,6 +782,13 @@ def _rows3(t, what: str):
     return t
 
 
+def _frame_major(X):
+    """complex64 [rows][frames][bins] with unit bin stride of a [..., bins, frames] tensor (the library's frame-major layout)."""
+    import torch
+    Xf = X.to(torch.complex64).transpose(-1, -2).reshape(-1, X.shape[-1], X.shape[-2])
+    return Xf if Xf.stride(2) == 1 else Xf.contiguous()
+
+
 def _cstft_args(plan: CStftPlan, d_in, hop: int, n_frames: int, d_out, in_samples: int | None) -> capi.CstftArgs:
     import torch
     x = d_in[None] if d_in.dim() == 1 else d_in
@@ -817,11 +802,8 @@ def _cstft_args(plan: CStftPlan, d_in, hop: int, n_frames: int, d_out, in_sample
 def cstft(plan: CStftPlan, d_in, hop: int, n_frames: int, d_out, *, in_samples: int | None = None, stream: int | None = None):
     """jsg_cstft_launch: d_in float32 [rows][samples] (frame j of a row at j * hop, any hop 1..n) -> d_out complex64 [rows][frames][>= n/2+1],
     the bins of numpy.fft.rfft(window * frame).  in_samples: the readable length of a row (default d_in.shape[-1]; 0: not checked)."""
-    import torch
     a = _cstft_args(plan, d_in, hop, n_frames, d_out, in_samples)
-    if stream is None:
-        stream = torch.cuda.current_stream(d_in.device).cuda_stream
-    check(lib().jsg_cstft_launch(plan._p, C.byref(a), C.c_void_p(stream)))
+    check(lib().jsg_cstft_launch(plan._p, C.byref(a), _stream_handle(stream, d_in)))
 
 
 def _istft_args(plan: CStftPlan, d_X, hop: int, n_frames: int, d_out, out_samples: int | None) -> capi.IstftArgs:
@@ -847,15 +829,8 @@ def istft_launch(plan: CStftPlan, d_X, hop: int, n_frames: int, d_out, out_sampl
     size is allocated with torch for this call); any accepted size gives the same bits."""
     import torch
     a = _istft_args(plan, d_X, hop, n_frames, d_out, out_samples)
-    temporary = d_scratch is None
-    if temporary:
-        d_scratch = torch.empty(int(check(lib().jsg_istft_scratch_floats(plan._p, C.byref(a)))), dtype=torch.float32, device=d_out.device)
-    assert d_scratch.is_cuda and d_scratch.dtype == torch.float32 and d_scratch.is_contiguous()
-    if stream is None:
-        stream = torch.cuda.current_stream(d_out.device).cuda_stream
-    elif temporary:   # the caching allocator must not hand the block out again before the launch on the caller's stream is done
-        d_scratch.record_stream(torch.cuda.ExternalStream(stream, device=d_out.device))
-    check(lib().jsg_istft_launch(plan._p, C.byref(a), d_scratch.data_ptr(), d_scratch.numel(), C.c_void_p(stream)))
+    d_scratch, stream = _scratch_and_stream(d_scratch, stream, d_out, lambda: check(lib().jsg_istft_scratch_floats(plan._p, C.byref(a))), torch.float32)
+    check(lib().jsg_istft_launch(plan._p, C.byref(a), d_scratch.data_ptr(), d_scratch.numel(), stream))
 
 
 def istft_nola(n: int, hop: int, window_table) -> tuple[bool, float]:
@@ -919,7 +894,7 @@ def stft(x, n_fft: int, hop_length: int | None = None, win_length: int | None = 
     if L < n_fft:
         raise JsgError(capi.JSG_ERR_INVALID, f"stft: {L} samples hold no frame of {n_fft}")
     frames = 1 + (L - n_fft) // hop
-    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    dev = _device_index(x)
     plan = _cstft_plan(dev, n_fft, w)
     out = torch.empty((xr.shape[0], frames, n_fft // 2 + 1), dtype=torch.complex64, device=x.device)
     with torch.cuda.device(dev):
@@ -954,9 +929,7 @@ def istft(X, n_fft: int, hop_length: int | None = None, win_length: int | None =
         raise JsgError(capi.JSG_ERR_INVALID, f"istft: {X.shape[-2]} bins, expected n_fft//2+1 = {n_fft // 2 + 1}")
     batch = tuple(X.shape[:-2])
     frames = int(X.shape[-1])
-    Xf = X.to(torch.complex64).transpose(-1, -2).reshape(-1, frames, n_fft // 2 + 1)
-    if Xf.stride(2) != 1:
-        Xf = Xf.contiguous()
+    Xf = _frame_major(X)
     T = (frames - 1) * hop + n_fft
     start = n_fft // 2 if center else 0
     end = (T - n_fft // 2 if center else T) if length is None else start + int(length)
@@ -964,7 +937,7 @@ def istft(X, n_fft: int, hop_length: int | None = None, win_length: int | None =
     env = _envelope(w, hop, frames)[start:stop]
     if env.size and not (np.abs(env) > 1e-11).all():
         raise JsgError(capi.JSG_ERR_INVALID, f"istft: window overlap-add envelope <= 1e-11 at sample {start + int(np.argmin(np.abs(env)))}")
-    dev = X.device.index if X.device.index is not None else torch.cuda.current_device()
+    dev = _device_index(X)
     plan = _cstft_plan(dev, n_fft, w)
     y = torch.empty((Xf.shape[0], max(stop, 1)), dtype=torch.float32, device=X.device)
     with torch.cuda.device(dev):
@@ -999,15 +972,9 @@ def phase_vocoder_launch(d_X, rate: float, hop: int, n: int, d_out, *, chunk_fra
     (None: one is allocated with torch for this call)."""
     import torch
     a = _pvoc_args(d_X, rate, hop, n, d_out, chunk_frames)
-    temporary = d_scratch is None
-    if temporary:
-        d_scratch = torch.empty(int(check(lib().jsg_pvoc_scratch_bytes(C.byref(a)))) // 4, dtype=torch.int32, device=d_out.device)
-    assert d_scratch.is_cuda and d_scratch.is_contiguous()
-    if stream is None:
-        stream = torch.cuda.current_stream(d_out.device).cuda_stream
-    elif temporary:   # the caching allocator must not hand the block out again before the launch on the caller's stream is done
-        d_scratch.record_stream(torch.cuda.ExternalStream(stream, device=d_out.device))
-    check(lib().jsg_pvoc_launch(C.byref(a), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), C.c_void_p(stream)))
+    d_scratch, stream = _scratch_and_stream(d_scratch, stream, d_out, lambda: check(lib().jsg_pvoc_scratch_bytes(C.byref(a))) // 4, torch.int32,
+                                            any_dtype=True)
+    check(lib().jsg_pvoc_launch(C.byref(a), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), stream))
 
 
 def phase_vocoder(X, rate: float, hop_length: int, n_fft: int | None = None):
@@ -1020,11 +987,9 @@ def phase_vocoder(X, rate: float, hop_length: int, n_fft: int | None = None):
     if bins != n // 2 + 1:
         raise JsgError(capi.JSG_ERR_INVALID, f"phase_vocoder: {bins} bins, expected n_fft//2+1 = {n // 2 + 1}")
     batch = tuple(X.shape[:-2])
-    Xf = X.to(torch.complex64).transpose(-1, -2).reshape(-1, frames, bins)
-    if Xf.stride(2) != 1:
-        Xf = Xf.contiguous()
+    Xf = _frame_major(X)
     out = torch.empty((Xf.shape[0], pvoc_frames(frames, rate), bins), dtype=torch.complex64, device=X.device)
-    dev = X.device.index if X.device.index is not None else torch.cuda.current_device()
+    dev = _device_index(X)
     with torch.cuda.device(dev):
         phase_vocoder_launch(Xf, rate, hop_length, n, out)
     return out.reshape(*batch, out.shape[1], bins).transpose(-1, -2)

@@ -21,6 +21,40 @@ def test_library_exports_every_declared_symbol(jsg):
     assert lib.jsg_abi_version() == 6
 
 
+STRUCTS = ("jsg_stft_args", "jsg_colormap_args", "jsg_stft_image_args", "jsg_fb_spec", "jsg_axis_spec", "jsg_cstft_args", "jsg_istft_args",
+           "jsg_pvoc_args")
+
+
+def test_ctypes_structs_match_the_header_layout(jsg, tmp_path):
+    """capi.py restates the argument structs of include/jsg.h by hand: same fields, in the same order, at the same offsets, of the same
+    sizes as the host C compiler lays them out (`in` is `in_` in Python, where `in` is a keyword)."""
+    import ctypes
+    import shutil
+    import subprocess
+    cc = next((c for c in (os.environ.get("CC"), "cc", "gcc", "clang") if c and shutil.which(c)), None)
+    if cc is None:
+        pytest.skip("no C compiler")
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "jsg.h")).read(), flags=re.S)
+    declared = {}
+    for name in STRUCTS:
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, flags=re.S).group(1)
+        declared[name] = [re.search(r"(\w+)\s*$", piece).group(1) for decl in body.split(";") if decl.strip() for piece in decl.split(",")]
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "jsg.h"', "int main(void) {"]
+    for name, names in declared.items():
+        lines.append(f'    printf("{name} %zu\\n", sizeof({name}));')
+        lines += [f'    printf("{f} %zu %zu\\n", offsetof({name}, {f}), sizeof((({name}*)0)->{f}));' for f in names]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines + ["    return 0;", "}", ""]))
+    subprocess.check_call([cc, "-I", os.path.join(ROOT, "include"), "-o", str(tmp_path / "layout"), str(src)])
+    out = iter(subprocess.check_output([str(tmp_path / "layout")], text=True).split("\n"))
+    for name, names in declared.items():
+        cls = getattr(jsg.capi, "".join(part.capitalize() for part in name.split("_")[1:]))      # jsg_stft_image_args -> StftImageArgs
+        assert next(out) == f"{name} {ctypes.sizeof(cls)}"
+        assert [f for f, _ in cls._fields_] == ["in_" if f == "in" else f for f in names], name
+        for (f, _), c_name in zip(cls._fields_, names):
+            assert next(out) == f"{c_name} {getattr(cls, f).offset} {getattr(cls, f).size}", (name, f)
+
+
 def test_windows_bit_exact_vs_oracle(jsg, oracle):
     for kind in range(6):
         for n in (512, 1024, 2048, 4096, 8192):
