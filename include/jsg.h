@@ -47,7 +47,7 @@ extern "C" {
                                   display frequency axes (jsg_freq_axis_*, jsg_colormap_axis_launch, jsg_display_set_freq_axis,
                                   jsg_display_height, jsg_display_axis_centres; section 2c),
                                   complex STFT and inverse STFT with any hop (jsg_cstft_*, jsg_istft_*; section 2d); additive since: the
-                                 phase vocoder (jsg_pvoc_*; section 2e) */
+                                 phase vocoder (jsg_pvoc_*; section 2e), harmonic-percussive separation (jsg_hpss_*; section 2f) */
 
 typedef enum jsg_status {
     JSG_OK = 0,
@@ -542,6 +542,56 @@ JSG_API int64_t jsg_pvoc_scratch_bytes(const jsg_pvoc_args* args);
  * a rate that is not finite or <= 0, a T_out above 2^31-1, n_frames_out != T_out, pitches smaller than above, out overlapping in,
  * scratch that is null, not 16-byte aligned or smaller than jsg_pvoc_scratch_bytes.  JSG_ERR_NO_DEVICE without a HIP device. */
 JSG_API int jsg_pvoc_launch(const jsg_pvoc_args* args, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2f. Harmonic-percussive separation by median filtering (on the frames of jsg_cstft_launch, or on a power plane such as the
+ *     ring of linear_out = 1).  This is librosa.decompose.hpss(|X|, kernel_size=(W_f, W_t), power=2, margin=(margin_h, margin_p),
+ *     mask=True) and the masked input: the median commutes with squaring, so the whole operation is stated on float32 power.
+ *
+ *     Input in[r][j][k], frame-major, complex64 (in_complex = 1) or real power (in_complex = 0); T frames of K bins.  All values
+ *     are float32, every operation is rounded separately, there is no fused multiply-add:
+ *         P[j][k]  = re*re + im*im                      (real input: P = in)
+ *         refl(i,L): m = i mod 2L (non-negative);  m < L ? m : 2L-1-m        (scipy's "reflect", any distance past the edge)
+ *         H[j][k]  = the (h_t+1)-th smallest of P[refl(j+d,T)][k], d = -h_t..h_t,   h_t = (W_t-1)/2
+ *         C[j][k]  = the (h_f+1)-th smallest of P[j][refl(k+d,K)], d = -h_f..h_f,   h_f = (W_f-1)/2
+ *         g_h = margin_h*margin_h,  g_p = margin_p*margin_p
+ *         D_h = H + g_h*C;   M_h = D_h > 0 ? H / D_h : 0     (IEEE correctly rounded division)
+ *         D_p = C + g_p*H;   M_p = D_p > 0 ? C / D_p : 0
+ *         out_h = (M_h*re, M_h*im)   (real input: M_h*P);   out_p likewise;   mask_h = M_h, mask_p = M_p
+ *     A numpy restatement therefore agrees bit for bit.  Covered: inputs whose powers and products are zero or normal floats
+ *     (subnormal intermediates are outside the contract).  A NaN, an Inf or, for real input, a negative value at (j0, k0) is
+ *     contained: it may change only outputs whose time window in column k0 or frequency window in frame j0 holds it; every other
+ *     output keeps its bits, and nothing faults.  The bits do not depend on chunk_frames, the grid, the row count, the pitches or on
+ *     which outputs are requested.  Elements between n_bins and a pitch are not written.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSG_HPSS_MAX_WINDOW 63
+typedef struct jsg_hpss_args {
+    const float* in;             /* device; in_complex = 1: float pairs (re, im), 8-byte aligned; 0: real power values >= 0 */
+    int32_t in_complex;
+    int64_t in_frame_pitch;      /* elements (complex elements or floats) between frames, >= n_bins */
+    int64_t in_row_pitch;        /* rows > 1: >= (n_frames-1)*in_frame_pitch + n_bins */
+    int32_t rows;                /* 1..65535, independent */
+    int32_t n_bins;              /* K, 1..32769 */
+    int64_t n_frames;            /* T, 1..2^31-1 */
+    int32_t win_time, win_freq;  /* odd, 1..JSG_HPSS_MAX_WINDOW: W_t filters along frames (harmonic), W_f along bins (percussive) */
+    float margin_h, margin_p;    /* finite, >= 1 (librosa's margin) */
+    float* out_h; float* out_p;  /* masked input, same kind as `in`; either may be NULL */
+    int64_t out_frame_pitch, out_row_pitch;   /* as the input's; looked at only where out_h or out_p is given */
+    float* mask_h; float* mask_p;/* float planes; either may be NULL.  At least one of the four outputs is non-NULL */
+    int64_t mask_frame_pitch, mask_row_pitch; /* floats; looked at only where mask_h or mask_p is given */
+    int32_t chunk_frames;        /* frames per work item along time: 0 = the library's choice, else 1..65536; never changes the result */
+} jsg_hpss_args;
+/* Bytes of scratch the call needs (one float per row, frame and bin: the frequency medians; rounded up to 16).  < 0: the call would
+ * be refused.  Needs no device. */
+JSG_API int64_t jsg_hpss_scratch_bytes(const jsg_hpss_args* args);
+/* Enqueue only (two kernels: the medians along the bins to scratch, then the medians along the frames, the masks and the outputs):
+ * no allocation, no synchronisation; hipGraph capture on one stream works.  `scratch`: device memory, 16-byte aligned, layout
+ * private to the library.  Refused (JSG_ERR_INVALID, nothing enqueued, jsg_last_error set, decided before any device call): null
+ * args or input, all four outputs NULL, a window that is even or out of range, rows, n_bins, n_frames or chunk_frames out of range,
+ * a margin that is not finite or below 1, a pitch below its minimum, a misaligned pointer, an output that overlaps the input or
+ * another output, scratch that is null, not 16-byte aligned or smaller than jsg_hpss_scratch_bytes.  JSG_ERR_NO_DEVICE without a
+ * HIP device, after these checks. */
+JSG_API int jsg_hpss_launch(const jsg_hpss_args* args, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 3. Engine: the state of class Spectrogram (Spectrogram.h:81-169) living on the GPU.

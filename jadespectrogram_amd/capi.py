@@ -30,6 +30,7 @@ FB_NORM_NONE, FB_NORM_SLANEY, FB_NORM_UNIT_SUM = range(3)
 FB_MAX_BANDS = 8192
 AXIS_BINS, AXIS_LINEAR, AXIS_LOG, AXIS_MEL = range(4)
 AXIS_MAX_HEIGHT = 16384
+HPSS_MAX_WINDOW = 63
 
 
 class JsgError(RuntimeError):
@@ -79,6 +80,14 @@ class PvocArgs(C.Structure):
     _fields_ = [("in_", C.c_void_p), ("in_frame_pitch", C.c_int64), ("in_row_pitch", C.c_int64), ("rows", C.c_int32), ("n", C.c_int32),
                 ("hop", C.c_int32), ("n_frames_in", C.c_int64), ("rate", C.c_double), ("out", C.c_void_p), ("out_frame_pitch", C.c_int64),
                 ("out_row_pitch", C.c_int64), ("n_frames_out", C.c_int64), ("chunk_frames", C.c_int32)]
+
+
+class HpssArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("in_complex", C.c_int32), ("in_frame_pitch", C.c_int64), ("in_row_pitch", C.c_int64), ("rows", C.c_int32),
+                ("n_bins", C.c_int32), ("n_frames", C.c_int64), ("win_time", C.c_int32), ("win_freq", C.c_int32), ("margin_h", C.c_float),
+                ("margin_p", C.c_float), ("out_h", C.c_void_p), ("out_p", C.c_void_p), ("out_frame_pitch", C.c_int64), ("out_row_pitch", C.c_int64),
+                ("mask_h", C.c_void_p), ("mask_p", C.c_void_p), ("mask_frame_pitch", C.c_int64), ("mask_row_pitch", C.c_int64),
+                ("chunk_frames", C.c_int32)]
 
 
 class StftImageArgs(C.Structure):
@@ -141,6 +150,8 @@ SIGNATURES = {
     "jsg_pvoc_frames": (C.c_int64, [C.c_int64, C.c_double]),
     "jsg_pvoc_scratch_bytes": (C.c_int64, [C.POINTER(PvocArgs)]),
     "jsg_pvoc_launch": (C.c_int, [C.POINTER(PvocArgs), _P, C.c_int64, _P]),
+    "jsg_hpss_scratch_bytes": (C.c_int64, [C.POINTER(HpssArgs)]),
+    "jsg_hpss_launch": (C.c_int, [C.POINTER(HpssArgs), _P, C.c_int64, _P]),
     "jsg_create": (C.c_int, [C.POINTER(_P), C.c_int]),
     "jsg_create_on_device": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int]),
     "jsg_get_device": (C.c_int, [_P]),

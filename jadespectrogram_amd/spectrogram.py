@@ -1006,3 +1006,98 @@ def time_stretch(x, rate: float, n_fft: int = 2048, hop_length: int | None = Non
     X = stft(x, n_fft, hop, win_length, w, center)
     Y = phase_vocoder(X, rate, hop, n_fft)
     return istft(Y, n_fft, hop, win_length, w, center, length=length or int(round(x.shape[-1] / rate)))
+
+
+# --------------------------------------------------------------------------------------------------
+# harmonic-percussive separation by median filtering (include/jsg.h, section 2f)
+# --------------------------------------------------------------------------------------------------
+def _pair(v, kind):
+    """(harmonic / time, percussive / frequency) of a scalar or a pair."""
+    if isinstance(v, (tuple, list)):
+        assert len(v) == 2, "a pair (harmonic/time, percussive/frequency)"
+        return kind(v[0]), kind(v[1])
+    return kind(v), kind(v)
+
+
+def _hpss_args(d_in, d_harm, d_perc, d_mask_h, d_mask_p, kernel_size, margin, chunk_frames: int) -> capi.HpssArgs:
+    import torch
+    X = _rows3(d_in, "d_in")
+    assert X.is_cuda and X.dtype in (torch.complex64, torch.float32) and X.stride(2) == 1, "d_in: complex64 or float32 CUDA [rows][frames][bins]"
+
+    def plane(t, what, dtype):
+        if t is None:
+            return None
+        t = _rows3(t, what)
+        assert t.is_cuda and t.dtype == dtype and t.stride(2) == 1 and tuple(t.shape) == tuple(X.shape), \
+            f"{what}: {dtype} CUDA [rows][frames][bins] of d_in's shape"
+        return t
+
+    def pitches(a, b, what):
+        if a is not None and b is not None:
+            assert (a.stride(1), a.stride(0)) == (b.stride(1), b.stride(0)), f"{what}: the two buffers share one frame pitch and one row pitch"
+        t = a if a is not None else b
+        return (0, 0) if t is None else (t.stride(1), t.stride(0))
+
+    oh, op = plane(d_harm, "d_harm", X.dtype), plane(d_perc, "d_perc", X.dtype)
+    mh, mp = plane(d_mask_h, "d_mask_h", torch.float32), plane(d_mask_p, "d_mask_p", torch.float32)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    (w_t, w_f), (m_h, m_p) = _pair(kernel_size, int), _pair(margin, float)
+    return capi.HpssArgs(X.data_ptr(), int(X.dtype == torch.complex64), X.stride(1), X.stride(0), X.shape[0], X.shape[2], X.shape[1], w_t, w_f, m_h, m_p,
+                         ptr(oh), ptr(op), *pitches(oh, op, "d_harm, d_perc"), ptr(mh), ptr(mp), *pitches(mh, mp, "d_mask_h, d_mask_p"),
+                         int(chunk_frames))
+
+
+def hpss_scratch_bytes(d_in, *, d_harm=None, d_perc=None, d_mask_h=None, d_mask_p=None, kernel_size=31, margin=1.0, chunk_frames: int = 0) -> int:
+    """jsg_hpss_scratch_bytes: the bytes of scratch hpss_launch needs for these arguments."""
+    a = _hpss_args(d_in, d_harm, d_perc, d_mask_h, d_mask_p, kernel_size, margin, chunk_frames)
+    return int(check(lib().jsg_hpss_scratch_bytes(C.byref(a))))
+
+
+def hpss_launch(d_in, *, d_harm=None, d_perc=None, d_mask_h=None, d_mask_p=None, kernel_size=31, margin=1.0, chunk_frames: int = 0,
+                d_scratch=None, stream: int | None = None):
+    """jsg_hpss_launch: d_in complex64 (frames of a complex STFT) or float32 (power) [rows][frames][bins] -> the harmonic and the
+    percussive part (d_harm, d_perc: d_in's dtype and shape) and / or their soft masks (d_mask_h, d_mask_p: float32), median filtering
+    as librosa.decompose.hpss with power = 2.  kernel_size and margin: a scalar or a pair (harmonic / time, percussive / frequency).
+    chunk_frames (0: the library's choice) never changes the result.  d_scratch: a contiguous CUDA tensor of at least
+    hpss_scratch_bytes bytes (None: one is allocated with torch for this call)."""
+    import torch
+    a = _hpss_args(d_in, d_harm, d_perc, d_mask_h, d_mask_p, kernel_size, margin, chunk_frames)
+    d_scratch, stream = _scratch_and_stream(d_scratch, stream, d_in, lambda: check(lib().jsg_hpss_scratch_bytes(C.byref(a))) // 4, torch.float32,
+                                            any_dtype=True)
+    check(lib().jsg_hpss_launch(C.byref(a), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), stream))
+
+
+def hpss(X, kernel_size=31, margin=1.0, *, masks: bool = False):
+    """librosa.decompose.hpss with power = 2 on the GPU: X complex CUDA [..., bins, frames] (what stft returns) or a float32 power
+    tensor of that shape -> (harmonic, percussive) in X's shape and kind (the transposed views of the library's frame-major buffers,
+    as stft returns), or with masks = True the two float32 soft masks.  kernel_size and margin: a scalar or a pair (harmonic / time,
+    percussive / frequency)."""
+    import torch
+    assert X.is_cuda and (X.is_complex() or X.dtype == torch.float32), "hpss: X must be a complex or a float32 CUDA tensor"
+    bins, frames = int(X.shape[-2]), int(X.shape[-1])
+    batch = tuple(X.shape[:-2])
+    if X.is_complex():
+        Xf = _frame_major(X)
+    else:
+        Xf = X.transpose(-1, -2).reshape(-1, frames, bins)
+        Xf = Xf if Xf.stride(2) == 1 else Xf.contiguous()
+    a, b = (torch.empty(Xf.shape, dtype=torch.float32 if masks else Xf.dtype, device=X.device) for _ in range(2))
+    with torch.cuda.device(_device_index(X)):
+        if masks:
+            hpss_launch(Xf, d_mask_h=a, d_mask_p=b, kernel_size=kernel_size, margin=margin)
+        else:
+            hpss_launch(Xf, d_harm=a, d_perc=b, kernel_size=kernel_size, margin=margin)
+    return tuple(t.reshape(*batch, frames, bins).transpose(-1, -2) for t in (a, b))
+
+
+def hpss_audio(x, n_fft: int = 2048, hop_length: int | None = None, win_length: int | None = None, window=None, center: bool = True,
+               kernel_size=31, margin=1.0):
+    """The harmonic and the percussive part of a signal: x float32 CUDA [..., L] -> (y_harm, y_perc), each float32 [..., L].  Exactly
+    istft(hpss(stft(x, ...), kernel_size, margin)[i], ..., length=L) with the same n_fft, hop, win_length, window and center on both
+    sides.  window = None means a Hann window, as in time_stretch."""
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    w = capi.WIN_HANN if window is None else window
+    X = stft(x, n_fft, hop, win_length, w, center)
+    H, P = hpss(X, kernel_size, margin)
+    L = int(x.shape[-1])
+    return istft(H, n_fft, hop, win_length, w, center, length=L), istft(P, n_fft, hop, win_length, w, center, length=L)
