@@ -47,7 +47,8 @@ extern "C" {
                                   display frequency axes (jsg_freq_axis_*, jsg_colormap_axis_launch, jsg_display_set_freq_axis,
                                   jsg_display_height, jsg_display_axis_centres; section 2c),
                                   complex STFT and inverse STFT with any hop (jsg_cstft_*, jsg_istft_*; section 2d); additive since: the
-                                 phase vocoder (jsg_pvoc_*; section 2e), harmonic-percussive separation (jsg_hpss_*; section 2f) */
+                                 phase vocoder (jsg_pvoc_*; section 2e), harmonic-percussive separation (jsg_hpss_*; section 2f),
+                                 band-limited resampling (jsg_sinc_table_build, jsg_resampler_*, jsg_resample_*; section 2g) */
 
 typedef enum jsg_status {
     JSG_OK = 0,
@@ -104,6 +105,14 @@ JSG_API int jsg_window_build(int window, int n, float* out);
 JSG_API int jsg_colormap_build(int n_colors, int scheme, int32_t* lut_out);
 /* CColorPalette::setValueRange: resolves (lo,hi) -> m_Min, m_Max, m_AccessMult -- CColorpalette.cpp:39-54 */
 JSG_API int jsg_colormap_range(int n_colors, float lo, float hi, float* vmin, float* vmax, float* access_mult);
+/* The windowed-sinc table of section 2g, num_zeros * per_zero + 1 floats: with Z = num_zeros, P = per_zero,
+ *     out[j] = rolloff * sinc(rolloff * j / P) * I0(beta * sqrt(1 - (j / (Z P))^2)) / I0(beta),   sinc(x) = sin(pi x) / (pi x),
+ * evaluated in double (I0 by its power series) and rounded to float once; out[0] == (float)rolloff.  Kaiser designs in the style of
+ * resampy: "best" = (64, 512, 0.9475937167399596, 14.769656459379492), "fast" = (16, 512, 0.85, 8.555504641634386).
+ * Refused (JSG_ERR_INVALID): a null pointer, Z < 1, P < 1, Z * P > JSG_RESAMPLE_MAX_TABLE, a rolloff outside (0, 1], a beta that is
+ * negative or not finite. */
+#define JSG_RESAMPLE_MAX_TABLE 32768
+JSG_API int jsg_sinc_table_build(int num_zeros, int per_zero, double rolloff, double beta, float* out);
 
 /* ------------------------------------------------------------------------------------------------
  * 2. Stateless device operations.  Every data pointer is a DEVICE pointer on the current device;
@@ -592,6 +601,69 @@ JSG_API int64_t jsg_hpss_scratch_bytes(const jsg_hpss_args* args);
  * another output, scratch that is null, not 16-byte aligned or smaller than jsg_hpss_scratch_bytes.  JSG_ERR_NO_DEVICE without a
  * HIP device, after these checks. */
 JSG_API int jsg_hpss_launch(const jsg_hpss_args* args, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2g. Band-limited resampling by any real ratio (a windowed-sinc table read with linear interpolation; one table serves every ratio).
+ *
+ *     Table win[0..Z P], float32: Z zero crossings per wing, P entries per zero crossing (Z >= 1, P >= 1, Z P <= 32768), supplied by
+ *     the caller (jsg_sinc_table_build makes the usual one).  delta[o] = win[o+1] - win[o], a float32 subtraction of the float32
+ *     entries.  Rows x[r][0..L); step = input samples per output sample (sr_in / sr_out), finite, in [1/64, 64].  Output i sits at
+ *     t_i = (double)i * step (one IEEE multiply); there are T = #{i >= 0 : t_i < L} outputs (jsg_resample_length; ceil(L new / orig)
+ *     for a rational step).  The tap positions are fixed point, 2^32 units per table entry:
+ *         scale = step > 1 ? 1 / step : 1                    (double, one division)
+ *         S     = llrint(scale * P * 2^32)                   (int64: the table advance per input sample)
+ *         n = floor(t_i),  f = t_i - n,  F_L = llrint(f * (double)S),  F_R = S - F_L
+ *         left wing,  a = 0, 1, ...:  m = n - a,      pos = F_L + a S
+ *         right wing, b = 0, 1, ...:  m = n + 1 + b,  pos = F_R + b S
+ *         a tap is live iff  pos < (Z P) 2^32  and  0 <= m < L
+ *         o = pos >> 32,  eta = (float)((pos & 0xffffffff) >> 8) * 2^-24         (exact in float32)
+ *         w = fmaf(eta, delta[o], win[o])
+ *         y[r][i] = (float)scale * sum over the live taps of w * x[r][m]
+ *     The positions are integers, so every tap's weight is defined to the bit.  The library sums each wing in ascending a (b) with
+ *     fmaf into an accumulator of its own, adds the two once and scales once; the order depends on i only, so the bits do not
+ *     depend on chunk_outputs, the grid, the row count, the pitches or the alignment of the pointers.  The contract is a tolerance
+ *     against a float64 evaluation of the formulas above.  Taps that are not live contribute nothing (they are not multiplied by
+ *     zero): a NaN or an Inf at x[r][m0] changes exactly the outputs of row r that have a live tap at m0.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct jsg_resampler jsg_resampler;
+/* Uploads `table` (num_zeros * per_zero + 1 host floats) to the current device.  Refused (JSG_ERR_INVALID): null pointers, Z or P out
+ * of range, a table entry that is not finite.  JSG_ERR_NO_DEVICE without a HIP device, after these checks. */
+JSG_API int jsg_resampler_create(jsg_resampler** out, int num_zeros, int per_zero, const float* table);
+JSG_API int jsg_resampler_destroy(jsg_resampler* rs);
+JSG_API int jsg_resampler_zeros(const jsg_resampler* rs);
+JSG_API int jsg_resampler_per_zero(const jsg_resampler* rs);
+/* T for L = in_samples (1..2^31-1) and a finite step in [1/64, 64].  JSG_ERR_INVALID for other arguments.  Needs no device. */
+JSG_API int64_t jsg_resample_length(int64_t in_samples, double step);
+
+typedef struct jsg_resample_args {
+    const float* in;            /* device floats: x[r][m] at in[r*in_pitch + m] */
+    int64_t in_pitch;           /* rows > 1: >= in_samples */
+    int32_t rows;               /* 1..65535, independent */
+    int64_t in_samples;         /* L, 1..2^31-1 */
+    double step;                /* finite, in [1/64, 64]; > 1 lowers the sample rate */
+    float* out;                 /* device floats: y[r][i] at out[r*out_pitch + i]; elements from out_samples to the pitch are not written */
+    int64_t out_pitch;          /* rows > 1: >= out_samples */
+    int64_t out_samples;        /* must equal jsg_resample_length(in_samples, step) */
+    int32_t chunk_outputs;      /* consecutive outputs per work item: 0 = the library's choice, else 1..65536; never changes the result */
+} jsg_resample_args;
+/* Enqueue only (one kernel, no scratch): no allocation, no synchronisation; hipGraph capture works.  Refused (JSG_ERR_INVALID, nothing
+ * enqueued, jsg_last_error set, decided before any device call): null pointers, in or out not 4-byte aligned, a step that is not
+ * finite or outside [1/64, 64], rows, in_samples or chunk_outputs out of range, out_samples != jsg_resample_length, a pitch below
+ * in_samples / out_samples when rows > 1, out overlapping in.  Then JSG_ERR_NO_DEVICE without a HIP device, and JSG_ERR_INVALID for
+ * a plan of another device (asking for the current device is the first device call).  Every table and step that pass these checks
+ * are served: see the paths of jsg_resample_plan. */
+JSG_API int jsg_resample_launch(const jsg_resampler* rs, const jsg_resample_args* args, void* stream);
+/* What the launch would do for a table of num_zeros x per_zero and these arguments, without a plan and without a device: the path
+ * as text (name may be NULL, else name_len >= 24), the outputs a pass takes and the bytes of LDS a workgroup asks for (either may be
+ * NULL).  The paths: "resample_lds" (table and input span in LDS), "resample_l2" (the table does not fit beside the span of 256
+ * outputs and is read through L2), "resample_direct" (not even the whole LDS holds that span: a table with many zero crossings at a
+ * large step; only the table is staged, the input is read through L2).  Every accepted call has pass_outputs >= 1 and lds_bytes <=
+ * 163840.  Refused: what the launch refuses for `args`, and table sizes jsg_resampler_create refuses. */
+JSG_API int jsg_resample_plan(int num_zeros, int per_zero, const jsg_resample_args* args, char* name, int name_len, int32_t* pass_outputs,
+                              int32_t* lds_bytes);
+/* The path of jsg_resample_plan for the sizes of `rs` (out_len >= 24).  The argument refusals of the launch; then only the sizes of
+ * the plan are read: no device is needed and the plan's device is not looked at. */
+JSG_API int jsg_resample_kernel_name(const jsg_resampler* rs, const jsg_resample_args* args, char* out, int out_len);
 
 /* ------------------------------------------------------------------------------------------------
  * 3. Engine: the state of class Spectrogram (Spectrogram.h:81-169) living on the GPU.

@@ -10,11 +10,13 @@ from .spectrogram import (CColorPalette, Filterbank, FreqAxis, Plan, Spectrogram
                           mel_spectrogram_db, stft_fb_db, stft_fb_db_strided, stft_fb_kernel_name, stft_fb_scratch_floats,
                           CStftPlan, cstft, istft, istft_launch, istft_nola, istft_scratch_floats, stft,
                           phase_vocoder, phase_vocoder_launch, pvoc_frames, time_stretch,
-                          hpss, hpss_audio, hpss_launch, hpss_scratch_bytes)
+                          hpss, hpss_audio, hpss_launch, hpss_scratch_bytes,
+                          Resampler, pitch_shift, resample, resample_kernel_name, resample_launch, resample_length, resample_plan, sinc_table)
 
 __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_db", "colormap", "window", "colormap_lut",
            "colormap_range", "feed_samples", "memsize_blocks", "next_power_of_2", "JsgError", "capi",
            "Filterbank", "stft_fb_db", "stft_fb_db_strided", "stft_fb_kernel_name", "mel_spectrogram_db", "FreqAxis", "colormap_axis",
            "CStftPlan", "cstft", "istft_launch", "istft_nola", "istft_scratch_floats", "stft", "istft",
            "pvoc_frames", "phase_vocoder_launch", "phase_vocoder", "time_stretch",
-           "hpss_scratch_bytes", "hpss_launch", "hpss", "hpss_audio"]
+           "hpss_scratch_bytes", "hpss_launch", "hpss", "hpss_audio",
+           "sinc_table", "Resampler", "resample_length", "resample_launch", "resample_kernel_name", "resample_plan", "resample", "pitch_shift"]

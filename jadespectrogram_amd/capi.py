@@ -31,6 +31,7 @@ FB_MAX_BANDS = 8192
 AXIS_BINS, AXIS_LINEAR, AXIS_LOG, AXIS_MEL = range(4)
 AXIS_MAX_HEIGHT = 16384
 HPSS_MAX_WINDOW = 63
+RESAMPLE_MAX_TABLE = 32768
 
 
 class JsgError(RuntimeError):
@@ -90,6 +91,11 @@ class HpssArgs(C.Structure):
                 ("chunk_frames", C.c_int32)]
 
 
+class ResampleArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("in_pitch", C.c_int64), ("rows", C.c_int32), ("in_samples", C.c_int64), ("step", C.c_double),
+                ("out", C.c_void_p), ("out_pitch", C.c_int64), ("out_samples", C.c_int64), ("chunk_outputs", C.c_int32)]
+
+
 class StftImageArgs(C.Structure):
     _fields_ = [("stft", StftArgs), ("colour", ColormapArgs), ("index_scratch", C.c_void_p), ("index_scratch_pitch", C.c_int64)]
 
@@ -105,6 +111,7 @@ SIGNATURES = {
     "jsg_window_build": (C.c_int, [C.c_int, C.c_int, _P]),
     "jsg_colormap_build": (C.c_int, [C.c_int, C.c_int, _P]),
     "jsg_colormap_range": (C.c_int, [C.c_int, C.c_float, C.c_float, _P, _P, _P]),
+    "jsg_sinc_table_build": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, _P]),
     "jsg_plan_create": (C.c_int, [C.POINTER(_P), C.c_int, _P, C.c_float]),
     "jsg_plan_destroy": (C.c_int, [_P]),
     "jsg_plan_fft_size": (C.c_int, [_P]),
@@ -152,6 +159,14 @@ SIGNATURES = {
     "jsg_pvoc_launch": (C.c_int, [C.POINTER(PvocArgs), _P, C.c_int64, _P]),
     "jsg_hpss_scratch_bytes": (C.c_int64, [C.POINTER(HpssArgs)]),
     "jsg_hpss_launch": (C.c_int, [C.POINTER(HpssArgs), _P, C.c_int64, _P]),
+    "jsg_resampler_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, _P]),
+    "jsg_resampler_destroy": (C.c_int, [_P]),
+    "jsg_resampler_zeros": (C.c_int, [_P]),
+    "jsg_resampler_per_zero": (C.c_int, [_P]),
+    "jsg_resample_length": (C.c_int64, [C.c_int64, C.c_double]),
+    "jsg_resample_launch": (C.c_int, [_P, C.POINTER(ResampleArgs), _P]),
+    "jsg_resample_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(ResampleArgs), C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "jsg_resample_kernel_name": (C.c_int, [_P, C.POINTER(ResampleArgs), C.c_char_p, C.c_int]),
     "jsg_create": (C.c_int, [C.POINTER(_P), C.c_int]),
     "jsg_create_on_device": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int]),
     "jsg_get_device": (C.c_int, [_P]),

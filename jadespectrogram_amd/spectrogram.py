@@ -1101,3 +1101,125 @@ def hpss_audio(x, n_fft: int = 2048, hop_length: int | None = None, win_length: 
     H, P = hpss(X, kernel_size, margin)
     L = int(x.shape[-1])
     return istft(H, n_fft, hop, win_length, w, center, length=L), istft(P, n_fft, hop, win_length, w, center, length=L)
+
+
+# --------------------------------------------------------------------------------------------------
+# band-limited resampling and pitch shift (include/jsg.h, section 2g)
+# --------------------------------------------------------------------------------------------------
+SINC_TABLES = {"best": (64, 512, 0.9475937167399596, 14.769656459379492), "fast": (16, 512, 0.85, 8.555504641634386)}
+
+
+def sinc_table(num_zeros: int, per_zero: int, rolloff: float, beta: float) -> np.ndarray:
+    """jsg_sinc_table_build: the Kaiser-windowed sinc table, num_zeros * per_zero + 1 float32 entries (no GPU needed)."""
+    out = np.zeros(max(0, int(num_zeros)) * max(0, int(per_zero)) + 1, np.float32)
+    check(lib().jsg_sinc_table_build(int(num_zeros), int(per_zero), float(rolloff), float(beta), out.ctypes.data))
+    return out
+
+
+class Resampler(_PerDeviceHandles):
+    """The interpolation table of jsg_resample_launch: `num_zeros` zero crossings per wing, `per_zero` entries per zero crossing.  Built
+    on the host; uploaded to a device once, the first time a launch on that device needs it.  One table serves every ratio.
+
+        Resampler("best" | "fast")                          the Kaiser designs of SINC_TABLES
+        Resampler.from_table(table, num_zeros, per_zero)    any table of num_zeros * per_zero + 1 finite floats
+    """
+    _destroy = "jsg_resampler_destroy"
+
+    def __init__(self, quality: str = "best"):
+        if quality not in SINC_TABLES:
+            raise JsgError(capi.JSG_ERR_INVALID, f"Resampler: quality must be one of {sorted(SINC_TABLES)}, not {quality!r}")
+        Z, P, rolloff, beta = SINC_TABLES[quality]
+        self.table, self.num_zeros, self.per_zero, self._handles = sinc_table(Z, P, rolloff, beta), Z, P, {}
+
+    @classmethod
+    def from_table(cls, table, num_zeros: int, per_zero: int) -> "Resampler":
+        t = np.ascontiguousarray(table, dtype=np.float32).ravel()
+        assert t.size == int(num_zeros) * int(per_zero) + 1, "table: num_zeros * per_zero + 1 entries"
+        self = cls.__new__(cls)
+        self.table, self.num_zeros, self.per_zero, self._handles = t, int(num_zeros), int(per_zero), {}
+        return self
+
+    def _create(self, h):
+        check(lib().jsg_resampler_create(C.byref(h), self.num_zeros, self.per_zero, self.table.ctypes.data))
+
+
+def resample_length(in_samples: int, step: float) -> int:
+    """jsg_resample_length: the number of outputs i >= 0 with float(i) * step < in_samples."""
+    return int(check(lib().jsg_resample_length(int(in_samples), float(step))))
+
+
+def _resample_args(d_in, step: float, d_out, chunk_outputs: int) -> capi.ResampleArgs:
+    import torch
+    x = d_in[None] if d_in.dim() == 1 else d_in
+    y = d_out[None] if d_out.dim() == 1 else d_out
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1, "d_in: float32 CUDA [rows][samples]"
+    assert y.is_cuda and y.dtype == torch.float32 and y.dim() == 2 and y.stride(1) == 1 and y.shape[0] == x.shape[0], "d_out: float32 CUDA [rows][samples]"
+    return capi.ResampleArgs(x.data_ptr(), x.stride(0), x.shape[0], x.shape[1], float(step), y.data_ptr(), y.stride(0), y.shape[1], int(chunk_outputs))
+
+
+def resample_launch(rs: Resampler, d_in, step: float, d_out, *, chunk_outputs: int = 0, stream: int | None = None):
+    """jsg_resample_launch: d_in float32 [rows][L] -> d_out float32 [rows][resample_length(L, step)], step = input samples per output
+    sample.  chunk_outputs (0: the library's choice) never changes the result."""
+    a = _resample_args(d_in, step, d_out, chunk_outputs)
+    check(lib().jsg_resample_launch(rs.handle(_device_index(d_in)), C.byref(a), _stream_handle(stream, d_in)))
+
+
+def resample_kernel_name(rs: Resampler, d_in, step: float, d_out, *, chunk_outputs: int = 0) -> str:
+    """The path resample_launch takes for these arguments: "resample_lds", "resample_l2" or "resample_direct"."""
+    a = _resample_args(d_in, step, d_out, chunk_outputs)
+    return _kernel_name(lib().jsg_resample_kernel_name, rs.handle(_device_index(d_in)), C.byref(a))
+
+
+def resample_plan(rs: Resampler, d_in, step: float, d_out, *, chunk_outputs: int = 0):
+    """jsg_resample_plan: (path, outputs per pass, bytes of LDS per workgroup) of resample_launch for these arguments.  Needs no device."""
+    a = _resample_args(d_in, step, d_out, chunk_outputs)
+    name, sub, lds = C.create_string_buffer(32), C.c_int32(), C.c_int32()
+    check(lib().jsg_resample_plan(rs.num_zeros, rs.per_zero, C.byref(a), name, 32, C.byref(sub), C.byref(lds)))
+    return name.value.decode(), sub.value, lds.value
+
+
+_resamplers: dict = {}
+
+
+def _default_resampler(quality: str = "best") -> Resampler:
+    if quality not in _resamplers:
+        _resamplers[quality] = Resampler(quality)
+    return _resamplers[quality]
+
+
+def _resample_rows(rs: Resampler, xr, step: float):
+    """xr float32 CUDA [rows][L] (unit sample stride) -> a new [rows][resample_length(L, step)]."""
+    import torch
+    out = torch.empty((xr.shape[0], resample_length(xr.shape[1], step)), dtype=torch.float32, device=xr.device)
+    with torch.cuda.device(_device_index(xr)):
+        resample_launch(rs, xr, step, out)
+    return out
+
+
+def resample(x, orig_sr: float, new_sr: float, *, resampler: Resampler | None = None):
+    """Band-limited sample-rate conversion on the GPU: x float32 CUDA [..., L] -> float32 [..., resample_length(L, orig_sr / new_sr)]
+    (ceil(L new_sr / orig_sr) for integer rates, torchaudio's length).  resampler: default Resampler("best")."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.float32, "resample: x must be a float32 CUDA tensor"
+    rs = _default_resampler() if resampler is None else resampler
+    batch = tuple(x.shape[:-1])
+    xr = x.reshape(-1, x.shape[-1]).contiguous()
+    return _resample_rows(rs, xr, float(orig_sr) / float(new_sr)).reshape(*batch, -1)
+
+
+def pitch_shift(x, n_steps: float, bins_per_octave: int = 12, n_fft: int = 2048, hop_length: int | None = None, win_length: int | None = None,
+                window=None, center: bool = True, *, resampler: Resampler | None = None):
+    """librosa.effects.pitch_shift's composition on the GPU: x float32 CUDA [..., L] -> float32 [..., L], the pitch moved by n_steps
+    steps of 1 / bins_per_octave octave.  With rate = 2.0 ** (-n_steps / bins_per_octave): time_stretch(x, rate, ...) and then
+    resample_launch with step = 1 / rate, cut or zero-padded to L."""
+    import torch.nn.functional as Fn
+    import torch
+    assert x.is_cuda and x.dtype == torch.float32, "pitch_shift: x must be a float32 CUDA tensor"
+    rs = _default_resampler() if resampler is None else resampler
+    rate = 2.0 ** (-float(n_steps) / float(bins_per_octave))
+    L = int(x.shape[-1])
+    batch = tuple(x.shape[:-1])
+    z = time_stretch(x, rate, n_fft, hop_length, win_length, window, center)
+    y = _resample_rows(rs, z.reshape(-1, z.shape[-1]).contiguous(), 1.0 / rate)
+    y = y[:, :L] if y.shape[1] >= L else Fn.pad(y, (0, L - y.shape[1]))
+    return y.contiguous().reshape(*batch, L)
