@@ -48,7 +48,8 @@ extern "C" {
                                   jsg_display_height, jsg_display_axis_centres; section 2c),
                                   complex STFT and inverse STFT with any hop (jsg_cstft_*, jsg_istft_*; section 2d); additive since: the
                                  phase vocoder (jsg_pvoc_*; section 2e), harmonic-percussive separation (jsg_hpss_*; section 2f),
-                                 band-limited resampling (jsg_sinc_table_build, jsg_resampler_*, jsg_resample_*; section 2g) */
+                                 band-limited resampling (jsg_sinc_table_build, jsg_resampler_*, jsg_resample_*; section 2g),
+                                 constant-Q and variable-Q spectrograms by direct evaluation (jsg_cqt_*; section 2h) */
 
 typedef enum jsg_status {
     JSG_OK = 0,
@@ -664,6 +665,112 @@ JSG_API int jsg_resample_plan(int num_zeros, int per_zero, const jsg_resample_ar
 /* The path of jsg_resample_plan for the sizes of `rs` (out_len >= 24).  The argument refusals of the launch; then only the sizes of
  * the plan are read: no device is needed and the plan's device is not looked at. */
 JSG_API int jsg_resample_kernel_name(const jsg_resampler* rs, const jsg_resample_args* args, char* out, int out_len);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2h. Constant-Q and variable-Q spectrograms by direct evaluation in the time domain (one inner product per bin and frame; any
+ *     fmin, any hop; no FFT, no resampling chain).
+ *
+ *     A basis is K bins.  Bin k has a half length h_k >= 0 and N_k = 2 h_k + 1 complex float32 taps c_k[m], m = -h_k..h_k, stored
+ *     contiguously (re, im) from complex element offset[k] = sum of N_j over j < k (CSR as in section 2b).  For rows x[r][0..L),
+ *     hop >= 1 and frames t = 0..T-1 centred on sample t * hop (int64 arithmetic):
+ *         C[r][t][k] = sum over the live taps of  x[r][t*hop + m] * c_k[m]
+ *         a tap is live iff  0 <= t*hop + m < L
+ *     a real-by-complex product per tap, accumulated in float32 for re and im separately.  Taps that are not live are never
+ *     touched (they are not multiplied by zero): a NaN or an Inf at x[r][m0] changes exactly the (t, k) of row r with
+ *     |m0 - t*hop| <= h_k.  Frames past the signal are sums of no taps: +0.
+ *
+ *     The order of the float32 sum depends on k and on the tap index i = m + h_k alone.  With W_k = 64 where N_k > 32, else the
+ *     smallest power of two >= N_k: lane l of W_k takes the live taps i = l, l + W_k, l + 2 W_k, ... in ascending order,
+ *         acc_l = fmaf(x, c.re, acc_l)  (and the same for im),  acc_l = +0 at the start,
+ *     then a fixed halving tree: for s = W_k/2, W_k/4, ..., 1: acc_l = acc_l + acc_(l+s) for l < s; the result is acc_0.  The bits
+ *     therefore do not depend on t, r, L, chunk_frames, the grid, the row count, the pitches or the alignment of the pointers, and
+ *     an interior frame of a signal delayed by one hop has the bits of the previous frame of the undelayed signal.  The contract
+ *     is a tolerance against the float64 evaluation of the formula above on the float32 taps.
+ *
+ *     Output is frame-major: out_power = 0 writes float pairs (re, im) at out[(r*out_row_pitch + t*out_frame_pitch + k)] (pitches in
+ *     complex elements); out_power = 1 writes re*re + im*im (both products and the sum rounded separately, no fused multiply-add;
+ *     pitches in floats), the plane that jsg_db_from_power_launch, jsg_colormap_launch (height = K) and jsg_hpss_launch
+ *     (in_complex = 0) take.  Elements between K and the frame pitch are not written.
+ *
+ *     The standard basis (jsg_cqt_basis_build; all arithmetic in double, each tap component rounded to float32 once):
+ *         r = 2^(1/B),  alpha = (r^2 - 1) / (r^2 + 1),  Q = filter_scale / alpha,  f_k = fmin * 2^(k/B)
+ *         l_k = Q * fs / (f_k + gamma / alpha)          (gamma = 0: constant-Q; gamma > 0: variable-Q)
+ *         h_k = floor(l_k / 2)
+ *         g[m] = 1/2 + 1/2 cos(pi m / (h_k + 1)),  normalised to sum g = 1,  times sqrt(l_k) if scale is set
+ *         c_k[m] = g[m] * (cos phi, -sin phi),  phi = 2 pi frac(f_k * m / fs),  frac(u) = u - floor(u)
+ *     the shape of librosa's wavelet / cqt / vqt (the same alpha, Q and lengths, an L1-normalised Hann, the sqrt-length scale) on a
+ *     symmetric support of odd length; agreement with librosa has not been measured.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSG_CQT_MAX_BINS 4096
+#define JSG_CQT_MAX_HALF_LEN 131072
+#define JSG_CQT_MAX_TAPS 16777216       /* sum of N_k */
+#define JSG_CQT_MAX_CLASSES 20
+typedef struct jsg_cqt_spec {
+    double fs;                  /* sample rate, finite, > 0 */
+    double fmin;                /* centre of bin 0, finite, > 0 */
+    int32_t n_bins;             /* K, 1..JSG_CQT_MAX_BINS */
+    int32_t bins_per_octave;    /* B, 1..1200 */
+    double filter_scale;        /* finite, > 0 */
+    double gamma;               /* finite, >= 0 */
+    int32_t scale;              /* != 0: taps times sqrt(l_k) */
+} jsg_cqt_spec;
+/* The standard basis on the host (no device): half_len[K], offset[K] (complex elements), centre_hz[K] (any of the three may be NULL),
+ * taps[2 * n_taps] floats (re, im).  taps == NULL only counts: *n_taps = sum of N_k.  Refused (JSG_ERR_INVALID): a null spec or
+ * n_taps, fs, fmin, filter_scale or gamma out of range, n_bins or bins_per_octave out of range, f_(K-1) * (1 + alpha / 2) > fs / 2,
+ * an h_k above JSG_CQT_MAX_HALF_LEN, sum N_k above JSG_CQT_MAX_TAPS, taps_cap (complex elements) below sum N_k. */
+JSG_API int jsg_cqt_basis_build(const jsg_cqt_spec* spec, int32_t* half_len, int64_t* offset, float* centre_hz, float* taps,
+                                int64_t taps_cap, int64_t* n_taps);
+
+typedef struct jsg_cqt jsg_cqt;
+/* Builds the standard basis and uploads it to the current device; the kernel's dynamic LDS limit is set here, so that a first
+ * launch may sit inside a graph capture.  Refused: what jsg_cqt_basis_build refuses.  Then JSG_ERR_NO_DEVICE without a HIP device. */
+JSG_API int jsg_cqt_create(jsg_cqt** out, const jsg_cqt_spec* spec);
+/* The same for a caller's basis: n_bins half lengths and sum N_k complex taps (host memory).  Refused: null pointers, n_bins outside
+ * 1..JSG_CQT_MAX_BINS, an h_k outside 0..JSG_CQT_MAX_HALF_LEN, sum N_k above JSG_CQT_MAX_TAPS.  Then JSG_ERR_NO_DEVICE. */
+JSG_API int jsg_cqt_create_tables(jsg_cqt** out, int n_bins, const int32_t* half_len, const float* taps);
+JSG_API int jsg_cqt_destroy(jsg_cqt* cq);
+JSG_API int jsg_cqt_bins(const jsg_cqt* cq);
+JSG_API int jsg_cqt_half_len(const jsg_cqt* cq, int32_t* out);     /* n_bins entries */
+JSG_API int64_t jsg_cqt_total_taps(const jsg_cqt* cq);
+/* 1 + floor(L / hop) for L in 1..2^31-1 and hop in 1..2^20 (JSG_ERR_INVALID otherwise): the frames whose centre lies in 0..L.  The
+ * launch takes any T >= 1. */
+JSG_API int64_t jsg_cqt_frames(int64_t in_samples, int64_t hop);
+
+typedef struct jsg_cqt_args {
+    const float* in;            /* device floats: x[r][m] at in[r*in_pitch + m] */
+    int64_t in_pitch;           /* rows > 1: >= in_samples */
+    int32_t rows;               /* 1..65535, independent */
+    int64_t in_samples;         /* L, 1..2^31-1 */
+    int64_t hop;                /* 1..2^20 */
+    int64_t n_frames;           /* T, 1..2^31-1 */
+    void* out;                  /* device; out_power = 0: float pairs, 8-byte aligned; 1: floats, 4-byte aligned */
+    int64_t out_frame_pitch;    /* elements (complex elements or floats) between frames, >= K */
+    int64_t out_row_pitch;      /* rows > 1: >= (T-1)*out_frame_pitch + K */
+    int32_t out_power;          /* 0 or 1 */
+    int32_t chunk_frames;       /* upper bound on the frames per work item: 0 = the library's choice, else 1..65536; never changes the result */
+} jsg_cqt_args;
+/* Enqueue only (one kernel, no scratch): no allocation, no synchronisation; hipGraph capture works, a first launch included.  Refused
+ * (JSG_ERR_INVALID, nothing enqueued, jsg_last_error set), in this order and before any device call: a null basis, null args, a null
+ * data pointer, out_power other than 0 or 1, a misaligned pointer, rows outside 1..65535, in_samples outside 1..2^31-1, hop outside
+ * 1..2^20, n_frames outside 1..2^31-1, chunk_frames outside 0 or 1..65536, in_pitch below in_samples (rows > 1).  Then
+ * JSG_ERR_NO_DEVICE without a HIP device (asking for the current device is the first device call; the basis is read only after it).
+ * Then, still with nothing enqueued: out_frame_pitch below K, out_row_pitch below (T-1)*out_frame_pitch + K (rows > 1), out
+ * overlapping in, a basis of another device.  jsg_cqt_plan and jsg_cqt_kernel_name decide all of these without a device.  Every basis
+ * and call that pass are served: see the paths of jsg_cqt_plan. */
+JSG_API int jsg_cqt_launch(const jsg_cqt* cq, const jsg_cqt_args* args, void* stream);
+/* What the launch would do for a basis of these half lengths, without a basis object and without a device.  Bins are served in
+ * classes by length: class c holds the bins with 2^(c-1) < N_k <= 2^c (class 0: N_k = 1); the classes that hold bins are reported
+ * longest first: *n_classes of them (<= JSG_CQT_MAX_CLASSES) in the arrays class_max_taps (the largest N_k of the class),
+ * frames_per_item (frames a work item of the class takes: one staging of the input into LDS), taps_per_pass (taps of a bin that are
+ * staged at a time: < class_max_taps only on the "cqt_passes" path) and lds_bytes (of the class; a workgroup asks for the largest).
+ * Any output pointer may be NULL (name: else name_len >= 24).  The paths: "cqt_span" (every bin's taps are staged in one pass) and
+ * "cqt_passes" (a class with N_k > 12288 walks its taps in passes of 12288, the lane accumulators kept across the passes, so the
+ * order of the sum is the same).  Every accepted call has frames_per_item >= 1, taps_per_pass >= 1 and lds_bytes <= 163840.
+ * Refused: what the launch refuses for `args`, and what jsg_cqt_create_tables refuses for n_bins and half_len. */
+JSG_API int jsg_cqt_plan(int n_bins, const int32_t* half_len, const jsg_cqt_args* args, char* name, int name_len, int32_t* n_classes,
+                         int32_t* class_max_taps, int32_t* frames_per_item, int32_t* taps_per_pass, int32_t* lds_bytes);
+/* The path of jsg_cqt_plan for the basis `cq` (out_len >= 24).  The argument refusals of the launch; no device is needed. */
+JSG_API int jsg_cqt_kernel_name(const jsg_cqt* cq, const jsg_cqt_args* args, char* out, int out_len);
 
 /* ------------------------------------------------------------------------------------------------
  * 3. Engine: the state of class Spectrogram (Spectrogram.h:81-169) living on the GPU.

@@ -11,7 +11,8 @@ from .spectrogram import (CColorPalette, Filterbank, FreqAxis, Plan, Spectrogram
                           CStftPlan, cstft, istft, istft_launch, istft_nola, istft_scratch_floats, stft,
                           phase_vocoder, phase_vocoder_launch, pvoc_frames, time_stretch,
                           hpss, hpss_audio, hpss_launch, hpss_scratch_bytes,
-                          Resampler, pitch_shift, resample, resample_kernel_name, resample_launch, resample_length, resample_plan, sinc_table)
+                          Resampler, pitch_shift, resample, resample_kernel_name, resample_launch, resample_length, resample_plan, sinc_table,
+                          CqtBasis, cqt, cqt_db, cqt_frames, cqt_frequencies, cqt_kernel_name, cqt_launch, cqt_plan, vqt)
 
 __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_db", "colormap", "window", "colormap_lut",
            "colormap_range", "feed_samples", "memsize_blocks", "next_power_of_2", "JsgError", "capi",
@@ -19,4 +20,5 @@ __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_d
            "CStftPlan", "cstft", "istft_launch", "istft_nola", "istft_scratch_floats", "stft", "istft",
            "pvoc_frames", "phase_vocoder_launch", "phase_vocoder", "time_stretch",
            "hpss_scratch_bytes", "hpss_launch", "hpss", "hpss_audio",
-           "sinc_table", "Resampler", "resample_length", "resample_launch", "resample_kernel_name", "resample_plan", "resample", "pitch_shift"]
+           "sinc_table", "Resampler", "resample_length", "resample_launch", "resample_kernel_name", "resample_plan", "resample", "pitch_shift",
+           "CqtBasis", "cqt_frames", "cqt_launch", "cqt_plan", "cqt_kernel_name", "cqt", "vqt", "cqt_frequencies", "cqt_db"]

@@ -32,6 +32,7 @@ AXIS_BINS, AXIS_LINEAR, AXIS_LOG, AXIS_MEL = range(4)
 AXIS_MAX_HEIGHT = 16384
 HPSS_MAX_WINDOW = 63
 RESAMPLE_MAX_TABLE = 32768
+CQT_MAX_BINS, CQT_MAX_HALF_LEN, CQT_MAX_TAPS, CQT_MAX_CLASSES = 4096, 131072, 1 << 24, 20
 
 
 class JsgError(RuntimeError):
@@ -94,6 +95,17 @@ class HpssArgs(C.Structure):
 class ResampleArgs(C.Structure):
     _fields_ = [("in_", C.c_void_p), ("in_pitch", C.c_int64), ("rows", C.c_int32), ("in_samples", C.c_int64), ("step", C.c_double),
                 ("out", C.c_void_p), ("out_pitch", C.c_int64), ("out_samples", C.c_int64), ("chunk_outputs", C.c_int32)]
+
+
+class CqtSpec(C.Structure):
+    _fields_ = [("fs", C.c_double), ("fmin", C.c_double), ("n_bins", C.c_int32), ("bins_per_octave", C.c_int32), ("filter_scale", C.c_double),
+                ("gamma", C.c_double), ("scale", C.c_int32)]
+
+
+class CqtArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("in_pitch", C.c_int64), ("rows", C.c_int32), ("in_samples", C.c_int64), ("hop", C.c_int64),
+                ("n_frames", C.c_int64), ("out", C.c_void_p), ("out_frame_pitch", C.c_int64), ("out_row_pitch", C.c_int64),
+                ("out_power", C.c_int32), ("chunk_frames", C.c_int32)]
 
 
 class StftImageArgs(C.Structure):
@@ -167,6 +179,17 @@ SIGNATURES = {
     "jsg_resample_launch": (C.c_int, [_P, C.POINTER(ResampleArgs), _P]),
     "jsg_resample_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(ResampleArgs), C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "jsg_resample_kernel_name": (C.c_int, [_P, C.POINTER(ResampleArgs), C.c_char_p, C.c_int]),
+    "jsg_cqt_basis_build": (C.c_int, [C.POINTER(CqtSpec), _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "jsg_cqt_create": (C.c_int, [C.POINTER(_P), C.POINTER(CqtSpec)]),
+    "jsg_cqt_create_tables": (C.c_int, [C.POINTER(_P), C.c_int, _P, _P]),
+    "jsg_cqt_destroy": (C.c_int, [_P]),
+    "jsg_cqt_bins": (C.c_int, [_P]),
+    "jsg_cqt_half_len": (C.c_int, [_P, _P]),
+    "jsg_cqt_total_taps": (C.c_int64, [_P]),
+    "jsg_cqt_frames": (C.c_int64, [C.c_int64, C.c_int64]),
+    "jsg_cqt_launch": (C.c_int, [_P, C.POINTER(CqtArgs), _P]),
+    "jsg_cqt_plan": (C.c_int, [C.c_int, _P, C.POINTER(CqtArgs), C.c_char_p, C.c_int, C.POINTER(C.c_int32), _P, _P, _P, _P]),
+    "jsg_cqt_kernel_name": (C.c_int, [_P, C.POINTER(CqtArgs), C.c_char_p, C.c_int]),
     "jsg_create": (C.c_int, [C.POINTER(_P), C.c_int]),
     "jsg_create_on_device": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int]),
     "jsg_get_device": (C.c_int, [_P]),

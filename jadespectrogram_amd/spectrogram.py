@@ -1223,3 +1223,151 @@ def pitch_shift(x, n_steps: float, bins_per_octave: int = 12, n_fft: int = 2048,
     y = _resample_rows(rs, z.reshape(-1, z.shape[-1]).contiguous(), 1.0 / rate)
     y = y[:, :L] if y.shape[1] >= L else Fn.pad(y, (0, L - y.shape[1]))
     return y.contiguous().reshape(*batch, L)
+
+
+# --------------------------------------------------------------------------------------------------
+# constant-Q and variable-Q spectrograms by direct evaluation (include/jsg.h, section 2h)
+# --------------------------------------------------------------------------------------------------
+CQT_FMIN_C1 = 32.70319566257483
+
+
+class CqtBasis(_PerDeviceHandles):
+    """The basis of jsg_cqt_launch: n_bins bins, bin k with half length half_lengths[k] and 2 half_lengths[k] + 1 complex64 taps at
+    taps[offsets[k] :].  Built on the host by jsg_cqt_basis_build (no GPU needed) or taken from a caller's tables; uploaded to a device
+    once, the first time a launch on that device needs it.
+
+        CqtBasis(fs, fmin, n_bins, bins_per_octave=12, filter_scale=1.0, gamma=0.0, scale=True)    the standard basis (gamma > 0: variable-Q)
+        CqtBasis.from_tables(half_len, taps)                                                       any basis inside the size limits
+    """
+    _destroy = "jsg_cqt_destroy"
+
+    def __init__(self, fs: float, fmin: float, n_bins: int, bins_per_octave: int = 12, filter_scale: float = 1.0, gamma: float = 0.0,
+                 scale: bool = True):
+        spec = capi.CqtSpec(float(fs), float(fmin), int(n_bins), int(bins_per_octave), float(filter_scale), float(gamma), int(bool(scale)))
+        total = C.c_int64()
+        check(lib().jsg_cqt_basis_build(C.byref(spec), None, None, None, None, 0, C.byref(total)))
+        K = int(n_bins)
+        half, offset, freq = np.zeros(K, np.int32), np.zeros(K, np.int64), np.zeros(K, np.float32)
+        taps = np.zeros(total.value, np.complex64)
+        check(lib().jsg_cqt_basis_build(C.byref(spec), half.ctypes.data, offset.ctypes.data, freq.ctypes.data, taps.ctypes.data, total.value,
+                                        C.byref(total)))
+        self.half_lengths, self.offsets, self.frequencies, self.taps, self._handles = half, offset, freq, taps, {}
+
+    @classmethod
+    def from_tables(cls, half_len, taps) -> "CqtBasis":
+        h = np.ascontiguousarray(half_len, dtype=np.int32).ravel()
+        t = np.ascontiguousarray(taps, dtype=np.complex64).ravel()
+        n = 2 * h.astype(np.int64) + 1
+        assert h.size >= 1 and (h >= 0).all() and t.size == int(n.sum()), "taps: the sum of 2 half_len + 1 complex entries"
+        self = cls.__new__(cls)
+        self.half_lengths, self.offsets, self.frequencies, self.taps, self._handles = h, np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64), None, t, {}
+        return self
+
+    @property
+    def n_bins(self) -> int:
+        return int(self.half_lengths.size)
+
+    def _create(self, h):
+        check(lib().jsg_cqt_create_tables(C.byref(h), self.n_bins, self.half_lengths.ctypes.data, self.taps.ctypes.data))
+
+
+def cqt_frames(in_samples: int, hop: int) -> int:
+    """jsg_cqt_frames: 1 + in_samples // hop, the frames whose centre t * hop lies in 0..in_samples."""
+    return int(check(lib().jsg_cqt_frames(int(in_samples), int(hop))))
+
+
+def cqt_frequencies(n_bins: int, fmin: float | None = None, bins_per_octave: int = 12) -> np.ndarray:
+    """fmin * 2 ** (k / bins_per_octave) for k < n_bins, float64 (fmin None: C1)."""
+    f0 = CQT_FMIN_C1 if fmin is None else float(fmin)
+    return f0 * 2.0 ** (np.arange(int(n_bins), dtype=np.float64) / float(bins_per_octave))
+
+
+def _cqt_args(basis: CqtBasis, d_in, hop: int, n_frames: int, d_out, power: bool, chunk_frames: int) -> capi.CqtArgs:
+    import torch
+    x = d_in[None] if d_in.dim() == 1 else d_in
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1, "d_in: float32 CUDA [rows][samples]"
+    o = _rows3(d_out, "d_out")
+    want = torch.float32 if power else torch.complex64
+    assert o.is_cuda and o.dtype == want and o.stride(2) == 1 and o.shape[0] == x.shape[0] and o.shape[1] >= n_frames and o.shape[2] >= basis.n_bins, \
+        "d_out: CUDA [rows][>= n_frames][>= n_bins], complex64 (power: float32)"
+    return capi.CqtArgs(x.data_ptr(), x.stride(0), x.shape[0], x.shape[1], int(hop), int(n_frames), o.data_ptr(), o.stride(1), o.stride(0),
+                        int(bool(power)), int(chunk_frames))
+
+
+def cqt_launch(basis: CqtBasis, d_in, hop: int, n_frames: int, d_out, *, power: bool = False, chunk_frames: int = 0, stream: int | None = None):
+    """jsg_cqt_launch: d_in float32 [rows][L] -> d_out [rows][n_frames][>= n_bins], complex64 or (power) float32 re*re + im*im; frame t is
+    centred on sample t * hop.  chunk_frames (0: the library's choice) never changes the result."""
+    a = _cqt_args(basis, d_in, hop, n_frames, d_out, power, chunk_frames)
+    check(lib().jsg_cqt_launch(basis.handle(_device_index(d_in)), C.byref(a), _stream_handle(stream, d_in)))
+
+
+def cqt_kernel_name(basis: CqtBasis, d_in, hop: int, n_frames: int, d_out, *, power: bool = False, chunk_frames: int = 0) -> str:
+    """The path cqt_launch takes for these arguments: "cqt_span" or "cqt_passes"."""
+    a = _cqt_args(basis, d_in, hop, n_frames, d_out, power, chunk_frames)
+    return _kernel_name(lib().jsg_cqt_kernel_name, basis.handle(_device_index(d_in)), C.byref(a))
+
+
+def cqt_plan(basis: CqtBasis, d_in, hop: int, n_frames: int, d_out, *, power: bool = False, chunk_frames: int = 0):
+    """jsg_cqt_plan: (path, [(largest taps of the class, frames per item, taps per pass, bytes of LDS), ...] longest class first) of
+    cqt_launch for these arguments.  Needs no device."""
+    a = _cqt_args(basis, d_in, hop, n_frames, d_out, power, chunk_frames)
+    name, n = C.create_string_buffer(32), C.c_int32()
+    cols = [np.zeros(capi.CQT_MAX_CLASSES, np.int32) for _ in range(4)]
+    check(lib().jsg_cqt_plan(basis.n_bins, basis.half_lengths.ctypes.data, C.byref(a), name, 32, C.byref(n), *[c.ctypes.data for c in cols]))
+    return name.value.decode(), [tuple(int(c[i]) for c in cols) for i in range(n.value)]
+
+
+_cqt_bases: dict = {}
+
+
+def _cqt_basis(sr, fmin, n_bins, bins_per_octave, filter_scale, gamma, scale) -> CqtBasis:
+    key = (float(sr), CQT_FMIN_C1 if fmin is None else float(fmin), int(n_bins), int(bins_per_octave), float(filter_scale), float(gamma), bool(scale))
+    if key not in _cqt_bases:
+        _cqt_bases[key] = CqtBasis(*key)
+    return _cqt_bases[key]
+
+
+def _cqt_rows(x, basis: CqtBasis, hop: int, power: bool):
+    """x numpy array or CUDA tensor [..., L] -> (frame-major CUDA tensor [rows][frames][bins], batch shape, whether x was numpy)."""
+    import torch
+    was_numpy = not hasattr(x, "is_cuda")
+    if was_numpy:
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda()
+    assert x.is_cuda and x.dtype == torch.float32, "x must be a numpy array or a float32 CUDA tensor"
+    batch = tuple(x.shape[:-1])
+    xr = x.reshape(-1, x.shape[-1]).contiguous()
+    frames = cqt_frames(xr.shape[1], hop)
+    out = torch.empty((xr.shape[0], frames, basis.n_bins), dtype=torch.float32 if power else torch.complex64, device=x.device)
+    with torch.cuda.device(_device_index(x)):
+        cqt_launch(basis, xr, hop, frames, out, power=power)
+    return out, batch, was_numpy
+
+
+def vqt(x, sr: float, hop_length: int = 512, fmin: float | None = None, n_bins: int = 84, gamma: float = 0.0, bins_per_octave: int = 12,
+        filter_scale: float = 1.0, scale: bool = True):
+    """Variable-Q transform on the GPU: x [..., L] (numpy array or float32 CUDA tensor) -> complex64 [..., n_bins, 1 + L // hop_length]
+    (the transposed view of the library's frame-major buffer, as stft returns it; a numpy array for numpy input).  gamma = 0 is cqt."""
+    basis = _cqt_basis(sr, fmin, n_bins, bins_per_octave, filter_scale, gamma, scale)
+    out, batch, was_numpy = _cqt_rows(x, basis, int(hop_length), False)
+    out = out.reshape(*batch, out.shape[1], out.shape[2]).transpose(-1, -2)
+    return out.cpu().numpy() if was_numpy else out
+
+
+def cqt(x, sr: float, hop_length: int = 512, fmin: float | None = None, n_bins: int = 84, bins_per_octave: int = 12, filter_scale: float = 1.0,
+        scale: bool = True):
+    """Constant-Q transform on the GPU (fmin None: C1 = 32.70319566257483 Hz): vqt with gamma = 0."""
+    return vqt(x, sr, hop_length, fmin, n_bins, 0.0, bins_per_octave, filter_scale, scale)
+
+
+def cqt_db(x, sr: float, hop_length: int = 512, fmin: float | None = None, n_bins: int = 84, bins_per_octave: int = 12, filter_scale: float = 1.0,
+           scale: bool = True, gamma: float = 0.0, divisor: float = 1.0):
+    """10 log10(|C|^2 / divisor + 1e-11) of the constant-Q (gamma > 0: variable-Q) transform: the power plane of jsg_cqt_launch through
+    db_from_power.  float32 [..., n_bins, frames], a transposed view: result.transpose(-1, -2) of one row is the contiguous
+    [frames][n_bins] plane that colormap takes (height = n_bins)."""
+    basis = _cqt_basis(sr, fmin, n_bins, bins_per_octave, filter_scale, gamma, scale)
+    power, batch, was_numpy = _cqt_rows(x, basis, int(hop_length), True)
+    import torch
+    db = torch.empty_like(power)
+    db_from_power(power, db, divisor)
+    db = db.reshape(*batch, db.shape[1], db.shape[2]).transpose(-1, -2)
+    return db.cpu().numpy() if was_numpy else db
