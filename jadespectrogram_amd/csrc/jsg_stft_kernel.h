@@ -413,6 +413,23 @@ __device__ __forceinline__ cf to_cf(const f2u& v) { return cf{v.x, v.y}; }
 #define JSG_X_RUNLEN 2       // (variant builds sweep this: 2 / 4 / 8 -- measured 2 >= 4 > none > 8)
 #endif
 constexpr int kRunLen = JSG_X_RUNLEN;   // STREAM == 2 ("runs"): consecutive columns a wavefront transforms one after the other (see stft_db_kernel)
+// Bookkeeping trims of the runs kernel ("Runs bookkeeping"); same values, same bits.  The store form is the product's;
+// variant builds switch it off, and the two measured-and-not-adopted steps on, for A/B.
+#ifdef JSG_X_NO_RUNS_STORE    // column stores as scalar base + per-wave lane offset + immediate, lane-0 values selected up front, one lane-0 region
+constexpr bool kRunsStore = false;
+#else
+constexpr bool kRunsStore = true;
+#endif
+#ifdef JSG_X_RUNS_INCR        // ring column, output and tail-plane address of the later columns of a run by increment from the first
+constexpr bool kRunsIncr = true;     // (+0.4 / +0.9 % on C2 / the C4 shard with overlapping rounds: not adopted)
+#else
+constexpr bool kRunsIncr = false;
+#endif
+#ifdef JSG_X_RUNS_NY0         // bin M/2 computed on lane 0's own value, no broadcast (needs the selected lane-0 store of kRunsStore)
+constexpr bool kRunsNy0 = kRunsStore;   // (level on C2, -1 % on the C4 shard: not adopted)
+#else
+constexpr bool kRunsNy0 = false;
+#endif
 
 template <int N_, int R1_, int R2_, int R3_, int L_, int S1_, int AX_, int AY_, int AZ_, int WPB_, int TLOC_, int WPS_,
           int FPW_ = 1, int EARLY1_ = 0, int TWF_ = 0, int PAIR_ = 0, int RTAB_ = 0>
@@ -728,6 +745,15 @@ __device__ __forceinline__ cf mix_combine2(cf acc, cf pw) {
 // branch: as a branch (round 4) the routine moved the register allocation of every kernel (+3 VGPRs, spills in the index-out forms), so
 // the default path does not know it exists.  Round 4 ran it as a second elementwise pass over the columns of a launch (one more read and
 // write of the output, and no display path); since round 5 it sits in the epilogue of every output form.
+// v in the lanes whose bit is clear in `mask`, w in the others: ONE v_cndmask on a mask that lives in scalar registers.  Written out because a
+// C++ select on `lane == 0` next to a branch on the same condition is threaded into that branch by the compiler -- the runs kernel's column
+// epilogue then carried three exec regions with duplicated stores instead of four selects.
+__device__ __forceinline__ float lane0_select(float v, float w, unsigned long long mask) {
+    float r;
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(v), "v"(w), "s"(mask));
+    return r;
+}
+
 template <class C, int MIXOP, int OUTK = 0, int STREAM = 0, int XLOG = 0>
 // (RTAB instantiations: five waves per SIMD -- what the plan's LDS allows -- instead of the plan's C::WPS, see Cfg::RTAB.  Strided dispatches
 // only: a single launch of one 4096-frame batch gives every wave ONE frame, and reading the tables into registers first costs it 1-1.5 %
@@ -922,6 +948,17 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
     long long rn_in = 0;                  // input offset of the run's row
     bool nx_live = true, cu_live = true;  // the round's column exists (columns past the end of a row are transformed on whatever the clamped
                                           // loads bring and NOT stored; the other kernels repeat the row's last column instead)
+    // the store side of a run (scalar): ring column, column address and tail-plane row of the run's previous column -- the next column is
+    // one further (kRunsIncr: an add and one wrap compare instead of the 64-bit col * out_pitch product per column)
+    unsigned st_col = 0;
+    float* st_dst = nullptr;
+    float* st_tl = nullptr;
+    // byte offsets of this lane inside a store instruction's 256 bytes, once per wave (kRunsStore): lower half bin lane + 64 r, upper half
+    // bin M - 64 (r + 1) + ((64 - lane) & 63) -- lane 0 stores 64 bins further down, see "Whole 128-byte lines" in the store phase.  Opaque,
+    // so that they stay in two registers instead of being rebuilt (shift, move, 64-bit add) for every column.
+    unsigned st_vlo = 4u * (unsigned)lane, st_vup = 4u * (unsigned)((64 - lane) & 63);
+    if constexpr (RUNS && kRunsStore) asm volatile("" : "+v"(st_vlo), "+v"(st_vup));
+    const unsigned long long st_l0 = __builtin_amdgcn_ballot_w64(lane == 0);   // lane 0's bit, the mask of lane0_select (scalar, once per wave)
     // a new run: super-group `sg` of this workgroup -> row, first column of this wave's run, the row's input / ring offsets (scalar, once per RL rounds)
     auto runs_group = [&](unsigned sg) {
         unsigned g = lb + sg * nblk;
@@ -1403,7 +1440,10 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
                 {   // bin M/2 (held by the frame's lane 0): the window carries 1/2, so |X|^2 = 4 |Z'|^2.  For single-wave
                     // frames the value is broadcast so that every lane can take part in an unmasked store below.
                     cf z = x[f][reg_of(P / 2)];
-                    if constexpr (L == 64) {
+                    if constexpr (RUNS && kRunsNy0) {
+                        // (runs: lane 0 alone stores this value -- selected into the last mirrored store -- so it is computed on every lane's
+                        // own register and only lane 0's result is used: no broadcast)
+                    } else if constexpr (L == 64) {
                         z.x = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(z.x)));
                         z.y = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(z.y)));
                     } else if constexpr (L == 32) {
@@ -1502,8 +1542,16 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
                     tk = cu_col0 + slot0 + tsub * F + f;
                     tk = tk < a.n_frames ? tk : a.n_frames - 1;
                 } else tk = task_of(it, f);
-                unsigned col = a.ring_pos + tk;                    // n_frames <= ring_w (checked by the launcher)
-                if (col >= (unsigned)a.ring_w) col -= a.ring_w;
+                constexpr bool INCR = RUNS && kRunsIncr && T > 0;  // a later column of a run: the previous one's ring column plus one
+                unsigned col;
+                if constexpr (INCR) {                              // (a live column's predecessor is live and unclamped; dead columns are not stored)
+                    col = st_col + 1u;
+                    if (col == (unsigned)a.ring_w) col = 0u;
+                } else {
+                    col = a.ring_pos + tk;                         // n_frames <= ring_w (checked by the launcher)
+                    if (col >= (unsigned)a.ring_w) col -= a.ring_w;
+                }
+                if constexpr (RUNS && kRunsIncr) st_col = col;
                 const bool fuse_scale = !ONE && !XLOG && !a.linear && !a.exact_div;   // (uniform) v_log path of a mixing kernel: see below
                 if constexpr (ONE) {
                     // one channel: the launcher selects this instantiation only when the mix scale is exactly 1
@@ -1708,11 +1756,15 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
                         row_of(row, in_off, cofs);
                     }
                     float* dstA = a.out + (long long)colA * a.out_pitch + cofs;
+                    if constexpr (INCR) dstA = col == 0u ? a.out + cofs : st_dst + a.out_pitch;   // one column further, or back at the ring's start
+                    if constexpr (RUNS && kRunsIncr) st_dst = dstA;
                     float* dstB = a.out + (long long)colB * a.out_pitch + cofs;
                     float* dst = a.out + (long long)col * a.out_pitch + cofs;
                     // tail plane (jsg_stft_args.out_tail): bin N/2 -- the one value of a column that lies behind its sixteen (N = 1024)
                     // whole 128-byte lines -- goes to a dense plane of one float per column instead; row = batch x channel plane
                     float* tl_row = nullptr;
+                    if constexpr (INCR) tl_row = st_tl;   // (same row as the run's first column)
+                    else
                     if (a.tail) {
                         unsigned trow = a.per_channel ? (unsigned)c0 : 0u;
                         if constexpr (CARRY) trow = cu_row;
@@ -1722,6 +1774,35 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
                         }
                         tl_row = a.tail + (long long)trow * a.ring_w;
                     }
+                    if constexpr (RUNS && kRunsIncr) st_tl = tl_row;
+                    if constexpr (RUNS && kRunsStore) {
+                        // The column of "Whole 128-byte lines" below, with its bookkeeping taken off the vector pipe: every store is the
+                        // column's scalar address + one of the wave's two lane offsets (st_vlo / st_vup, set once) + an immediate; the
+                        // mirrored half is addressed from its lowest window upwards, so every immediate is non-negative (4 (M - 64 (r + 1)));
+                        // lane 0's exceptions are SELECTED (the next register's mirror value, bin M/2 in the last one) and the stores run
+                        // unmasked; bin M is the one lane-0 region of the column.  Which lane stores a value is as below, no value changes.
+                        static_assert(!(RUNS && kRunsStore) || (L == 64 && F == 1 && M % 64 == 0), "runs: one wavefront per frame");
+                        if (cu_live) {                                      // (uniform; a column past the end of its row is not stored)
+                            // (the offsets pass through an empty asm per column: the zero-extension then sits next to its stores, where the
+                            // instruction selector folds it into the scalar-base form -- hoisted out of the loop it became a 64-bit vector add)
+                            asm volatile("" : "+v"(st_vlo), "+v"(st_vup));
+                            char* const lo = reinterpret_cast<char*>(dstA) + (unsigned long long)st_vlo;
+                            char* const hi = reinterpret_cast<char*>(dstA) + (unsigned long long)st_vup;
+#pragma unroll
+                            for (int rho = 0; rho < P / 2; ++rho) {
+                                __builtin_nontemporal_store(acc[f][rho].x, reinterpret_cast<float*>(lo) + 64 * rho);
+                                const float nxt = rho + 1 < P / 2 ? acc[f][rho + 1].y : accNy[f];
+                                __builtin_nontemporal_store(lane0_select(acc[f][rho].y, nxt, st_l0), reinterpret_cast<float*>(hi) + (M - 64 * (rho + 1)));
+                            }
+                            // bin M, lane 0: into the tail plane (plain store: the pieces of 32 columns meet in L2), or alone into the column's
+                            // last line -- a scalar address either way
+                            if (tl_row) {
+                                if (lane == 0) tl_row[col] = acc[f][0].y;
+                            } else {
+                                if (lane == 0) __builtin_nontemporal_store(acc[f][0].y, &dstA[M]);
+                            }
+                        }
+                    } else
                     if constexpr (L == 16) {
                         // as the L <= 64 form below with four frames: register 4 q + j = window q (bins 64 q + lane and their mirror) of frame j
                         static_assert(L != 16 || OUTK == 0, "the 16-lane plan writes float columns");
