@@ -49,7 +49,8 @@ extern "C" {
                                   complex STFT and inverse STFT with any hop (jsg_cstft_*, jsg_istft_*; section 2d); additive since: the
                                  phase vocoder (jsg_pvoc_*; section 2e), harmonic-percussive separation (jsg_hpss_*; section 2f),
                                  band-limited resampling (jsg_sinc_table_build, jsg_resampler_*, jsg_resample_*; section 2g),
-                                 constant-Q and variable-Q spectrograms by direct evaluation (jsg_cqt_*; section 2h) */
+                                 constant-Q and variable-Q spectrograms by direct evaluation (jsg_cqt_*; section 2h),
+                                 the band launch query (jsg_fb_band_plan; section 2b) */
 
 typedef enum jsg_status {
     JSG_OK = 0,
@@ -399,6 +400,19 @@ JSG_API int jsg_stft_fb_launch_strided(const jsg_plan* plan, const jsg_filterban
 JSG_API int64_t jsg_stft_fb_scratch_floats(const jsg_plan* plan, const jsg_filterbank* fb, const jsg_stft_args* args, int n_batches);
 /* The STFT kernel every chunk of such a call takes ("Cfg1024", "Cfg2048B", ...; out_len >= 24). */
 JSG_API int jsg_stft_fb_kernel_name(const jsg_plan* plan, const jsg_filterbank* fb, const jsg_stft_args* args, int n_batches, char* out, int out_len);
+/* How the band kernel of one chunk is launched (host arithmetic only: no device, no objects; the launcher takes its numbers from the
+ * same routine).  A chunk of n_cols power columns (batches x rows x frames) of an n-point plan, a bank of n_bands bands and nnz weights,
+ * a device of n_cu compute units:
+ *   tile_cols    power columns per LDS tile: 8 (n <= 2048), 4 (4096), 2 (8192)
+ *   bank_in_lds  1 where descriptors and weights, 3 n_bands + nnz words, fit 28 KB and are staged in LDS; 0: read through the caches
+ *   pw_pitch     floats per power column in scratch: n/2 + 1 rounded up to whole 128-byte lines
+ *   lds_bytes    4 tile_cols pw_pitch, plus 4 (3 n_bands + nnz) where the bank is in LDS
+ *   grid         workgroups: max(1, min(ceil(n_cols / tile_cols), n_cu min(8, 163840 / lds_bytes))); a workgroup takes the tiles
+ *                blockIdx, blockIdx + grid, ...
+ * Any output pointer may be NULL.  JSG_ERR_INVALID: n not a power of two in 512..8192, n_bands outside 1..JSG_FB_MAX_BANDS, nnz outside
+ * 0..2^31-1, n_cols outside 1..2^28, n_cu < 1. */
+JSG_API int jsg_fb_band_plan(int n, int n_bands, int64_t nnz, int64_t n_cols, int n_cu, int32_t* tile_cols, int32_t* bank_in_lds,
+                             int32_t* pw_pitch, int32_t* lds_bytes, int32_t* grid);
 
 /* ------------------------------------------------------------------------------------------------
  * 2c. Frequency axis of the colour loop: `height` image rows on a linear, log or mel axis, drawn from the dB columns the ring

@@ -7,7 +7,7 @@ from . import capi  # noqa: F401
 from .capi import JsgError  # noqa: F401
 from .spectrogram import (CColorPalette, Filterbank, FreqAxis, Plan, Spectrogram, SpectrogramDisplay, StftLaunch, colormap, colormap_lut,  # noqa: F401
                           colormap_axis, colormap_range, columns_from_tail_layout, feed_samples, memsize_blocks, next_power_of_2, stft_db, stft_db_batches, stft_db_strided, stft_db_strided_kernel_name, stft_image, stft_image_needs_scratch, stft_image_strided, stft_image_strided_needs_scratch, stft_kernel_name, window,
-                          mel_spectrogram_db, stft_fb_db, stft_fb_db_strided, stft_fb_kernel_name, stft_fb_scratch_floats,
+                          mel_spectrogram_db, stft_fb_db, stft_fb_db_strided, stft_fb_kernel_name, stft_fb_scratch_floats, fb_band_plan,
                           CStftPlan, cstft, istft, istft_launch, istft_nola, istft_scratch_floats, stft,
                           phase_vocoder, phase_vocoder_launch, pvoc_frames, time_stretch,
                           hpss, hpss_audio, hpss_launch, hpss_scratch_bytes,
@@ -16,7 +16,7 @@ from .spectrogram import (CColorPalette, Filterbank, FreqAxis, Plan, Spectrogram
 
 __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_db", "colormap", "window", "colormap_lut",
            "colormap_range", "feed_samples", "memsize_blocks", "next_power_of_2", "JsgError", "capi",
-           "Filterbank", "stft_fb_db", "stft_fb_db_strided", "stft_fb_kernel_name", "mel_spectrogram_db", "FreqAxis", "colormap_axis",
+           "Filterbank", "stft_fb_db", "stft_fb_db_strided", "stft_fb_kernel_name", "fb_band_plan", "mel_spectrogram_db", "FreqAxis", "colormap_axis",
            "CStftPlan", "cstft", "istft_launch", "istft_nola", "istft_scratch_floats", "stft", "istft",
            "pvoc_frames", "phase_vocoder_launch", "phase_vocoder", "time_stretch",
            "hpss_scratch_bytes", "hpss_launch", "hpss", "hpss_audio",

@@ -154,6 +154,7 @@ SIGNATURES = {
     "jsg_stft_fb_launch_strided": (C.c_int, [_P, _P, C.POINTER(StftArgs), C.c_int, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
     "jsg_stft_fb_scratch_floats": (C.c_int64, [_P, _P, C.POINTER(StftArgs), C.c_int]),
     "jsg_stft_fb_kernel_name": (C.c_int, [_P, _P, C.POINTER(StftArgs), C.c_int, C.c_char_p, C.c_int]),
+    "jsg_fb_band_plan": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int] + [C.POINTER(C.c_int32)] * 5),
     "jsg_freq_axis_build": (C.c_int, [C.POINTER(AxisSpec), _P, _P, _P, _P]),
     "jsg_freq_axis_create": (C.c_int, [C.POINTER(_P), C.POINTER(AxisSpec)]),
     "jsg_freq_axis_destroy": (C.c_int, [_P]),

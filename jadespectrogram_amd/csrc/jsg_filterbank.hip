@@ -102,29 +102,47 @@ __global__ __launch_bounds__(kFbThreads) void fb_band_kernel(const FbKArgs a) {
     }
 }
 
-// columns per tile: at most 34 KB of whole power columns in LDS (8 columns at <= 2048 points, 4 at 4096, 2 at 8192)
+// The numbers of one band launch, in one place: jsg_fb_band_plan reports them, the launcher launches them.
+//   tile_cols  columns per tile: at most 34 KB of whole power columns in LDS (8 columns at <= 2048 points, 4 at 4096, 2 at 8192)
+//   pw_pitch   floats per power column in scratch: whole 128-byte lines
+//   grid       as many resident workgroups per CU as its 160 KB of LDS holds (up to 8): tiles of the other workgroups are loading while one sums
+struct FbBandPlan {
+    int tile_cols = 0;
+    bool bank_lds = false;
+    long long pw_pitch = 0;
+    size_t lds = 0;
+    int grid = 0;
+};
+
 static int fb_tile_cols(int n) { return n <= 2048 ? 8 : n == 4096 ? 4 : 2; }
-static long long fb_pw_pitch(int n) { return ((long long)(n / 2 + 1) + 31) / 32 * 32; }   // whole 128-byte lines per power column
+static long long fb_pw_pitch(int n) { return ((long long)(n / 2 + 1) + 31) / 32 * 32; }
+
+static FbBandPlan fb_band_plan(int n, int n_bands, long long nnz, long long n_cols, int n_cu) {
+    FbBandPlan p;
+    p.tile_cols = fb_tile_cols(n);
+    p.pw_pitch = fb_pw_pitch(n);
+    const long long bank_words = 3ll * n_bands + nnz;
+    p.bank_lds = bank_words * 4 <= kFbBankBytes;
+    p.lds = size_t(p.tile_cols) * size_t(p.pw_pitch) * 4 + (p.bank_lds ? size_t(bank_words) * 4 : 0);
+    const long long n_tiles = (n_cols + p.tile_cols - 1) / p.tile_cols;
+    const int per_cu = std::max(1, std::min(8, int((160u * 1024u) / std::max<size_t>(p.lds, 1))));
+    p.grid = int(std::max(1ll, std::min(n_tiles, (long long)n_cu * per_cu)));
+    return p;
+}
 
 template <int T>
-static hipError_t launch_band(const FbKArgs& a, bool bank_lds, int n_cu, hipStream_t s) {
-    const size_t tile = size_t(T) * a.pw_pitch * 4;
-    const size_t lds = tile + (bank_lds ? size_t(3 * a.n_bands + a.nnz) * 4 : 0);
-    const int n_tiles = (a.n_cols + T - 1) / T;
-    // as many resident workgroups per CU as its 160 KB of LDS holds (up to 8): tiles of the other workgroups are loading while one sums
-    const int per_cu = std::max(1, std::min(8, int((160u * 1024u) / std::max<size_t>(lds, 1))));
-    const int grid = std::max(1, std::min(n_tiles, n_cu * per_cu));
-    if (bank_lds) hipLaunchKernelGGL((fb_band_kernel<T, true>), dim3(grid), dim3(kFbThreads), lds, s, a);
-    else hipLaunchKernelGGL((fb_band_kernel<T, false>), dim3(grid), dim3(kFbThreads), lds, s, a);
+static hipError_t launch_band(const FbKArgs& a, const FbBandPlan& p, hipStream_t s) {
+    if (p.bank_lds) hipLaunchKernelGGL((fb_band_kernel<T, true>), dim3(p.grid), dim3(kFbThreads), p.lds, s, a);
+    else hipLaunchKernelGGL((fb_band_kernel<T, false>), dim3(p.grid), dim3(kFbThreads), p.lds, s, a);
     return hipGetLastError();
 }
 
 static hipError_t launch_band_kernel(int n, const FbKArgs& a, int n_cu, hipStream_t s) {
-    const bool bank_lds = (3ll * a.n_bands + a.nnz) * 4 <= kFbBankBytes;
-    switch (fb_tile_cols(n)) {
-        case 8: return launch_band<8>(a, bank_lds, n_cu, s);
-        case 4: return launch_band<4>(a, bank_lds, n_cu, s);
-        default: return launch_band<2>(a, bank_lds, n_cu, s);
+    const FbBandPlan p = fb_band_plan(n, a.n_bands, a.nnz, a.n_cols, n_cu);
+    switch (p.tile_cols) {
+        case 8: return launch_band<8>(a, p, s);
+        case 4: return launch_band<4>(a, p, s);
+        default: return launch_band<2>(a, p, s);
     }
 }
 
@@ -270,6 +288,23 @@ int jsg_stft_fb_kernel_name(const jsg_plan* plan, const jsg_filterbank* fb, cons
     const int rc = fb_resolve(plan, fb, g, n_batches, c, "jsg_stft_fb_kernel_name");
     if (rc != JSG_OK) return rc;
     std::snprintf(out, size_t(out_len), "%s", c.stft->name);
+    return JSG_OK;
+}
+
+int jsg_fb_band_plan(int n, int n_bands, int64_t nnz, int64_t n_cols, int n_cu, int32_t* tile_cols, int32_t* bank_in_lds, int32_t* pw_pitch,
+                     int32_t* lds_bytes, int32_t* grid) {
+    static const char* who = "jsg_fb_band_plan";
+    if (n != 512 && n != 1024 && n != 2048 && n != 4096 && n != 8192) return jsg_fail_who(JSG_ERR_INVALID, who, "n must be a power of two in 512..8192");
+    if (n_bands < 1 || n_bands > JSG_FB_MAX_BANDS) return jsg_fail_who(JSG_ERR_INVALID, who, "n_bands outside 1..JSG_FB_MAX_BANDS");
+    if (nnz < 0 || nnz > 0x7fffffffll) return jsg_fail_who(JSG_ERR_INVALID, who, "nnz outside 0..2^31-1");
+    if (n_cols < 1 || n_cols > (1ll << 28)) return jsg_fail_who(JSG_ERR_INVALID, who, "n_cols outside 1..2^28 (the columns of one chunk)");
+    if (n_cu < 1) return jsg_fail_who(JSG_ERR_INVALID, who, "n_cu must be >= 1");
+    const FbBandPlan p = fb_band_plan(n, n_bands, nnz, n_cols, n_cu);
+    if (tile_cols) *tile_cols = p.tile_cols;
+    if (bank_in_lds) *bank_in_lds = p.bank_lds ? 1 : 0;
+    if (pw_pitch) *pw_pitch = int32_t(p.pw_pitch);
+    if (lds_bytes) *lds_bytes = int32_t(p.lds);
+    if (grid) *grid = p.grid;
     return JSG_OK;
 }
 

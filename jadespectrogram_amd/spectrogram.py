@@ -723,6 +723,15 @@ def stft_fb_kernel_name(plan: Plan, fb: Filterbank, d_in, hop: int, n_frames: in
     return _kernel_name(lib().jsg_stft_fb_kernel_name, plan._p, fb.handle(d_in.device.index), C.byref(a), k)
 
 
+def fb_band_plan(n: int, n_bands: int, nnz: int, n_cols: int, n_cu: int) -> dict:
+    """jsg_fb_band_plan: how the band kernel of one chunk of n_cols power columns is launched -- tile_cols, bank_in_lds, pw_pitch,
+    lds_bytes, grid (host arithmetic only; what the launcher itself uses)."""
+    v = [C.c_int32() for _ in range(5)]
+    check(lib().jsg_fb_band_plan(int(n), int(n_bands), int(nnz), int(n_cols), int(n_cu), *(C.byref(x) for x in v)))
+    tile_cols, bank_in_lds, pw_pitch, lds_bytes, grid = (x.value for x in v)
+    return dict(tile_cols=tile_cols, bank_in_lds=bool(bank_in_lds), pw_pitch=pw_pitch, lds_bytes=lds_bytes, grid=grid)
+
+
 _mel_cache: dict = {}
 _window_table = window      # (mel_spectrogram_db takes a `window` argument)
 

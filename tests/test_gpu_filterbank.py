@@ -3,12 +3,15 @@
 The bit-exact chain: the STFT kernel's linear power is reproduced by the CPU mirror of the kernel (oracle/jsg_mirror.c, plan named by
 jsg_stft_fb_kernel_name), the bank by a float32 numpy loop in the specified order (bins ascending from +0.0f, every product and every sum
 rounded on its own), the logarithm by the shared float32 routine (exact_log).  Beside it: the LINEAR identity bank against stft_db, the
-hardware logarithm, a float64 bound, chunking, strided calls and ring wrap, NaN containment, refusals, graph capture, colour, torch."""
+hardware logarithm, a float64 bound, chunking, strided calls and ring wrap, NaN containment, refusals, graph capture, colour, torch.
+The band kernel on its own -- every tile size and bank path, second tiles, partial tiles, band-count edges -- is in tests/test_gpu_fb_band.py
+(references: tests/fb_band_ref.py)."""
 import ctypes
 
 import numpy as np
 import pytest
 
+from fb_band_ref import band_dense, band_f32
 from parity_util import DB_SLACK, FLOOR_BY_N, LOG_FLOOR
 from test_gpu_fullsize import _b_rule
 
@@ -32,19 +35,6 @@ def torch_cuda():
 def mir():
     from oracle import mirror
     return mirror.load()
-
-
-def band_f32(P, fb):
-    """P [F][n/2+1] float32 -> [F][B] float32: the bank in the specified order."""
-    P = np.asarray(P, np.float32)
-    out = np.zeros((P.shape[0], fb.n_bands), np.float32)
-    for b in range(fb.n_bands):
-        acc = np.zeros(P.shape[0], np.float32)
-        f, o = int(fb.first_bin[b]), int(fb.offset[b])
-        for k in range(int(fb.n_bins[b])):
-            acc = acc + fb.weights[o + k] * P[:, f + k]      # float32 * float32 -> rounded product; + -> rounded sum
-        out[:, b] = acc
-    return out
 
 
 def bank_for(jsg, n, scale, B=48):
@@ -329,19 +319,6 @@ def test_refused_call_enqueues_nothing(jsg, oracle, torch_cuda):
         assert call(b) < 0, change
         assert (out == -7.0).all(), change
     assert call(a) == C.JSG_OK and not (out == -7.0).any()
-
-
-def band_dense(P, W):
-    """P [F][n/2+1] -> [F][B] straight from a dense bank: bins from the first to the last nonzero of every row, ascending, float32."""
-    P = np.asarray(P, np.float32)
-    out = np.zeros((P.shape[0], W.shape[0]), np.float32)
-    for b in range(W.shape[0]):
-        nz = np.flatnonzero(W[b])
-        acc = np.zeros(P.shape[0], np.float32)
-        for k in range(nz[0], nz[-1] + 1) if nz.size else ():
-            acc = acc + W[b, k] * P[:, k]
-        out[:, b] = acc
-    return out
 
 
 def test_dense_caller_bank(jsg, oracle, mir, torch_cuda):
