@@ -50,7 +50,8 @@ extern "C" {
                                  phase vocoder (jsg_pvoc_*; section 2e), harmonic-percussive separation (jsg_hpss_*; section 2f),
                                  band-limited resampling (jsg_sinc_table_build, jsg_resampler_*, jsg_resample_*; section 2g),
                                  constant-Q and variable-Q spectrograms by direct evaluation (jsg_cqt_*; section 2h),
-                                 the band launch query (jsg_fb_band_plan; section 2b) */
+                                 the band launch query (jsg_fb_band_plan; section 2b),
+                                 YIN fundamental-frequency tracking (jsg_yin_*; section 2i) */
 
 typedef enum jsg_status {
     JSG_OK = 0,
@@ -785,6 +786,82 @@ JSG_API int jsg_cqt_plan(int n_bins, const int32_t* half_len, const jsg_cqt_args
                          int32_t* class_max_taps, int32_t* frames_per_item, int32_t* taps_per_pass, int32_t* lds_bytes);
 /* The path of jsg_cqt_plan for the basis `cq` (out_len >= 24).  The argument refusals of the launch; no device is needed. */
 JSG_API int jsg_cqt_kernel_name(const jsg_cqt* cq, const jsg_cqt_args* args, char* out, int out_len);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2i. YIN fundamental-frequency tracking (de Cheveigne and Kawahara 2002), the difference function evaluated directly in the time
+ *     domain (their eq. 6: a sum of non-negative terms, no autocorrelation by FFT, so nothing cancels where a voiced frame dips).
+ *
+ *     Rows x[r][0..L), a window w, lags tau_min <= tau_max, hop >= 1.  Frame t covers x[t*hop .. t*hop + w + tau_max); there are
+ *     jsg_yin_frames(L, w, tau_max, hop) = 1 + (L - w - tau_max) / hop of them for L >= w + tau_max, else 0: no frame reaches outside
+ *     its row, and a launch reads nothing outside the spans of its frames.  Per frame, with x[j] = x[r][t*hop + j], all in float32:
+ *
+ *     1. d[0] = 0;  d[tau] = sum over j = 0..w-1 of (x[j] - x[j+tau])^2  for tau = 1..tau_max.  The order of the sum depends on w and
+ *        j alone: one accumulator per lag, acc = +0, and for jb = 0, 512, 1024, ...: for j0 = 0..63: for jj = 0..7:
+ *            j = jb + j0 + 64 jj;  if j < w:  e = x[j] - x[j+tau];  acc = fmaf(e, e, acc)
+ *        (j ascends by 64 inside a block of 512, the blocks and the j0 ascend outside; for w <= 64 this is j = 0, 1, ..., w-1).
+ *     2. S[tau] = the running sum of d[1..tau], in groups of 64 lags: with tau = 1 + 64 c + l, l = 0..63 (d = +0 past tau_max), the
+ *        group is scanned in place by v_l = v_l + v_(l-s) for l >= s, for s = 1, 2, 4, 8, 16, 32 in turn (all l at once per s), then
+ *        S[tau] = carry + v_l with carry = +0 for c = 0 and carry = S[64 c] (the last S of the group before) otherwise.
+ *        d'[0] = 1;  d'[tau] = (d[tau] * (float)tau) / S[tau], the product rounded, the divide correctly rounded;  d'[tau] = 1 where
+ *        S[tau] == 0.
+ *     3. tau = the smallest lag in tau_min..tau_max with d'[tau] < threshold (strict); from there tau += 1 while tau + 1 <= tau_max and
+ *        d'[tau+1] < d'[tau].  If no lag is below the threshold: the lag of the minimum of d' over tau_min..tau_max, the lowest on ties.
+ *     4. If tau + 1 <= tau_max: a, b, c = d'[tau-1], d'[tau], d'[tau+1];  den = (a - b) + (c - b);  if den > 0:
+ *        s = (0.5f * (a - c)) / den, kept if |s| <= 1, else 0.  In every other case s = 0.  period = (float)tau + s.
+ *     5. f0[r][t] = sample_rate / period at f0[r*out_pitch + t], aper[r][t] = d'[tau] at aper[r*out_pitch + t],
+ *        cmnd[r][t][0..tau_max] = d' at cmnd[r*cmnd_row_pitch + t*cmnd_frame_pitch + tau] (a [frames][lags] plane as in section 2h: what
+ *        jsg_db_from_power_launch and jsg_colormap_launch (height = tau_max + 1) take).  Any of the three may be NULL, not all.  Elements
+ *        between tau_max + 1 and the frame pitch are not written.  Voicing is the caller's aper < threshold.
+ *     6. If any d'[tau], tau in tau_min..tau_max, is NaN, f0 and aper of that frame are NaN (a NaN sample does this to exactly the
+ *        frames whose span holds it; no other frame is touched).  A silent frame has d' = 1 everywhere: tau = tau_min, s = 0,
+ *        f0 = sample_rate / (float)tau_min, aper = 1.
+ *
+ *     The bits do not depend on t, r, L, the hop, chunk_frames, the grid, the row count, the pitches or which outputs are NULL.  The
+ *     contract for d' is a relative tolerance against the float64 evaluation: (2w + tau + 12) 2^-24 d'[tau].  librosa.yin integrates
+ *     over a window of frame_length - tau_max samples too but takes the difference function from an FFT autocorrelation
+ *     (r(0) + r_tau(0) - 2 r(tau)) and has other details of its own; agreement with it has not been measured.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSG_YIN_MAX_WINDOW 8192
+#define JSG_YIN_MAX_LAG 8192
+/* 1 + (L - w - tau_max) / hop for L >= w + tau_max, else 0.  JSG_ERR_INVALID: in_samples outside 1..2^31-1, window outside
+ * 1..JSG_YIN_MAX_WINDOW, tau_max outside 1..JSG_YIN_MAX_LAG, hop outside 1..2^20. */
+JSG_API int64_t jsg_yin_frames(int64_t in_samples, int32_t window, int32_t tau_max, int64_t hop);
+
+typedef struct jsg_yin_args {
+    const float* in;            /* device floats: x[r][m] at in[r*in_pitch + m] */
+    int64_t in_pitch;           /* rows > 1: >= in_samples */
+    int32_t rows;               /* 1..65535, independent */
+    int32_t window;             /* w, 1..JSG_YIN_MAX_WINDOW */
+    int64_t in_samples;         /* L, 1..2^31-1 */
+    int32_t tau_min;            /* 1..tau_max */
+    int32_t tau_max;            /* 1..JSG_YIN_MAX_LAG */
+    int64_t hop;                /* 1..2^20 */
+    int64_t n_frames;           /* T, 1..jsg_yin_frames(in_samples, window, tau_max, hop) */
+    float threshold;            /* finite, > 0 */
+    float sample_rate;          /* finite, > 0 */
+    float* f0;                  /* device floats or NULL */
+    float* aper;                /* device floats or NULL */
+    int64_t out_pitch;          /* of f0 and aper, rows > 1: >= n_frames */
+    float* cmnd;                /* device floats or NULL */
+    int64_t cmnd_frame_pitch;   /* floats between frames, >= tau_max + 1 */
+    int64_t cmnd_row_pitch;     /* rows > 1: >= (T-1)*cmnd_frame_pitch + tau_max + 1 */
+    int32_t chunk_frames;       /* upper bound on the frames per work item: 0 = the library's choice, else 1..65536; never changes the result */
+} jsg_yin_args;
+/* Enqueue only (one kernel, no scratch): no allocation, no synchronisation; hipGraph capture works, a first launch included.  Refused
+ * (JSG_ERR_INVALID, nothing enqueued, jsg_last_error set), in this order and before any device call: null args, a null in, f0, aper
+ * and cmnd all null, a pointer that is not 4-byte aligned, rows outside 1..65535, in_samples outside 1..2^31-1, window outside
+ * 1..8192, tau_max outside 1..8192, tau_min outside 1..tau_max, hop outside 1..2^20, n_frames outside
+ * 1..jsg_yin_frames(in_samples, window, tau_max, hop), chunk_frames outside 0 or 1..65536, a threshold that is not finite and > 0, a
+ * sample_rate that is not finite and > 0, in_pitch below in_samples (rows > 1), out_pitch below n_frames (rows > 1, f0 or aper given),
+ * cmnd_frame_pitch below tau_max + 1 (cmnd given), cmnd_row_pitch below (T-1)*cmnd_frame_pitch + tau_max + 1 (rows > 1, cmnd given),
+ * an output overlapping in.  Then JSG_ERR_NO_DEVICE without a HIP device.  Every call that passes is served. */
+JSG_API int jsg_yin_launch(const jsg_yin_args* args, void* stream);
+/* What the launch would do, without a device: the path ("yin_lags1", "yin_lags2", "yin_lags4" or "yin_lags8": the lags a lane
+ * accumulates at a time, by tau_max alone), the frames a work item takes (one staging of their span into LDS) and the bytes of LDS a
+ * workgroup asks for (<= 163840).  Any output pointer may be NULL (name: else name_len >= 24).  Refused: what the launch refuses. */
+JSG_API int jsg_yin_plan(const jsg_yin_args* args, char* name, int name_len, int32_t* frames_per_item, int32_t* lds_bytes);
+/* The path of jsg_yin_plan (out_len >= 24).  The refusals of the launch; no device is needed. */
+JSG_API int jsg_yin_kernel_name(const jsg_yin_args* args, char* out, int out_len);
 
 /* ------------------------------------------------------------------------------------------------
  * 3. Engine: the state of class Spectrogram (Spectrogram.h:81-169) living on the GPU.

@@ -12,7 +12,8 @@ from .spectrogram import (CColorPalette, Filterbank, FreqAxis, Plan, Spectrogram
                           phase_vocoder, phase_vocoder_launch, pvoc_frames, time_stretch,
                           hpss, hpss_audio, hpss_launch, hpss_scratch_bytes,
                           Resampler, pitch_shift, resample, resample_kernel_name, resample_launch, resample_length, resample_plan, sinc_table,
-                          CqtBasis, cqt, cqt_db, cqt_frames, cqt_frequencies, cqt_kernel_name, cqt_launch, cqt_plan, vqt)
+                          CqtBasis, cqt, cqt_db, cqt_frames, cqt_frequencies, cqt_kernel_name, cqt_launch, cqt_plan, vqt,
+                          yin, yin_cmnd, yin_frames, yin_kernel_name, yin_launch, yin_plan)
 
 __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_db", "colormap", "window", "colormap_lut",
            "colormap_range", "feed_samples", "memsize_blocks", "next_power_of_2", "JsgError", "capi",
@@ -21,4 +22,5 @@ __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_d
            "pvoc_frames", "phase_vocoder_launch", "phase_vocoder", "time_stretch",
            "hpss_scratch_bytes", "hpss_launch", "hpss", "hpss_audio",
            "sinc_table", "Resampler", "resample_length", "resample_launch", "resample_kernel_name", "resample_plan", "resample", "pitch_shift",
-           "CqtBasis", "cqt_frames", "cqt_launch", "cqt_plan", "cqt_kernel_name", "cqt", "vqt", "cqt_frequencies", "cqt_db"]
+           "CqtBasis", "cqt_frames", "cqt_launch", "cqt_plan", "cqt_kernel_name", "cqt", "vqt", "cqt_frequencies", "cqt_db",
+           "yin_frames", "yin_launch", "yin_plan", "yin_kernel_name", "yin", "yin_cmnd"]

@@ -33,6 +33,7 @@ AXIS_MAX_HEIGHT = 16384
 HPSS_MAX_WINDOW = 63
 RESAMPLE_MAX_TABLE = 32768
 CQT_MAX_BINS, CQT_MAX_HALF_LEN, CQT_MAX_TAPS, CQT_MAX_CLASSES = 4096, 131072, 1 << 24, 20
+YIN_MAX_WINDOW, YIN_MAX_LAG = 8192, 8192
 
 
 class JsgError(RuntimeError):
@@ -106,6 +107,13 @@ class CqtArgs(C.Structure):
     _fields_ = [("in_", C.c_void_p), ("in_pitch", C.c_int64), ("rows", C.c_int32), ("in_samples", C.c_int64), ("hop", C.c_int64),
                 ("n_frames", C.c_int64), ("out", C.c_void_p), ("out_frame_pitch", C.c_int64), ("out_row_pitch", C.c_int64),
                 ("out_power", C.c_int32), ("chunk_frames", C.c_int32)]
+
+
+class YinArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("in_pitch", C.c_int64), ("rows", C.c_int32), ("window", C.c_int32), ("in_samples", C.c_int64),
+                ("tau_min", C.c_int32), ("tau_max", C.c_int32), ("hop", C.c_int64), ("n_frames", C.c_int64), ("threshold", C.c_float),
+                ("sample_rate", C.c_float), ("f0", C.c_void_p), ("aper", C.c_void_p), ("out_pitch", C.c_int64), ("cmnd", C.c_void_p),
+                ("cmnd_frame_pitch", C.c_int64), ("cmnd_row_pitch", C.c_int64), ("chunk_frames", C.c_int32)]
 
 
 class StftImageArgs(C.Structure):
@@ -191,6 +199,10 @@ SIGNATURES = {
     "jsg_cqt_launch": (C.c_int, [_P, C.POINTER(CqtArgs), _P]),
     "jsg_cqt_plan": (C.c_int, [C.c_int, _P, C.POINTER(CqtArgs), C.c_char_p, C.c_int, C.POINTER(C.c_int32), _P, _P, _P, _P]),
     "jsg_cqt_kernel_name": (C.c_int, [_P, C.POINTER(CqtArgs), C.c_char_p, C.c_int]),
+    "jsg_yin_frames": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int64]),
+    "jsg_yin_launch": (C.c_int, [C.POINTER(YinArgs), _P]),
+    "jsg_yin_plan": (C.c_int, [C.POINTER(YinArgs), C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "jsg_yin_kernel_name": (C.c_int, [C.POINTER(YinArgs), C.c_char_p, C.c_int]),
     "jsg_create": (C.c_int, [C.POINTER(_P), C.c_int]),
     "jsg_create_on_device": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int]),
     "jsg_get_device": (C.c_int, [_P]),

@@ -76,6 +76,25 @@ int check_stft_args(int n, const jsg_stft_args* g, const char* who);
 // jsg_display_axis.hip: preload_code_object of the axis kernel (jsg_freq_axis_create)
 void touch_axis_module();
 
+// jsg_yin_host.cpp: the refusals of jsg_yin_args and how a call that passes is served (jsg_yin.hip launches by it).  A work item is a
+// row and F consecutive frames; its LDS holds the frames' span ((F - 1) S + w + tau_max floats, S = min(hop, w + tau_max) between
+// the frames), kYinPad floats that lanes past tau_max may read, and F rows of tau_max + 1 floats for d'.
+constexpr int kYinThreads = 256;
+constexpr int kYinPad = 1024;
+constexpr int kYinLdsFour = 10240;          // 40 KiB: four workgroups per compute unit, where a frame fits
+constexpr int kYinLdsTwo = 20480;           // 80 KiB: two
+constexpr int kYinLdsOne = 40960;           // 160 KiB
+constexpr int kYinFrames = 16;              // frames per item where the caller does not say
+struct YinPlan {
+    int NL;                    // lags a lane accumulates at a time: 1, 2, 4 or 8
+    int F, S;
+    long long chunks;          // ceil(T / F)
+    int lds_floats;
+};
+int yin_check(const jsg_yin_args* g, const char* who);
+void yin_resolve(const jsg_yin_args* g, YinPlan* p);
+const char* yin_path_name(const YinPlan& p);
+
 // Slaney's mel scale (librosa.filters.mel, htk = False): linear below 1 kHz (200/3 Hz per mel), logarithmic above (27 mels per
 // factor 6.4).  Shared by the MEL_SLANEY filterbank and the MEL display axis.
 inline double slaney_logstep() { return std::log(6.4) / 27.0; }

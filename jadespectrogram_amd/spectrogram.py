@@ -1380,3 +1380,119 @@ def cqt_db(x, sr: float, hop_length: int = 512, fmin: float | None = None, n_bin
     db_from_power(power, db, divisor)
     db = db.reshape(*batch, db.shape[1], db.shape[2]).transpose(-1, -2)
     return db.cpu().numpy() if was_numpy else db
+
+
+# --------------------------------------------------------------------------------------------------
+# YIN fundamental-frequency tracking (include/jsg.h, section 2i)
+# --------------------------------------------------------------------------------------------------
+def yin_frames(in_samples: int, window: int, tau_max: int, hop: int) -> int:
+    """jsg_yin_frames: 1 + (in_samples - window - tau_max) // hop, the frames whose span lies inside the row (0 for a shorter row)."""
+    return int(check(lib().jsg_yin_frames(int(in_samples), int(window), int(tau_max), int(hop))))
+
+
+def _yin_args(d_in, window: int, tau_min: int, tau_max: int, hop: int, n_frames: int, threshold: float, sample_rate: float, d_f0, d_aper, d_cmnd,
+              chunk_frames: int) -> capi.YinArgs:
+    import torch
+    x = d_in[None] if d_in.dim() == 1 else d_in
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1, "d_in: float32 CUDA [rows][samples]"
+    R = x.shape[0]
+    line_pitch = 0
+    lines = []
+    for o, what in ((d_f0, "d_f0"), (d_aper, "d_aper")):
+        if o is not None:
+            o = o[None] if o.dim() == 1 else o
+            assert o.is_cuda and o.dtype == torch.float32 and o.dim() == 2 and o.stride(1) == 1 and o.shape[0] == R and o.shape[1] >= n_frames, \
+                f"{what}: float32 CUDA [rows][>= n_frames]"
+            assert all(v is None for v in lines) or R == 1 or o.stride(0) == line_pitch, "d_f0 and d_aper share one row pitch"
+            line_pitch = o.stride(0)
+        lines.append(o)
+    c = None
+    if d_cmnd is not None:
+        c = _rows3(d_cmnd, "d_cmnd")
+        assert c.is_cuda and c.dtype == torch.float32 and c.stride(2) == 1 and c.shape[0] == R and c.shape[1] >= n_frames and c.shape[2] >= tau_max + 1, \
+            "d_cmnd: float32 CUDA [rows][>= n_frames][>= tau_max + 1]"
+    ptr = lambda t: None if t is None else t.data_ptr()
+    return capi.YinArgs(x.data_ptr(), x.stride(0), R, int(window), x.shape[1], int(tau_min), int(tau_max), int(hop), int(n_frames), float(threshold),
+                        float(sample_rate), ptr(lines[0]), ptr(lines[1]), line_pitch, ptr(c), 0 if c is None else c.stride(1), 0 if c is None else c.stride(0),
+                        int(chunk_frames))
+
+
+def yin_launch(d_in, window: int, tau_min: int, tau_max: int, hop: int, n_frames: int, threshold: float, sample_rate: float, *, d_f0=None, d_aper=None,
+               d_cmnd=None, chunk_frames: int = 0, stream: int | None = None):
+    """jsg_yin_launch: d_in float32 [rows][L] -> d_f0, d_aper float32 [rows][n_frames] and d_cmnd float32 [rows][n_frames][>= tau_max + 1]
+    (any of the three may be None, not all); frame t covers the samples t * hop .. t * hop + window + tau_max.  chunk_frames (0: the
+    library's choice) never changes the result."""
+    a = _yin_args(d_in, window, tau_min, tau_max, hop, n_frames, threshold, sample_rate, d_f0, d_aper, d_cmnd, chunk_frames)
+    check(lib().jsg_yin_launch(C.byref(a), _stream_handle(stream, d_in)))
+
+
+def yin_kernel_name(d_in, window: int, tau_min: int, tau_max: int, hop: int, n_frames: int, threshold: float, sample_rate: float, *, d_f0=None,
+                    d_aper=None, d_cmnd=None, chunk_frames: int = 0) -> str:
+    """The path yin_launch takes for these arguments: "yin_lags1", "yin_lags2", "yin_lags4" or "yin_lags8"."""
+    a = _yin_args(d_in, window, tau_min, tau_max, hop, n_frames, threshold, sample_rate, d_f0, d_aper, d_cmnd, chunk_frames)
+    return _kernel_name(lib().jsg_yin_kernel_name, C.byref(a))
+
+
+def yin_plan(d_in, window: int, tau_min: int, tau_max: int, hop: int, n_frames: int, threshold: float, sample_rate: float, *, d_f0=None, d_aper=None,
+             d_cmnd=None, chunk_frames: int = 0):
+    """jsg_yin_plan: (path, frames per work item, bytes of LDS per workgroup) of yin_launch for these arguments.  Needs no device."""
+    a = _yin_args(d_in, window, tau_min, tau_max, hop, n_frames, threshold, sample_rate, d_f0, d_aper, d_cmnd, chunk_frames)
+    name, frames, lds = C.create_string_buffer(32), C.c_int32(), C.c_int32()
+    check(lib().jsg_yin_plan(C.byref(a), name, 32, C.byref(frames), C.byref(lds)))
+    return name.value.decode(), frames.value, lds.value
+
+
+def _yin_rows(x, sr, fmin, fmax, frame_length, hop_length, threshold, center, want_cmnd: bool):
+    """x numpy array or CUDA tensor [..., L] -> (f0, aper or the d' plane [rows][frames][tau_max + 1], batch shape, whether x was numpy)."""
+    import math
+    import torch
+    frame_length = int(frame_length)
+    hop = frame_length // 4 if hop_length is None else int(hop_length)
+    tau_min = max(1, int(math.floor(float(sr) / float(fmax))))
+    tau_max = int(math.ceil(float(sr) / float(fmin)))
+    window = frame_length - tau_max
+    if window < 1:
+        raise JsgError(capi.JSG_ERR_INVALID, f"yin: frame_length {frame_length} leaves no window beside tau_max {tau_max} (= ceil(sr / fmin))")
+    was_numpy = not hasattr(x, "is_cuda")
+    if was_numpy:
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda()
+    assert x.is_cuda and x.dtype == torch.float32, "x must be a numpy array or a float32 CUDA tensor"
+    batch = tuple(x.shape[:-1])
+    xr = x.reshape(-1, x.shape[-1])
+    if center:
+        xr = torch.nn.functional.pad(xr, (frame_length // 2, frame_length // 2))
+    xr = xr.contiguous()
+    T = yin_frames(xr.shape[1], window, tau_max, hop)
+    if T < 1:
+        raise JsgError(capi.JSG_ERR_INVALID, f"yin: {xr.shape[1]} samples hold no frame of {frame_length}")
+    R = xr.shape[0]
+    with torch.cuda.device(_device_index(x)):
+        if want_cmnd:
+            plane = torch.empty((R, T, tau_max + 1), dtype=torch.float32, device=x.device)
+            yin_launch(xr, window, tau_min, tau_max, hop, T, threshold, sr, d_cmnd=plane)
+            return plane, None, batch, was_numpy
+        f0 = torch.empty((R, T), dtype=torch.float32, device=x.device)
+        aper = torch.empty((R, T), dtype=torch.float32, device=x.device)
+        yin_launch(xr, window, tau_min, tau_max, hop, T, threshold, sr, d_f0=f0, d_aper=aper)
+    return f0, aper, batch, was_numpy
+
+
+def yin(x, sr: float, fmin: float, fmax: float, frame_length: int = 2048, hop_length: int | None = None, threshold: float = 0.1, center: bool = True):
+    """YIN fundamental-frequency tracking on the GPU: x [..., L] (numpy array or float32 CUDA tensor) -> (f0, aperiodicity), float32
+    [..., frames] each (numpy arrays for numpy input).  tau_min = max(1, floor(sr / fmax)), tau_max = ceil(sr / fmin), the integration
+    window is frame_length - tau_max samples (refused below 1), hop_length defaults to frame_length // 4, and center pads
+    frame_length // 2 zeros at both ends.  A frame is voiced where aperiodicity < threshold; f0 of an unvoiced frame is the lag of the
+    global minimum of d'.  The difference function is summed directly in the time domain (librosa.yin takes it from an FFT
+    autocorrelation and differs in further details; agreement with it has not been measured)."""
+    f0, aper, batch, was_numpy = _yin_rows(x, sr, fmin, fmax, frame_length, hop_length, threshold, center, False)
+    f0, aper = f0.reshape(*batch, -1), aper.reshape(*batch, -1)
+    return (f0.cpu().numpy(), aper.cpu().numpy()) if was_numpy else (f0, aper)
+
+
+def yin_cmnd(x, sr: float, fmin: float, fmax: float, frame_length: int = 2048, hop_length: int | None = None, threshold: float = 0.1, center: bool = True):
+    """The cumulative-mean-normalised difference d' of yin's frames, a correlogram: float32 [..., frames, tau_max + 1], lag tau at index
+    tau (d'[0] = 1).  One row of it is a contiguous [frames][lags] plane that db_from_power and colormap (height = tau_max + 1) take
+    like any spectrogram plane."""
+    plane, _, batch, was_numpy = _yin_rows(x, sr, fmin, fmax, frame_length, hop_length, threshold, center, True)
+    plane = plane.reshape(*batch, plane.shape[1], plane.shape[2])
+    return plane.cpu().numpy() if was_numpy else plane
