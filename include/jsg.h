@@ -51,7 +51,8 @@ extern "C" {
                                  band-limited resampling (jsg_sinc_table_build, jsg_resampler_*, jsg_resample_*; section 2g),
                                  constant-Q and variable-Q spectrograms by direct evaluation (jsg_cqt_*; section 2h),
                                  the band launch query (jsg_fb_band_plan; section 2b),
-                                 YIN fundamental-frequency tracking (jsg_yin_*; section 2i) */
+                                 YIN fundamental-frequency tracking (jsg_yin_*; section 2i),
+                                 onset strength, autocorrelation tempogram and tempo (jsg_onset_*, jsg_tempogram_*, jsg_tempo_*; section 2j) */
 
 typedef enum jsg_status {
     JSG_OK = 0,
@@ -862,6 +863,138 @@ JSG_API int jsg_yin_launch(const jsg_yin_args* args, void* stream);
 JSG_API int jsg_yin_plan(const jsg_yin_args* args, char* name, int name_len, int32_t* frames_per_item, int32_t* lds_bytes);
 /* The path of jsg_yin_plan (out_len >= 24).  The refusals of the launch; no device is needed. */
 JSG_API int jsg_yin_kernel_name(const jsg_yin_args* args, char* out, int out_len);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2j. Onset strength, autocorrelation tempogram and tempo: spectral flux of a [frames][bands] plane (what jsg_stft_fb_launch and
+ *     the dB conversion write), the local autocorrelation of that envelope evaluated directly (no FFT), and the lag of the best
+ *     tempo under a log-normal prior.  All arithmetic is float32; no sum depends on the row, the frame index, the number of rows or
+ *     frames, the pitches, chunk_frames, the grid or which outputs are NULL.
+ *
+ *     Onset strength.  Rows S[r][t][b] at in[r*row_pitch + t*frame_pitch + b], t = 0..T-1, b = 0..B-1, a lag and a filter size m:
+ *         ref[t][b] = the maximum of S[t][b'] over b' in [b - m/2, b + (m-1)/2] (integer division) clipped to [0, B), taken with
+ *                     b' ascending by  mx = S[t][first b'];  then  mx = v  where  v > mx  or  v is NaN  (a NaN stays)
+ *         e = S[t][b] - ref[t-lag][b];   p(b) = e where e > 0 or e is NaN, else +0       (fmaxf would drop the NaN)
+ *         o[r][t] = (sum over b of p(b)) / (float)B  for t >= lag,  o[r][t] = +0 for t < lag (written too), at out[r*out_pitch + t]
+ *     The order of the sum depends on B alone.  With W = 64 where B > 32, else the smallest power of two >= B: lane l of W adds
+ *     b = l, l + W, l + 2W, ... ascending with plain adds from +0, then a halving tree: for s = W/2, W/4, ..., 1:
+ *     acc_l = acc_l + acc_(l+s) for l < s; the sum is acc_0.  o[t] is NaN exactly when S[t] or S[t-lag] holds a NaN (for finite
+ *     input otherwise); no other frame is touched, and nothing outside the T x B elements of a row is read.
+ *
+ *     Tempogram.  Rows o[r][t] at in[r*in_pitch + t], t = 0..T-1, a window table w[0..Wn), Lg lags, hop >= 1.  There are
+ *     jsg_tempogram_frames(T, hop) = 1 + (T-1)/hop frames; frame i is centred on c = i*hop:
+ *         y[j] = fl(o[c - Wn/2 + j] * w[j])  where 0 <= c - Wn/2 + j < T,  else +0  (nothing outside the row is read or multiplied)
+ *         A[tau] = sum over j = 0..Wn-1-tau of y[j] * y[j+tau],  tau = 0..Lg-1
+ *     one accumulator per lag, acc = +0, and for j = 0, 1, 2, ..., Wn-1-tau in this order:  acc = fmaf(y[j], y[j+tau], acc).
+ *     Pairs past the window are left out, not multiplied by zero.
+ *         normalise = 0:  TG[tau] = A[tau]
+ *         normalise = 1:  TG[tau] = A[tau] / A[0], the divide correctly rounded;  +0 for every tau where A[0] == 0
+ *     TG[r][i][tau] goes to out[r*row_pitch + i*frame_pitch + tau], a [frames][lags] plane as in sections 2h and 2i (what
+ *     jsg_db_from_power_launch and jsg_colormap_launch with height = Lg take).  Elements between Lg and the frame pitch are not
+ *     written.  A NaN at y[j0] makes, with normalise = 0, exactly the lags NaN whose sum pairs it (tau <= max(j0, Wn-1-j0)); with
+ *     normalise = 1 the whole frame.  An all-zero window gives +0 everywhere.
+ *     Against the same sums in float64 on the float32 products y, with u = 2^-24 and M[tau] = sum |y[j]| |y[j+tau]|:
+ *         normalise = 0:  |TG - TG64| <= (Wn - tau + 4) u M[tau]            (one rounding per fmaf, Wn - tau of them; second order in the 4)
+ *         normalise = 1:  |TG - TG64| <= ((Wn - tau + 4) M[tau] / A64[0] + (Wn + 8) |TG64|) u     (A[0] is a sum of non-negative terms:
+ *                         its relative error is at most (Wn + 4) u; then the divide and the second-order terms)
+ *
+ *     Tempo.  A plane TG[r][i][tau], i = 0..N-1, tau = 0..Lg-1 (Lg >= 2), and a prior table of Lg floats:
+ *         g[tau] = (sum over i of TG[i][tau]) / (float)N, the sum in blocks of 64 frames: P_k = the sum of the frames 64k .. 64k+63
+ *                  below N, i ascending, plain adds from +0;  total = +0, then total = total + P_k for k ascending
+ *         s[tau] = fl(fmaf(1e6f, g[tau], 1.0f) * prior[tau])
+ *         tau* = the tau in 1..Lg-1 with the largest s, the lowest on ties (a NaN s never wins; tau* = 1 where none does)
+ *         bpm[r] = fl(60.0f * frame_rate) / (float)tau*,  lag[r] = tau*,  profile[r][0..Lg) = g at profile[r*profile_pitch + tau]
+ *     If any g[tau], tau >= 1, is NaN: bpm = NaN and lag = -1.  In exact arithmetic tau* is the argmax of log1p(1e6 g) + log prior,
+ *     the rule of librosa.feature.tempo, so no logarithm runs on the device.  The standard prior (jsg_tempo_prior_build, in double,
+ *     rounded to float32 once): prior[0] = 0;  prior[tau] = exp(-0.5 ((log2(60 frame_rate / tau) - log2(start_bpm)) / std_bpm)^2);
+ *     prior[tau] = 0 where 60 frame_rate / tau > max_bpm (max_bpm <= 0: no limit).
+ *
+ *     These definitions differ from librosa.onset.onset_strength / librosa.feature.tempogram / librosa.feature.tempo on purpose: the
+ *     envelope is not shifted by n_fft / (2 hop) frames for centring; the maximum filter is clipped at the band edges, not
+ *     reflected; the envelope is taken as zero outside the row, where librosa pads with a linear ramp to zero; the autocorrelation
+ *     is summed directly, not taken from an FFT of the padded frame.  Agreement with librosa has not been measured.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSG_ONSET_MAX_BANDS 65536
+#define JSG_ONSET_MAX_LAG 4096
+#define JSG_ONSET_MAX_SIZE 255
+#define JSG_TEMPOGRAM_MAX_WINDOW 4096
+typedef struct jsg_onset_args {
+    const float* in;            /* device floats: S[r][t][b] at in[r*row_pitch + t*frame_pitch + b] */
+    int64_t frame_pitch;        /* floats between frames, >= n_bands */
+    int64_t row_pitch;          /* rows > 1: >= (T-1)*frame_pitch + n_bands */
+    int32_t rows;               /* 1..65535, independent */
+    int32_t n_bands;            /* B, 1..JSG_ONSET_MAX_BANDS */
+    int64_t n_frames;           /* T, 1..2^31-1 */
+    int32_t lag;                /* 1..JSG_ONSET_MAX_LAG */
+    int32_t max_size;           /* m, 1..JSG_ONSET_MAX_SIZE */
+    float* out;                 /* device floats: o[r][t] at out[r*out_pitch + t] */
+    int64_t out_pitch;          /* rows > 1: >= n_frames */
+} jsg_onset_args;
+/* Enqueue only (one kernel, no scratch): no allocation, no synchronisation; hipGraph capture works, a first launch included.  Refused
+ * (JSG_ERR_INVALID, nothing enqueued, jsg_last_error set), in this order and before any device call: null args, a null in, a null
+ * out, a pointer that is not 4-byte aligned, rows outside 1..65535, n_bands outside 1..65536, n_frames outside 1..2^31-1, lag
+ * outside 1..4096, max_size outside 1..255, frame_pitch below n_bands, row_pitch below (T-1)*frame_pitch + n_bands (rows > 1),
+ * out_pitch below n_frames (rows > 1), out overlapping in.  Then JSG_ERR_NO_DEVICE without a HIP device.  Every call that passes is
+ * served. */
+JSG_API int jsg_onset_strength_launch(const jsg_onset_args* args, void* stream);
+
+/* 1 + (n_in - 1) / hop.  JSG_ERR_INVALID: n_in outside 1..2^31-1, hop outside 1..2^20. */
+JSG_API int64_t jsg_tempogram_frames(int64_t n_in, int64_t hop);
+typedef struct jsg_tempogram_args {
+    const float* in;            /* device floats: o[r][t] at in[r*in_pitch + t] */
+    int64_t in_pitch;           /* rows > 1: >= n_in */
+    int32_t rows;               /* 1..65535, independent */
+    int32_t win_length;         /* Wn, 2..JSG_TEMPOGRAM_MAX_WINDOW */
+    int64_t n_in;               /* T, 1..2^31-1 */
+    int64_t hop;                /* 1..2^20 */
+    int64_t n_frames;           /* 1..jsg_tempogram_frames(n_in, hop) */
+    int32_t lags;               /* Lg, 1..win_length */
+    int32_t normalise;          /* 0 or 1 */
+    const float* window;        /* device floats: w[0..Wn) */
+    float* out;                 /* device floats: TG[r][i][tau] at out[r*row_pitch + i*frame_pitch + tau] */
+    int64_t frame_pitch;        /* floats between frames, >= lags */
+    int64_t row_pitch;          /* rows > 1: >= (n_frames-1)*frame_pitch + lags */
+    int32_t chunk_frames;       /* upper bound on the frames per work item: 0 = the library's choice, else 1..65536; never changes the result */
+} jsg_tempogram_args;
+/* Enqueue only (one kernel, no scratch): no allocation, no synchronisation; hipGraph capture works, a first launch included.  Refused
+ * (JSG_ERR_INVALID, nothing enqueued, jsg_last_error set), in this order and before any device call: null args, a null in, a null
+ * window, a null out, a pointer that is not 4-byte aligned, rows outside 1..65535, n_in outside 1..2^31-1, win_length outside
+ * 2..4096, lags outside 1..win_length, hop outside 1..2^20, n_frames outside 1..jsg_tempogram_frames(n_in, hop), normalise other than
+ * 0 or 1, chunk_frames outside 0 or 1..65536, in_pitch below n_in (rows > 1), frame_pitch below lags, row_pitch below
+ * (n_frames-1)*frame_pitch + lags (rows > 1), out overlapping in or window.  Then JSG_ERR_NO_DEVICE without a HIP device.  Every
+ * call that passes is served. */
+JSG_API int jsg_tempogram_launch(const jsg_tempogram_args* args, void* stream);
+/* What the launch would do, without a device: the path ("tempogram_lags1", "tempogram_lags2", "tempogram_lags4" or
+ * "tempogram_lags8": the lags a lane accumulates at a time, by `lags` alone), the frames a work item takes (one staging of their span
+ * of the envelope and of the window into LDS) and the bytes of LDS a workgroup asks for (<= 163840).  Any output pointer may be NULL
+ * (name: else name_len >= 24).  Refused: what the launch refuses. */
+JSG_API int jsg_tempogram_plan(const jsg_tempogram_args* args, char* name, int name_len, int32_t* frames_per_item, int32_t* lds_bytes);
+/* The path of jsg_tempogram_plan (out_len >= 24).  The refusals of the launch; no device is needed. */
+JSG_API int jsg_tempogram_kernel_name(const jsg_tempogram_args* args, char* out, int out_len);
+
+/* The standard prior on the host (no device): out[0..lags).  JSG_ERR_INVALID: a null out, lags outside 1..JSG_TEMPOGRAM_MAX_WINDOW,
+ * frame_rate, start_bpm or std_bpm not finite and > 0, max_bpm not finite. */
+JSG_API int jsg_tempo_prior_build(int32_t lags, double frame_rate, double start_bpm, double std_bpm, double max_bpm, float* out);
+typedef struct jsg_tempo_args {
+    const float* in;            /* device floats: TG[r][i][tau] at in[r*row_pitch + i*frame_pitch + tau] */
+    int64_t frame_pitch;        /* floats between frames, >= lags */
+    int64_t row_pitch;          /* rows > 1: >= (N-1)*frame_pitch + lags */
+    int32_t rows;               /* 1..65535, independent */
+    int32_t lags;               /* Lg, 2..JSG_TEMPOGRAM_MAX_WINDOW */
+    int64_t n_frames;           /* N, 1..2^31-1 */
+    float frame_rate;           /* frames of the envelope per second, finite, > 0 */
+    const float* prior;         /* device floats: prior[0..Lg) */
+    float* bpm;                 /* device floats [rows] or NULL */
+    int32_t* lag;               /* device int32 [rows] or NULL */
+    float* profile;             /* device floats or NULL: g[r][tau] at profile[r*profile_pitch + tau] */
+    int64_t profile_pitch;      /* rows > 1: >= lags */
+} jsg_tempo_args;
+/* Enqueue only (one kernel, no scratch): no allocation, no synchronisation; hipGraph capture works, a first launch included.  Refused
+ * (JSG_ERR_INVALID, nothing enqueued, jsg_last_error set), in this order and before any device call: null args, a null in, a null
+ * prior, bpm, lag and profile all null, a pointer that is not 4-byte aligned, rows outside 1..65535, lags outside 2..4096, n_frames
+ * outside 1..2^31-1, a frame_rate that is not finite and > 0, frame_pitch below lags, row_pitch below (N-1)*frame_pitch + lags
+ * (rows > 1), profile_pitch below lags (rows > 1, profile given), an output overlapping in or prior.  Then JSG_ERR_NO_DEVICE without
+ * a HIP device.  Every call that passes is served. */
+JSG_API int jsg_tempo_launch(const jsg_tempo_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 3. Engine: the state of class Spectrogram (Spectrogram.h:81-169) living on the GPU.

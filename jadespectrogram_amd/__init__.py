@@ -13,7 +13,9 @@ from .spectrogram import (CColorPalette, Filterbank, FreqAxis, Plan, Spectrogram
                           hpss, hpss_audio, hpss_launch, hpss_scratch_bytes,
                           Resampler, pitch_shift, resample, resample_kernel_name, resample_launch, resample_length, resample_plan, sinc_table,
                           CqtBasis, cqt, cqt_db, cqt_frames, cqt_frequencies, cqt_kernel_name, cqt_launch, cqt_plan, vqt,
-                          yin, yin_cmnd, yin_frames, yin_kernel_name, yin_launch, yin_plan)
+                          yin, yin_cmnd, yin_frames, yin_kernel_name, yin_launch, yin_plan,
+                          estimate_tempo, onset_strength, onset_strength_launch, tempo, tempo_launch, tempo_prior, tempogram, tempogram_frames,
+                          tempogram_kernel_name, tempogram_launch, tempogram_plan)
 
 __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_db", "colormap", "window", "colormap_lut",
            "colormap_range", "feed_samples", "memsize_blocks", "next_power_of_2", "JsgError", "capi",
@@ -23,4 +25,6 @@ __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_d
            "hpss_scratch_bytes", "hpss_launch", "hpss", "hpss_audio",
            "sinc_table", "Resampler", "resample_length", "resample_launch", "resample_kernel_name", "resample_plan", "resample", "pitch_shift",
            "CqtBasis", "cqt_frames", "cqt_launch", "cqt_plan", "cqt_kernel_name", "cqt", "vqt", "cqt_frequencies", "cqt_db",
-           "yin_frames", "yin_launch", "yin_plan", "yin_kernel_name", "yin", "yin_cmnd"]
+           "yin_frames", "yin_launch", "yin_plan", "yin_kernel_name", "yin", "yin_cmnd",
+           "onset_strength", "onset_strength_launch", "tempogram", "tempogram_launch", "tempogram_frames", "tempogram_plan", "tempogram_kernel_name",
+           "tempo_prior", "tempo_launch", "tempo", "estimate_tempo"]

@@ -34,6 +34,7 @@ HPSS_MAX_WINDOW = 63
 RESAMPLE_MAX_TABLE = 32768
 CQT_MAX_BINS, CQT_MAX_HALF_LEN, CQT_MAX_TAPS, CQT_MAX_CLASSES = 4096, 131072, 1 << 24, 20
 YIN_MAX_WINDOW, YIN_MAX_LAG = 8192, 8192
+ONSET_MAX_BANDS, ONSET_MAX_LAG, ONSET_MAX_SIZE, TEMPOGRAM_MAX_WINDOW = 65536, 4096, 255, 4096
 
 
 class JsgError(RuntimeError):
@@ -114,6 +115,23 @@ class YinArgs(C.Structure):
                 ("tau_min", C.c_int32), ("tau_max", C.c_int32), ("hop", C.c_int64), ("n_frames", C.c_int64), ("threshold", C.c_float),
                 ("sample_rate", C.c_float), ("f0", C.c_void_p), ("aper", C.c_void_p), ("out_pitch", C.c_int64), ("cmnd", C.c_void_p),
                 ("cmnd_frame_pitch", C.c_int64), ("cmnd_row_pitch", C.c_int64), ("chunk_frames", C.c_int32)]
+
+
+class OnsetArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("frame_pitch", C.c_int64), ("row_pitch", C.c_int64), ("rows", C.c_int32), ("n_bands", C.c_int32),
+                ("n_frames", C.c_int64), ("lag", C.c_int32), ("max_size", C.c_int32), ("out", C.c_void_p), ("out_pitch", C.c_int64)]
+
+
+class TempogramArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("in_pitch", C.c_int64), ("rows", C.c_int32), ("win_length", C.c_int32), ("n_in", C.c_int64),
+                ("hop", C.c_int64), ("n_frames", C.c_int64), ("lags", C.c_int32), ("normalise", C.c_int32), ("window", C.c_void_p),
+                ("out", C.c_void_p), ("frame_pitch", C.c_int64), ("row_pitch", C.c_int64), ("chunk_frames", C.c_int32)]
+
+
+class TempoArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("frame_pitch", C.c_int64), ("row_pitch", C.c_int64), ("rows", C.c_int32), ("lags", C.c_int32),
+                ("n_frames", C.c_int64), ("frame_rate", C.c_float), ("prior", C.c_void_p), ("bpm", C.c_void_p), ("lag", C.c_void_p),
+                ("profile", C.c_void_p), ("profile_pitch", C.c_int64)]
 
 
 class StftImageArgs(C.Structure):
@@ -203,6 +221,13 @@ SIGNATURES = {
     "jsg_yin_launch": (C.c_int, [C.POINTER(YinArgs), _P]),
     "jsg_yin_plan": (C.c_int, [C.POINTER(YinArgs), C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "jsg_yin_kernel_name": (C.c_int, [C.POINTER(YinArgs), C.c_char_p, C.c_int]),
+    "jsg_onset_strength_launch": (C.c_int, [C.POINTER(OnsetArgs), _P]),
+    "jsg_tempogram_frames": (C.c_int64, [C.c_int64, C.c_int64]),
+    "jsg_tempogram_launch": (C.c_int, [C.POINTER(TempogramArgs), _P]),
+    "jsg_tempogram_plan": (C.c_int, [C.POINTER(TempogramArgs), C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "jsg_tempogram_kernel_name": (C.c_int, [C.POINTER(TempogramArgs), C.c_char_p, C.c_int]),
+    "jsg_tempo_prior_build": (C.c_int, [C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
+    "jsg_tempo_launch": (C.c_int, [C.POINTER(TempoArgs), _P]),
     "jsg_create": (C.c_int, [C.POINTER(_P), C.c_int]),
     "jsg_create_on_device": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int]),
     "jsg_get_device": (C.c_int, [_P]),

@@ -95,6 +95,28 @@ int yin_check(const jsg_yin_args* g, const char* who);
 void yin_resolve(const jsg_yin_args* g, YinPlan* p);
 const char* yin_path_name(const YinPlan& p);
 
+// jsg_rhythm_host.cpp: the refusals of section 2j and how a tempogram call that passes is served (jsg_rhythm.hip launches by it).  A
+// work item is a row and F consecutive frames; its LDS holds F rows of windowed samples y (Wn rounded up to 4 floats each), F rows of
+// Lg sums, kTgPad floats (a 16-byte read may end one float past the last row), the window table and the span of the frames
+// ((F - 1) S + Wn floats, S = min(hop, Wn)).
+constexpr int kTgThreads = 256;
+constexpr int kTgPad = 64;
+constexpr int kTgLdsFour = 10240;           // 40 KiB: four workgroups per compute unit, where a frame fits
+constexpr int kTgLdsTwo = 20480;            // 80 KiB: two
+constexpr int kTgLdsOne = 40960;            // 160 KiB
+constexpr int kTgFrames = 16;               // frames per item where the caller does not say
+struct TgPlan {
+    int NL;                    // lags a lane accumulates at a time: 1, 2, 4 or 8
+    int F, S;
+    long long chunks;          // ceil(n_frames / F)
+    int lds_floats;
+};
+int onset_check(const jsg_onset_args* g, const char* who);
+int tempogram_check(const jsg_tempogram_args* g, const char* who);
+void tempogram_resolve(const jsg_tempogram_args* g, TgPlan* p);
+const char* tempogram_path_name(const TgPlan& p);
+int tempo_check(const jsg_tempo_args* g, const char* who);
+
 // Slaney's mel scale (librosa.filters.mel, htk = False): linear below 1 kHz (200/3 Hz per mel), logarithmic above (27 mels per
 // factor 6.4).  Shared by the MEL_SLANEY filterbank and the MEL display axis.
 inline double slaney_logstep() { return std::log(6.4) / 27.0; }

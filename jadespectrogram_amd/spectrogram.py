@@ -1496,3 +1496,190 @@ def yin_cmnd(x, sr: float, fmin: float, fmax: float, frame_length: int = 2048, h
     plane, _, batch, was_numpy = _yin_rows(x, sr, fmin, fmax, frame_length, hop_length, threshold, center, True)
     plane = plane.reshape(*batch, plane.shape[1], plane.shape[2])
     return plane.cpu().numpy() if was_numpy else plane
+
+
+# --------------------------------------------------------------------------------------------------
+# onset strength, autocorrelation tempogram and tempo (include/jsg.h, section 2j)
+# --------------------------------------------------------------------------------------------------
+def _lines(t, rows: int, least: int, what: str):
+    """[rows][>= least] float32 CUDA view with unit stride of a 1- or 2-dimensional tensor."""
+    import torch
+    t = t[None] if t.dim() == 1 else t
+    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == rows and t.shape[1] >= least, \
+        f"{what}: float32 CUDA [rows][>= {least}]"
+    return t
+
+
+def _plane(t, what: str):
+    """[rows][frames][bins] float32 CUDA view with unit bin stride."""
+    import torch
+    t = _rows3(t, what)
+    assert t.is_cuda and t.dtype == torch.float32 and t.stride(2) == 1, f"{what}: float32 CUDA [rows][frames][bins]"
+    return t
+
+
+def onset_strength_launch(d_S, d_out, *, lag: int = 1, max_size: int = 1, stream: int | None = None):
+    """jsg_onset_strength_launch: d_S float32 [rows][frames][bands] (or one [frames][bands] plane; views with pitches) -> d_out float32
+    [rows][frames]: the mean over the bands of max(0, S[t][b] - ref[t - lag][b]), ref the maximum over max_size neighbouring bands;
+    +0 for t < lag."""
+    s = _plane(d_S, "d_S")
+    R, T, B = s.shape
+    o = _lines(d_out, R, T, "d_out")
+    a = capi.OnsetArgs(s.data_ptr(), s.stride(1), s.stride(0), R, B, T, int(lag), int(max_size), o.data_ptr(), o.stride(0))
+    check(lib().jsg_onset_strength_launch(C.byref(a), _stream_handle(stream, s)))
+
+
+def tempogram_frames(n_in: int, hop: int = 1) -> int:
+    """jsg_tempogram_frames: 1 + (n_in - 1) // hop frames, frame i centred on sample i * hop of the envelope."""
+    return int(check(lib().jsg_tempogram_frames(int(n_in), int(hop))))
+
+
+def _tempogram_args(d_in, d_window, d_out, lags, hop, n_frames, normalise, chunk_frames) -> capi.TempogramArgs:
+    import torch
+    x = d_in[None] if d_in.dim() == 1 else d_in
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1, "d_in: float32 CUDA [rows][samples]"
+    assert d_window.is_cuda and d_window.dtype == torch.float32 and d_window.dim() == 1 and d_window.stride(0) == 1, "d_window: float32 CUDA [win_length]"
+    Wn = d_window.shape[0]
+    lags = Wn if lags is None else int(lags)
+    n_frames = tempogram_frames(x.shape[1], hop) if n_frames is None else int(n_frames)
+    o = _plane(d_out, "d_out")
+    assert o.shape[0] == x.shape[0] and o.shape[1] >= n_frames and o.shape[2] >= lags, "d_out: float32 CUDA [rows][>= n_frames][>= lags]"
+    return capi.TempogramArgs(x.data_ptr(), x.stride(0), x.shape[0], Wn, x.shape[1], int(hop), n_frames, lags, int(bool(normalise)), d_window.data_ptr(),
+                              o.data_ptr(), o.stride(1), o.stride(0), int(chunk_frames))
+
+
+def tempogram_launch(d_in, d_window, d_out, *, lags: int | None = None, hop: int = 1, n_frames: int | None = None, normalise: bool = True,
+                     chunk_frames: int = 0, stream: int | None = None):
+    """jsg_tempogram_launch: d_in float32 [rows][T] (an onset envelope), d_window float32 [win_length] -> d_out float32
+    [rows][n_frames][>= lags]: the autocorrelation of the windowed envelope around sample i * hop at the lags 0..lags-1 (default: all
+    win_length of them), divided by its lag 0 where normalise.  chunk_frames (0: the library's choice) never changes the result."""
+    a = _tempogram_args(d_in, d_window, d_out, lags, hop, n_frames, normalise, chunk_frames)
+    check(lib().jsg_tempogram_launch(C.byref(a), _stream_handle(stream, d_in)))
+
+
+def tempogram_kernel_name(d_in, d_window, d_out, *, lags: int | None = None, hop: int = 1, n_frames: int | None = None, normalise: bool = True,
+                          chunk_frames: int = 0) -> str:
+    """The path tempogram_launch takes for these arguments: "tempogram_lags1", "tempogram_lags2", "tempogram_lags4" or "tempogram_lags8"."""
+    a = _tempogram_args(d_in, d_window, d_out, lags, hop, n_frames, normalise, chunk_frames)
+    return _kernel_name(lib().jsg_tempogram_kernel_name, C.byref(a))
+
+
+def tempogram_plan(d_in, d_window, d_out, *, lags: int | None = None, hop: int = 1, n_frames: int | None = None, normalise: bool = True,
+                   chunk_frames: int = 0):
+    """jsg_tempogram_plan: (path, frames per work item, bytes of LDS per workgroup) of tempogram_launch for these arguments.  Needs no
+    device."""
+    a = _tempogram_args(d_in, d_window, d_out, lags, hop, n_frames, normalise, chunk_frames)
+    name, frames, lds = C.create_string_buffer(32), C.c_int32(), C.c_int32()
+    check(lib().jsg_tempogram_plan(C.byref(a), name, 32, C.byref(frames), C.byref(lds)))
+    return name.value.decode(), frames.value, lds.value
+
+
+def tempo_prior(lags: int, frame_rate: float, start_bpm: float = 120.0, std_bpm: float = 1.0, max_bpm: float = 320.0) -> np.ndarray:
+    """jsg_tempo_prior_build: the log-normal tempo prior of librosa.feature.tempo over the lags 0..lags-1 of an envelope of frame_rate
+    frames per second (0 at lag 0 and where 60 * frame_rate / lag exceeds max_bpm; max_bpm <= 0: no limit), float32."""
+    out = np.zeros(int(lags), dtype=np.float32)
+    check(lib().jsg_tempo_prior_build(int(lags), float(frame_rate), float(start_bpm), float(std_bpm), float(max_bpm), out.ctypes.data))
+    return out
+
+
+def tempo_launch(d_tg, d_prior, frame_rate: float, *, d_bpm=None, d_lag=None, d_profile=None, lags: int | None = None, n_frames: int | None = None,
+                 stream: int | None = None):
+    """jsg_tempo_launch: d_tg float32 [rows][frames][>= lags] (a tempogram), d_prior float32 [lags] -> d_bpm float32 [rows], d_lag int32
+    [rows], d_profile float32 [rows][>= lags] (the mean over the frames); any of the three may be None, not all."""
+    import torch
+    tg = _plane(d_tg, "d_tg")
+    R = tg.shape[0]
+    lags = d_prior.shape[0] if lags is None else int(lags)
+    n_frames = tg.shape[1] if n_frames is None else int(n_frames)
+    assert d_prior.is_cuda and d_prior.dtype == torch.float32 and d_prior.dim() == 1 and d_prior.stride(0) == 1 and d_prior.shape[0] >= lags, "d_prior: float32 CUDA [lags]"
+    assert tg.shape[1] >= n_frames and tg.shape[2] >= lags, "d_tg: float32 CUDA [rows][>= n_frames][>= lags]"
+    for o, dtype, what in ((d_bpm, torch.float32, "d_bpm"), (d_lag, torch.int32, "d_lag")):
+        assert o is None or (o.is_cuda and o.dtype == dtype and o.dim() == 1 and o.stride(0) == 1 and o.shape[0] >= R), f"{what}: CUDA [rows]"
+    p = None if d_profile is None else _lines(d_profile, R, lags, "d_profile")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    a = capi.TempoArgs(tg.data_ptr(), tg.stride(1), tg.stride(0), R, lags, n_frames, float(frame_rate), d_prior.data_ptr(), ptr(d_bpm), ptr(d_lag), ptr(p),
+                       0 if p is None else p.stride(0))
+    check(lib().jsg_tempo_launch(C.byref(a), _stream_handle(stream, tg)))
+
+
+def _to_cuda(x):
+    """(float32 CUDA tensor, whether x was a numpy array)."""
+    import torch
+    was_numpy = not hasattr(x, "is_cuda")
+    if was_numpy:
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda()
+    assert x.is_cuda and x.dtype == torch.float32, "expected a numpy array or a float32 CUDA tensor"
+    return x, was_numpy
+
+
+def onset_strength(S, lag: int = 1, max_size: int = 1):
+    """Onset strength (spectral flux) of S [..., frames, bands] (numpy array or float32 CUDA tensor; what mel_spectrogram_db returns) ->
+    float32 [..., frames], the same kind.  Differs from librosa.onset.onset_strength on purpose: no centring shift of the envelope, the
+    maximum filter is clipped at the band edges (not reflected), and the bands lie along the last axis."""
+    import torch
+    s, was_numpy = _to_cuda(S)
+    batch = tuple(s.shape[:-2])
+    sr = s.reshape(-1, s.shape[-2], s.shape[-1]).contiguous()
+    out = torch.empty((sr.shape[0], sr.shape[1]), dtype=torch.float32, device=s.device)
+    with torch.cuda.device(_device_index(s)):
+        onset_strength_launch(sr, out, lag=lag, max_size=max_size)
+    out = out.reshape(*batch, -1)
+    return out.cpu().numpy() if was_numpy else out
+
+
+def _hann_window(win_length: int, device):
+    import torch
+    return torch.from_numpy(window(capi.WIN_HANN, int(win_length))).to(device)
+
+
+def tempogram(onset_envelope, win_length: int = 384, hop_length: int = 1, lags: int | None = None, window_table=None, normalise: bool = True):
+    """Autocorrelation tempogram of an onset envelope [..., T] (numpy array or float32 CUDA tensor) -> float32 [..., frames, lags], lag tau
+    at index tau, frames = 1 + (T - 1) // hop_length, the same kind.  window_table: win_length floats (default: the library's periodic
+    Hann).  One row of the result is a contiguous [frames][lags] plane that db_from_power and colormap (height = lags) take.  Differs from
+    librosa.feature.tempogram on purpose: zeros (not a linear ramp) outside the envelope, and a direct (not FFT) autocorrelation."""
+    import torch
+    x, was_numpy = _to_cuda(onset_envelope)
+    batch = tuple(x.shape[:-1])
+    xr = x.reshape(-1, x.shape[-1]).contiguous()
+    w = _hann_window(win_length, x.device) if window_table is None else torch.as_tensor(np.ascontiguousarray(window_table, dtype=np.float32)).to(x.device)
+    lags = w.shape[0] if lags is None else int(lags)
+    n_frames = tempogram_frames(xr.shape[1], hop_length)
+    out = torch.empty((xr.shape[0], n_frames, lags), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(_device_index(x)):
+        tempogram_launch(xr, w, out, lags=lags, hop=hop_length, normalise=normalise)
+    out = out.reshape(*batch, n_frames, lags)
+    return out.cpu().numpy() if was_numpy else out
+
+
+def tempo(tg, frame_rate: float, start_bpm: float = 120.0, std_bpm: float = 1.0, max_bpm: float = 320.0):
+    """Tempo of a tempogram [..., frames, lags] (numpy array or float32 CUDA tensor) over all its frames -> (bpm float32 [...], lag int32
+    [...]), the same kind: the lag >= 1 that maximises (1 + 1e6 * mean autocorrelation) * prior, the rule of librosa.feature.tempo with
+    aggregate = mean.  frame_rate: frames of the onset envelope per second (sr / hop).  bpm is NaN and lag -1 where the mean holds a NaN."""
+    import torch
+    t, was_numpy = _to_cuda(tg)
+    batch = tuple(t.shape[:-2])
+    tr = t.reshape(-1, t.shape[-2], t.shape[-1])
+    tr = tr if tr.stride(2) == 1 else tr.contiguous()
+    prior = torch.from_numpy(tempo_prior(tr.shape[2], frame_rate, start_bpm, std_bpm, max_bpm)).to(t.device)
+    bpm = torch.empty((tr.shape[0],), dtype=torch.float32, device=t.device)
+    lag = torch.empty((tr.shape[0],), dtype=torch.int32, device=t.device)
+    with torch.cuda.device(_device_index(t)):
+        tempo_launch(tr, prior, frame_rate, d_bpm=bpm, d_lag=lag)
+    bpm, lag = bpm.reshape(batch), lag.reshape(batch)
+    return (bpm.cpu().numpy(), lag.cpu().numpy()) if was_numpy else (bpm, lag)
+
+
+def estimate_tempo(x, sr: float, n_fft: int = 2048, hop: int = 512, n_mels: int = 128, win_length: int = 384, start_bpm: float = 120.0,
+                   std_bpm: float = 1.0, max_bpm: float = 320.0):
+    """Tempo of audio x [samples] (numpy array or float32 CUDA tensor): mel_spectrogram_db -> onset_strength -> tempogram (periodic Hann of
+    win_length envelope frames, every frame) -> tempo, all on the GPU with nothing returned to the host in between.  Returns (bpm, lag):
+    floats and ints of the host for numpy input, 0-dimensional CUDA tensors otherwise."""
+    import torch
+    xt, was_numpy = _to_cuda(x)
+    assert xt.dim() == 1, "estimate_tempo: x is one channel [samples]"
+    with torch.cuda.device(_device_index(xt)):
+        S = mel_spectrogram_db(xt, sr, n_fft, hop, n_mels)
+        env = onset_strength(S)
+        tg = tempogram(env, win_length=win_length)
+        bpm, lag = tempo(tg, float(sr) / float(hop), start_bpm, std_bpm, max_bpm)
+    return (float(bpm.cpu()), int(lag.cpu())) if was_numpy else (bpm, lag)
