@@ -52,7 +52,8 @@ extern "C" {
                                  constant-Q and variable-Q spectrograms by direct evaluation (jsg_cqt_*; section 2h),
                                  the band launch query (jsg_fb_band_plan; section 2b),
                                  YIN fundamental-frequency tracking (jsg_yin_*; section 2i),
-                                 onset strength, autocorrelation tempogram and tempo (jsg_onset_*, jsg_tempogram_*, jsg_tempo_*; section 2j) */
+                                 onset strength, autocorrelation tempogram and tempo (jsg_onset_*, jsg_tempogram_*, jsg_tempo_*; section 2j),
+                                 cepstral coefficients and delta features (jsg_mfcc_*, jsg_delta_*; section 2k) */
 
 typedef enum jsg_status {
     JSG_OK = 0,
@@ -995,6 +996,117 @@ typedef struct jsg_tempo_args {
  * (rows > 1), profile_pitch below lags (rows > 1, profile given), an output overlapping in or prior.  Then JSG_ERR_NO_DEVICE without
  * a HIP device.  Every call that passes is served. */
 JSG_API int jsg_tempo_launch(const jsg_tempo_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2k. Cepstral coefficients and delta features: a [frames][bands] plane (what jsg_stft_fb_launch and the dB conversion write)
+ *     projected through a dense table (the DCT-II of MFCCs, its zero-padded inverse, or any table of yours), and the
+ *     Savitzky-Golay derivative of a plane along its frames.  All device arithmetic is float32 (denormals kept, NaN and infinity as
+ *     the fmaf chains give them, as in section 2j); no sum depends on the row, the frame index, the number of rows or frames, the
+ *     pitches, chunk_frames, the grid or the path jsg_mfcc_plan names.
+ *
+ *     Projection.  Rows S[r][t][b] at in[r*row_pitch + t*frame_pitch + b], t = 0..T-1, b = 0..B-1 (B = n_in), and a table D[m][b]
+ *     at table[m*B + b], m = 0..M-1 (M = n_out):
+ *         C[r][t][m] = acc after  acc = +0;  for b = 0, 1, ..., B-1 in this order:  acc = fmaf(D[m][b], S[t][b], acc)
+ *     at out[r*out_row_pitch + t*out_frame_pitch + m].  Elements between M and the frame pitch are not written.  A NaN or an
+ *     infinity at S[t0][b0] reaches exactly the outputs of frame t0 of that row, as the chain gives them (a zero in the table does
+ *     not stop a NaN); no other frame is touched, and nothing outside the T x B elements of a row is read.  Against the same sum in
+ *     float64 of the exact products of the float32 operands, with u = 2^-24:
+ *         |C - C64| <= (B + 2) u * sum over b of |D[m][b]| |S[t][b]|           (one rounding per fmaf; second order in the 2)
+ *
+ *     Tables (jsg_mfcc_table_build, on the host in double, rounded to float32 once).  k = m*(2b+1) mod 4B in integers,
+ *     c = cos(pi*k / (2B)):
+ *         forward, M x B, the DCT-II of scipy.fft.dct(type=2):  D[m][b] = 2c * s[m] * L[m]
+ *             s[m] = 1 (JSG_DCT_NORM_NONE);  sqrt(1/(4B)) for m = 0, sqrt(1/(2B)) otherwise (JSG_DCT_NORM_ORTHO)
+ *             L[m] = 1 + (lifter/2) * sin(pi*(m+1)/lifter),  1 for lifter 0      (the lifter of librosa.feature.mfcc, in the table)
+ *         inverse, B x M in the layout of a launch with n_in = M, n_out = B: the zero-padded inverse of scipy.fft.idct(type=2, n=B)
+ *             ortho:  I[b][m] = 2c * s[m] / L[m];     none:  I[b][m] = (m == 0 ? 1 : 2c) / (2B) / L[m]
+ *
+ *     Delta.  Rows X[r][t][m] with the pitches of a plane, M = n_coeffs values per frame, weights w[0..Wd), Wd odd, h = Wd/2:
+ *         JSG_DELTA_EDGE_INTERP  (T >= Wd):  s = min(max(t - h, 0), T - Wd);  window j is frame s + j
+ *         JSG_DELTA_EDGE_NEAREST (T >= 1):   window j is frame min(max(t - h + j, 0), T - 1)
+ *         Y[r][t][m] = acc after  acc = +0;  for j = 0..Wd-1 in this order:  acc = fmaf(w[j], X[frame j][m], acc)
+ *     With a polynomial order equal to the derivative order (what librosa.feature.delta passes to scipy.signal.savgol_filter) the
+ *     derivative of the fit is constant over the window, so mode = 'interp' is the interior weights on the first or last Wd frames.
+ *     A NaN at X[t0][m0] reaches exactly the frames whose window holds t0, in coefficient m0 only.
+ *         |Y - Y64| <= (Wd + 2) u * sum over j of |w[j]| |X[frame j][m]|
+ *     jsg_delta_weights_build: w = order! * row `order` of the pseudo-inverse of the Vandermonde matrix of j - h, in double, rounded
+ *     once; the centre weight of an odd order is exactly 0; width 9, order 1 gives (j - 4) / 60.
+ *
+ *     Differences from librosa.feature.mfcc / delta / inverse.mfcc_to_mel, on purpose: the frames lie along axis -2 and the
+ *     coefficients along the last axis; the mel dB plane of the Python layer is 10 log10(power + 1e-11) without top_db clipping or
+ *     centring; the lifter is folded into the table before its one rounding.  Agreement with librosa has not been measured.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSG_MFCC_MAX_BANDS 4096
+#define JSG_MFCC_MAX_COEFFS 4096
+#define JSG_MFCC_MAX_TABLE 32768        /* n_in * n_out floats (128 KB): the whole table sits in LDS next to the staged tile */
+#define JSG_DCT_NORM_NONE 0
+#define JSG_DCT_NORM_ORTHO 1
+#define JSG_DELTA_MAX_WIDTH 255
+#define JSG_DELTA_MAX_ORDER 4
+#define JSG_DELTA_MAX_COEFFS 65536
+#define JSG_DELTA_EDGE_INTERP 0
+#define JSG_DELTA_EDGE_NEAREST 1
+typedef struct jsg_mfcc_args {
+    const float* in;            /* device floats: S[r][t][b] at in[r*row_pitch + t*frame_pitch + b] */
+    int64_t frame_pitch;        /* floats between frames, >= n_in */
+    int64_t row_pitch;          /* rows > 1: >= (T-1)*frame_pitch + n_in */
+    int32_t rows;               /* 1..65535, independent */
+    int32_t n_in;               /* B, 1..JSG_MFCC_MAX_BANDS */
+    int64_t n_frames;           /* T, 1..2^31-1 */
+    const float* table;         /* device floats: D[m][b] at table[m*n_in + b]; n_in*n_out <= JSG_MFCC_MAX_TABLE */
+    int32_t n_out;              /* M, 1..JSG_MFCC_MAX_COEFFS */
+    float* out;                 /* device floats: C[r][t][m] at out[r*out_row_pitch + t*out_frame_pitch + m] */
+    int64_t out_frame_pitch;    /* floats between frames, >= n_out */
+    int64_t out_row_pitch;      /* rows > 1: >= (T-1)*out_frame_pitch + n_out */
+    int32_t chunk_frames;       /* upper bound on the frames per work item: 0 = the library's choice, else 1..65536; never changes the result */
+} jsg_mfcc_args;
+/* Applies any dense table (the inverse runs through it with the roles of B and M exchanged).  Enqueue only (one kernel, no scratch):
+ * no allocation, no synchronisation; hipGraph capture works, a first launch included.  Refused (JSG_ERR_INVALID, nothing enqueued,
+ * jsg_last_error set), in this order and before any device call: null args, a null in, a null table, a null out, a pointer that is
+ * not 4-byte aligned, rows outside 1..65535, n_in outside 1..4096, n_out outside 1..4096, n_in*n_out above 32768, n_frames outside
+ * 1..2^31-1, chunk_frames outside 0 or 1..65536, frame_pitch below n_in, row_pitch below (T-1)*frame_pitch + n_in (rows > 1),
+ * out_frame_pitch below n_out, out_row_pitch below (T-1)*out_frame_pitch + n_out (rows > 1), out overlapping in or table.  Then
+ * JSG_ERR_NO_DEVICE without a HIP device.  Every call that passes is served. */
+JSG_API int jsg_mfcc_launch(const jsg_mfcc_args* args, void* stream);
+/* What the launch would do, without a device: the path ("mfcc_block4", "mfcc_block5", "mfcc_block8", "mfcc_block10" or
+ * "mfcc_block16": the coefficients a lane accumulates at a time, by n_out alone), the frames a work item takes (at most 64, one per
+ * lane; fewer where chunk_frames, n_frames or the LDS next to a large table say so) and the bytes of LDS a workgroup asks for
+ * (<= 163840: the table, the tile and the staged outputs).  Any output pointer may be NULL
+ * (name: else name_len >= 24).  Refused: what the launch refuses. */
+JSG_API int jsg_mfcc_plan(const jsg_mfcc_args* args, char* name, int name_len, int32_t* frames_per_item, int32_t* lds_bytes);
+/* The path of jsg_mfcc_plan (out_len >= 24).  The refusals of the launch; no device is needed. */
+JSG_API int jsg_mfcc_kernel_name(const jsg_mfcc_args* args, char* out, int out_len);
+/* A DCT table on the host (no device): forward, out[n_coeffs][n_bands]; inverse, out[n_bands][n_coeffs].  JSG_ERR_INVALID, in this
+ * order: a null out, n_bands outside 1..4096, n_coeffs outside 1..4096, n_coeffs above n_bands, n_bands*n_coeffs above 32768, norm
+ * other than JSG_DCT_NORM_NONE or JSG_DCT_NORM_ORTHO, inverse other than 0 or 1, a lifter that is negative or not finite, an inverse
+ * whose L[m] is zero for some m. */
+JSG_API int jsg_mfcc_table_build(int32_t n_bands, int32_t n_coeffs, int32_t norm, double lifter, int32_t inverse, float* out);
+
+/* The Savitzky-Golay derivative weights on the host (no device): out[0..width).  JSG_ERR_INVALID, in this order: a null out, a width
+ * that is even or outside 3..255, an order outside 1..4 or not below width. */
+JSG_API int jsg_delta_weights_build(int32_t width, int32_t order, float* out);
+typedef struct jsg_delta_args {
+    const float* in;            /* device floats: X[r][t][m] at in[r*row_pitch + t*frame_pitch + m] */
+    int64_t frame_pitch;        /* floats between frames, >= n_coeffs */
+    int64_t row_pitch;          /* rows > 1: >= (T-1)*frame_pitch + n_coeffs */
+    int32_t rows;               /* 1..65535, independent */
+    int32_t n_coeffs;           /* M, 1..JSG_DELTA_MAX_COEFFS */
+    int64_t n_frames;           /* T, 1..2^31-1 */
+    const float* weights;       /* device floats: w[0..width) */
+    int32_t width;              /* Wd, odd, 3..JSG_DELTA_MAX_WIDTH */
+    int32_t mode;               /* JSG_DELTA_EDGE_INTERP or JSG_DELTA_EDGE_NEAREST */
+    float* out;                 /* device floats: Y[r][t][m] at out[r*out_row_pitch + t*out_frame_pitch + m] */
+    int64_t out_frame_pitch;    /* floats between frames, >= n_coeffs */
+    int64_t out_row_pitch;      /* rows > 1: >= (T-1)*out_frame_pitch + n_coeffs */
+} jsg_delta_args;
+/* Enqueue only (one kernel, no scratch): no allocation, no synchronisation; hipGraph capture works, a first launch included.  Refused
+ * (JSG_ERR_INVALID, nothing enqueued, jsg_last_error set), in this order and before any device call: null args, a null in, a null
+ * weights, a null out, a pointer that is not 4-byte aligned, rows outside 1..65535, n_coeffs outside 1..65536, n_frames outside
+ * 1..2^31-1, a width that is even or outside 3..255, a mode other than the two, n_frames below width under JSG_DELTA_EDGE_INTERP,
+ * frame_pitch below n_coeffs, row_pitch below (T-1)*frame_pitch + n_coeffs (rows > 1), out_frame_pitch below n_coeffs, out_row_pitch
+ * below (T-1)*out_frame_pitch + n_coeffs (rows > 1), out overlapping in or weights.  Then JSG_ERR_NO_DEVICE without a HIP device.
+ * Every call that passes is served. */
+JSG_API int jsg_delta_launch(const jsg_delta_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 3. Engine: the state of class Spectrogram (Spectrogram.h:81-169) living on the GPU.

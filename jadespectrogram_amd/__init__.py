@@ -15,7 +15,8 @@ from .spectrogram import (CColorPalette, Filterbank, FreqAxis, Plan, Spectrogram
                           CqtBasis, cqt, cqt_db, cqt_frames, cqt_frequencies, cqt_kernel_name, cqt_launch, cqt_plan, vqt,
                           yin, yin_cmnd, yin_frames, yin_kernel_name, yin_launch, yin_plan,
                           estimate_tempo, onset_strength, onset_strength_launch, tempo, tempo_launch, tempo_prior, tempogram, tempogram_frames,
-                          tempogram_kernel_name, tempogram_launch, tempogram_plan)
+                          tempogram_kernel_name, tempogram_launch, tempogram_plan,
+                          delta, delta_launch, delta_weights, mfcc, mfcc_audio, mfcc_kernel_name, mfcc_launch, mfcc_plan, mfcc_table, mfcc_to_mel_db)
 
 __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_db", "colormap", "window", "colormap_lut",
            "colormap_range", "feed_samples", "memsize_blocks", "next_power_of_2", "JsgError", "capi",
@@ -27,4 +28,5 @@ __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_d
            "CqtBasis", "cqt_frames", "cqt_launch", "cqt_plan", "cqt_kernel_name", "cqt", "vqt", "cqt_frequencies", "cqt_db",
            "yin_frames", "yin_launch", "yin_plan", "yin_kernel_name", "yin", "yin_cmnd",
            "onset_strength", "onset_strength_launch", "tempogram", "tempogram_launch", "tempogram_frames", "tempogram_plan", "tempogram_kernel_name",
-           "tempo_prior", "tempo_launch", "tempo", "estimate_tempo"]
+           "tempo_prior", "tempo_launch", "tempo", "estimate_tempo",
+           "mfcc_table", "mfcc_launch", "mfcc_plan", "mfcc_kernel_name", "delta_weights", "delta_launch", "mfcc", "mfcc_to_mel_db", "delta", "mfcc_audio"]

@@ -35,6 +35,8 @@ RESAMPLE_MAX_TABLE = 32768
 CQT_MAX_BINS, CQT_MAX_HALF_LEN, CQT_MAX_TAPS, CQT_MAX_CLASSES = 4096, 131072, 1 << 24, 20
 YIN_MAX_WINDOW, YIN_MAX_LAG = 8192, 8192
 ONSET_MAX_BANDS, ONSET_MAX_LAG, ONSET_MAX_SIZE, TEMPOGRAM_MAX_WINDOW = 65536, 4096, 255, 4096
+MFCC_MAX_BANDS, MFCC_MAX_COEFFS, MFCC_MAX_TABLE, DCT_NORM_NONE, DCT_NORM_ORTHO = 4096, 4096, 32768, 0, 1
+DELTA_MAX_WIDTH, DELTA_MAX_ORDER, DELTA_MAX_COEFFS, DELTA_EDGE_INTERP, DELTA_EDGE_NEAREST = 255, 4, 65536, 0, 1
 
 
 class JsgError(RuntimeError):
@@ -134,6 +136,18 @@ class TempoArgs(C.Structure):
                 ("profile", C.c_void_p), ("profile_pitch", C.c_int64)]
 
 
+class MfccArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("frame_pitch", C.c_int64), ("row_pitch", C.c_int64), ("rows", C.c_int32), ("n_in", C.c_int32),
+                ("n_frames", C.c_int64), ("table", C.c_void_p), ("n_out", C.c_int32), ("out", C.c_void_p), ("out_frame_pitch", C.c_int64),
+                ("out_row_pitch", C.c_int64), ("chunk_frames", C.c_int32)]
+
+
+class DeltaArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("frame_pitch", C.c_int64), ("row_pitch", C.c_int64), ("rows", C.c_int32), ("n_coeffs", C.c_int32),
+                ("n_frames", C.c_int64), ("weights", C.c_void_p), ("width", C.c_int32), ("mode", C.c_int32), ("out", C.c_void_p),
+                ("out_frame_pitch", C.c_int64), ("out_row_pitch", C.c_int64)]
+
+
 class StftImageArgs(C.Structure):
     _fields_ = [("stft", StftArgs), ("colour", ColormapArgs), ("index_scratch", C.c_void_p), ("index_scratch_pitch", C.c_int64)]
 
@@ -228,6 +242,12 @@ SIGNATURES = {
     "jsg_tempogram_kernel_name": (C.c_int, [C.POINTER(TempogramArgs), C.c_char_p, C.c_int]),
     "jsg_tempo_prior_build": (C.c_int, [C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
     "jsg_tempo_launch": (C.c_int, [C.POINTER(TempoArgs), _P]),
+    "jsg_mfcc_launch": (C.c_int, [C.POINTER(MfccArgs), _P]),
+    "jsg_mfcc_plan": (C.c_int, [C.POINTER(MfccArgs), C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "jsg_mfcc_kernel_name": (C.c_int, [C.POINTER(MfccArgs), C.c_char_p, C.c_int]),
+    "jsg_mfcc_table_build": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P]),
+    "jsg_delta_weights_build": (C.c_int, [C.c_int32, C.c_int32, _P]),
+    "jsg_delta_launch": (C.c_int, [C.POINTER(DeltaArgs), _P]),
     "jsg_create": (C.c_int, [C.POINTER(_P), C.c_int]),
     "jsg_create_on_device": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int]),
     "jsg_get_device": (C.c_int, [_P]),

@@ -117,6 +117,24 @@ void tempogram_resolve(const jsg_tempogram_args* g, TgPlan* p);
 const char* tempogram_path_name(const TgPlan& p);
 int tempo_check(const jsg_tempo_args* g, const char* who);
 
+// jsg_cepstral_host.cpp: the refusals of section 2k and how a projection that passes is served (jsg_cepstral.hip launches by it).  A
+// work item is a row and F consecutive frames.  Its LDS holds the table (M rows of B floats, staged once per workgroup), the tile (F
+// rows of P = B | 1 floats: lane-per-frame reads fall into different banks) and the staged outputs (F rows of M | 1 floats).  A lane
+// owns a frame, so F <= 64; a wave takes blocks of MB coefficients of all F frames; MB is 4, 5, 8, 10 or 16 by M alone.
+constexpr int kMfccThreads = 256;
+constexpr int kMfccLdsOne = 40960;          // 160 KiB
+constexpr int kMfccFrames = 64;             // frames per item: one per lane of a wave
+struct MfccPlan {
+    int MB;                    // coefficients a lane accumulates at a time
+    int F;
+    long long chunks;          // ceil(n_frames / F)
+    int lds_floats;
+};
+int mfcc_check(const jsg_mfcc_args* g, const char* who);
+void mfcc_resolve(const jsg_mfcc_args* g, MfccPlan* p);
+const char* mfcc_path_name(const MfccPlan& p);
+int delta_check(const jsg_delta_args* g, const char* who);
+
 // Slaney's mel scale (librosa.filters.mel, htk = False): linear below 1 kHz (200/3 Hz per mel), logarithmic above (27 mels per
 // factor 6.4).  Shared by the MEL_SLANEY filterbank and the MEL display axis.
 inline double slaney_logstep() { return std::log(6.4) / 27.0; }

@@ -1683,3 +1683,161 @@ def estimate_tempo(x, sr: float, n_fft: int = 2048, hop: int = 512, n_mels: int 
         tg = tempogram(env, win_length=win_length)
         bpm, lag = tempo(tg, float(sr) / float(hop), start_bpm, std_bpm, max_bpm)
     return (float(bpm.cpu()), int(lag.cpu())) if was_numpy else (bpm, lag)
+
+
+# --------------------------------------------------------------------------------------------------
+# cepstral coefficients and delta features (include/jsg.h, section 2k)
+# --------------------------------------------------------------------------------------------------
+_NORMS = {"ortho": capi.DCT_NORM_ORTHO, None: capi.DCT_NORM_NONE, "none": capi.DCT_NORM_NONE}
+_EDGES = {"interp": capi.DELTA_EDGE_INTERP, "nearest": capi.DELTA_EDGE_NEAREST}
+_cepstral_cache: dict = {}
+
+
+def _named(table: dict, key, what: str) -> int:
+    if key not in table:
+        raise JsgError(capi.JSG_ERR_INVALID, f"{what} must be one of {sorted(k for k in table if k is not None)}, not {key!r}")
+    return table[key]
+
+
+def mfcc_table(n_bands: int, n_coeffs: int = 20, norm="ortho", lifter: float = 0.0, inverse: bool = False) -> np.ndarray:
+    """jsg_mfcc_table_build: the DCT-II table of scipy.fft.dct(type=2, norm=norm) with the lifter of librosa.feature.mfcc folded in,
+    float32 [n_coeffs][n_bands]; inverse: the zero-padded inverse of scipy.fft.idct(type=2, n=n_bands) with the lifter divided out,
+    float32 [n_bands][n_coeffs] (the table of a launch from n_coeffs to n_bands values per frame).  Built in double, rounded once."""
+    B, M = int(n_bands), int(n_coeffs)
+    out = np.zeros((B, M) if inverse else (M, B), dtype=np.float32)
+    check(lib().jsg_mfcc_table_build(B, M, _named(_NORMS, norm, "norm"), float(lifter), int(bool(inverse)), out.ctypes.data if out.size else None))
+    return out
+
+
+def _mfcc_args(d_S, d_table, d_out, chunk_frames) -> capi.MfccArgs:
+    import torch
+    s = _plane(d_S, "d_S")
+    R, T, B = s.shape
+    assert d_table.is_cuda and d_table.dtype == torch.float32 and d_table.dim() == 2 and d_table.is_contiguous() and d_table.shape[1] == B, \
+        "d_table: contiguous float32 CUDA [n_out][n_in]"
+    M = d_table.shape[0]
+    o = _plane(d_out, "d_out")
+    assert o.shape[0] == R and o.shape[1] >= T and o.shape[2] >= M, "d_out: float32 CUDA [rows][>= frames][>= n_out]"
+    return capi.MfccArgs(s.data_ptr(), s.stride(1), s.stride(0), R, B, T, d_table.data_ptr(), M, o.data_ptr(), o.stride(1), o.stride(0), int(chunk_frames))
+
+
+def mfcc_launch(d_S, d_table, d_out, *, chunk_frames: int = 0, stream: int | None = None):
+    """jsg_mfcc_launch: d_S float32 [rows][frames][n_in] (or one [frames][n_in] plane; views with pitches), d_table float32
+    [n_out][n_in] -> d_out float32 [rows][frames][>= n_out]: out[t][m] = sum over b ascending of fmaf(table[m][b], S[t][b], acc).
+    Applies any dense table: mfcc_table(...) gives MFCCs, mfcc_table(..., inverse=True) takes them back to the mel dB plane.
+    chunk_frames (0: the library's choice) never changes the result."""
+    a = _mfcc_args(d_S, d_table, d_out, chunk_frames)
+    check(lib().jsg_mfcc_launch(C.byref(a), _stream_handle(stream, d_S)))
+
+
+def mfcc_kernel_name(d_S, d_table, d_out, *, chunk_frames: int = 0) -> str:
+    """The path mfcc_launch takes for these arguments: "mfcc_block4", "mfcc_block5", "mfcc_block8", "mfcc_block10" or "mfcc_block16"."""
+    a = _mfcc_args(d_S, d_table, d_out, chunk_frames)
+    return _kernel_name(lib().jsg_mfcc_kernel_name, C.byref(a))
+
+
+def mfcc_plan(d_S, d_table, d_out, *, chunk_frames: int = 0):
+    """jsg_mfcc_plan: (path, frames per work item, bytes of LDS per workgroup) of mfcc_launch for these arguments.  Needs no device."""
+    a = _mfcc_args(d_S, d_table, d_out, chunk_frames)
+    name, frames, lds = C.create_string_buffer(32), C.c_int32(), C.c_int32()
+    check(lib().jsg_mfcc_plan(C.byref(a), name, 32, C.byref(frames), C.byref(lds)))
+    return name.value.decode(), frames.value, lds.value
+
+
+def delta_weights(width: int = 9, order: int = 1) -> np.ndarray:
+    """jsg_delta_weights_build: the Savitzky-Golay weights of the order-th derivative of a degree-order fit over `width` frames
+    (scipy.signal.savgol_filter(deriv=order, polyorder=order), what librosa.feature.delta uses), float32 [width], to be applied as
+    sum over j of w[j] * X[first frame of the window + j]."""
+    out = np.zeros(max(int(width), 1), dtype=np.float32)
+    check(lib().jsg_delta_weights_build(int(width), int(order), out.ctypes.data))
+    return out[:int(width)]
+
+
+def delta_launch(d_X, d_weights, d_out, *, mode: str = "interp", stream: int | None = None):
+    """jsg_delta_launch: d_X float32 [rows][frames][n_coeffs] (or one plane; views with pitches), d_weights float32 [width] -> d_out
+    float32 [rows][frames][>= n_coeffs]: the weighted sum over a window of `width` frames around every frame, j ascending.  mode
+    "interp": the window is shifted to stay inside the row (needs frames >= width); "nearest": frames outside repeat the edge."""
+    import torch
+    x = _plane(d_X, "d_X")
+    R, T, M = x.shape
+    assert d_weights.is_cuda and d_weights.dtype == torch.float32 and d_weights.dim() == 1 and d_weights.stride(0) == 1, "d_weights: float32 CUDA [width]"
+    o = _plane(d_out, "d_out")
+    assert o.shape[0] == R and o.shape[1] >= T and o.shape[2] >= M, "d_out: float32 CUDA [rows][>= frames][>= n_coeffs]"
+    a = capi.DeltaArgs(x.data_ptr(), x.stride(1), x.stride(0), R, M, T, d_weights.data_ptr(), d_weights.shape[0], _named(_EDGES, mode, "mode"),
+                       o.data_ptr(), o.stride(1), o.stride(0))
+    check(lib().jsg_delta_launch(C.byref(a), _stream_handle(stream, x)))
+
+
+def _cepstral_table(device, key, build):
+    """A host-built table on `device`, cached per (device, geometry) like _mel_cache."""
+    import torch
+    key = (_device_index(torch.empty(0, device=device)),) + key
+    if key not in _cepstral_cache:
+        _cepstral_cache[key] = torch.from_numpy(build()).to(device)
+    return _cepstral_cache[key]
+
+
+def _project(S, table_of):
+    import torch
+    s, was_numpy = _to_cuda(S)
+    assert s.dim() >= 2, "expected [..., frames, values]"
+    batch = tuple(s.shape[:-2])
+    sr = s.reshape(-1, s.shape[-2], s.shape[-1])
+    sr = sr if sr.stride(2) == 1 else sr.contiguous()
+    table = table_of(s.device, sr.shape[2])
+    out = torch.empty((sr.shape[0], sr.shape[1], table.shape[0]), dtype=torch.float32, device=s.device)
+    with torch.cuda.device(_device_index(s)):
+        mfcc_launch(sr, table, out)
+    out = out.reshape(*batch, sr.shape[1], table.shape[0])
+    return out.cpu().numpy() if was_numpy else out
+
+
+def mfcc(S, n_mfcc: int = 20, norm="ortho", lifter: float = 0.0):
+    """MFCCs of a log-mel plane S [..., frames, bands] (numpy array or float32 CUDA tensor; what mel_spectrogram_db returns) -> float32
+    [..., frames, n_mfcc], the same kind: the DCT-II (scipy.fft.dct type 2, norm) over the bands, first n_mfcc coefficients, times the
+    lifter of librosa.feature.mfcc.  Differs from librosa.feature.mfcc on purpose: the frames lie along axis -2 and the coefficients
+    along the last axis, and the lifter is folded into the table before its one rounding to float32.  Agreement with librosa was not
+    measured."""
+    M = int(n_mfcc)
+    return _project(S, lambda dev, B: _cepstral_table(dev, ("dct", B, M, norm, float(lifter)), lambda: mfcc_table(B, M, norm, lifter)))
+
+
+def mfcc_to_mel_db(C, n_mels: int = 128, norm="ortho", lifter: float = 0.0):
+    """The log-mel plane of MFCCs C [..., frames, n_mfcc] (numpy array or float32 CUDA tensor) -> float32 [..., frames, n_mels], the
+    same kind: the lifter divided out and the zero-padded inverse DCT (scipy.fft.idct type 2, n = n_mels), the first step of
+    librosa.feature.inverse.mfcc_to_mel (which goes on to power; this stays in dB).  Frames along axis -2; agreement with librosa was
+    not measured."""
+    B = int(n_mels)
+    return _project(C, lambda dev, M: _cepstral_table(dev, ("idct", B, M, norm, float(lifter)), lambda: mfcc_table(B, M, norm, lifter, inverse=True)))
+
+
+def delta(X, width: int = 9, order: int = 1, mode: str = "interp"):
+    """Delta features of X [..., frames, coefficients] (numpy array or float32 CUDA tensor) -> float32 of the same shape and kind: the
+    order-th Savitzky-Golay derivative along the frames over `width` frames (librosa.feature.delta: savgol_filter with polyorder =
+    deriv = order).  mode "interp" needs frames >= width; "nearest" repeats the edge frames.  Differs from librosa.feature.delta on
+    purpose: the frames lie along axis -2.  Agreement with librosa was not measured."""
+    import torch
+    x, was_numpy = _to_cuda(X)
+    assert x.dim() >= 2, "expected [..., frames, coefficients]"
+    xr = x.reshape(-1, x.shape[-2], x.shape[-1])
+    xr = xr if xr.stride(2) == 1 else xr.contiguous()
+    w = _cepstral_table(x.device, ("delta", int(width), int(order)), lambda: delta_weights(width, order))
+    out = torch.empty(xr.shape, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(_device_index(x)):
+        delta_launch(xr, w, out, mode=mode)
+    out = out.reshape(x.shape)
+    return out.cpu().numpy() if was_numpy else out
+
+
+def mfcc_audio(x, sr: float, n_mfcc: int = 20, n_fft: int = 2048, hop: int = 512, n_mels: int = 128, fmin: float = 0.0, fmax: float | None = None,
+               lifter: float = 0.0):
+    """MFCCs of audio x [samples] (numpy array or float32 CUDA tensor): mel_spectrogram_db -> mfcc (orthonormal DCT), on the GPU with
+    nothing returned to the host in between -> float32 [frames, n_mfcc], the same kind.  Differs from librosa.feature.mfcc on purpose:
+    the mel dB plane is 10 log10(power + 1e-11) without top_db clipping, the frames start at t * hop (no centring), they lie along axis
+    -2, and the lifter is folded into the table.  Agreement with librosa was not measured."""
+    import torch
+    xt, was_numpy = _to_cuda(x)
+    assert xt.dim() == 1, "mfcc_audio: x is one channel [samples]"
+    with torch.cuda.device(_device_index(xt)):
+        out = mfcc(mel_spectrogram_db(xt, sr, n_fft, hop, n_mels, fmin, fmax), n_mfcc, "ortho", lifter)
+    return out.cpu().numpy() if was_numpy else out
