@@ -430,6 +430,20 @@ constexpr bool kRunsNy0 = kRunsStore;   // (level on C2, -1 % on the C4 shard: n
 #else
 constexpr bool kRunsNy0 = false;
 #endif
+// Table and load trims of the runs kernel ("Runs tables"); same values, same operand order, same bits.  Each one is a
+// switch of variant builds (-DJSG_X_...=value), measured on its own on top of what was adopted before it; the defaults are the product's.
+#ifndef JSG_X_RUNS_WINREG     // window values of the LOWER frame half (wlo) held in registers for the wave's life: 0, 2 or 4 of the P/2 = 4 complex
+#define JSG_X_RUNS_WINREG 0   // pairs, i.e. 0 / 1 / 2 of a column's eight 16-byte lane-table reads (4: 90 / 92 of the 96 VGPRs of five waves per SIMD,
+#endif                        // no spill; +0.6 / +1.2 % on C2 / the C4 shard alone, level on top of the hint below, rounds overlap: not adopted)
+constexpr int kRunsWinReg = JSG_X_RUNS_WINREG;
+#ifndef JSG_X_RUNS_ONCETAB    // 1: the two register-resident tables (stage 1, post pass) by 16-byte loads from global memory (L2) instead of the
+#define JSG_X_RUNS_ONCETAB 0  // detour L2 -> LDS-DMA -> barrier -> ds_read: the LDS table block holds the window and stage-2 tables only
+#endif                        // (-0.9 / -0.5 % alone, level on top of the others: not adopted)
+constexpr bool kRunsOnceTab = JSG_X_RUNS_ONCETAB != 0;
+#ifndef JSG_X_RUNS_NT1        // 1: the hop that no other run reads -- the upper half of a run's FIRST frame -- loaded with the non-temporal hint
+#define JSG_X_RUNS_NT1 1      // (+3.4 / +4.3 %, every round ahead of every round without it on both geometries: the product's; 0 in variant builds)
+#endif
+constexpr bool kRunsNt1 = JSG_X_RUNS_NT1 != 0;
 
 template <int N_, int R1_, int R2_, int R3_, int L_, int S1_, int AX_, int AY_, int AZ_, int WPB_, int TLOC_, int WPS_,
           int FPW_ = 1, int EARLY1_ = 0, int TWF_ = 0, int PAIR_ = 0, int RTAB_ = 0>
@@ -774,7 +788,14 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
     a.xcd_remap = (k_flags >> 2) & 1; a.chunked = (k_flags >> 3) & 1; a.tab = k_tab; a.feedblocks = k_feedblocks;
     // Two distinct LDS objects on purpose: the (read-only) lane tables and the exchange buffers.  With one object
     // the compiler must assume that a table read may alias an exchange store and serialises them.
-    __shared__ __attribute__((aligned(16))) cf s_tab[C::TLOC == 1 ? C::TAB_ELEMS : 2];
+    // ONCETAB (runs, kRunsOnceTab): the stage-1 and post-pass tables never enter LDS (see "lane tables first" below): the block holds the window
+    // table at 0 and the stage-2 table at LT_TW2 -- moved down by whole bank sweeps (32 elements = 256 bytes) only, so that both tables keep the
+    // phase against the 64 banks that the plan's full block gives them.  Everywhere else LT_TW2 == Cfg::TAB_TW2.
+    constexpr bool ONCETAB = kRunsOnceTab && STREAM == 2 && JSG_RTAB_OF(C, MIXOP, OUTK);
+    constexpr int LT_TW2 = ONCETAB ? C::P * C::TL + (C::TAB_TW2 - C::TAB_TW1) % 32 : C::TAB_TW2;
+    constexpr int LT_ELEMS = ONCETAB ? LT_TW2 + C::P * C::TL : C::TAB_ELEMS;
+    static_assert((C::TAB_TW2 - LT_TW2) % 32 == 0 && LT_TW2 % 2 == 0, "the stage-2 table keeps its bank phase and its 16-byte alignment");
+    __shared__ __attribute__((aligned(16))) cf s_tab[C::TLOC == 1 ? LT_ELEMS : 2];
     __shared__ int s_lut[OUTK == 2 ? 256 : 1];
     static_assert(OUTK != 2 || (C::L == 64 && C::FPW == 1 && C::LDS_TOTAL + 1024 <= 160 * 1024), "single-kernel display path: one wavefront per frame");
     constexpr bool BAT = STREAM != 0;   // rows (batches, or batch x channel) numbered through the launch
@@ -975,12 +996,52 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
         const long long start = (long long)(a.first_frame + nx_col0) * a.hop + rn_in + (long long)c0 * a.in_pitch;
         return reinterpret_cast<const f2u*>(a.in + start) + ll;
     };
+    // A load of the hop that is read ONCE on the whole chip.  With run length 2 the run of columns (c, c + 1) reads hops c, c + 1 and c + 2: the
+    // even hops c and c + 2 are shared with the neighbouring runs, the odd hop c + 1 -- the upper half of the run's first frame -- is nobody
+    // else's.  kRunsNt1: that one takes the non-temporal hint (same instruction, 8 bytes of 4-byte alignment); the shared hops stay plain.
+    auto load_once = [](const f2u* p) -> f2u {
+        if constexpr (kRunsNt1) {
+            typedef float cf_a4 __attribute__((ext_vector_type(2), aligned(4)));
+            const cf v = __builtin_nontemporal_load(reinterpret_cast<const cf_a4*>(p));
+            return f2u{v.x, v.y};
+        } else return *p;
+    };
     // ---- lane tables first: two 16-byte LDS-DMA pieces per thread bring the tables from L2 straight into LDS (wave-uniform
     //      base + lane * 16 bytes, no VGPR round trip).  They are issued AHEAD of the frame loads: every wave's FFT start is
     //      gated by the workgroup barrier behind the tables, so they are the latency-critical load (frame loads first, or
     //      half of them first, measured 0.3-0.5 us slower per C2 launch) ----
     constexpr int NTL = C::TLOC == 1 ? (C::TAB_ELEMS / 2 + C::WPB * 64 - 1) / (C::WPB * 64) : 1;   // 16-byte pieces per thread
     constexpr bool TAB_EVEN = (C::TAB_ELEMS / 2) % (C::WPB * 64) == 0;
+    // RTAB: stage-1 row and post-pass twiddles of this lane, read once and held in registers
+    constexpr bool RTAB = JSG_RTAB_OF(C, MIXOP, OUTK);
+    cf rt1[RTAB ? R1 : 1], rpost[RTAB ? P / 2 : 1];
+    if constexpr (ONCETAB) {
+        // ... straight from the plan's table in global memory (resident in L2: every workgroup of every dispatch reads it), as 16-byte loads
+        // issued AHEAD of the table pieces: the counted wait in front of the barrier below retires them with the pieces, and what follows it is
+        // still the frame loads alone.  The LDS block shrinks to the two tables the rounds read: one piece per thread and table.
+        static_assert(!ONCETAB || (U1 == 1 && !C::TWF && !C::PAIR && C::TLOC == 1 && (P * C::TL / 2) == C::WPB * 64), "one 16-byte piece per thread and table");
+        const v4f* const g4 = reinterpret_cast<const v4f*>(a.tab);
+        const v4f* const g1 = g4 + (C::TAB_TW1 + (ll / R3) * C::TS1) / 2;
+#pragma unroll
+        for (int k1 = 1; k1 < R1; k1 += 2) {
+            const v4f q4 = g1[(k1 - 1) / 2];
+            rt1[k1] = cf{q4.x, q4.y};
+            if (k1 + 1 < R1) rt1[k1 + 1] = cf{q4.z, q4.w};
+        }
+#pragma unroll
+        for (int rho = 0; rho < P / 2; rho += 2) {
+            const v4f q4 = g4[(C::TAB_POST + C::tab_idx(rho, tl)) / 2];
+            rpost[rho] = cf{q4.x, q4.y};
+            rpost[rho + 1] = cf{q4.z, q4.w};
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        char* sbase = reinterpret_cast<char*>(s_tab) + wave * 1024;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g4 + C::TAB_WIN / 2 + threadIdx.x),
+                                         (__attribute__((address_space(3))) void*)sbase, 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g4 + C::TAB_TW2 / 2 + threadIdx.x),
+                                         (__attribute__((address_space(3))) void*)(sbase + LT_TW2 * 8), 16, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    } else
     if constexpr (C::TLOC == 1) {
         const v4f* g4 = reinterpret_cast<const v4f*>(a.tab) + threadIdx.x;
         char* sbase = reinterpret_cast<char*>(s_tab) + wave * 1024;
@@ -999,7 +1060,7 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
 #pragma unroll
         for (int m = 0; m < P / 2; ++m) rw[0][m] = src[L * m];
 #pragma unroll
-        for (int m = 0; m < P / 2; ++m) rw[1][m] = src[L * (m + P / 2)];
+        for (int m = 0; m < P / 2; ++m) rw[1][m] = load_once(src + L * (m + P / 2));
         __builtin_amdgcn_sched_barrier(0);
     } else {
 #pragma unroll
@@ -1035,8 +1096,11 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
 #pragma unroll
     for (int u = 0; u < U1; ++u) tw1row[u] = ((ll + L * u) / R3) * C::TS1;
     // RTAB: stage-1 row and post-pass twiddles of this lane, read once (the tables are in LDS behind the barrier above)
-    constexpr bool RTAB = JSG_RTAB_OF(C, MIXOP, OUTK);
-    cf rt1[RTAB ? R1 : 1], rpost[RTAB ? P / 2 : 1];
+    if constexpr (ONCETAB) {
+        // (they came from global memory ahead of the table pieces and are retired by the counted wait above.  The compiler does not know that,
+        // but it needs no wait of its own for them either: they are older than the first frame's loads, and its wait for those -- at the window
+        // multiply of round 0, ahead of the first prefetch -- covers them.  Touching them here instead put a vmcnt(0) right behind the barrier.)
+    } else
     if constexpr (RTAB) {
         static_assert(!RTAB || (U1 == 1 && !C::TWF && !C::PAIR && C::TLOC == 1), "register tables: one stage-1 butterfly per lane, whole tables in LDS");
 #pragma unroll
@@ -1058,6 +1122,14 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
         a0 = cf{q4.x, q4.y};
         a1 = cf{q4.z, q4.w};
     };
+    // runs, kRunsWinReg: the first WR window values of the lower frame half stay in registers (read here, behind the table barrier)
+    constexpr int WR = RUNS ? kRunsWinReg : 0;
+    static_assert(WR % 2 == 0 && WR >= 0 && WR <= P / 2, "whole 16-byte pairs of the lower half");
+    cf rwin[WR ? WR : 1];
+    if constexpr (WR > 0) {
+#pragma unroll
+        for (int m = 0; m < WR; m += 2) tab2(C::TAB_WIN, m, rwin[m], rwin[m + 1]);
+    }
     // exchange synchronisation: lock-step lanes of one wave need only a compiler fence; frames that span several
     // waves (L > 64) need the workgroup barrier (every wave of the workgroup runs the same number of them)
     auto frame_sync = [&]() {
@@ -1125,7 +1197,8 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
 #pragma unroll
         for (int m = 0; m < P; m += 2) {
             cf w0, w1;
-            tab2(C::TAB_WIN, m, w0, w1);
+            if (m < WR) { w0 = rwin[m < WR ? m : 0]; w1 = rwin[m < WR ? m + 1 : 0]; }
+            else tab2(C::TAB_WIN, m, w0, w1);
             static_assert((P / 2) % 2 == 0 || P == 2, "the window pairs do not straddle the halves");
 #pragma unroll
             for (int f = 0; f < F; ++f) {
@@ -1201,7 +1274,7 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
 #pragma unroll
                 for (int m = 0; m < P / 2; ++m) rw[PAR ^ 1][m] = src[L * m];
 #pragma unroll
-                for (int m = 0; m < P / 2; ++m) rw[PAR][m] = src[L * (m + P / 2)];
+                for (int m = 0; m < P / 2; ++m) rw[PAR][m] = load_once(src + L * (m + P / 2));
             }
         } else
         if (!LAST) {   // the next round's frames travel while this one is transformed
@@ -1311,7 +1384,7 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
                         const v4f q4 = *reinterpret_cast<const v4f*>(tBase + twBrow + k2);
                         w0 = cmul(cf{q4.x, q4.y}, twA[v]);
                         w1 = cmul(cf{q4.z, q4.w}, twA[v]);
-                    } else tab2(C::TAB_TW2, v * R2 + k2, w0, w1);
+                    } else tab2(LT_TW2, v * R2 + k2, w0, w1);
 #pragma unroll
                     for (int f = 0; f < F; ++f) {
                         lds0[f * C::LDS_ELEMS + e2w[v] + k2 * C::AY] = cmul(t[f][k2], w0);
