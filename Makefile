@@ -52,13 +52,16 @@ $(OBJ)/jsg_rhythm.o: $(SRC)/jsg_rhythm.hip $(SRC)/jsg_internal.h include/jsg.h
 $(OBJ)/jsg_cepstral.o: $(SRC)/jsg_cepstral.hip $(SRC)/jsg_internal.h include/jsg.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(OBJ)/jsg_spectral.o: $(SRC)/jsg_spectral.hip $(SRC)/jsg_internal.h $(SRC)/jsg_exact_math.h include/jsg.h
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(OBJ)/%.o: $(SRC)/%.cpp $(SRC)/jsg_internal.h $(SRC)/jsg_block_queue.h $(SRC)/jsg_exact_math.h $(SRC)/jsg_colormap_tables.inc include/jsg.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude -ffp-contract=off -D__HIP_PLATFORM_AMD__ -c $< -o $@
 
-$(OUT): $(OBJ)/jsg_kernels.o $(OBJ)/jsg_stft_a.o $(OBJ)/jsg_stft_b.o $(OBJ)/jsg_filterbank.o $(OBJ)/jsg_display_axis.o $(OBJ)/jsg_cstft.o $(OBJ)/jsg_pvoc.o $(OBJ)/jsg_hpss.o $(OBJ)/jsg_resample.o $(OBJ)/jsg_cqt.o $(OBJ)/jsg_yin.o $(OBJ)/jsg_rhythm.o $(OBJ)/jsg_cepstral.o $(OBJ)/jsg_engine.o \
-        $(OBJ)/jsg_host_math.o $(OBJ)/jsg_filterbank_host.o $(OBJ)/jsg_display_axis_host.o $(OBJ)/jsg_cqt_host.o $(OBJ)/jsg_yin_host.o $(OBJ)/jsg_rhythm_host.o $(OBJ)/jsg_cepstral_host.o
+$(OUT): $(OBJ)/jsg_kernels.o $(OBJ)/jsg_stft_a.o $(OBJ)/jsg_stft_b.o $(OBJ)/jsg_filterbank.o $(OBJ)/jsg_display_axis.o $(OBJ)/jsg_cstft.o $(OBJ)/jsg_pvoc.o $(OBJ)/jsg_hpss.o $(OBJ)/jsg_resample.o $(OBJ)/jsg_cqt.o $(OBJ)/jsg_yin.o $(OBJ)/jsg_rhythm.o $(OBJ)/jsg_cepstral.o $(OBJ)/jsg_spectral.o $(OBJ)/jsg_engine.o \
+        $(OBJ)/jsg_host_math.o $(OBJ)/jsg_filterbank_host.o $(OBJ)/jsg_display_axis_host.o $(OBJ)/jsg_cqt_host.o $(OBJ)/jsg_yin_host.o $(OBJ)/jsg_rhythm_host.o $(OBJ)/jsg_cepstral_host.o $(OBJ)/jsg_spectral_host.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^
 
 oracle:

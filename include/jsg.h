@@ -53,7 +53,8 @@ extern "C" {
                                  the band launch query (jsg_fb_band_plan; section 2b),
                                  YIN fundamental-frequency tracking (jsg_yin_*; section 2i),
                                  onset strength, autocorrelation tempogram and tempo (jsg_onset_*, jsg_tempogram_*, jsg_tempo_*; section 2j),
-                                 cepstral coefficients and delta features (jsg_mfcc_*, jsg_delta_*; section 2k) */
+                                 cepstral coefficients and delta features (jsg_mfcc_*, jsg_delta_*; section 2k),
+                                 spectral shape descriptors (jsg_spectral_shape_*; section 2l) */
 
 typedef enum jsg_status {
     JSG_OK = 0,
@@ -1107,6 +1108,104 @@ typedef struct jsg_delta_args {
  * below (T-1)*out_frame_pitch + n_coeffs (rows > 1), out overlapping in or weights.  Then JSG_ERR_NO_DEVICE without a HIP device.
  * Every call that passes is served. */
 JSG_API int jsg_delta_launch(const jsg_delta_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2l. Spectral shape descriptors: energy, centroid, spread, rolloff, flatness and crest of every frame of a [frames][bins] plane
+ *     (the power plane of jsg_stft_db_launch with linear_out, a mel plane of jsg_stft_fb_launch, a power plane of jsg_cqt_launch),
+ *     one kernel that reads the plane once and writes a few floats per frame.  All arithmetic is float32, denormals are kept; no
+ *     result depends on the row, the frame index, the number of rows or frames, the pitches, the grid, the path
+ *     jsg_spectral_shape_plan names or which outputs are NULL.
+ *
+ *     Input.  Rows S[r][t][k] at in[r*row_pitch + t*frame_pitch + k], t = 0..T-1, k = 0..K-1 (K = n_bins), and a table f[0..K) of
+ *     frequencies (the Hz of FFT bins, mel or CQT centres, anything), the same for every row; roll_percent p in (0, 1].  S is
+ *     non-negative; negative values are outside the contract, but even then nothing outside the T x K elements of a row and the K
+ *     of the table is read, and no index leaves [0, K).
+ *
+ *     The lane sum (the rule of section 2j).  W = 64 where K > 32, else the smallest power of two >= K.  Lane l of W takes
+ *     k = l, l + W, l + 2W, ... ascending, from acc_l = +0; then a halving tree: for s = W/2, W/4, ..., 1:
+ *     acc_l = acc_l + acc_(l+s) for l < s; the sum is acc_0.  Per frame:
+ *         E  = lane sum with  acc = acc + S[k]
+ *         N1 = lane sum with  acc = fmaf(f[k], S[k], acc)
+ *         mx = +0;  then  mx = v  where  v > mx  or  v is NaN  (a NaN stays; for non-NaN values the largest S[k], in any order)
+ *         L  = lane sum with  acc = acc + dB(S[k])          (dB(p) = 10 log10(p + 1e-11f) by the shared routine jsg_exact_db of
+ *                                                              csrc/jsg_exact_math.h: bit-reproducible on a CPU)
+ *         centroid = N1 / E, the divide correctly rounded
+ *         M2 = lane sum with  d = f[k] - centroid;  acc = fmaf(fl(d*d), S[k], acc)
+ *         spread = sqrt(M2 / E), the divide and the square root correctly rounded      (librosa's spectral_bandwidth with p = 2)
+ *         crest = mx / (E / (float)K)
+ *         flatness_db = L / (float)K - dB(E / (float)K)     (10 log10 of geometric over arithmetic mean, the floor
+ *                       1e-11f inside each logarithm; no exponential runs on the device, the linear value is 10^(flatness_db/10))
+ *     Where E == 0: centroid, spread and crest are +0; flatness_db is what its chain gives.
+ *
+ *     Rolloff.  A prefix sum in a stated order, so that "the first bin" is defined.  Chunk j holds the W bins jW .. jW+W-1, bins
+ *     past K count as +0.  Within a chunk, an inclusive scan: x_l = S[jW + l];  for s = 1, 2, 4, ..., W/2: every lane l >= s does
+ *     x_l = x_l + x_(l-s), reading the values of the step before.  cum[jW + l] = base_j + x_l;  base_0 = +0,
+ *     base_(j+1) = base_j + x_(W-1) of chunk j.
+ *         thr = fl(p * cum[K-1]);   k* = the lowest k in [0, K) with cum[k] >= thr
+ *         rolloff = f[k*],  rolloff_bin = k*
+ *     k* is the first in ascending k: cum is not assumed to be monotone, and the bin is searched, not the frequency (f need not
+ *     ascend).  For finite non-negative input k* exists, since thr <= cum[K-1]; where no k qualifies (possible only outside the
+ *     contract) k* = K-1.  An all-zero frame gives k* = 0.
+ *
+ *     NaN and infinity.  A NaN at S[t0][k0] makes every float output of frame t0 of that row NaN and rolloff_bin -1, and touches
+ *     no other frame: the sums carry it, mx keeps it by the rule above (a plain > would drop it), and for the rolloff: where thr
+ *     is NaN (cum[K-1] carries every bin), rolloff = NaN and rolloff_bin = -1 (every comparison with a NaN is false).  A +inf
+ *     gives what the chains give (energy +inf, centroid NaN from inf/inf, k* at the first infinite cum).
+ *
+ *     Outputs, each optional, each [rows][T] at out[r*out_pitch + t] with one shared out_pitch: energy (E), centroid, spread,
+ *     rolloff, rolloff_bin (int32), flatness_db, crest.  A NULL output does not cost its separable work: without rolloff and
+ *     rolloff_bin no scan runs, without flatness_db no logarithm, without spread no second pass, without centroid and spread no N1.
+ *
+ *     Against the same sums in float64 on the float32 inputs, with u = 2^-24, n = ceil(K/W) + log2 W (every term non-negative, so
+ *     the bounds are relative; one rounding per add or fmaf, the first of a lane exact; products that do not underflow):
+ *         |E - E64| <= (n + 1) u E64          |N1 - N164| <= (n + 1) u N164   (f >= 0)
+ *         |centroid - centroid64| <= (2n + 4) u centroid64   (f >= 0: both sums and the divide)
+ *     The spread is ill-conditioned where the spectrum is narrow (d = f - centroid cancels): no bound is given; its measured error
+ *     is in profiles/spectral_accuracy.md.
+ *
+ *     Differences from librosa.feature.spectral_centroid / spectral_bandwidth / spectral_rolloff / spectral_flatness, on purpose:
+ *     the plane is taken as it is (the Python layer's default is power, librosa's magnitude); the frames lie along axis -2; the
+ *     floor inside the logarithms is 1e-11 (librosa: amin = 1e-10); no centring of frames.  Agreement with librosa has not been
+ *     measured.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSG_SPECTRAL_MAX_BINS 65536
+typedef struct jsg_spectral_args {
+    const float* in;            /* device floats: S[r][t][k] at in[r*row_pitch + t*frame_pitch + k] */
+    int64_t frame_pitch;        /* floats between frames, >= n_bins */
+    int64_t row_pitch;          /* rows > 1: >= (T-1)*frame_pitch + n_bins */
+    int32_t rows;               /* 1..65535, independent */
+    int32_t n_bins;             /* K, 1..JSG_SPECTRAL_MAX_BINS */
+    int64_t n_frames;           /* T, 1..2^31-1 */
+    const float* freqs;         /* device floats: f[0..K) */
+    float roll_percent;         /* p, in (0, 1] */
+    int32_t reserved0;          /* ignored */
+    float* energy;              /* each output: device floats [rows][T] at out[r*out_pitch + t], or NULL */
+    float* centroid;
+    float* spread;
+    float* rolloff;
+    int32_t* rolloff_bin;       /* device int32, same layout, or NULL */
+    float* flatness_db;
+    float* crest;
+    int64_t out_pitch;          /* rows > 1: >= n_frames; shared by all outputs */
+} jsg_spectral_args;
+/* Enqueue only (one kernel, no scratch): no allocation, no synchronisation; hipGraph capture works, a first launch included.  Refused
+ * (JSG_ERR_INVALID, nothing enqueued, jsg_last_error set), in this order and before any device call: null args, a null in, a null
+ * freqs, all outputs null, a pointer that is not 4-byte aligned, rows outside 1..65535, n_bins outside 1..65536, n_frames outside
+ * 1..2^31-1, a roll_percent that is not in (0, 1] (NaN included), frame_pitch below n_bins, row_pitch below
+ * (T-1)*frame_pitch + n_bins (rows > 1), out_pitch below n_frames (rows > 1), an output overlapping in or freqs.  Then
+ * JSG_ERR_NO_DEVICE without a HIP device.  Every call that passes is served. */
+JSG_API int jsg_spectral_shape_launch(const jsg_spectral_args* args, void* stream);
+/* What the launch would do, without a device: the path, by n_bins alone -- "spectral_regs1", "spectral_regs2", "spectral_regs4",
+ * "spectral_regs9", "spectral_regs17", "spectral_regs33" or "spectral_regs65": a lane keeps its ceil(K/W) values of a frame (at most
+ * the number in the name: K <= 64 times it) in registers between the passes, so the plane crosses memory once; "spectral_stream"
+ * (K > 4160): the second pass re-reads the frame through the caches -- the lanes that own a frame (W) and the frames a group of W
+ * lanes has in flight at a time (a workgroup of 256 threads takes 256/W times as many consecutive frames per step of its grid
+ * stride), and the bytes of LDS a workgroup asks for (0: the frequency table of the register paths sits in registers, loaded once
+ * per workgroup).  Any output pointer may be NULL (name: else name_len >= 24).  Refused: what the launch refuses. */
+JSG_API int jsg_spectral_shape_plan(const jsg_spectral_args* args, char* name, int name_len, int32_t* lanes_per_frame, int32_t* frames_per_group,
+                                    int32_t* lds_bytes);
+/* The path of jsg_spectral_shape_plan (out_len >= 24).  The refusals of the launch; no device is needed. */
+JSG_API int jsg_spectral_shape_kernel_name(const jsg_spectral_args* args, char* out, int out_len);
 
 /* ------------------------------------------------------------------------------------------------
  * 3. Engine: the state of class Spectrogram (Spectrogram.h:81-169) living on the GPU.

@@ -16,7 +16,9 @@ from .spectrogram import (CColorPalette, Filterbank, FreqAxis, Plan, Spectrogram
                           yin, yin_cmnd, yin_frames, yin_kernel_name, yin_launch, yin_plan,
                           estimate_tempo, onset_strength, onset_strength_launch, tempo, tempo_launch, tempo_prior, tempogram, tempogram_frames,
                           tempogram_kernel_name, tempogram_launch, tempogram_plan,
-                          delta, delta_launch, delta_weights, mfcc, mfcc_audio, mfcc_kernel_name, mfcc_launch, mfcc_plan, mfcc_table, mfcc_to_mel_db)
+                          delta, delta_launch, delta_weights, mfcc, mfcc_audio, mfcc_kernel_name, mfcc_launch, mfcc_plan, mfcc_table, mfcc_to_mel_db,
+                          fft_frequencies, spectral_bandwidth, spectral_centroid, spectral_crest, spectral_flatness, spectral_rolloff, spectral_shape,
+                          spectral_shape_audio, spectral_shape_kernel_name, spectral_shape_launch, spectral_shape_plan)
 
 __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_db", "colormap", "window", "colormap_lut",
            "colormap_range", "feed_samples", "memsize_blocks", "next_power_of_2", "JsgError", "capi",
@@ -29,4 +31,6 @@ __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_d
            "yin_frames", "yin_launch", "yin_plan", "yin_kernel_name", "yin", "yin_cmnd",
            "onset_strength", "onset_strength_launch", "tempogram", "tempogram_launch", "tempogram_frames", "tempogram_plan", "tempogram_kernel_name",
            "tempo_prior", "tempo_launch", "tempo", "estimate_tempo",
-           "mfcc_table", "mfcc_launch", "mfcc_plan", "mfcc_kernel_name", "delta_weights", "delta_launch", "mfcc", "mfcc_to_mel_db", "delta", "mfcc_audio"]
+           "mfcc_table", "mfcc_launch", "mfcc_plan", "mfcc_kernel_name", "delta_weights", "delta_launch", "mfcc", "mfcc_to_mel_db", "delta", "mfcc_audio",
+           "spectral_shape_launch", "spectral_shape_plan", "spectral_shape_kernel_name", "fft_frequencies", "spectral_shape", "spectral_centroid",
+           "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "spectral_crest", "spectral_shape_audio"]

@@ -37,6 +37,7 @@ YIN_MAX_WINDOW, YIN_MAX_LAG = 8192, 8192
 ONSET_MAX_BANDS, ONSET_MAX_LAG, ONSET_MAX_SIZE, TEMPOGRAM_MAX_WINDOW = 65536, 4096, 255, 4096
 MFCC_MAX_BANDS, MFCC_MAX_COEFFS, MFCC_MAX_TABLE, DCT_NORM_NONE, DCT_NORM_ORTHO = 4096, 4096, 32768, 0, 1
 DELTA_MAX_WIDTH, DELTA_MAX_ORDER, DELTA_MAX_COEFFS, DELTA_EDGE_INTERP, DELTA_EDGE_NEAREST = 255, 4, 65536, 0, 1
+SPECTRAL_MAX_BINS = 65536
 
 
 class JsgError(RuntimeError):
@@ -148,6 +149,13 @@ class DeltaArgs(C.Structure):
                 ("out_frame_pitch", C.c_int64), ("out_row_pitch", C.c_int64)]
 
 
+class SpectralArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("frame_pitch", C.c_int64), ("row_pitch", C.c_int64), ("rows", C.c_int32), ("n_bins", C.c_int32),
+                ("n_frames", C.c_int64), ("freqs", C.c_void_p), ("roll_percent", C.c_float), ("reserved0", C.c_int32), ("energy", C.c_void_p),
+                ("centroid", C.c_void_p), ("spread", C.c_void_p), ("rolloff", C.c_void_p), ("rolloff_bin", C.c_void_p), ("flatness_db", C.c_void_p),
+                ("crest", C.c_void_p), ("out_pitch", C.c_int64)]
+
+
 class StftImageArgs(C.Structure):
     _fields_ = [("stft", StftArgs), ("colour", ColormapArgs), ("index_scratch", C.c_void_p), ("index_scratch_pitch", C.c_int64)]
 
@@ -248,6 +256,9 @@ SIGNATURES = {
     "jsg_mfcc_table_build": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P]),
     "jsg_delta_weights_build": (C.c_int, [C.c_int32, C.c_int32, _P]),
     "jsg_delta_launch": (C.c_int, [C.POINTER(DeltaArgs), _P]),
+    "jsg_spectral_shape_launch": (C.c_int, [C.POINTER(SpectralArgs), _P]),
+    "jsg_spectral_shape_plan": (C.c_int, [C.POINTER(SpectralArgs), C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "jsg_spectral_shape_kernel_name": (C.c_int, [C.POINTER(SpectralArgs), C.c_char_p, C.c_int]),
     "jsg_create": (C.c_int, [C.POINTER(_P), C.c_int]),
     "jsg_create_on_device": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int]),
     "jsg_get_device": (C.c_int, [_P]),

@@ -135,6 +135,19 @@ void mfcc_resolve(const jsg_mfcc_args* g, MfccPlan* p);
 const char* mfcc_path_name(const MfccPlan& p);
 int delta_check(const jsg_delta_args* g, const char* who);
 
+// jsg_spectral_host.cpp: the refusals of section 2l and how a call that passes is served (jsg_spectral.hip launches by it).  A group
+// of W lanes owns a frame and has FK frames in flight; a workgroup takes FK * 256 / W consecutive frames of a row per step.  NC > 0:
+// the register path whose lanes hold up to NC values of a frame (K <= 64 NC); NC == 0: the streaming path.  By K alone.
+constexpr int kSpThreads = 256;
+constexpr int kSpMaxRegs = 65;              // values of a frame a lane keeps at most: the 4097 bins of an 8192-point transform
+struct SpectralPlan {
+    int NC, FK, W;
+    long long groups;          // ceil(T / (FK * 256 / W)) work items per row
+};
+int spectral_check(const jsg_spectral_args* g, const char* who);
+void spectral_resolve(const jsg_spectral_args* g, SpectralPlan* p);
+const char* spectral_path_name(const SpectralPlan& p);
+
 // Slaney's mel scale (librosa.filters.mel, htk = False): linear below 1 kHz (200/3 Hz per mel), logarithmic above (27 mels per
 // factor 6.4).  Shared by the MEL_SLANEY filterbank and the MEL display axis.
 inline double slaney_logstep() { return std::log(6.4) / 27.0; }

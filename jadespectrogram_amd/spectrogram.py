@@ -1841,3 +1841,177 @@ def mfcc_audio(x, sr: float, n_mfcc: int = 20, n_fft: int = 2048, hop: int = 512
     with torch.cuda.device(_device_index(xt)):
         out = mfcc(mel_spectrogram_db(xt, sr, n_fft, hop, n_mels, fmin, fmax), n_mfcc, "ortho", lifter)
     return out.cpu().numpy() if was_numpy else out
+
+
+# --------------------------------------------------------------------------------------------------
+# spectral shape descriptors (include/jsg.h, section 2l)
+# --------------------------------------------------------------------------------------------------
+_SHAPE_OUTPUTS = ("energy", "centroid", "spread", "rolloff", "rolloff_bin", "flatness_db", "crest")
+_shape_plan_cache: dict = {}
+
+
+def _spectral_args(d_S, d_freqs, outs: dict, roll_percent: float) -> capi.SpectralArgs:
+    import torch
+    s = _plane(d_S, "d_S")
+    R, T, K = s.shape
+    assert d_freqs.is_cuda and d_freqs.dtype == torch.float32 and d_freqs.dim() == 1 and d_freqs.stride(0) == 1 and d_freqs.shape[0] >= K, \
+        "d_freqs: float32 CUDA [>= bins]"
+    ptrs, pitch = {}, None
+    for name in _SHAPE_OUTPUTS:
+        o = outs.get(name)
+        if o is None:
+            ptrs[name] = None
+            continue
+        o = o[None] if o.dim() == 1 else o
+        want = torch.int32 if name == "rolloff_bin" else torch.float32
+        assert o.is_cuda and o.dtype == want and o.dim() == 2 and o.stride(1) == 1 and o.shape[0] == R and o.shape[1] >= T, \
+            f"d_{name}: {'int32' if name == 'rolloff_bin' else 'float32'} CUDA [rows][>= frames]"
+        assert R == 1 or pitch is None or pitch == o.stride(0), "the outputs share one row pitch"
+        pitch = o.stride(0)
+        ptrs[name] = o.data_ptr()
+    return capi.SpectralArgs(s.data_ptr(), s.stride(1), s.stride(0), R, K, T, d_freqs.data_ptr(), float(roll_percent), 0, ptrs["energy"], ptrs["centroid"],
+                             ptrs["spread"], ptrs["rolloff"], ptrs["rolloff_bin"], ptrs["flatness_db"], ptrs["crest"], pitch or 0)
+
+
+def spectral_shape_launch(d_S, d_freqs, *, d_energy=None, d_centroid=None, d_spread=None, d_rolloff=None, d_rolloff_bin=None, d_flatness_db=None,
+                          d_crest=None, roll_percent: float = 0.85, stream: int | None = None):
+    """jsg_spectral_shape_launch: d_S float32 [rows][frames][bins] (or one [frames][bins] plane; views with pitches), non-negative, and
+    d_freqs float32 [bins] -> per frame, each output float32 [rows][>= frames] (d_rolloff_bin: int32) or None, with one shared row pitch:
+    the energy (sum over the bins), the centroid (sum f S / sum S), the spread (sqrt of sum (f - centroid)^2 S / sum S), the rolloff (f at
+    the first bin whose prefix sum reaches roll_percent of the total) and its bin, flatness_db (10 log10 of geometric over arithmetic
+    mean, 1e-11 inside each logarithm) and the crest (largest bin over the mean).  One kernel that reads the plane once; an output that
+    is None does not cost its separable work.  The summation orders are those of include/jsg.h section 2l."""
+    outs = dict(energy=d_energy, centroid=d_centroid, spread=d_spread, rolloff=d_rolloff, rolloff_bin=d_rolloff_bin, flatness_db=d_flatness_db, crest=d_crest)
+    a = _spectral_args(d_S, d_freqs, outs, roll_percent)
+    check(lib().jsg_spectral_shape_launch(C.byref(a), _stream_handle(stream, d_S)))
+
+
+def spectral_shape_kernel_name(d_S, d_freqs, *, roll_percent: float = 0.85, **outs) -> str:
+    """The path spectral_shape_launch takes for these arguments (d_energy= ... as there): "spectral_regs1" ... "spectral_regs65" (a
+    lane keeps its share of a frame in registers between the passes) or "spectral_stream", by the number of bins alone."""
+    a = _spectral_args(d_S, d_freqs, {k[2:]: v for k, v in outs.items()}, roll_percent)
+    return _kernel_name(lib().jsg_spectral_shape_kernel_name, C.byref(a))
+
+
+def spectral_shape_plan(d_S, d_freqs, *, roll_percent: float = 0.85, **outs):
+    """jsg_spectral_shape_plan: (path, lanes per frame, frames a group of lanes has in flight, bytes of LDS per workgroup) of
+    spectral_shape_launch for these arguments (d_energy= ... as there).  A workgroup takes frames * 256 / lanes consecutive frames per
+    step.  Needs no device."""
+    a = _spectral_args(d_S, d_freqs, {k[2:]: v for k, v in outs.items()}, roll_percent)
+    name, lanes, frames, lds = C.create_string_buffer(32), C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib().jsg_spectral_shape_plan(C.byref(a), name, 32, C.byref(lanes), C.byref(frames), C.byref(lds)))
+    return name.value.decode(), lanes.value, frames.value, lds.value
+
+
+def fft_frequencies(sr: float, n_fft: int) -> np.ndarray:
+    """The centre frequencies k * sr / n_fft of the n_fft / 2 + 1 bins of an n_fft-point transform (librosa.fft_frequencies), computed
+    in double and rounded to float32 once."""
+    n = int(n_fft)
+    return (np.arange(n // 2 + 1, dtype=np.float64) * float(sr) / n).astype(np.float32)
+
+
+def _shape_freqs(s, freqs, sr):
+    """The frequency table of a plane s [..., frames, bins] on its device: `freqs` (any array of bins floats), else the FFT bins of sr."""
+    import torch
+    K = s.shape[-1]
+    if freqs is None:
+        if sr is None:
+            raise JsgError(capi.JSG_ERR_INVALID, "spectral_shape: give freqs (one frequency per bin) or sr (the plane is then taken as FFT bins)")
+        return _cepstral_table(s.device, ("fft_frequencies", float(sr), 2 * (K - 1)), lambda: fft_frequencies(sr, 2 * (K - 1)) if K > 1 else np.zeros(1, np.float32))
+    f = freqs if hasattr(freqs, "is_cuda") else torch.from_numpy(np.ascontiguousarray(freqs, dtype=np.float32))
+    f = f.to(device=s.device, dtype=torch.float32).contiguous()
+    assert f.dim() == 1 and f.shape[0] == K, "freqs: one frequency per bin"
+    return f
+
+
+def _shape(S, freqs, sr, roll_percent, names):
+    """The outputs `names` of one launch over S [..., frames, bins]: a dict of [..., frames] arrays of the kind of S."""
+    import torch
+    s, was_numpy = _to_cuda(S)
+    assert s.dim() >= 2, "expected [..., frames, bins]"
+    batch = tuple(s.shape[:-2])
+    sr3 = s.reshape(-1, s.shape[-2], s.shape[-1])
+    sr3 = sr3 if sr3.stride(2) == 1 else sr3.contiguous()
+    f = _shape_freqs(s, freqs, sr)
+    outs = {n: torch.empty((sr3.shape[0], sr3.shape[1]), dtype=torch.int32 if n == "rolloff_bin" else torch.float32, device=s.device) for n in names}
+    with torch.cuda.device(_device_index(s)):
+        spectral_shape_launch(sr3, f, roll_percent=roll_percent, **{"d_" + n: o for n, o in outs.items()})
+    outs = {n: o.reshape(*batch, sr3.shape[1]) for n, o in outs.items()}
+    if "flatness_db" in outs:
+        outs["flatness"] = torch.pow(10.0, outs["flatness_db"] / 10.0)
+    return {n: (o.cpu().numpy() if was_numpy else o) for n, o in outs.items()}
+
+
+def spectral_shape(S, freqs=None, sr=None, roll_percent: float = 0.85):
+    """The spectral shape descriptors of every frame of S [..., frames, bins] (numpy array or float32 CUDA tensor, non-negative: the power
+    plane of stft_db(..., linear_out=True), a mel plane, a cqt(..., power=True) plane) in one launch -> a dict of [..., frames] arrays
+    of the same kind: energy, centroid, spread, rolloff, rolloff_bin (int32), flatness_db, crest, and flatness = 10^(flatness_db / 10).
+    freqs: one frequency per bin (mel or CQT centres, anything); None: fft_frequencies(sr, 2 * (bins - 1)).  Differs from
+    librosa.feature.spectral_centroid / spectral_bandwidth / spectral_rolloff / spectral_flatness on purpose: the plane is taken as it is,
+    and it is power by default here where librosa's default is magnitude; the frames lie along axis -2; the floor inside the logarithms is
+    1e-11 where librosa uses amin = 1e-10; no centring of frames.  Agreement with librosa was not measured."""
+    return _shape(S, freqs, sr, roll_percent, _SHAPE_OUTPUTS)
+
+
+def spectral_centroid(S, freqs=None, sr=None):
+    """The centroid sum f S / sum S of every frame of S [..., frames, bins] -> [..., frames], the same kind; a launch with this output
+    alone, the same bits as spectral_shape(...)["centroid"].  As there: power rather than magnitude as the plane's default, frames along
+    axis -2, no centring, where librosa.feature.spectral_centroid differs; agreement with librosa was not measured."""
+    return _shape(S, freqs, sr, 0.85, ("centroid",))["centroid"]
+
+
+def spectral_bandwidth(S, freqs=None, sr=None):
+    """The spread sqrt(sum (f - centroid)^2 S / sum S) of every frame of S [..., frames, bins] -> [..., frames], the same kind
+    (librosa.feature.spectral_bandwidth with p = 2 and S as the weights); a launch with this output alone, the same bits as
+    spectral_shape(...)["spread"].  Power rather than magnitude as the plane's default, frames along axis -2, no centring; agreement with
+    librosa was not measured."""
+    return _shape(S, freqs, sr, 0.85, ("spread",))["spread"]
+
+
+def spectral_rolloff(S, freqs=None, sr=None, roll_percent: float = 0.85):
+    """The frequency of the first bin of every frame of S [..., frames, bins] whose prefix sum reaches roll_percent of the frame's total
+    -> [..., frames], the same kind; a launch with this output alone, the same bits as spectral_shape(...)["rolloff"].  Power rather than
+    magnitude as the plane's default, frames along axis -2, no centring, where librosa.feature.spectral_rolloff differs; agreement with
+    librosa was not measured."""
+    return _shape(S, freqs, sr, roll_percent, ("rolloff",))["rolloff"]
+
+
+def spectral_flatness(S):
+    """The flatness (geometric over arithmetic mean, linear) of every frame of S [..., frames, bins] -> [..., frames], the same kind; a
+    launch with flatness_db alone, then 10^(flatness_db / 10) as in spectral_shape(...)["flatness"].  Power rather than magnitude as the
+    plane's default (librosa.feature.spectral_flatness squares a magnitude itself), frames along axis -2, the floor 1e-11 inside the
+    logarithms where librosa uses amin = 1e-10, no centring; agreement with librosa was not measured."""
+    return _shape(S, np.zeros(S.shape[-1], np.float32), None, 0.85, ("flatness_db",))["flatness"]          # the table is not read
+
+
+def spectral_crest(S):
+    """The crest (largest bin over the mean of the bins) of every frame of S [..., frames, bins] -> [..., frames], the same kind; a launch
+    with this output alone, the same bits as spectral_shape(...)["crest"].  librosa has no counterpart; as for the others, the plane is
+    power by default, the frames lie along axis -2, there is no centring, and agreement with librosa was not measured."""
+    return _shape(S, np.zeros(S.shape[-1], np.float32), None, 0.85, ("crest",))["crest"]                   # the table is not read
+
+
+def spectral_shape_audio(x, sr: float, n_fft: int = 2048, hop: int = 512, roll_percent: float = 0.85):
+    """The spectral shape descriptors of audio x [samples] (numpy array or float32 CUDA tensor): Plan (the library's Hann window) ->
+    stft_db(..., linear_out=True) -> spectral_shape on the power plane with the FFT bin frequencies of sr, on the GPU with nothing
+    returned to the host in between -> the dict of spectral_shape, [frames] each, frames = 1 + (samples - n_fft) // hop.  n_fft is one
+    of the engine's sizes (512 .. 8192) and hop divides it.  Differs from librosa on purpose: power rather than magnitude as the plane,
+    the frames start at t * hop (no centring) and lie along axis -2 of the plane, the floor 1e-11 inside the logarithms where librosa uses
+    amin = 1e-10.  Agreement with librosa was not measured."""
+    import torch
+    xt, was_numpy = _to_cuda(x)
+    assert xt.dim() == 1, "spectral_shape_audio: x is one channel [samples]"
+    n_fft, hop = int(n_fft), int(hop)
+    if hop <= 0 or hop > n_fft or n_fft % hop:
+        raise JsgError(capi.JSG_ERR_INVALID, f"spectral_shape_audio: hop {hop} must divide n_fft {n_fft} (frames at t * hop)")
+    frames = 1 + (xt.shape[0] - n_fft) // hop
+    if frames < 1:
+        raise JsgError(capi.JSG_ERR_INVALID, f"spectral_shape_audio: {xt.shape[0]} samples hold no frame of {n_fft}")
+    dev = _device_index(xt)
+    with torch.cuda.device(dev):
+        if (dev, n_fft) not in _shape_plan_cache:
+            _shape_plan_cache[(dev, n_fft)] = Plan(n_fft, window(capi.WIN_HANN, n_fft))
+        power = torch.empty((frames, n_fft // 2 + 1), dtype=torch.float32, device=xt.device)
+        stft_db(_shape_plan_cache[(dev, n_fft)], xt[None, :].contiguous(), hop, frames, power, feedblocks=n_fft // hop, linear_out=True)
+        out = spectral_shape(power, sr=sr, roll_percent=roll_percent)
+    return {n: o.cpu().numpy() for n, o in out.items()} if was_numpy else out

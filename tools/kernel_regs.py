@@ -2,14 +2,15 @@
 """Per-kernel resource usage of the built STFT units (VGPRs, SGPRs, spills, scratch, LDS) from the code objects' metadata, plus
 instruction-mix counts from the disassembly.  CPU only (llvm-objcopy / clang-offload-bundler / llvm-readelf / llvm-objdump).
 
-    python tools/kernel_regs.py [--isa PATTERN] [obj ...]      (default objects: jadespectrogram_amd/build/jsg_stft_{a,b}.o, jsg_cstft.o, jsg_pvoc.o, jsg_hpss.o, jsg_resample.o, jsg_cqt.o, jsg_yin.o, jsg_rhythm.o and jsg_cepstral.o; jsg_filterbank.o holds the band kernel,
+    python tools/kernel_regs.py [--isa PATTERN] [obj ...]      (default objects: jadespectrogram_amd/build/jsg_stft_{a,b}.o, jsg_cstft.o, jsg_pvoc.o, jsg_hpss.o, jsg_resample.o, jsg_cqt.o, jsg_yin.o, jsg_rhythm.o, jsg_cepstral.o and jsg_spectral.o; jsg_filterbank.o holds the band kernel,
                                                                jsg_display_axis.o the display-axis colour kernel, jsg_cstft.o the
                                                                complex STFT / inverse STFT kernels, jsg_pvoc.o the phase vocoder,
                                                                jsg_hpss.o the harmonic-percussive separation, jsg_resample.o the
                                                                band-limited resampler, jsg_cqt.o the constant-Q kernel,
                                                                jsg_yin.o the YIN kernel,
                                                                jsg_rhythm.o the onset, tempogram and tempo kernels,
-                                                               jsg_cepstral.o the projection (MFCC) and delta kernels)
+                                                               jsg_cepstral.o the projection (MFCC) and delta kernels,
+                                                               jsg_spectral.o the spectral shape kernels)
 """
 import os
 import re
@@ -45,7 +46,7 @@ def main():
     if args and args[0] == "--isa":
         isa_pat = args[1]
         args = args[2:]
-    objs = args or [os.path.join(ROOT, "jadespectrogram_amd", "build", f) for f in ("jsg_stft_a.o", "jsg_stft_b.o", "jsg_cstft.o", "jsg_pvoc.o", "jsg_hpss.o", "jsg_resample.o", "jsg_cqt.o", "jsg_yin.o", "jsg_rhythm.o", "jsg_cepstral.o")]
+    objs = args or [os.path.join(ROOT, "jadespectrogram_amd", "build", f) for f in ("jsg_stft_a.o", "jsg_stft_b.o", "jsg_cstft.o", "jsg_pvoc.o", "jsg_hpss.o", "jsg_resample.o", "jsg_cqt.o", "jsg_yin.o", "jsg_rhythm.o", "jsg_cepstral.o", "jsg_spectral.o")]
     with tempfile.TemporaryDirectory() as tmp:
         for obj in objs:
             co = code_object(obj, tmp)
@@ -67,7 +68,8 @@ def main():
                 g = lambda k: (re.search(rf"\.{k}:\s+(\S+)", blk) or [None, "?"])[1]
                 name = g("name")
                 if not any(k in name for k in ("stft_db_kernel", "fb_band_kernel", "colormap_axis_kernel", "cstft_fwd_kernel", "istft_c2r_kernel", "istft_ola_kernel", "pvoc_walk_kernel",
-                                               "pvoc_scan_kernel", "hpss_freq_kernel", "hpss_time_kernel", "resample_kernel", "cqt_kernel", "yin_kernel", "onset_kernel", "tempogram_kernel", "tempo_kernel", "mfcc_kernel", "delta_kernel")):
+                                               "pvoc_scan_kernel", "hpss_freq_kernel", "hpss_time_kernel", "resample_kernel", "cqt_kernel", "yin_kernel", "onset_kernel", "tempogram_kernel", "tempo_kernel", "mfcc_kernel", "delta_kernel", "spectral_regs_kernel",
+                                               "spectral_stream_kernel")):
                     continue
                 mx = mix.get(name, {})
                 valu = sum(c for o, c in mx.items() if o.startswith("v_"))
