@@ -10,7 +10,7 @@ OBJ   := jadespectrogram_amd/build
 lib: $(OUT)
 
 HIPFLAGS := -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude --offload-arch=$(ARCH) -fno-slp-vectorize -mllvm -amdgpu-kernarg-preload-count=16
-KDEPS    := $(SRC)/jsg_stft_kernel.h $(SRC)/jsg_internal.h $(SRC)/jsg_exact_math.h include/jsg.h
+KDEPS    := $(SRC)/jsg_stft_kernel.h $(SRC)/jsg_runs_grid.h $(SRC)/jsg_internal.h $(SRC)/jsg_exact_math.h include/jsg.h
 
 $(OBJ)/jsg_kernels.o: $(SRC)/jsg_kernels.hip $(KDEPS)
 	@mkdir -p $(OBJ)

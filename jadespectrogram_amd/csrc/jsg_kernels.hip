@@ -13,6 +13,7 @@
 #include <memory>
 
 #include "jsg_stft_kernel.h"
+#include "jsg_runs_grid.h"
 
 namespace jsg {
 
@@ -529,7 +530,28 @@ static int stft_launch_impl(const jsg_plan* plan, const jsg_stft_args* g, const 
     // last round (a grid of max_blocks would leave up to max_blocks - 1 of them: 9 workgroups per CU for 30 720 steps measured
     // 0.54 against 0.58 of 8 TB/s at 8 per CU)
     ka.iters = int((want + max_blocks - 1) / max_blocks);
-    const int nblk = int((want + ka.iters - 1) / ka.iters);
+    int nblk = int((want + ka.iters - 1) / ka.iters);
+    ka.pop_nl = ka.pop_g0 = 0;   // the uniform grid: every workgroup a "fill" workgroup of iters steps (StftKArgs::pop_*)
+    ka.pop_iters = ka.iters;
+    // Two populations of workgroups (jsg_runs_grid.h: one resident generation of long-lived ones, short-lived ones behind them) for the runs
+    // kernel where the grid is the library's own choice and the launch is several resident generations long.  An explicit blocks_per_cu,
+    // the grid knobs of variant builds, every other plan and the small launches keep the uniform grid.  DESIGN.md section 6, "Two populations".
+    if (&v == &row_of(Variant::k1024Runs) && g->blocks_per_cu == 0 && blocks_per_cu_env == 0 && max_blocks_env <= 0 && ny == 1) {
+        // (variant builds only, read at every launch so that one process can interleave settings: JSG_POPS=1 | 0 switches the form on / off,
+        // JSG_POP_FILL16 / JSG_POP_ITS set the fill's share in sixteenths and the steps of a fill workgroup, JSG_POP_MIN_GEN the threshold)
+        const int pops_knob = dev_knob_set("JSG_POPS") ? dev_knob_int("JSG_POPS") : jsg::kRunsTwoPopulations;
+        const int fill16 = dev_knob_int("JSG_POP_FILL16") > 0 ? dev_knob_int("JSG_POP_FILL16") : JSG_X_POP_FILL16;
+        const int its = dev_knob_int("JSG_POP_ITS") > 0 ? dev_knob_int("JSG_POP_ITS") : JSG_X_POP_ITS;
+        const int min_gen = dev_knob_int("JSG_POP_MIN_GEN") > 0 ? dev_knob_int("JSG_POP_MIN_GEN") : jsg::kRunsPopMinGenerations;
+        jsg::RunsGrid rg;
+        if (pops_knob && jsg::runs_two_populations(want, n_cu, fill16, its, &rg, min_gen)) {
+            nblk = int(rg.nblk);
+            ka.iters = rg.it_long;
+            ka.pop_nl = rg.n_long;
+            ka.pop_g0 = rg.g0;
+            ka.pop_iters = rg.it_short;
+        }
+    }
     const hipError_t err = v.launch(ka, mixop, bs != nullptr, dim3(nblk, ny), reinterpret_cast<hipStream_t>(stream));
     if (err != hipSuccess) return jsg_fail_hip(err, bs ? "jsg_stft_db_launch_strided" : "jsg_stft_db_launch");
     return JSG_OK;

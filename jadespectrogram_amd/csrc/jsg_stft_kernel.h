@@ -632,6 +632,11 @@ struct StftKArgs {
     unsigned bat_cpb;             // rows per batch: channels in per-channel mode, else 1
     unsigned long long bat_magic; // ceil(2^40 / bat_cpb)
     long long out_batch_stride;   // floats between the rings of consecutive batches
+    // STREAM == 2, two populations of workgroups in one launch (jsg_runs_grid.h): logical blocks [0, pop_nl) are the bulk -- a.iters steps
+    // g = lb + sg * pop_nl -- the others the fill: pop_iters steps g = pop_g0 + (lb - pop_nl) + sg * (nblk - pop_nl).  The uniform grid is the
+    // fill alone: pop_nl = 0, pop_g0 = 0, pop_iters = iters.
+    unsigned pop_nl, pop_g0;
+    int pop_iters;
 };
 
 // dB = 10*log10(p + 1e-11f) -- reference Spectrogram.cpp:107 with g_minValForLogSpectrogram (:36).
@@ -981,9 +986,14 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
     if constexpr (RUNS && kRunsStore) asm volatile("" : "+v"(st_vlo), "+v"(st_vup));
     const unsigned long long st_l0 = __builtin_amdgcn_ballot_w64(lane == 0);   // lane 0's bit, the mask of lane0_select (scalar, once per wave)
     // a new run: super-group `sg` of this workgroup -> row, first column of this wave's run, the row's input / ring offsets (scalar, once per RL rounds)
+    // the workgroup's population (scalar; StftKArgs::pop_*): first super-group, stride and number of its steps
+    const bool rg_fill = lb >= a.pop_nl;
+    const unsigned rg_base = rg_fill ? a.pop_g0 + (lb - a.pop_nl) : lb, rg_stride = rg_fill ? nblk - a.pop_nl : a.pop_nl;
+    const int rg_iters = rg_fill ? a.pop_iters : a.iters;
+    __builtin_assume(rg_iters >= 1);
     auto runs_group = [&](unsigned sg) {
-        unsigned g = lb + sg * nblk;
-        if (g >= a.n_groups) g -= a.n_groups;                     // surplus steps of the last round start over with the first groups
+        unsigned g = rg_base + sg * rg_stride;
+        if (g >= a.n_groups) g = g - a.n_groups + a.pop_g0;       // surplus steps of the last round (fill only) start over with the fill's first groups
         const unsigned row = (unsigned)(((unsigned long long)g * a.img_magic) >> 40);
         rn_col0 = (g - row * a.img_gpi) * (unsigned)(C::TPB * RL) + (unsigned)(slot0 * RL);
         row_of(row, rn_in, nx_out);
@@ -1969,7 +1979,7 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
     };
 
     using t0 = std::integral_constant<int, 0>;
-    if constexpr (RUNS) {   // a.iters runs of RL rounds each, every run written out (a round's place in its run is a compile-time fact);
+    if constexpr (RUNS) {   // rg_iters runs of RL rounds each, every run written out (a round's place in its run is a compile-time fact);
                             // the last round of the last run prefetches nothing
         auto run = [&](int s0, auto last_tag) __attribute__((always_inline)) {
             for_each_t([&](auto t_tag) __attribute__((always_inline)) {
@@ -1979,7 +1989,7 @@ __global__ __launch_bounds__(C::WPB * 64, (JSG_RTAB_OF(C, MIXOP, OUTK) ? 5 : C::
             }, std::make_integer_sequence<int, RL>{});
         };
         int s = 0;
-        for (int r = 0; r + 1 < a.iters; ++r, s += RL) run(s, std::false_type{});
+        for (int r = 0; r + 1 < rg_iters; ++r, s += RL) run(s, std::false_type{});
         run(s, std::true_type{});
     } else {
         for (int s = 0; s + 1 < n_fft; ++s) process(s, std::false_type{}, t0{});

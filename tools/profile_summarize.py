@@ -79,6 +79,10 @@ for kname, d in res["counters_mean_per_dispatch"].items():
            "valu_instructions_per_fft": d.get("SQ_INSTS_VALU", 0.0) / ffts, "lds_instructions_per_fft": d.get("SQ_INSTS_LDS", 0.0) / ffts,
            "vmem_instructions_per_fft": d.get("SQ_INSTS_VMEM", 0.0) / ffts,
            "wave_lifetime_cycles": 4.0 * d["SQ_WAVE_CYCLES"] / max(w, 1.0),
+           # SQ_WAVE_CYCLES x 4 = wave-cycles, SQ_BUSY_CU_CYCLES = cycles a CU holds at least one wave, summed over the CUs; four SIMDs per CU.
+           # Units checked on the runs kernel at a known residency ("Two populations"): a grid of one four-wave workgroup
+           # per CU gives exactly 1.0.
+           "mean_resident_waves_per_simd": (d["SQ_WAVE_CYCLES"] * 4.0 / d["SQ_BUSY_CU_CYCLES"] / 4.0) if d.get("SQ_BUSY_CU_CYCLES") else None,
            "share_of_wave_cycles": {k: d[v] / d["SQ_WAVE_CYCLES"] for k, v in (("issuing_valu", "SQ_ACTIVE_INST_VALU"), ("issuing_any", "SQ_ACTIVE_INST_ANY"),
                                                                               ("waiting_to_issue", "SQ_WAIT_INST_ANY"), ("parked_on_waitcnt_or_barrier", "SQ_WAIT_ANY"),
                                                                               ("waiting_to_issue_lds", "SQ_WAIT_INST_LDS")) if v in d},
