@@ -1,13 +1,14 @@
-# Builds libjsg.so (hand-written HIP for gfx950 + C-ABI) without Python; the same commands as
-# jadespectrogram_amd/_build.py.  `make test-cpp` builds the C++ drop-in test driver against it.
+# Builds libjsg.so (hand-written HIP for gfx950 + C-ABI) and its companion libjsgx.so (include/jsgx.h) without Python; the same
+# commands as jadespectrogram_amd/_build.py.  `make test-cpp` builds the C++ drop-in test driver against it.
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 SRC   := jadespectrogram_amd/csrc
 OUT   := jadespectrogram_amd/libjsg.so
+OUTX  := jadespectrogram_amd/libjsgx.so
 OBJ   := jadespectrogram_amd/build
 
 .PHONY: lib oracle test-cpp clean
-lib: $(OUT)
+lib: $(OUT) $(OUTX)
 
 HIPFLAGS := -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude --offload-arch=$(ARCH) -fno-slp-vectorize -mllvm -amdgpu-kernarg-preload-count=16
 KDEPS    := $(SRC)/jsg_stft_kernel.h $(SRC)/jsg_runs_grid.h $(SRC)/jsg_internal.h $(SRC)/jsg_exact_math.h include/jsg.h
@@ -64,6 +65,17 @@ $(OUT): $(OBJ)/jsg_kernels.o $(OBJ)/jsg_stft_a.o $(OBJ)/jsg_stft_b.o $(OBJ)/jsg_
         $(OBJ)/jsg_host_math.o $(OBJ)/jsg_filterbank_host.o $(OBJ)/jsg_display_axis_host.o $(OBJ)/jsg_cqt_host.o $(OBJ)/jsg_yin_host.o $(OBJ)/jsg_rhythm_host.o $(OBJ)/jsg_cepstral_host.o $(OBJ)/jsg_spectral_host.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^
 
+# the companion library: its own units and headers, the same flags, nothing of libjsg.so
+XDEPS := $(SRC)/jsgx_internal.h include/jsgx.h
+$(OBJ)/jsgx_beat.o: $(SRC)/jsgx_beat.hip $(XDEPS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(OBJ)/jsgx_beat_host.o: $(SRC)/jsgx_beat_host.cpp $(XDEPS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude -ffp-contract=off -D__HIP_PLATFORM_AMD__ -c $< -o $@
+$(OUTX): $(OBJ)/jsgx_beat.o $(OBJ)/jsgx_beat_host.o
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^
+
 oracle:
 	$(MAKE) -C oracle port ref
 
@@ -72,4 +84,4 @@ test-cpp: lib
 	    -Ljadespectrogram_amd -ljsg -Wl,-rpath,$(CURDIR)/jadespectrogram_amd
 
 clean:
-	rm -rf $(OBJ) $(OUT)
+	rm -rf $(OBJ) $(OUT) $(OUTX)

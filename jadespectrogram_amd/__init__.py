@@ -3,7 +3,7 @@
 The compute path is hand-written HIP in libjsg.so (csrc/), reached through the C-ABI of include/jsg.h.
 Importing this package does not load the library; the first call does, and fails loudly if it is missing.
 """
-from . import capi  # noqa: F401
+from . import capi, capix  # noqa: F401
 from .capi import JsgError  # noqa: F401
 from .spectrogram import (CColorPalette, Filterbank, FreqAxis, Plan, Spectrogram, SpectrogramDisplay, StftLaunch, colormap, colormap_lut,  # noqa: F401
                           colormap_axis, colormap_range, columns_from_tail_layout, feed_samples, memsize_blocks, next_power_of_2, stft_db, stft_db_batches, stft_db_strided, stft_db_strided_kernel_name, stft_image, stft_image_needs_scratch, stft_image_strided, stft_image_strided_needs_scratch, stft_kernel_name, window,
@@ -16,6 +16,7 @@ from .spectrogram import (CColorPalette, Filterbank, FreqAxis, Plan, Spectrogram
                           yin, yin_cmnd, yin_frames, yin_kernel_name, yin_launch, yin_plan,
                           estimate_tempo, onset_strength, onset_strength_launch, tempo, tempo_launch, tempo_prior, tempogram, tempogram_frames,
                           tempogram_kernel_name, tempogram_launch, tempogram_plan,
+                          beat_launch, beat_log_table, beat_plan, beat_scratch_bytes, beat_track, beat_track_audio,
                           delta, delta_launch, delta_weights, mfcc, mfcc_audio, mfcc_kernel_name, mfcc_launch, mfcc_plan, mfcc_table, mfcc_to_mel_db,
                           fft_frequencies, spectral_bandwidth, spectral_centroid, spectral_crest, spectral_flatness, spectral_rolloff, spectral_shape,
                           spectral_shape_audio, spectral_shape_kernel_name, spectral_shape_launch, spectral_shape_plan)
@@ -31,6 +32,7 @@ __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_d
            "yin_frames", "yin_launch", "yin_plan", "yin_kernel_name", "yin", "yin_cmnd",
            "onset_strength", "onset_strength_launch", "tempogram", "tempogram_launch", "tempogram_frames", "tempogram_plan", "tempogram_kernel_name",
            "tempo_prior", "tempo_launch", "tempo", "estimate_tempo",
+           "capix", "beat_log_table", "beat_scratch_bytes", "beat_launch", "beat_plan", "beat_track", "beat_track_audio",
            "mfcc_table", "mfcc_launch", "mfcc_plan", "mfcc_kernel_name", "delta_weights", "delta_launch", "mfcc", "mfcc_to_mel_db", "delta", "mfcc_audio",
            "spectral_shape_launch", "spectral_shape_plan", "spectral_shape_kernel_name", "fft_frequencies", "spectral_shape", "spectral_centroid",
            "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "spectral_crest", "spectral_shape_audio"]

@@ -1,4 +1,5 @@
-"""In-tree build of libjsg.so (hand-written HIP for gfx950 + the C-ABI).  hipcc cross-compiles without a GPU."""
+"""In-tree build of libjsg.so (hand-written HIP for gfx950 + the C-ABI) and of its companion libjsgx.so (include/jsgx.h).  hipcc
+cross-compiles without a GPU."""
 from __future__ import annotations
 
 import os
@@ -25,6 +26,10 @@ VISIBILITY = ["-fvisibility=hidden", "-fvisibility-inlines-hidden"]
 # gives the measurements); the 4096-point kernels (jsg_stft_b.hip) keep the default one
 UNIT_FLAGS = {"jsg_stft_a.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 ARCH = "gfx950"
+# the companion library (include/jsgx.h): its own units and headers, the same flags, nothing shared with libjsg.so
+LIBX = os.path.join(PKG, "libjsgx.so")
+SOURCES_X = ["jsgx_beat.hip", "jsgx_beat_host.cpp"]
+HEADERS_X = ["jsgx_internal.h", os.path.join(ROOT, "include", "jsgx.h")]
 
 
 def _hipcc() -> str:
@@ -69,20 +74,12 @@ def build_variant(name: str, hip_flags, verbose: bool = False) -> str:
     return out
 
 
-def build_lib(force: bool = False, verbose: bool = False) -> str:
-    """Compile csrc/* into jadespectrogram_amd/libjsg.so (only what is out of date)."""
-    hipcc = _hipcc()
-    objdir = os.path.join(PKG, "build")
-    os.makedirs(objdir, exist_ok=True)
-    hdrs = [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HEADERS]
-    flavour_file = os.path.join(objdir, "flavour")
-    flavour = "product"
-    if not os.path.exists(flavour_file) or open(flavour_file).read().strip() != flavour:
-        force = True
+def _build_one(hipcc: str, objdir: str, sources, hdrs, lib: str, force: bool, verbose: bool):
+    """Compile the stale units of one library and link it where an object is newer: (objects, recompiled units, relinked)."""
     objs = []
     recompiled, relinked = [], False
     cmds = []
-    for src in SOURCES:
+    for src in sources:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
         objs.append(o)
@@ -102,18 +99,36 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
     failed = [c for c, p in zip(cmds, procs) if p.wait() != 0]
     if failed:
         raise subprocess.CalledProcessError(1, failed[0])
-    if force or _stale(LIB, objs):
+    if force or _stale(lib, objs):
         relinked = True
-        cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs
+        cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib] + objs
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.check_call(cmd)
+    return objs, recompiled, relinked
+
+
+def build_lib(force: bool = False, verbose: bool = False) -> str:
+    """Compile csrc/* into jadespectrogram_amd/libjsg.so and jadespectrogram_amd/libjsgx.so (only what is out of date).  Returns the
+    path of libjsg.so."""
+    hipcc = _hipcc()
+    objdir = os.path.join(PKG, "build")
+    os.makedirs(objdir, exist_ok=True)
+    hdrs = [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HEADERS]
+    flavour_file = os.path.join(objdir, "flavour")
+    flavour = "product"
+    if not os.path.exists(flavour_file) or open(flavour_file).read().strip() != flavour:
+        force = True
+    objs, recompiled, relinked = _build_one(hipcc, objdir, SOURCES, hdrs, LIB, force, verbose)
+    hdrs_x = [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HEADERS_X]
+    objs_x, recompiled_x, relinked_x = _build_one(hipcc, objdir, SOURCES_X, hdrs_x, LIBX, force, verbose)
     with open(flavour_file, "w") as f:
         f.write(flavour + "\n")
     # build record: what was compiled in this call and what was reused, for whoever reads the driver's log
     import json, time
     info = {"flavour": flavour, "recompiled": recompiled, "relinked": relinked, "lib_mtime": time.strftime("%Y-%m-%d %H:%M:%S", time.localtime(os.path.getmtime(LIB))),
-            "objects": {os.path.basename(o): time.strftime("%Y-%m-%d %H:%M:%S", time.localtime(os.path.getmtime(o))) for o in objs}}
+            "objects": {os.path.basename(o): time.strftime("%Y-%m-%d %H:%M:%S", time.localtime(os.path.getmtime(o))) for o in objs},
+            "companion": {"recompiled": recompiled_x, "relinked": relinked_x}}
     try:
         info["commit"] = subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
         info["dirty"] = bool(subprocess.check_output(["git", "-C", ROOT, "status", "--porcelain", "--", "jadespectrogram_amd", "include"],

@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import capi
+from . import capi, capix
 from .capi import JsgError, check, lib
 
 
@@ -1683,6 +1683,141 @@ def estimate_tempo(x, sr: float, n_fft: int = 2048, hop: int = 512, n_mels: int 
         tg = tempogram(env, win_length=win_length)
         bpm, lag = tempo(tg, float(sr) / float(hop), start_bpm, std_bpm, max_bpm)
     return (float(bpm.cpu()), int(lag.cpu())) if was_numpy else (bpm, lag)
+
+
+# --------------------------------------------------------------------------------------------------
+# beat tracking by dynamic programming (include/jsgx.h, section 1: the companion library libjsgx.so)
+# --------------------------------------------------------------------------------------------------
+_beat_cache: dict = {}
+
+
+def beat_log_table(n: int = capix.BEAT_LOG_TABLE) -> np.ndarray:
+    """jsgx_log_table_build: float32 [n], 0 at index 0 and ln(k) at index k (in double, rounded once).  beat_launch takes the table of
+    2 * BEAT_MAX_PERIOD + 1 entries on the device."""
+    out = np.zeros(int(n), dtype=np.float32)
+    capix.check(capix.lib().jsgx_log_table_build(int(n), out.ctypes.data))
+    return out
+
+
+def _device_table(key, device, make):
+    """A host table uploaded once per device and key (so that a steady-state call copies nothing from the host)."""
+    import torch
+    key = (str(device),) + key
+    if key not in _beat_cache:
+        _beat_cache[key] = torch.from_numpy(np.ascontiguousarray(make(), dtype=np.float32)).to(device)
+    return _beat_cache[key]
+
+
+def _beat_args(d_in, d_log_table, d_beats, d_n_beats, d_period, period, tightness, smooth, normalise, max_beats, d_local_score, d_cum_score) -> capix.BeatArgs:
+    import torch
+    x = d_in[None] if d_in.dim() == 1 else d_in
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1, "d_in: float32 CUDA [rows][frames]"
+    R, T = x.shape
+    assert d_log_table.is_cuda and d_log_table.dtype == torch.float32 and d_log_table.dim() == 1 and d_log_table.stride(0) == 1 and \
+        d_log_table.shape[0] >= capix.BEAT_LOG_TABLE, f"d_log_table: float32 CUDA [{capix.BEAT_LOG_TABLE}]"
+    b = d_beats[None] if d_beats.dim() == 1 else d_beats
+    assert b.is_cuda and b.dtype == torch.int32 and b.dim() == 2 and b.stride(1) == 1 and b.shape[0] == R, "d_beats: int32 CUDA [rows][max_beats]"
+    max_beats = b.shape[1] if max_beats is None else int(max_beats)
+    assert b.shape[1] >= max_beats, "d_beats: int32 CUDA [rows][>= max_beats]"
+    for o, what in ((d_n_beats, "d_n_beats"), (d_period, "d_period")):
+        assert o is None or (o.is_cuda and o.dtype == torch.int32 and o.dim() == 1 and o.stride(0) == 1 and o.shape[0] >= R), f"{what}: int32 CUDA [rows]"
+    assert d_n_beats is not None and (d_period is None) != (period is None), "d_n_beats, and exactly one of d_period and period"
+    ls = None if d_local_score is None else _lines(d_local_score, R, T, "d_local_score")
+    cs = None if d_cum_score is None else _lines(d_cum_score, R, T, "d_cum_score")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    return capix.BeatArgs(x.data_ptr(), x.stride(0), R, T, ptr(d_period), 0 if period is None else int(period), int(bool(smooth)), d_log_table.data_ptr(),
+                          float(tightness), int(bool(normalise)), b.data_ptr(), b.stride(0), max_beats, 0, d_n_beats.data_ptr(),
+                          ptr(ls), 0 if ls is None else ls.stride(0), ptr(cs), 0 if cs is None else cs.stride(0))
+
+
+def beat_scratch_bytes(d_in, d_log_table, d_beats, d_n_beats, *, d_period=None, period: int | None = None, tightness: float = 100.0, smooth: bool = True,
+                       normalise: bool = True, max_beats: int | None = None, d_local_score=None, d_cum_score=None) -> int:
+    """jsgx_beat_scratch_bytes: the bytes of scratch beat_launch needs for these arguments."""
+    a = _beat_args(d_in, d_log_table, d_beats, d_n_beats, d_period, period, tightness, smooth, normalise, max_beats, d_local_score, d_cum_score)
+    return int(capix.check(capix.lib().jsgx_beat_scratch_bytes(C.byref(a))))
+
+
+def beat_launch(d_in, d_log_table, d_beats, d_n_beats, *, d_period=None, period: int | None = None, tightness: float = 100.0, smooth: bool = True,
+                normalise: bool = True, max_beats: int | None = None, d_local_score=None, d_cum_score=None, d_scratch=None, stream: int | None = None):
+    """jsgx_beat_launch: d_in float32 [rows][frames] (an onset envelope), d_log_table float32 [2049] (beat_log_table on the device), the
+    period of every row in d_period (int32 [rows], what tempo_launch writes into d_lag) or one `period` for all -> d_beats int32
+    [rows][max_beats] (the beat frames, ascending) and d_n_beats int32 [rows] (their number; -1 for a row whose period is outside
+    1..1024 or whose envelope holds a NaN).  d_local_score, d_cum_score: float32 [rows][>= frames] or None.  d_scratch: a contiguous
+    CUDA tensor of at least beat_scratch_bytes bytes (None: one is allocated with torch for this call)."""
+    import torch
+    a = _beat_args(d_in, d_log_table, d_beats, d_n_beats, d_period, period, tightness, smooth, normalise, max_beats, d_local_score, d_cum_score)
+    d_scratch, stream = _scratch_and_stream(d_scratch, stream, d_in, lambda: capix.check(capix.lib().jsgx_beat_scratch_bytes(C.byref(a))) // 4, torch.int32,
+                                            any_dtype=True)
+    capix.check(capix.lib().jsgx_beat_launch(C.byref(a), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), stream))
+
+
+def beat_plan(period: int, n_frames: int = 1024, rows: int = 1):
+    """jsgx_beat_plan: (form, lanes per workgroup, bytes of LDS per workgroup) of the kernel for a row of this period: "beat_frames" (one
+    lane per frame) from period 511 on, "beat_split" (the lanes of a frame split the look-back range) below.  Needs no device."""
+    a = capix.BeatArgs(in_=1 << 44, in_pitch=int(n_frames), rows=int(rows), n_frames=int(n_frames), period_all=int(period) if 1 <= period <= capix.BEAT_MAX_PERIOD else 1,
+                       log_table=2 << 44, tightness=100.0, beats=3 << 44, beats_pitch=int(n_frames), max_beats=int(n_frames), n_beats=4 << 44)   # never dereferenced
+    name, threads, lds = C.create_string_buffer(32), C.c_int32(), C.c_int32()
+    capix.check(capix.lib().jsgx_beat_plan(C.byref(a), int(period), name, 32, C.byref(threads), C.byref(lds)))
+    return name.value.decode(), threads.value, lds.value
+
+
+def beat_track(onset_envelope, period=None, bpm=None, frame_rate=None, tightness=100.0, smooth=True, normalise=True, max_beats=None):
+    """Beat frames of an onset envelope [..., T] (numpy array or float32 CUDA tensor) by dynamic programming (Ellis 2007, the core of
+    librosa.beat.beat_track) -> (beats int32 [..., max_beats], n_beats int32 [...]) as CUDA tensors: beats[..., :n_beats] ascending.
+    period: an int (frames per beat, for every row), an int32 CUDA tensor with one period per row (what tempo returns as lag), or None:
+    round(60 * frame_rate / bpm).  max_beats None: as many as a row can hold.  Differs from librosa on purpose: an integer period, Ellis'
+    end rule, no trimming of weak beats (include/jsgx.h)."""
+    import torch
+    x, _ = _to_cuda(onset_envelope)
+    batch = tuple(x.shape[:-1])
+    xr = x.reshape(-1, x.shape[-1]).contiguous()
+    R, T = xr.shape
+    d_period = None
+    if period is None:
+        assert bpm is not None and frame_rate is not None, "beat_track: a period, or bpm and frame_rate"
+        period = int(round(60.0 * float(frame_rate) / float(bpm)))
+    elif hasattr(period, "is_cuda"):
+        d_period, period = period.reshape(-1).to(torch.int32).contiguous(), None
+        assert d_period.is_cuda and d_period.shape[0] == R, "beat_track: one period per row"
+    if max_beats is None:
+        max_beats = T if period is None else 1 + (T - 1) // max(1, (int(period) + 1) // 2)
+    beats = torch.zeros((R, int(max_beats)), dtype=torch.int32, device=x.device)
+    n_beats = torch.empty((R,), dtype=torch.int32, device=x.device)
+    with torch.cuda.device(_device_index(x)):
+        beat_launch(xr, _device_table(("log",), x.device, beat_log_table), beats, n_beats, d_period=d_period, period=period, tightness=tightness,
+                    smooth=smooth, normalise=normalise)
+    return beats.reshape(*batch, int(max_beats)), n_beats.reshape(batch)
+
+
+def beat_track_audio(x, sr, n_fft=2048, hop=512, n_mels=128, win_length=384, start_bpm=120.0, std_bpm=1.0, max_bpm=320.0, tightness=100.0, smooth=True,
+                     normalise=True, max_beats=None):
+    """Tempo and beats of audio x [samples] (numpy array or float32 CUDA tensor): mel_spectrogram_db -> onset_strength_launch ->
+    tempogram_launch -> tempo_launch (its lag stays on the device) -> beat_launch, enqueued one after the other with no host
+    synchronisation and, from the second call of a geometry on, no host copy.  Returns (bpm float32 [], beats int32 [max_beats], n_beats
+    int32 []) as CUDA tensors; the beat frames are frames of the mel spectrogram (frame t starts at sample t * hop)."""
+    import torch
+    xt, _ = _to_cuda(x)
+    assert xt.dim() == 1, "beat_track_audio: x is one channel [samples]"
+    dev = xt.device
+    rate = float(sr) / float(hop)
+    with torch.cuda.device(_device_index(xt)):
+        S = mel_spectrogram_db(xt, sr, n_fft, hop, n_mels)
+        T = S.shape[0]
+        env = torch.empty((1, T), dtype=torch.float32, device=dev)
+        onset_strength_launch(S, env)
+        w = _device_table(("hann", int(win_length)), dev, lambda: window(capi.WIN_HANN, int(win_length)))
+        tg = torch.empty((1, T, int(win_length)), dtype=torch.float32, device=dev)
+        tempogram_launch(env, w, tg)
+        prior = _device_table(("prior", int(win_length), rate, float(start_bpm), float(std_bpm), float(max_bpm)), dev,
+                              lambda: tempo_prior(int(win_length), rate, start_bpm, std_bpm, max_bpm))
+        bpm = torch.empty((1,), dtype=torch.float32, device=dev)
+        lag = torch.empty((1,), dtype=torch.int32, device=dev)
+        tempo_launch(tg, prior, rate, d_bpm=bpm, d_lag=lag)
+        max_beats = T if max_beats is None else int(max_beats)
+        beats = torch.zeros((1, max_beats), dtype=torch.int32, device=dev)
+        n_beats = torch.empty((1,), dtype=torch.int32, device=dev)
+        beat_launch(env, _device_table(("log",), dev, beat_log_table), beats, n_beats, d_period=lag, tightness=tightness, smooth=smooth, normalise=normalise)
+    return bpm[0], beats[0], n_beats[0]
 
 
 # --------------------------------------------------------------------------------------------------
