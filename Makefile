@@ -70,10 +70,19 @@ XDEPS := $(SRC)/jsgx_internal.h include/jsgx.h
 $(OBJ)/jsgx_beat.o: $(SRC)/jsgx_beat.hip $(XDEPS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(OBJ)/jsgx_cdist.o: $(SRC)/jsgx_cdist.hip $(XDEPS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(OBJ)/jsgx_dtw.o: $(SRC)/jsgx_dtw.hip $(XDEPS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(OBJ)/jsgx_beat_host.o: $(SRC)/jsgx_beat_host.cpp $(XDEPS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude -ffp-contract=off -D__HIP_PLATFORM_AMD__ -c $< -o $@
-$(OUTX): $(OBJ)/jsgx_beat.o $(OBJ)/jsgx_beat_host.o
+$(OBJ)/jsgx_dtw_host.o: $(SRC)/jsgx_dtw_host.cpp $(XDEPS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude -ffp-contract=off -D__HIP_PLATFORM_AMD__ -c $< -o $@
+$(OUTX): $(OBJ)/jsgx_beat.o $(OBJ)/jsgx_cdist.o $(OBJ)/jsgx_dtw.o $(OBJ)/jsgx_beat_host.o $(OBJ)/jsgx_dtw_host.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^
 
 oracle:

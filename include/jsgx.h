@@ -11,7 +11,7 @@
  *     no synchronisation, so a launch can be captured into a hipGraph, a first launch included
  *   - every failure returns a negative jsgx_status and leaves a text for jsgx_last_error() (thread-local)
  *   - the definitions below are complete: every order of summation, tie rule and NaN rule is stated, all device arithmetic is
- *     float32 and uncontracted except where fmaf is written, so a CPU restatement (tests/beat_ref.py) gives the same bits
+ *     float32 and uncontracted except where fmaf is written, so a CPU restatement (tests/beat_ref.py, tests/dtw_ref.py) gives the same bits
  */
 #ifndef JSGX_H
 #define JSGX_H
@@ -169,6 +169,177 @@ JSGX_API int jsgx_beat_launch(const jsgx_beat_args* args, void* scratch, int64_t
  * name_len >= 16).  Refused: a name_len below 16 with a name, then what jsgx_beat_scratch_bytes refuses, then a period outside
  * 1..1024. */
 JSGX_API int jsgx_beat_plan(const jsgx_beat_args* args, int32_t period, char* name, int name_len, int32_t* threads, int32_t* lds_bytes);
+
+/* Sections 2 and 3 were added to version 1: JSGX_ABI_VERSION counts changes to what exists, and version 1 grows by addition only.
+ * Section 1, its struct and its constants are as they were; a program built against the earlier header runs unchanged. */
+
+/* ------------------------------------------------------------------------------------------------
+ * 2. The pairwise cost of two feature sequences (scipy.spatial.distance.cdist for three metrics): the first half of
+ *    librosa.sequence.dtw.  A pair p has N frames x[i][k] = x[p*x_pair_pitch + i*x_frame_pitch + k] and M frames
+ *    y[j][k] = y[p*y_pair_pitch + j*y_frame_pitch + k], k = 0..K-1: the frame-major layout the feature kernels of libjsg.so write.
+ *    A pair pitch of 0 is one sequence shared by every pair (query by example).  cost[p*cost_pair_pitch + i*cost_pitch + j] = c(i, j).
+ *    All arithmetic is float32 and uncontracted; fmaf is written where it is meant; k ascends; every accumulator starts at +0;
+ *    fl(.) is one rounding to float32; sqrtf and the divide are correctly rounded.
+ *
+ *    JSGX_METRIC_SQEUCLIDEAN:  d = fl(x[i][k] - y[j][k]);  acc = fmaf(d, d, acc);  c = acc.
+ *    JSGX_METRIC_EUCLIDEAN:    the same acc;  c = sqrtf(acc).
+ *    JSGX_METRIC_COSINE:       dot = fmaf(x, y, dot);  nx = fmaf(x, x, nx);  ny = fmaf(y, y, ny);  den = fl(sqrtf(nx) * sqrtf(ny));
+ *                              c = 1.0f where den == 0, else fl(1.0f - fl(dot / den)).
+ *    A zero vector under the cosine metric gives 1 here; scipy gives NaN: a stated difference.  NaN and infinity go through these
+ *    operations as IEEE 754 has it; nothing is special-cased.  The result depends on nothing but x[i][.], y[j][.], K and the metric.
+ *
+ *    Error bounds against exact arithmetic on the same float32 inputs, u = 2^-24, to first order in u.  d is one rounding and d*d
+ *    is exact inside the fmaf, so a term carries (1 + u)^2 and each of the K sums one more rounding; the terms are non-negative, so
+ *    acc = S (1 + t) with |t| <= (K + 2) u: sqeuclidean is relative (K + 2) u.  The root halves that and adds its own rounding:
+ *    euclidean is relative (K/2 + 2) u.  The second-order part is below K^2 u^2 / 2 < 0.04 u at K = 1024, so both are inside
+ *    (K + 3) u, which tests/test_dtw_ref.py asserts.  Cosine: |dot - DOT| <= K u sum|x y| <= K u |x||y| (Cauchy-Schwarz); nx and
+ *    ny are sums of non-negative terms, relative K u each, K u / 2 + u after their roots, so den = |x||y| (1 + h), |h| <= (K + 3) u;
+ *    the quotient and the subtraction add u |q| and u |1 - q| <= 2 u.  With r = DOT / (|x||y|):  |c - C| <= (K + (K + 4) |r| + 2) u,
+ *    (2 K + 6) u in the worst case (parallel vectors, every rounding in one direction) and (K + 2) u for orthogonal ones.  The test
+ *    asserts the tighter (K + 5) u that was set for it; it is not a worst-case bound: the roundings of dot and of den would all have
+ *    to point one way to pass it, and over normal, positive and near-duplicate data up to K = 1024 the worst error found is 24 u
+ *    (34 u relative for sqeuclidean, 17 u for euclidean; profiles/dtw_accuracy.md).
+ *
+ *    The kernel ("cdist_64x64"): a workgroup of JSGX_CDIST_THREADS lanes computes JSGX_CDIST_TILE x JSGX_CDIST_TILE costs of one
+ *    pair; panels of 32 features of 64 frames of x and of y are staged in LDS feature-major, a lane reads four x and four y with
+ *    two 16-byte LDS reads per feature and holds a 4 x 4 register tile; k ascends within a lane, so the order is the one above.
+ *    The accumulation order is stated, so this runs on the vector pipe, not on MFMA.  One kernel, no scratch.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSGX_METRIC_SQEUCLIDEAN 0
+#define JSGX_METRIC_EUCLIDEAN 1
+#define JSGX_METRIC_COSINE 2
+#define JSGX_CDIST_MAX_FEATURES 1024
+#define JSGX_DTW_MAX_LEN 65536
+#define JSGX_CDIST_TILE 64
+#define JSGX_CDIST_THREADS 256
+#define JSGX_CDIST_LDS_BYTES 17408         /* static: two panels of 32 features x 68 words */
+
+typedef struct jsgx_cdist_args {
+    const float* x;             /* device floats */
+    int64_t x_frame_pitch;      /* >= n_features */
+    int64_t x_pair_pitch;       /* 0 (shared), or >= (n - 1) * x_frame_pitch + n_features */
+    const float* y;             /* device floats */
+    int64_t y_frame_pitch;      /* >= n_features */
+    int64_t y_pair_pitch;       /* 0 (shared), or >= (m - 1) * y_frame_pitch + n_features */
+    int32_t pairs;              /* 1..65535 */
+    int32_t n_features;         /* K, 1..JSGX_CDIST_MAX_FEATURES */
+    int32_t n;                  /* N, 1..JSGX_DTW_MAX_LEN */
+    int32_t m;                  /* M, 1..JSGX_DTW_MAX_LEN */
+    int32_t metric;             /* JSGX_METRIC_* */
+    int32_t reserved0;          /* 0 */
+    float* cost;                /* device floats */
+    int64_t cost_pitch;         /* >= m */
+    int64_t cost_pair_pitch;    /* pairs > 1: >= (n - 1) * cost_pitch + m */
+} jsgx_cdist_args;
+
+/* Enqueue only (one kernel, no scratch).  Refused (JSGX_ERR_INVALID, nothing enqueued), in this order and before any device call:
+ * null args, a null x, a null y, a null cost; a pointer that is not 4-byte aligned; pairs outside 1..65535, n_features outside
+ * 1..1024, n outside 1..65536, m outside 1..65536, a metric outside 0..2; a non-zero reserved0; x_frame_pitch below n_features,
+ * y_frame_pitch below n_features, a non-zero x_pair_pitch that does not cover a sequence, the same for y_pair_pitch, cost_pitch
+ * below m, cost_pair_pitch that does not cover a plane (pairs > 1); cost overlapping x, cost overlapping y.  Then
+ * JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_cdist_launch(const jsgx_cdist_args* args, void* stream);
+/* The kernel of these arguments, without a device: its name ("cdist_64x64"), JSGX_CDIST_THREADS and JSGX_CDIST_LDS_BYTES.  Any
+ * output pointer may be NULL (name: else name_len >= 16).  Refused: a name_len below 16 with a name, then what the launch refuses. */
+JSGX_API int jsgx_cdist_plan(const jsgx_cdist_args* args, char* name, int name_len, int32_t* threads, int32_t* lds_bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * 3. Dynamic time warping over a cost plane (the second half of librosa.sequence.dtw).  C[i][j] = cost[p*cost_pair_pitch +
+ *    i*cost_pitch + j], i < N, j < M: the plane of section 2 or any plane the caller filled.  Pairs are independent.  The steps are
+ *    k = 0: (1, 1), k = 1: (0, 1), k = 2: (1, 0) as (di, dj): librosa's default step_sizes_sigma in its order; weights_mul[k] and
+ *    weights_add[k] are librosa's.  All arithmetic is float32 and uncontracted.
+ *
+ *    Band.  band = 0: none.  band = R >= 1: the cell (i, j) is inside iff |j*(N-1) - i*(M-1)| <= R*max(N-1, 1), in int64.  A cell
+ *    outside has D = +inf.  band together with subseq is refused.
+ *
+ *    Recurrence.  D[0][0] = C[0][0];  with subseq, D[0][j] = C[0][j] for every j.  For every other inside cell:
+ *        e_k = fl(fl(weights_mul[k] * C[i][j]) + weights_add[k])
+ *        v_k = fl(D[i - di_k][j - dj_k] + e_k),  a predecessor outside the matrix counting as +inf
+ *        best = v_0;  for k = 1, 2:  if (v_k < best) best = v_k;        D[i][j] = best
+ *    The comparison is strict: the lowest k wins ties and a NaN v_k never replaces best (a NaN v_0 stays).  +0 and -0 compare
+ *    equal but the bits of D are what they are: 1*c + 0 is +0 for c = -0, and the operations are kept as written.  D[i][j] is a
+ *    function of the cell alone: it does not depend on the tile sizes, on pairs or on the pitches.
+ *
+ *    End cell.  Global: (N-1, M-1).  subseq: i = N-1 and the lowest j among the minimal D[N-1][j]; if any D[N-1][j] is a NaN the
+ *    pair has no path.
+ *    Backtrace.  At (i, j): D[i][j] a NaN or +inf: path_len[p] = -1 and nothing else is written for the pair (D apart).  Else
+ *    v_0..v_2 are recomputed from D and C with the same operations and the same selection, and the walk moves to that predecessor;
+ *    it ends at (0, 0) (global) or at i = 0 (subseq).  No step matrix is kept: the recomputation repeats the forward choice.
+ *    Outputs.  path_len[p] = L;  path_i and path_j at [p*path_pitch + n], n < L, ascending, the start first;  total[p] = D at the
+ *    end cell.  acc receives D: acc[p*acc_pair_pitch + i*acc_pitch + j].
+ *
+ *    Known answers.  An all-zero C, global: D = +0 everywhere (weights 1, 0); every v ties, so step 0 is taken while i > 0 and
+ *    j > 0: the path runs on the diagonal back from (N-1, M-1) and then along the edge to (0, 0).  A band whose diagonal slope
+ *    (M-1)/(N-1) exceeds 2R + 1 leaves no path: 65 x 200 has none with R = 1 and one with R = 2; 10 x 100 none with R = 4, one
+ *    with R = 5.
+ *    total against exact arithmetic, for non-negative costs and weights: min is monotone and every sum is of non-negative terms,
+ *    so a cell adds at most 3 roundings (two for e, one for v) to the relative error of its best predecessor, and a path has at
+ *    most N + M - 1 cells: relative 3 (N + M) 2^-24.
+ *
+ *    Differences from librosa.sequence.dtw: only the three unit steps; the band is the integer rule above, not the float rule of
+ *    fill_off_diagonal; the tie and NaN rules are the ones above.  Agreement with librosa has not been measured.
+ *
+ *    The kernels.  D is cut into tiles of JSGX_DTW_TILE_ROWS x JSGX_DTW_TILE_COLS; the tiles of one tile anti-diagonal are
+ *    independent, and "dtw_tiles" is launched once per tile anti-diagonal over pairs x (tiles on it), one wavefront per tile: a
+ *    tile reads its top row, left column and corner from D itself, which the earlier launches on the stream wrote, so no workgroup
+ *    waits for another.  Inside a tile the sweep is skewed: lane l owns row l and computes column s - l at step s; its three
+ *    neighbours are its own last value and the last two of lane l - 1, moved by a DPP wave shift.  C comes in and D goes out
+ *    through LDS in whole lines; the row pitch of 64 words lets lane l read column s - l from 64 different banks.  A tile wholly
+ *    outside the band is filled with +inf without reading C.  "dtw_backtrace" is one more kernel, one wavefront per pair: it
+ *    finds the end cell, then fetches 32 x 32 windows of D and C that end at the current cell and walks inside each (at least 31
+ *    steps per round trip to memory), writes the path backwards into the scratch and copies it out reversed.
+ * ------------------------------------------------------------------------------------------------ */
+/* The tile sizes were chosen by measurement on an MI355X (profiles/dtw_bench.md): the chain of dependent sweep steps decides the time, and
+ * N x M takes about (N / rows + M / cols) (cols + rows - 1) of them, least at cols = rows; 128 and 256 columns were 31 % and 82 % slower at
+ * 16384 x 16384.  The lane move is the DPP wave shift: 5 % ahead of __shfl_up, and it keeps the LDS pipe off the chain. */
+#define JSGX_DTW_TILE_ROWS 64
+#define JSGX_DTW_TILE_COLS 64
+#define JSGX_DTW_THREADS 64
+#define JSGX_DTW_LDS_BYTES 16656           /* static, of the forward kernel: the tile 64 x 64 words, the top row with its corner 65 + 3 */
+
+typedef struct jsgx_dtw_args {
+    const float* cost;          /* device floats: C */
+    int64_t cost_pitch;         /* >= m */
+    int64_t cost_pair_pitch;    /* pairs > 1: >= (n - 1) * cost_pitch + m */
+    int32_t pairs;              /* 1..65535 */
+    int32_t n;                  /* N, 1..JSGX_DTW_MAX_LEN */
+    int32_t m;                  /* M, 1..JSGX_DTW_MAX_LEN */
+    int32_t subseq;             /* 0 or 1 */
+    int32_t band;               /* 0, or R in 1..JSGX_DTW_MAX_LEN */
+    int32_t reserved0;          /* 0 */
+    float weights_mul[3];       /* finite */
+    float weights_add[3];       /* finite */
+    float* acc;                 /* device floats: D, required */
+    int64_t acc_pitch;          /* >= m */
+    int64_t acc_pair_pitch;     /* pairs > 1: >= (n - 1) * acc_pitch + m */
+    int32_t* path_i;            /* device int32 or NULL (then path_j NULL too) */
+    int32_t* path_j;
+    int64_t path_pitch;         /* pairs > 1 and paths given: >= max_path */
+    int32_t max_path;           /* paths given: >= n + m - 1 */
+    int32_t* path_len;          /* device int32 [pairs]; required with the paths, else optional */
+    float* total;               /* device floats [pairs] or NULL */
+} jsgx_dtw_args;
+
+/* The bytes of scratch the launch needs: 8 * pairs * (n + m - 1) where the paths are given, else 0.  Refused: what the launch
+ * refuses before it looks at the scratch. */
+JSGX_API int64_t jsgx_dtw_scratch_bytes(const jsgx_dtw_args* args);
+/* Enqueue only: no allocation, no synchronisation; capture works, a first launch included.  The kernels (one per tile
+ * anti-diagonal, then the backtrace where path_len or total is given) go onto the one stream as a plain chain.  Refused
+ * (JSGX_ERR_INVALID, nothing enqueued), in this order and before any device call: null args, a null cost, a null acc, one of
+ * path_i and path_j without the other, paths without path_len; a pointer that is not 4-byte aligned; pairs outside 1..65535, n
+ * outside 1..65536, m outside 1..65536, subseq other than 0 or 1, band outside 0..65536, a weight that is not finite; a non-zero
+ * reserved0; band together with subseq; max_path below n + m - 1 (paths given); cost_pitch below m, cost_pair_pitch that does
+ * not cover a plane (pairs > 1), the same for acc_pitch and acc_pair_pitch, path_pitch below max_path (pairs > 1, paths given);
+ * acc overlapping cost, another output (path_i, path_j, path_len, total) overlapping cost, another output overlapping acc; a
+ * null scratch, a scratch that is not 4-byte aligned, scratch_bytes below the size above (each only where that size is not 0).
+ * Then JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_dtw_launch(const jsgx_dtw_args* args, void* scratch, int64_t scratch_bytes, void* stream);
+/* What the launch enqueues, without a device: the name of the forward kernel ("dtw_tiles"), the tile sizes, the number of kernel
+ * launches (the tile anti-diagonals, ceil(n / tile_rows) + ceil(m / tile_cols) - 1, plus one for the backtrace where path_len or
+ * total is given), JSGX_DTW_THREADS and JSGX_DTW_LDS_BYTES.  Any output pointer may be NULL (name: else name_len >= 16).  Refused:
+ * a name_len below 16 with a name, then what the scratch size refuses. */
+JSGX_API int jsgx_dtw_plan(const jsgx_dtw_args* args, char* name, int name_len, int32_t* tile_rows, int32_t* tile_cols, int32_t* n_launches,
+                           int32_t* threads, int32_t* lds_bytes);
 
 #ifdef __cplusplus
 }

@@ -31,6 +31,25 @@ class BeatArgs(C.Structure):
                 ("local_score", C.c_void_p), ("local_pitch", C.c_int64), ("cum_score", C.c_void_p), ("cum_pitch", C.c_int64)]
 
 
+METRIC_SQEUCLIDEAN, METRIC_EUCLIDEAN, METRIC_COSINE = 0, 1, 2
+CDIST_MAX_FEATURES, DTW_MAX_LEN = 1024, 65536
+CDIST_TILE, CDIST_THREADS, CDIST_LDS_BYTES = 64, 256, 17408
+DTW_TILE_ROWS, DTW_TILE_COLS, DTW_THREADS, DTW_LDS_BYTES = 64, 64, 64, 16656
+
+
+class CdistArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_frame_pitch", C.c_int64), ("x_pair_pitch", C.c_int64), ("y", C.c_void_p), ("y_frame_pitch", C.c_int64),
+                ("y_pair_pitch", C.c_int64), ("pairs", C.c_int32), ("n_features", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("metric", C.c_int32),
+                ("reserved0", C.c_int32), ("cost", C.c_void_p), ("cost_pitch", C.c_int64), ("cost_pair_pitch", C.c_int64)]
+
+
+class DtwArgs(C.Structure):
+    _fields_ = [("cost", C.c_void_p), ("cost_pitch", C.c_int64), ("cost_pair_pitch", C.c_int64), ("pairs", C.c_int32), ("n", C.c_int32), ("m", C.c_int32),
+                ("subseq", C.c_int32), ("band", C.c_int32), ("reserved0", C.c_int32), ("weights_mul", C.c_float * 3), ("weights_add", C.c_float * 3),
+                ("acc", C.c_void_p), ("acc_pitch", C.c_int64), ("acc_pair_pitch", C.c_int64), ("path_i", C.c_void_p), ("path_j", C.c_void_p),
+                ("path_pitch", C.c_int64), ("max_path", C.c_int32), ("path_len", C.c_void_p), ("total", C.c_void_p)]
+
+
 # every symbol include/jsgx.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -40,6 +59,11 @@ SIGNATURES = {
     "jsgx_beat_scratch_bytes": (C.c_int64, [C.POINTER(BeatArgs)]),
     "jsgx_beat_launch": (C.c_int, [C.POINTER(BeatArgs), _P, C.c_int64, _P]),
     "jsgx_beat_plan": (C.c_int, [C.POINTER(BeatArgs), C.c_int32, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "jsgx_cdist_launch": (C.c_int, [C.POINTER(CdistArgs), _P]),
+    "jsgx_cdist_plan": (C.c_int, [C.POINTER(CdistArgs), C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "jsgx_dtw_scratch_bytes": (C.c_int64, [C.POINTER(DtwArgs)]),
+    "jsgx_dtw_launch": (C.c_int, [C.POINTER(DtwArgs), _P, C.c_int64, _P]),
+    "jsgx_dtw_plan": (C.c_int, [C.POINTER(DtwArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 5),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-// libjsgx.so, what its two units share (include/jsgx.h): the error text, the argument check and the float32 routines whose every
+// libjsgx.so, what its units share (include/jsgx.h): the error text, the argument check and the float32 routines whose every
 // operation the header states.  Nothing of libjsg.so is used here.
 #pragma once
 
@@ -22,6 +22,11 @@ int fail(int code, const char* who, const char* what);
 // every refusal of jsgx_beat_launch that does not look at the scratch, in the header's order
 int beat_check(const jsgx_beat_args* g, const char* who);
 int64_t beat_scratch_bytes(const jsgx_beat_args* g);
+// sections 2 and 3 (jsgx_dtw_host.cpp): every refusal that does not look at the scratch, in the header's order
+int cdist_check(const jsgx_cdist_args* g, const char* who);
+int dtw_check(const jsgx_dtw_args* g, const char* who);
+int64_t dtw_scratch_bytes(const jsgx_dtw_args* g);
+int dtw_launches(const jsgx_dtw_args* g);          // the kernels jsgx_dtw_launch enqueues
 
 constexpr int kBeatRing = 4096;                                  // >= 2 * JSGX_BEAT_MAX_PERIOD + JSGX_BEAT_THREADS, a power of two
 constexpr int kBeatPen = 2 * JSGX_BEAT_MAX_PERIOD + 4;           // pen[tau], tau <= 2P

@@ -1821,6 +1821,151 @@ def beat_track_audio(x, sr, n_fft=2048, hop=512, n_mels=128, win_length=384, sta
 
 
 # --------------------------------------------------------------------------------------------------
+# pairwise cost and dynamic time warping (include/jsgx.h, sections 2 and 3: libjsgx.so)
+# --------------------------------------------------------------------------------------------------
+_METRICS = {"sqeuclidean": capix.METRIC_SQEUCLIDEAN, "euclidean": capix.METRIC_EUCLIDEAN, "cosine": capix.METRIC_COSINE}
+
+
+def _planes(t, what: str, dtype=None):
+    """A float32 CUDA tensor [rows][cols] or [pairs][rows][cols] with unit stride along cols, as [pairs][rows][cols]."""
+    import torch
+    t = t[None] if t.dim() == 2 else t
+    assert t.is_cuda and t.dtype == (dtype or torch.float32) and t.dim() == 3 and (t.stride(2) == 1 or t.shape[2] == 1), \
+        f"{what}: CUDA [rows][cols] or [pairs][rows][cols], unit stride along cols"
+    return t
+
+
+def _cdist_args(d_x, d_y, d_cost, metric) -> capix.CdistArgs:
+    c = _planes(d_cost, "d_cost")
+    P, N, M = c.shape
+    x, y = _planes(d_x, "d_x"), _planes(d_y, "d_y")
+    K = x.shape[2]
+    assert x.shape[1] == N and y.shape[1] == M and y.shape[2] == K and x.shape[0] in (1, P) and y.shape[0] in (1, P), \
+        "d_x [pairs or 1][n][features], d_y [pairs or 1][m][features], d_cost [pairs][n][m]"
+    pair = lambda t: 0 if t.shape[0] == 1 else t.stride(0)      # one sequence for every pair: a pair pitch of 0
+    return capix.CdistArgs(x.data_ptr(), x.stride(1), pair(x), y.data_ptr(), y.stride(1), pair(y), P, K, N, M, _named(_METRICS, metric, "metric"), 0,
+                           c.data_ptr(), c.stride(1), c.stride(0))
+
+
+def cdist_launch(d_x, d_y, d_cost, *, metric: str = "euclidean", stream: int | None = None):
+    """jsgx_cdist_launch: d_x float32 [n][features] or [pairs][n][features], d_y likewise with m frames (frame-major, what the feature
+    kernels write; a 2-D tensor, a leading 1 or an expanded tensor is one sequence shared by every pair) -> d_cost float32 [n][m] or
+    [pairs][n][m].  metric: "sqeuclidean", "euclidean" or "cosine" (1 for a zero vector).  Enqueue only."""
+    a = _cdist_args(d_x, d_y, d_cost, metric)
+    capix.check(capix.lib().jsgx_cdist_launch(C.byref(a), _stream_handle(stream, d_cost)))
+
+
+def cdist_plan(n: int, m: int, n_features: int, pairs: int = 1, metric: str = "euclidean"):
+    """jsgx_cdist_plan: (kernel name, lanes per workgroup, bytes of LDS per workgroup) for this shape.  Needs no device."""
+    a = capix.CdistArgs(1 << 44, int(n_features), int(n) * int(n_features), 2 << 44, int(n_features), int(m) * int(n_features), int(pairs), int(n_features),
+                        int(n), int(m), _named(_METRICS, metric, "metric"), 0, 3 << 44, int(m), int(n) * int(m))      # never dereferenced
+    name, threads, lds = C.create_string_buffer(32), C.c_int32(), C.c_int32()
+    capix.check(capix.lib().jsgx_cdist_plan(C.byref(a), name, 32, C.byref(threads), C.byref(lds)))
+    return name.value.decode(), threads.value, lds.value
+
+
+def cdist(X, Y, metric: str = "euclidean"):
+    """The pairwise cost of two feature sequences X [N, K] and Y [M, K] (numpy arrays or float32 CUDA tensors, frame-major; a leading
+    axis of P pairs on either or both) -> a CUDA tensor [N, M] or [P, N, M]: scipy.spatial.distance.cdist for "sqeuclidean", "euclidean"
+    and "cosine", with every operation as include/jsgx.h states it."""
+    import torch
+    x, _ = _to_cuda(X)
+    y, _ = _to_cuda(Y)
+    assert x.dim() in (2, 3) and y.dim() in (2, 3), "cdist: X [N, K] or [P, N, K], Y [M, K] or [P, M, K]"
+    x, y = x.contiguous(), y.contiguous()
+    P = max(x.shape[0] if x.dim() == 3 else 1, y.shape[0] if y.dim() == 3 else 1)
+    shape = (x.shape[-2], y.shape[-2])
+    cost = torch.empty(((P,) if x.dim() == 3 or y.dim() == 3 else ()) + shape, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(_device_index(x)):
+        cdist_launch(x, y, cost, metric=metric)
+    return cost
+
+
+def _dtw_args(d_cost, d_acc, weights_mul, weights_add, subseq, band, d_path_i, d_path_j, d_path_len, d_total) -> capix.DtwArgs:
+    import torch
+    c, d = _planes(d_cost, "d_cost"), _planes(d_acc, "d_acc")
+    P, N, M = c.shape
+    assert tuple(d.shape) == (P, N, M), "d_acc: the shape of d_cost"
+    ptr = lambda t: None if t is None else t.data_ptr()
+    path_pitch = max_path = 0
+    if d_path_i is not None and d_path_j is not None:
+        pi, pj = (t[None] if t.dim() == 1 else t for t in (d_path_i, d_path_j))
+        for t in (pi, pj):
+            assert t.is_cuda and t.dtype == torch.int32 and t.dim() == 2 and t.shape[0] == P and (t.stride(1) == 1 or t.shape[1] == 1), "d_path_i, d_path_j: int32 CUDA [pairs][max_path]"
+        assert pi.shape == pj.shape and pi.stride(0) == pj.stride(0), "d_path_i and d_path_j: one shape and pitch"
+        path_pitch, max_path = pi.stride(0), pi.shape[1]
+    for t, dtype, what in ((d_path_len, torch.int32, "d_path_len: int32"), (d_total, torch.float32, "d_total: float32")):
+        assert t is None or (t.is_cuda and t.dtype == dtype and t.dim() == 1 and t.shape[0] >= P and t.is_contiguous()), f"{what} CUDA [pairs]"
+    wm = (1.0, 1.0, 1.0) if weights_mul is None else tuple(float(w) for w in weights_mul)
+    wa = (0.0, 0.0, 0.0) if weights_add is None else tuple(float(w) for w in weights_add)
+    assert len(wm) == 3 and len(wa) == 3, "weights_mul, weights_add: three values, for the steps (1, 1), (0, 1), (1, 0)"
+    return capix.DtwArgs(c.data_ptr(), c.stride(1), c.stride(0), P, N, M, int(bool(subseq)), int(band), 0, (C.c_float * 3)(*wm), (C.c_float * 3)(*wa),
+                         d.data_ptr(), d.stride(1), d.stride(0), ptr(d_path_i), ptr(d_path_j), path_pitch, max_path, ptr(d_path_len), ptr(d_total))
+
+
+def dtw_scratch_bytes(d_cost, d_acc, *, weights_mul=None, weights_add=None, subseq: bool = False, band: int = 0, d_path_i=None, d_path_j=None,
+                      d_path_len=None, d_total=None) -> int:
+    """jsgx_dtw_scratch_bytes: the bytes of scratch dtw_launch needs for these arguments (0 without paths)."""
+    a = _dtw_args(d_cost, d_acc, weights_mul, weights_add, subseq, band, d_path_i, d_path_j, d_path_len, d_total)
+    return int(capix.check(capix.lib().jsgx_dtw_scratch_bytes(C.byref(a))))
+
+
+def dtw_launch(d_cost, d_acc, *, weights_mul=None, weights_add=None, subseq: bool = False, band: int = 0, d_path_i=None, d_path_j=None,
+               d_path_len=None, d_total=None, d_scratch=None, stream: int | None = None):
+    """jsgx_dtw_launch: d_cost float32 [n][m] or [pairs][n][m] -> d_acc (the accumulated cost D, the same shape), and where given
+    d_path_i, d_path_j int32 [pairs][max_path >= n + m - 1] (the warping path, ascending), d_path_len int32 [pairs] (its length; -1:
+    no path) and d_total float32 [pairs] (D at the end cell).  The steps are (1, 1), (0, 1), (1, 0) with librosa's weights_mul and
+    weights_add; band: 0 or the half-width R of include/jsgx.h.  Enqueue only: one kernel per tile anti-diagonal, then the backtrace."""
+    import torch
+    a = _dtw_args(d_cost, d_acc, weights_mul, weights_add, subseq, band, d_path_i, d_path_j, d_path_len, d_total)
+    d_scratch, stream = _scratch_and_stream(d_scratch, stream, d_cost, lambda: max(1, capix.check(capix.lib().jsgx_dtw_scratch_bytes(C.byref(a))) // 4), torch.int32,
+                                            any_dtype=True)
+    capix.check(capix.lib().jsgx_dtw_launch(C.byref(a), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), stream))
+
+
+def dtw_plan(n: int, m: int, pairs: int = 1, backtrack: bool = True):
+    """jsgx_dtw_plan: (kernel name, tile rows, tile columns, kernel launches, lanes per workgroup, bytes of LDS per workgroup) for this
+    shape: one launch per tile anti-diagonal and one for the backtrace.  Needs no device."""
+    a = capix.DtwArgs(cost=1 << 44, cost_pitch=int(m), cost_pair_pitch=int(n) * int(m), pairs=int(pairs), n=int(n), m=int(m), weights_mul=(C.c_float * 3)(1, 1, 1),
+                      acc=2 << 44, acc_pitch=int(m), acc_pair_pitch=int(n) * int(m), path_len=(3 << 44) if backtrack else None)      # never dereferenced
+    name, out = C.create_string_buffer(32), [C.c_int32() for _ in range(5)]
+    capix.check(capix.lib().jsgx_dtw_plan(C.byref(a), name, 32, *[C.byref(o) for o in out]))
+    return (name.value.decode(),) + tuple(o.value for o in out)
+
+
+def dtw(X=None, Y=None, *, C=None, metric="euclidean", weights_mul=None, weights_add=None, subseq=False, band=0, backtrack=True):
+    """librosa.sequence.dtw on the GPU for the default steps: from two feature sequences X [N, K] and Y [M, K] (frame-major; numpy arrays
+    or float32 CUDA tensors) or a cost plane C [N, M] -> (D, wp): the accumulated cost [N, M] and the warping path wp int32 [L, 2] as CUDA
+    tensors, ascending from the start (librosa returns it descending).  backtrack False: D alone.  A leading axis of P pairs is allowed:
+    D is [P, N, M] and wp a list.  Reading the path lengths is the one host synchronisation; JsgError where a pair has no path (a band too
+    narrow, a NaN).  band: 0 or the half-width R of include/jsgx.h; differences from librosa are listed there."""
+    import torch
+    assert (C is None) != (X is None and Y is None) and (X is None) == (Y is None), "dtw: X and Y, or C"
+    if C is None:
+        cost = cdist(X, Y, metric)
+    else:
+        cost, _ = _to_cuda(C)
+        assert cost.dim() in (2, 3), "dtw: C [N, M] or [P, N, M]"
+        cost = cost.contiguous()
+    batched = cost.dim() == 3
+    c3 = cost if batched else cost[None]
+    P, N, M = c3.shape
+    D = torch.empty_like(c3)
+    with torch.cuda.device(_device_index(cost)):
+        if not backtrack:
+            dtw_launch(c3, D, weights_mul=weights_mul, weights_add=weights_add, subseq=subseq, band=band)
+            return D if batched else D[0]
+        path = torch.empty((2, P, N + M - 1), dtype=torch.int32, device=cost.device)
+        length = torch.empty((P,), dtype=torch.int32, device=cost.device)
+        dtw_launch(c3, D, weights_mul=weights_mul, weights_add=weights_add, subseq=subseq, band=band, d_path_i=path[0], d_path_j=path[1], d_path_len=length)
+    lengths = length.tolist()           # the one host synchronisation
+    if min(lengths) < 0:
+        raise JsgError(capix.JSGX_ERR_INVALID, f"dtw: no warping path for pair {lengths.index(min(lengths))} (a band too narrow for the shape, or a NaN)")
+    wp = [torch.stack((path[0, p, :L], path[1, p, :L]), dim=1) for p, L in enumerate(lengths)]
+    return (D, wp) if batched else (D[0], wp[0])
+
+
+# --------------------------------------------------------------------------------------------------
 # cepstral coefficients and delta features (include/jsg.h, section 2k)
 # --------------------------------------------------------------------------------------------------
 _NORMS = {"ortho": capi.DCT_NORM_ORTHO, None: capi.DCT_NORM_NONE, "none": capi.DCT_NORM_NONE}
