@@ -11,7 +11,7 @@ OBJ   := jadespectrogram_amd/build
 lib: $(OUT) $(OUTX)
 
 HIPFLAGS := -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude --offload-arch=$(ARCH) -fno-slp-vectorize -mllvm -amdgpu-kernarg-preload-count=16
-KDEPS    := $(SRC)/jsg_stft_kernel.h $(SRC)/jsg_runs_grid.h $(SRC)/jsg_internal.h $(SRC)/jsg_exact_math.h include/jsg.h
+KDEPS    := $(SRC)/jsg_stft_kernel.h $(SRC)/jsg_runs_grid.h $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h $(SRC)/jsg_exact_math.h include/jsg.h
 
 $(OBJ)/jsg_kernels.o: $(SRC)/jsg_kernels.hip $(KDEPS)
 	@mkdir -p $(OBJ)
@@ -29,35 +29,35 @@ $(OBJ)/jsg_filterbank.o: $(SRC)/jsg_filterbank.hip $(KDEPS)
 $(OBJ)/jsg_display_axis.o: $(SRC)/jsg_display_axis.hip $(KDEPS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_cstft.o: $(SRC)/jsg_cstft.hip $(SRC)/jsg_internal.h include/jsg.h
+$(OBJ)/jsg_cstft.o: $(SRC)/jsg_cstft.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_pvoc.o: $(SRC)/jsg_pvoc.hip $(SRC)/jsg_internal.h include/jsg.h
+$(OBJ)/jsg_pvoc.o: $(SRC)/jsg_pvoc.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_hpss.o: $(SRC)/jsg_hpss.hip $(SRC)/jsg_internal.h include/jsg.h
+$(OBJ)/jsg_hpss.o: $(SRC)/jsg_hpss.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_resample.o: $(SRC)/jsg_resample.hip $(SRC)/jsg_internal.h include/jsg.h
+$(OBJ)/jsg_resample.o: $(SRC)/jsg_resample.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_cqt.o: $(SRC)/jsg_cqt.hip $(SRC)/jsg_internal.h include/jsg.h
+$(OBJ)/jsg_cqt.o: $(SRC)/jsg_cqt.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_yin.o: $(SRC)/jsg_yin.hip $(SRC)/jsg_internal.h include/jsg.h
+$(OBJ)/jsg_yin.o: $(SRC)/jsg_yin.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_rhythm.o: $(SRC)/jsg_rhythm.hip $(SRC)/jsg_internal.h include/jsg.h
+$(OBJ)/jsg_rhythm.o: $(SRC)/jsg_rhythm.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_cepstral.o: $(SRC)/jsg_cepstral.hip $(SRC)/jsg_internal.h include/jsg.h
+$(OBJ)/jsg_cepstral.o: $(SRC)/jsg_cepstral.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_spectral.o: $(SRC)/jsg_spectral.hip $(SRC)/jsg_internal.h $(SRC)/jsg_exact_math.h include/jsg.h
+$(OBJ)/jsg_spectral.o: $(SRC)/jsg_spectral.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h $(SRC)/jsg_exact_math.h include/jsg.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(OBJ)/%.o: $(SRC)/%.cpp $(SRC)/jsg_internal.h $(SRC)/jsg_block_queue.h $(SRC)/jsg_exact_math.h $(SRC)/jsg_colormap_tables.inc include/jsg.h
+$(OBJ)/%.o: $(SRC)/%.cpp $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h $(SRC)/jsg_block_queue.h $(SRC)/jsg_exact_math.h $(SRC)/jsg_colormap_tables.inc include/jsg.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude -ffp-contract=off -D__HIP_PLATFORM_AMD__ -c $< -o $@
 

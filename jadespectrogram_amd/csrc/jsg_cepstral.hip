@@ -237,32 +237,28 @@ namespace {
 // The grid is what a compute unit holds at a time, by the LDS of this call and by the registers of this instantiation, so that no
 // workgroup waits for another to end (each stages the table and takes a fixed share of the items).
 template <int MB>
-hipError_t mfcc_enqueue(const MfArgs& k, int dev, long long by_lds, size_t lds_bytes, hipStream_t s, bool first) {
-    static std::atomic<int> by_regs[64];        // workgroups per compute unit that the registers allow, per device
+hipError_t mfcc_enqueue(const MfArgs& k, int dev, long long by_lds, size_t lds_bytes, hipStream_t s) {
+    static std::atomic<int> by_regs[64];        // workgroups per compute unit that the registers allow, per device; asked once
     int regs = dev >= 0 && dev < 64 ? by_regs[dev].load(std::memory_order_acquire) : 0;
-    // the kernel may ask for more than 48 KB of dynamic LDS: said once per device, before the first launch there
-    if (first || regs < 1) {
-        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&mfcc_kernel<MB>), hipFuncAttributeMaxDynamicSharedMemorySize, kMfccLdsOne * 4);
-        if (err != hipSuccess) return err;
-        err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&regs, mfcc_kernel<MB>, kMfccThreads, 0);
+    if (regs < 1) {
+        const hipError_t err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&regs, mfcc_kernel<MB>, kMfccThreads, 0);
         if (err != hipSuccess) return err;
         regs = std::max(1, regs);
         if (dev >= 0 && dev < 64) by_regs[dev].store(regs, std::memory_order_release);
     }
-    const long long per_cu = std::max<long long>(1, std::min<long long>(by_lds, regs));
-    const dim3 grid((unsigned)std::min<long long>(k.n_items, (long long)cu_count_of_device(dev) * per_cu));
-    hipLaunchKernelGGL((mfcc_kernel<MB>), grid, dim3(kMfccThreads), lds_bytes, s, k);
-    return hipGetLastError();
+    const dim3 grid(resident_grid(k.n_items, dev, std::max<long long>(1, std::min<long long>(by_lds, regs))));
+    static OncePerDevice told;      // of this path: one bit
+    return launch_large_lds(told, dev, 1u, mfcc_kernel<MB>, kMfccLdsOne * 4, grid, dim3(kMfccThreads), lds_bytes, s, k);
 }
 
 }  // namespace
 
 extern "C" int jsg_mfcc_launch(const jsg_mfcc_args* g, void* stream) {
     static const char* who = "jsg_mfcc_launch";
-    const int rc = mfcc_check(g, who);
-    if (rc != JSG_OK) return rc;
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return jsg_fail_who(JSG_ERR_NO_DEVICE, who, "no HIP device");
+    int rc = mfcc_check(g, who);
+    if (rc == JSG_OK) rc = current_device(&dev, who);
+    if (rc != JSG_OK) return rc;
     // every refusal is behind us
     MfccPlan p{};
     mfcc_resolve(g, &p);
@@ -284,28 +280,23 @@ extern "C" int jsg_mfcc_launch(const jsg_mfcc_args* g, void* stream) {
     k.vec = (g->n_in % 4 == 0) && (reinterpret_cast<uintptr_t>(g->in) % 16 == 0) && (g->frame_pitch % 4 == 0) && (k.row_pitch % 4 == 0);
     k.pre = k.vec && ((long long)p.F * (g->n_in / 4) + kMfccThreads - 1) / kMfccThreads <= kMfccPre;
     const size_t lds_bytes = sizeof(float) * (size_t)p.lds_floats;
+    // tests/test_gpu_cepstral_grid.py reads the cap from the next line
     const long long by_lds = std::min<long long>(8, kMfccLdsOne / p.lds_floats);      // 2048 threads per compute unit
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    // one flag per device and path
-    static std::atomic<unsigned> told[64];
-    const unsigned bit = 1u << p.MB;
-    const bool first = dev < 0 || dev >= 64 || !(told[dev].load(std::memory_order_acquire) & bit);
-    const hipError_t err = p.MB == 4 ? mfcc_enqueue<4>(k, dev, by_lds, lds_bytes, s, first)
-                         : p.MB == 5 ? mfcc_enqueue<5>(k, dev, by_lds, lds_bytes, s, first)
-                         : p.MB == 8 ? mfcc_enqueue<8>(k, dev, by_lds, lds_bytes, s, first)
-                         : p.MB == 10 ? mfcc_enqueue<10>(k, dev, by_lds, lds_bytes, s, first)
-                                      : mfcc_enqueue<16>(k, dev, by_lds, lds_bytes, s, first);
-    if (err != hipSuccess) return jsg_fail_hip(err, who);
-    if (first && dev >= 0 && dev < 64) told[dev].fetch_or(bit, std::memory_order_release);
-    return JSG_OK;
+    const hipError_t err = p.MB == 4 ? mfcc_enqueue<4>(k, dev, by_lds, lds_bytes, s)
+                         : p.MB == 5 ? mfcc_enqueue<5>(k, dev, by_lds, lds_bytes, s)
+                         : p.MB == 8 ? mfcc_enqueue<8>(k, dev, by_lds, lds_bytes, s)
+                         : p.MB == 10 ? mfcc_enqueue<10>(k, dev, by_lds, lds_bytes, s)
+                                      : mfcc_enqueue<16>(k, dev, by_lds, lds_bytes, s);
+    return err == hipSuccess ? JSG_OK : jsg_fail_hip(err, who);
 }
 
 extern "C" int jsg_delta_launch(const jsg_delta_args* g, void* stream) {
     static const char* who = "jsg_delta_launch";
-    const int rc = delta_check(g, who);
-    if (rc != JSG_OK) return rc;
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return jsg_fail_who(JSG_ERR_NO_DEVICE, who, "no HIP device");
+    int rc = delta_check(g, who);
+    if (rc == JSG_OK) rc = current_device(&dev, who);
+    if (rc != JSG_OK) return rc;
     // every refusal is behind us
     DlArgs k{};
     const bool multi = g->rows > 1;
@@ -323,8 +314,6 @@ extern "C" int jsg_delta_launch(const jsg_delta_args* g, void* stream) {
     k.FC = std::max(1, 4096 / g->n_coeffs);
     k.chunks = (g->n_frames + k.FC - 1) / k.FC;
     k.n_items = (long long)g->rows * k.chunks;
-    const dim3 grid((unsigned)std::min<long long>(k.n_items, (long long)cu_count_of_device(dev) * 8));
-    hipLaunchKernelGGL(delta_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? JSG_OK : jsg_fail_hip(err, who);
+    hipLaunchKernelGGL(delta_kernel, dim3(resident_grid(k.n_items, dev, 8)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k);
+    return finish_launch(who);
 }

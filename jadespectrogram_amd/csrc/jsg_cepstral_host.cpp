@@ -3,17 +3,12 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 
 #include "jsg_internal.h"
 
 namespace jsg {
 
 namespace {
-typedef __int128 i128;
-
-i128 addr(const void* p) { return (i128)reinterpret_cast<uintptr_t>(p); }
-bool overlap(i128 a0, i128 a_bytes, i128 b0, i128 b_bytes) { return a0 && b0 && a0 < b0 + b_bytes && b0 < a0 + a_bytes; }
 const double kPi = 3.14159265358979323846;
 }  // namespace
 
@@ -22,9 +17,9 @@ int mfcc_check(const jsg_mfcc_args* g, const char* who) {
     if (!g->in) return jsg_fail_who(JSG_ERR_INVALID, who, "null in");
     if (!g->table) return jsg_fail_who(JSG_ERR_INVALID, who, "null table");
     if (!g->out) return jsg_fail_who(JSG_ERR_INVALID, who, "null out");
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(g->in) | reinterpret_cast<uintptr_t>(g->table) | reinterpret_cast<uintptr_t>(g->out);
-    if ((bits & 3) != 0) return jsg_fail_who(JSG_ERR_INVALID, who, "pointers must be 4-byte aligned");
-    if (g->rows < 1 || g->rows > 65535) return jsg_fail_who(JSG_ERR_INVALID, who, "rows must be in 1..65535");
+    int rc = check_aligned4(who, g->in, g->table, g->out);
+    if (rc == JSG_OK) rc = check_rows(g->rows, who);
+    if (rc != JSG_OK) return rc;
     if (g->n_in < 1 || g->n_in > JSG_MFCC_MAX_BANDS) return jsg_fail_who(JSG_ERR_INVALID, who, "n_in must be in 1..4096");
     if (g->n_out < 1 || g->n_out > JSG_MFCC_MAX_COEFFS) return jsg_fail_who(JSG_ERR_INVALID, who, "n_out must be in 1..4096");
     if ((long long)g->n_in * g->n_out > JSG_MFCC_MAX_TABLE) return jsg_fail_who(JSG_ERR_INVALID, who, "n_in*n_out must be at most 32768");
@@ -32,14 +27,13 @@ int mfcc_check(const jsg_mfcc_args* g, const char* who) {
     if (g->chunk_frames < 0 || g->chunk_frames > 65536) return jsg_fail_who(JSG_ERR_INVALID, who, "chunk_frames must be 0 or in 1..65536");
     if (g->frame_pitch < g->n_in) return jsg_fail_who(JSG_ERR_INVALID, who, "frame_pitch smaller than n_in");
     const bool multi = g->rows > 1;
-    const i128 plane = (i128)(g->n_frames - 1) * g->frame_pitch + g->n_in;
-    if (multi && (i128)g->row_pitch < plane) return jsg_fail_who(JSG_ERR_INVALID, who, "row_pitch smaller than (n_frames-1)*frame_pitch + n_in");
+    const i128 in_plane = plane(g->n_frames, g->frame_pitch, g->n_in);
+    if (multi && (i128)g->row_pitch < in_plane) return jsg_fail_who(JSG_ERR_INVALID, who, "row_pitch smaller than (n_frames-1)*frame_pitch + n_in");
     if (g->out_frame_pitch < g->n_out) return jsg_fail_who(JSG_ERR_INVALID, who, "out_frame_pitch smaller than n_out");
-    const i128 out_plane = (i128)(g->n_frames - 1) * g->out_frame_pitch + g->n_out;
+    const i128 out_plane = plane(g->n_frames, g->out_frame_pitch, g->n_out);
     if (multi && (i128)g->out_row_pitch < out_plane) return jsg_fail_who(JSG_ERR_INVALID, who, "out_row_pitch smaller than (n_frames-1)*out_frame_pitch + n_out");
-    const i128 rows1 = g->rows - 1;
-    const i128 out_bytes = 4 * (rows1 * (multi ? g->out_row_pitch : 0) + out_plane);
-    if (overlap(addr(g->in), 4 * (rows1 * (multi ? g->row_pitch : 0) + plane), addr(g->out), out_bytes)) return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps in");
+    const i128 out_bytes = span_bytes(g->rows, g->out_row_pitch, out_plane, 4);
+    if (overlap(addr(g->in), span_bytes(g->rows, g->row_pitch, in_plane, 4), addr(g->out), out_bytes)) return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps in");
     if (overlap(addr(g->table), 4 * (i128)g->n_in * g->n_out, addr(g->out), out_bytes)) return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps table");
     return JSG_OK;
 }
@@ -74,9 +68,9 @@ int delta_check(const jsg_delta_args* g, const char* who) {
     if (!g->in) return jsg_fail_who(JSG_ERR_INVALID, who, "null in");
     if (!g->weights) return jsg_fail_who(JSG_ERR_INVALID, who, "null weights");
     if (!g->out) return jsg_fail_who(JSG_ERR_INVALID, who, "null out");
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(g->in) | reinterpret_cast<uintptr_t>(g->weights) | reinterpret_cast<uintptr_t>(g->out);
-    if ((bits & 3) != 0) return jsg_fail_who(JSG_ERR_INVALID, who, "pointers must be 4-byte aligned");
-    if (g->rows < 1 || g->rows > 65535) return jsg_fail_who(JSG_ERR_INVALID, who, "rows must be in 1..65535");
+    int rc = check_aligned4(who, g->in, g->weights, g->out);
+    if (rc == JSG_OK) rc = check_rows(g->rows, who);
+    if (rc != JSG_OK) return rc;
     if (g->n_coeffs < 1 || g->n_coeffs > JSG_DELTA_MAX_COEFFS) return jsg_fail_who(JSG_ERR_INVALID, who, "n_coeffs must be in 1..65536");
     if (g->n_frames < 1 || g->n_frames >= (1ll << 31)) return jsg_fail_who(JSG_ERR_INVALID, who, "n_frames must be in 1..2^31-1");
     if (g->width < 3 || g->width > JSG_DELTA_MAX_WIDTH || g->width % 2 == 0) return jsg_fail_who(JSG_ERR_INVALID, who, "width must be odd and in 3..255");
@@ -84,14 +78,13 @@ int delta_check(const jsg_delta_args* g, const char* who) {
     if (g->mode == JSG_DELTA_EDGE_INTERP && g->n_frames < g->width) return jsg_fail_who(JSG_ERR_INVALID, who, "n_frames smaller than width (interp)");
     if (g->frame_pitch < g->n_coeffs) return jsg_fail_who(JSG_ERR_INVALID, who, "frame_pitch smaller than n_coeffs");
     const bool multi = g->rows > 1;
-    const i128 plane = (i128)(g->n_frames - 1) * g->frame_pitch + g->n_coeffs;
-    if (multi && (i128)g->row_pitch < plane) return jsg_fail_who(JSG_ERR_INVALID, who, "row_pitch smaller than (n_frames-1)*frame_pitch + n_coeffs");
+    const i128 in_plane = plane(g->n_frames, g->frame_pitch, g->n_coeffs);
+    if (multi && (i128)g->row_pitch < in_plane) return jsg_fail_who(JSG_ERR_INVALID, who, "row_pitch smaller than (n_frames-1)*frame_pitch + n_coeffs");
     if (g->out_frame_pitch < g->n_coeffs) return jsg_fail_who(JSG_ERR_INVALID, who, "out_frame_pitch smaller than n_coeffs");
-    const i128 out_plane = (i128)(g->n_frames - 1) * g->out_frame_pitch + g->n_coeffs;
+    const i128 out_plane = plane(g->n_frames, g->out_frame_pitch, g->n_coeffs);
     if (multi && (i128)g->out_row_pitch < out_plane) return jsg_fail_who(JSG_ERR_INVALID, who, "out_row_pitch smaller than (n_frames-1)*out_frame_pitch + n_coeffs");
-    const i128 rows1 = g->rows - 1;
-    const i128 out_bytes = 4 * (rows1 * (multi ? g->out_row_pitch : 0) + out_plane);
-    if (overlap(addr(g->in), 4 * (rows1 * (multi ? g->row_pitch : 0) + plane), addr(g->out), out_bytes)) return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps in");
+    const i128 out_bytes = span_bytes(g->rows, g->out_row_pitch, out_plane, 4);
+    if (overlap(addr(g->in), span_bytes(g->rows, g->row_pitch, in_plane, 4), addr(g->out), out_bytes)) return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps in");
     if (overlap(addr(g->weights), 4 * (i128)g->width, addr(g->out), out_bytes)) return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps weights");
     return JSG_OK;
 }
@@ -100,31 +93,28 @@ int delta_check(const jsg_delta_args* g, const char* who) {
 
 using namespace jsg;
 
-extern "C" {
-
-int jsg_mfcc_plan(const jsg_mfcc_args* g, char* name, int name_len, int32_t* frames_per_item, int32_t* lds_bytes) {
-    static const char* who = "jsg_mfcc_plan";
-    if (name && name_len < 24) return jsg_fail_who(JSG_ERR_INVALID, who, "bad argument");
-    const int rc = mfcc_check(g, who);
+namespace {
+// jsg_mfcc_plan (the name is optional) and jsg_mfcc_kernel_name (the name is all it gives)
+int mfcc_plan_call(const char* who, const jsg_mfcc_args* g, char* name, int name_len, bool need_name, int32_t* frames_per_item, int32_t* lds_bytes) {
+    int rc = check_name_buffer(who, name, name_len, need_name);
+    if (rc == JSG_OK) rc = mfcc_check(g, who);
     if (rc != JSG_OK) return rc;
     MfccPlan p{};
     mfcc_resolve(g, &p);
-    if (name) std::strncpy(name, mfcc_path_name(p), name_len);
+    put_path_name(name, name_len, mfcc_path_name(p));
     if (frames_per_item) *frames_per_item = p.F;
     if (lds_bytes) *lds_bytes = 4 * p.lds_floats;
     return JSG_OK;
 }
+}  // namespace
 
-int jsg_mfcc_kernel_name(const jsg_mfcc_args* g, char* out, int out_len) {
-    static const char* who = "jsg_mfcc_kernel_name";
-    if (!out || out_len < 24) return jsg_fail_who(JSG_ERR_INVALID, who, "bad argument");
-    const int rc = mfcc_check(g, who);
-    if (rc != JSG_OK) return rc;
-    MfccPlan p{};
-    mfcc_resolve(g, &p);
-    std::strncpy(out, mfcc_path_name(p), out_len);
-    return JSG_OK;
+extern "C" {
+
+int jsg_mfcc_plan(const jsg_mfcc_args* g, char* name, int name_len, int32_t* frames_per_item, int32_t* lds_bytes) {
+    return mfcc_plan_call("jsg_mfcc_plan", g, name, name_len, false, frames_per_item, lds_bytes);
 }
+
+int jsg_mfcc_kernel_name(const jsg_mfcc_args* g, char* out, int out_len) { return mfcc_plan_call("jsg_mfcc_kernel_name", g, out, out_len, true, nullptr, nullptr); }
 
 int jsg_mfcc_table_build(int32_t n_bands, int32_t n_coeffs, int32_t norm, double lifter, int32_t inverse, float* out) {
     static const char* who = "jsg_mfcc_table_build";

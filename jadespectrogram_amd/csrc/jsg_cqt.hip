@@ -237,8 +237,6 @@ using namespace jsg;
 
 namespace {
 
-typedef __int128 i128;
-
 int cq_class_of(int N) {        // 2^(c-1) < N <= 2^c
     int c = 0;
     while ((1 << c) < N) ++c;
@@ -253,7 +251,7 @@ int cqt_check(const jsg_cqt_args* g, const char* who) {
     const uintptr_t pi = reinterpret_cast<uintptr_t>(g->in), po = reinterpret_cast<uintptr_t>(g->out);
     if ((pi & 3) != 0) return jsg_fail_who(JSG_ERR_INVALID, who, "in must be 4-byte aligned");
     if ((po & (g->out_power ? 3 : 7)) != 0) return jsg_fail_who(JSG_ERR_INVALID, who, "out must be 8-byte aligned (power: 4-byte)");
-    if (g->rows < 1 || g->rows > 65535) return jsg_fail_who(JSG_ERR_INVALID, who, "rows must be in 1..65535");
+    if (const int rc = check_rows(g->rows, who); rc != JSG_OK) return rc;
     if (g->in_samples < 1 || g->in_samples >= (1ll << 31)) return jsg_fail_who(JSG_ERR_INVALID, who, "in_samples must be in 1..2^31-1");
     if (g->hop < 1 || g->hop > (1ll << 20)) return jsg_fail_who(JSG_ERR_INVALID, who, "hop must be in 1..2^20");
     if (g->n_frames < 1 || g->n_frames >= (1ll << 31)) return jsg_fail_who(JSG_ERR_INVALID, who, "n_frames must be in 1..2^31-1");
@@ -265,12 +263,10 @@ int cqt_check(const jsg_cqt_args* g, const char* who) {
 // the refusals that need K
 int cqt_check_out(int K, const jsg_cqt_args* g, const char* who) {
     if (g->out_frame_pitch < K) return jsg_fail_who(JSG_ERR_INVALID, who, "out_frame_pitch smaller than the number of bins");
-    const i128 row_min = (i128)(g->n_frames - 1) * g->out_frame_pitch + K;
+    const i128 row_min = plane(g->n_frames, g->out_frame_pitch, K);
     if (g->rows > 1 && (i128)g->out_row_pitch < row_min) return jsg_fail_who(JSG_ERR_INVALID, who, "out_row_pitch smaller than (n_frames-1)*out_frame_pitch + bins");
-    const i128 pi = (i128)reinterpret_cast<uintptr_t>(g->in), po = (i128)reinterpret_cast<uintptr_t>(g->out);
-    const i128 in_end = pi + 4 * ((i128)(g->rows - 1) * (g->rows > 1 ? g->in_pitch : 0) + g->in_samples);
-    const i128 out_end = po + (g->out_power ? 4 : 8) * ((i128)(g->rows - 1) * (g->rows > 1 ? g->out_row_pitch : 0) + row_min);
-    if (pi < out_end && po < in_end) return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps in");
+    if (overlap(addr(g->in), span_bytes(g->rows, g->in_pitch, g->in_samples, 4), addr(g->out), span_bytes(g->rows, g->out_row_pitch, row_min, g->out_power ? 4 : 8)))
+        return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps in");
     return JSG_OK;
 }
 
@@ -433,12 +429,11 @@ int64_t jsg_cqt_frames(int64_t in_samples, int64_t hop) {
 int jsg_cqt_launch(const jsg_cqt* cq, const jsg_cqt_args* g, void* stream) {
     static const char* who = "jsg_cqt_launch";
     if (g && !cq) return jsg_fail_who(JSG_ERR_INVALID, who, "null basis");
-    int rc = cqt_check(g, who);
-    if (rc != JSG_OK) return rc;
-    // the basis is read only once there is a device
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return jsg_fail_who(JSG_ERR_NO_DEVICE, who, "no HIP device");
-    rc = cqt_check_out(cq->K, g, who);
+    int rc = cqt_check(g, who);
+    // the basis is read only once there is a device
+    if (rc == JSG_OK) rc = current_device(&dev, who);
+    if (rc == JSG_OK) rc = cqt_check_out(cq->K, g, who);
     if (rc != JSG_OK) return rc;
     if (cq->blob.device() != dev) return jsg_fail_who(JSG_ERR_INVALID, who, "the basis was created on another device");
     CqPlan p;
@@ -472,25 +467,22 @@ int jsg_cqt_launch(const jsg_cqt* cq, const jsg_cqt_args* g, void* stream) {
     k.first_item[p.n_classes] = items;
     k.n_items = items;
     const size_t lds_bytes = sizeof(float) * (size_t)p.lds_floats;
-    const long long per_cu = std::max<long long>(1, std::min<long long>(8, 160 * 1024 / (long long)lds_bytes));      // 2048 threads per compute unit
-    const dim3 grid((unsigned)std::min<long long>(items, (long long)cu_count_of_device(dev) * per_cu));
+    const dim3 grid(resident_grid(items, dev, per_cu_by_lds(160 * 1024, (long long)lds_bytes, 8)));      // 2048 threads per compute unit
     hipLaunchKernelGGL(cqt_kernel, grid, dim3(CQ_THREADS), lds_bytes, reinterpret_cast<hipStream_t>(stream), k);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return jsg_fail_hip(err, who);
-    return JSG_OK;
+    return finish_launch(who);
 }
 
 int jsg_cqt_plan(int n_bins, const int32_t* half_len, const jsg_cqt_args* g, char* name, int name_len, int32_t* n_classes, int32_t* class_max_taps,
                  int32_t* frames_per_item, int32_t* taps_per_pass, int32_t* lds_bytes) {
     static const char* who = "jsg_cqt_plan";
-    if (name && name_len < 24) return jsg_fail_who(JSG_ERR_INVALID, who, "bad argument");
-    int rc = cqt_check_sizes(n_bins, half_len, who, nullptr);
+    int rc = check_name_buffer(who, name, name_len, false);
+    if (rc == JSG_OK) rc = cqt_check_sizes(n_bins, half_len, who, nullptr);
     if (rc == JSG_OK) rc = cqt_check(g, who);
     if (rc == JSG_OK) rc = cqt_check_out(n_bins, g, who);
     CqPlan p;
     if (rc == JSG_OK) rc = cqt_resolve(n_bins, half_len, g, who, &p);
     if (rc != JSG_OK) return rc;
-    if (name) std::strncpy(name, path_name(p), name_len);
+    put_path_name(name, name_len, path_name(p));
     if (n_classes) *n_classes = p.n_classes;
     for (int c = 0; c < p.n_classes; ++c) {
         if (class_max_taps) class_max_taps[c] = p.cls[c].n_max;
@@ -503,14 +495,14 @@ int jsg_cqt_plan(int n_bins, const int32_t* half_len, const jsg_cqt_args* g, cha
 
 int jsg_cqt_kernel_name(const jsg_cqt* cq, const jsg_cqt_args* g, char* out, int out_len) {
     static const char* who = "jsg_cqt_kernel_name";
-    if (!out || out_len < 24) return jsg_fail_who(JSG_ERR_INVALID, who, "bad argument");
+    if (const int rn = check_name_buffer(who, out, out_len, true); rn != JSG_OK) return rn;
     if (g && !cq) return jsg_fail_who(JSG_ERR_INVALID, who, "null basis");
     int rc = cqt_check(g, who);          // before the basis is read
     if (rc == JSG_OK) rc = cqt_check_out(cq->K, g, who);
     CqPlan p;
     if (rc == JSG_OK) rc = cqt_resolve(cq->K, cq->half.data(), g, who, &p);
     if (rc != JSG_OK) return rc;
-    std::strncpy(out, path_name(p), out_len);
+    put_path_name(out, out_len, path_name(p));
     return JSG_OK;
 }
 

@@ -294,14 +294,12 @@ int cs_check_device(const jsg_cstft* p, const char* who) {
     return JSG_OK;
 }
 
-int cs_grid(long long tiles, int bpc, int dev) { return (int)std::max(1LL, std::min(tiles, (long long)cu_count_of_device(dev) * bpc)); }
-
 template <int N>
 hipError_t fwd_launch(const CsFwdArgs& ka, int rows, long long n_frames, int dev, hipStream_t s) {
     CsFwdArgs k = ka;
     k.tiles_per_row = (int)((n_frames + CsGeom<N>::FPB - 1) / CsGeom<N>::FPB);
     k.n_tiles = (long long)k.tiles_per_row * rows;
-    hipLaunchKernelGGL(cstft_fwd_kernel<N>, dim3(cs_grid(k.n_tiles, cs_blocks_per_cu<N>(), dev)), dim3(CS_THREADS), 0, s, k);
+    hipLaunchKernelGGL(cstft_fwd_kernel<N>, dim3(resident_grid(k.n_tiles, dev, cs_blocks_per_cu<N>())), dim3(CS_THREADS), 0, s, k);      // n_tiles >= 1
     return hipGetLastError();
 }
 
@@ -310,7 +308,7 @@ hipError_t c2r_launch(const CsInvArgs& ka, int rows, int dev, hipStream_t s) {
     CsInvArgs k = ka;
     k.tiles_per_row = (int)((k.n_frames + CsGeom<N>::FPB - 1) / CsGeom<N>::FPB);
     k.n_tiles = (long long)k.tiles_per_row * rows;
-    hipLaunchKernelGGL(istft_c2r_kernel<N>, dim3(cs_grid(k.n_tiles, cs_blocks_per_cu<N>(), dev)), dim3(CS_THREADS), 0, s, k);
+    hipLaunchKernelGGL(istft_c2r_kernel<N>, dim3(resident_grid(k.n_tiles, dev, cs_blocks_per_cu<N>())), dim3(CS_THREADS), 0, s, k);      // n_tiles >= 1
     return hipGetLastError();
 }
 

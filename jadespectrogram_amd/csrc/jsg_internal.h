@@ -2,11 +2,15 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
+#include <atomic>
 #include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/jsg.h"
+#include "jsg_spans.h"
 
 namespace jsg {
 
@@ -75,6 +79,72 @@ int plan_device(const jsg_plan* plan);
 int check_stft_args(int n, const jsg_stft_args* g, const char* who);
 // jsg_display_axis.hip: preload_code_object of the axis kernel (jsg_freq_axis_create)
 void touch_axis_module();
+
+// ---- what the feature units (jsg_cstft.hip and every unit after it) share; the spans of their overlap refusals are in jsg_spans.h ----
+
+// the refusals that every unit words alike; JSG_OK where the call passes.  A unit calls them at its own place in the header's order
+inline int check_rows(long long rows, const char* who) {
+    return rows >= 1 && rows <= 65535 ? JSG_OK : jsg_fail_who(JSG_ERR_INVALID, who, "rows must be in 1..65535");
+}
+template <class... P>
+int check_aligned4(const char* who, const P*... p) {
+    return ((reinterpret_cast<uintptr_t>(p) | ...) & 3) == 0 ? JSG_OK : jsg_fail_who(JSG_ERR_INVALID, who, "pointers must be 4-byte aligned");
+}
+
+// The two ends of a ..._plan or ..._kernel_name call: the refusal of a name buffer below 24 bytes, before any other (a plan call may
+// pass no buffer, a kernel_name call must pass one), and the path's name into the buffer once the call has passed.
+inline int check_name_buffer(const char* who, const char* buf, int len, bool required) {
+    return (required ? !buf || len < 24 : buf && len < 24) ? jsg_fail_who(JSG_ERR_INVALID, who, "bad argument") : JSG_OK;
+}
+inline void put_path_name(char* buf, int len, const char* path) {
+    if (buf) std::strncpy(buf, path, len);
+}
+
+// the device a launch goes to
+inline int current_device(int* dev, const char* who) {
+    return hipGetDevice(dev) == hipSuccess ? JSG_OK : jsg_fail_who(JSG_ERR_NO_DEVICE, who, "no HIP device");
+}
+// The grid of a kernel whose workgroups walk n_items with a grid stride: what the device holds at a time at per_cu workgroups per
+// compute unit, or the items where they are fewer.  per_cu_by_lds: as many as `limit` bytes of LDS hold at `lds` bytes each, 1..cap.
+inline unsigned resident_grid(long long n_items, int dev, long long per_cu) {
+    return (unsigned)std::min<long long>(n_items, (long long)cu_count_of_device(dev) * per_cu);
+}
+inline long long per_cu_by_lds(long long limit, long long lds, long long cap) { return std::max<long long>(1, std::min<long long>(cap, limit / lds)); }
+// after the last launch of a call: what the launches left, as the call's return code
+inline int finish_launch(const char* who) {
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? JSG_OK : jsg_fail_hip(err, who);
+}
+
+// What has been said once per device, a bit per path of a unit.  A device index outside 0..63 has no slot: there every call is the
+// first.  done() after the step has succeeded, so that a failed first attempt is made again.
+class OncePerDevice {
+public:
+    bool first(int dev, unsigned bit) const { return dev < 0 || dev >= 64 || !(told_[dev].load(std::memory_order_acquire) & bit); }
+    void done(int dev, unsigned bit) {
+        if (dev >= 0 && dev < 64) told_[dev].fetch_or(bit, std::memory_order_release);
+    }
+
+private:
+    std::atomic<unsigned> told_[64] = {};
+};
+
+// Launches a kernel that may ask for more than 48 KB of dynamic LDS, up to lds_max bytes.  It has to be said once per device before
+// the first launch there; `once` and the path's bit remember it, so it is said at the first launch of a path on a device.
+template <class Args>
+hipError_t launch_large_lds(OncePerDevice& once, int dev, unsigned bit, void (*kernel)(Args), int lds_max, dim3 grid, dim3 block, size_t lds_bytes,
+                            hipStream_t s, const Args& k) {
+    const bool first = once.first(dev, bit);
+    if (first) {
+        const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        if (err != hipSuccess) return err;
+    }
+    void* args[] = {const_cast<Args*>(&k)};
+    (void)hipLaunchKernel(reinterpret_cast<const void*>(kernel), grid, block, args, lds_bytes, s);
+    const hipError_t err = hipGetLastError();
+    if (err == hipSuccess && first) once.done(dev, bit);
+    return err;
+}
 
 // jsg_yin_host.cpp: the refusals of jsg_yin_args and how a call that passes is served (jsg_yin.hip launches by it).  A work item is a
 // row and F consecutive frames; its LDS holds the frames' span ((F - 1) S + w + tau_max floats, S = min(hop, w + tau_max) between

@@ -158,8 +158,6 @@ using namespace jsg;
 
 namespace {
 
-typedef __int128 i128;
-
 struct PvCall {
     long long K, tiles, chunk, chunks;
     long long scratch_bytes;
@@ -190,7 +188,7 @@ int pvoc_check(const jsg_pvoc_args* g, const char* who, PvCall* c) {
     if (!g->in || !g->out) return jsg_fail_who(JSG_ERR_INVALID, who, "null data pointer");
     if (g->n < 2 || g->n > 65536 || (g->n & 1)) return jsg_fail_who(JSG_ERR_INVALID, who, "n must be even and in 2..65536");
     if (g->hop < 1 || g->hop > g->n) return jsg_fail_who(JSG_ERR_INVALID, who, "hop must be in 1..n");
-    if (g->rows < 1 || g->rows > 65535) return jsg_fail_who(JSG_ERR_INVALID, who, "rows must be in 1..65535");
+    if (const int rc = check_rows(g->rows, who); rc != JSG_OK) return rc;
     if (!rate_ok(g->rate)) return jsg_fail_who(JSG_ERR_INVALID, who, "rate must be finite and > 0");
     if (g->n_frames_in < 1 || g->n_frames_in >= (1ll << 31)) return jsg_fail_who(JSG_ERR_INVALID, who, "n_frames_in must be in 1..2^31-1");
     const long long T = g->n_frames_in, T_out = pvoc_count(T, g->rate);
@@ -200,15 +198,13 @@ int pvoc_check(const jsg_pvoc_args* g, const char* who, PvCall* c) {
     const long long K = g->n / 2 + 1;
     if (g->in_frame_pitch < K) return jsg_fail_who(JSG_ERR_INVALID, who, "in_frame_pitch smaller than n/2+1");
     if (g->out_frame_pitch < K) return jsg_fail_who(JSG_ERR_INVALID, who, "out_frame_pitch smaller than n/2+1");
-    const i128 in_row = (i128)(T - 1) * g->in_frame_pitch + K, out_row = (i128)(T_out - 1) * g->out_frame_pitch + K;
+    const i128 in_row = plane(T, g->in_frame_pitch, K), out_row = plane(T_out, g->out_frame_pitch, K);
     if (g->rows > 1 && g->in_row_pitch < in_row) return jsg_fail_who(JSG_ERR_INVALID, who, "in_row_pitch smaller than one row of frames");
     if (g->rows > 1 && g->out_row_pitch < out_row) return jsg_fail_who(JSG_ERR_INVALID, who, "out_row_pitch smaller than one row of frames");
     const uintptr_t pi = reinterpret_cast<uintptr_t>(g->in), po = reinterpret_cast<uintptr_t>(g->out);
     if ((pi & 7) != 0 || (po & 7) != 0) return jsg_fail_who(JSG_ERR_INVALID, who, "in and out must be 8-byte aligned (complex float pairs)");
-    // the bytes either side spans, first to last element
-    const i128 in_end = (i128)pi + 8 * ((i128)(g->rows - 1) * (g->rows > 1 ? g->in_row_pitch : 0) + in_row);
-    const i128 out_end = (i128)po + 8 * ((i128)(g->rows - 1) * (g->rows > 1 ? g->out_row_pitch : 0) + out_row);
-    if ((i128)pi < out_end && (i128)po < in_end) return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps in");
+    if (overlap(addr(g->in), span_bytes(g->rows, g->in_row_pitch, in_row, 8), addr(g->out), span_bytes(g->rows, g->out_row_pitch, out_row, 8)))
+        return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps in");
     c->K = K;
     c->tiles = (K + PV_TILE - 1) / PV_TILE;
     c->chunk = g->chunk_frames ? g->chunk_frames : default_chunk(T_out, g->rows, c->tiles);
@@ -246,7 +242,8 @@ int jsg_pvoc_launch(const jsg_pvoc_args* g, void* scratch, int64_t scratch_bytes
     if ((reinterpret_cast<uintptr_t>(scratch) & 15) != 0) return jsg_fail_who(JSG_ERR_INVALID, who, "scratch must be 16-byte aligned");
     if (scratch_bytes < c.scratch_bytes) return jsg_fail_who(JSG_ERR_INVALID, who, "scratch smaller than jsg_pvoc_scratch_bytes");
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return jsg_fail_who(JSG_ERR_NO_DEVICE, who, "no HIP device");
+    rc = current_device(&dev, who);
+    if (rc != JSG_OK) return rc;
     // every refusal is behind us
     PvArgs k{};
     k.in = reinterpret_cast<const pv_v2*>(g->in);
@@ -266,23 +263,21 @@ int jsg_pvoc_launch(const jsg_pvoc_args* g, void* scratch, int64_t scratch_bytes
     k.n = g->n;
     k.hop = g->hop;
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const long long max_grid = (long long)cu_count_of_device(dev) * 64;   // twice the wavefronts a compute unit holds
+    const long long per_cu = 64;   // twice the wavefronts a compute unit holds
     const long long per_chunk = (long long)g->rows * c.tiles;
     if (c.chunks > 1) {
         k.n_items = per_chunk * (c.chunks - 1);
-        hipLaunchKernelGGL(pvoc_walk_kernel<false>, dim3((unsigned)std::min(k.n_items, max_grid)), dim3(PV_TILE), 0, s, k);
-        hipError_t err = hipGetLastError();
-        if (err != hipSuccess) return jsg_fail_hip(err, who);
+        hipLaunchKernelGGL(pvoc_walk_kernel<false>, dim3(resident_grid(k.n_items, dev, per_cu)), dim3(PV_TILE), 0, s, k);
+        rc = finish_launch(who);
+        if (rc != JSG_OK) return rc;
     }
     k.n_items = per_chunk;
-    hipLaunchKernelGGL(pvoc_scan_kernel, dim3((unsigned)std::min(k.n_items, max_grid)), dim3(PV_TILE * PV_SEGS), 0, s, k);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return jsg_fail_hip(err, who);
+    hipLaunchKernelGGL(pvoc_scan_kernel, dim3(resident_grid(k.n_items, dev, per_cu)), dim3(PV_TILE * PV_SEGS), 0, s, k);
+    rc = finish_launch(who);
+    if (rc != JSG_OK) return rc;
     k.n_items = per_chunk * c.chunks;
-    hipLaunchKernelGGL(pvoc_walk_kernel<true>, dim3((unsigned)std::min(k.n_items, max_grid)), dim3(PV_TILE), 0, s, k);
-    err = hipGetLastError();
-    if (err != hipSuccess) return jsg_fail_hip(err, who);
-    return JSG_OK;
+    hipLaunchKernelGGL(pvoc_walk_kernel<true>, dim3(resident_grid(k.n_items, dev, per_cu)), dim3(PV_TILE), 0, s, k);
+    return finish_launch(who);
 }
 
 }  // extern "C"

@@ -131,8 +131,6 @@ using namespace jsg;
 
 namespace {
 
-typedef __int128 i128;
-
 struct RsCall {
     long long T, chunk, chunks;
     double scale, Sd;
@@ -163,7 +161,7 @@ int resample_check(const jsg_resample_args* g, const char* who, RsCall* c) {
     if (!g->in || !g->out) return jsg_fail_who(JSG_ERR_INVALID, who, "null data pointer");
     const uintptr_t pi = reinterpret_cast<uintptr_t>(g->in), po = reinterpret_cast<uintptr_t>(g->out);
     if ((pi & 3) != 0 || (po & 3) != 0) return jsg_fail_who(JSG_ERR_INVALID, who, "in and out must be 4-byte aligned");
-    if (g->rows < 1 || g->rows > 65535) return jsg_fail_who(JSG_ERR_INVALID, who, "rows must be in 1..65535");
+    if (const int rc = check_rows(g->rows, who); rc != JSG_OK) return rc;
     if (g->in_samples < 1 || g->in_samples >= (1ll << 31)) return jsg_fail_who(JSG_ERR_INVALID, who, "in_samples must be in 1..2^31-1");
     if (!step_ok(g->step)) return jsg_fail_who(JSG_ERR_INVALID, who, "step must be finite and in 1/64..64");
     const long long L = g->in_samples, T = resample_count(L, g->step);
@@ -171,10 +169,8 @@ int resample_check(const jsg_resample_args* g, const char* who, RsCall* c) {
     if (g->chunk_outputs < 0 || g->chunk_outputs > 65536) return jsg_fail_who(JSG_ERR_INVALID, who, "chunk_outputs must be 0 or in 1..65536");
     if (g->rows > 1 && g->in_pitch < L) return jsg_fail_who(JSG_ERR_INVALID, who, "in_pitch smaller than in_samples");
     if (g->rows > 1 && g->out_pitch < T) return jsg_fail_who(JSG_ERR_INVALID, who, "out_pitch smaller than out_samples");
-    // the bytes either side spans, first to last element
-    const i128 in_end = (i128)pi + 4 * ((i128)(g->rows - 1) * (g->rows > 1 ? g->in_pitch : 0) + L);
-    const i128 out_end = (i128)po + 4 * ((i128)(g->rows - 1) * (g->rows > 1 ? g->out_pitch : 0) + T);
-    if ((i128)pi < out_end && (i128)po < in_end) return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps in");
+    if (overlap(addr(g->in), span_bytes(g->rows, g->in_pitch, L, 4), addr(g->out), span_bytes(g->rows, g->out_pitch, T, 4)))
+        return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps in");
     c->T = T;
     c->chunk = g->chunk_outputs ? g->chunk_outputs : RS_DEFAULT_CHUNK;
     c->chunks = (T + c->chunk - 1) / c->chunk;
@@ -318,15 +314,15 @@ int jsg_resample_launch(const jsg_resampler* rs, const jsg_resample_args* g, voi
     static const char* who = "jsg_resample_launch";
     RsCall c{};
     if (g && !rs) return jsg_fail_who(JSG_ERR_INVALID, who, "null resampler");
-    const int rc = resample_check(g, who, &c);
-    if (rc != JSG_OK) return rc;
-    // every refusal of the arguments is behind us; the plan is looked at only once there is a device
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return jsg_fail_who(JSG_ERR_NO_DEVICE, who, "no HIP device");
+    int rc = resample_check(g, who, &c);
+    // every refusal of the arguments is behind us; the plan is looked at only once there is a device
+    if (rc == JSG_OK) rc = current_device(&dev, who);
+    if (rc != JSG_OK) return rc;
     if (rs->blob.device() != dev) return jsg_fail_who(JSG_ERR_INVALID, who, "the resampler was created on another device");
     RsPath p{};
-    const int rp = resample_resolve(rs->Z, rs->P, g, who, &c, &p);
-    if (rp != JSG_OK) return rp;
+    rc = resample_resolve(rs->Z, rs->P, g, who, &c, &p);
+    if (rc != JSG_OK) return rc;
     RsArgs k{};
     k.in = g->in;
     k.in_pitch = g->rows > 1 ? g->in_pitch : 0;
@@ -347,8 +343,7 @@ int jsg_resample_launch(const jsg_resampler* rs, const jsg_resample_args* g, voi
     k.hw = p.hw;
     k.tab_n = rs->Z * rs->P + 1;
     k.span_cap = p.span_cap;
-    const long long per_cu = std::max<long long>(1, std::min<long long>(2, RS_LDS_MAX / (long long)p.lds_bytes));   // 2048 threads per compute unit
-    const dim3 grid((unsigned)std::min<long long>(k.n_items, (long long)cu_count_of_device(dev) * per_cu));
+    const dim3 grid(resident_grid(k.n_items, dev, per_cu_by_lds(RS_LDS_MAX, (long long)p.lds_bytes, 2)));   // 2048 threads per compute unit
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (!p.span_lds)
         hipLaunchKernelGGL((resample_kernel<true, false>), grid, dim3(RS_THREADS), p.lds_bytes, s, k);
@@ -356,20 +351,18 @@ int jsg_resample_launch(const jsg_resampler* rs, const jsg_resample_args* g, voi
         hipLaunchKernelGGL((resample_kernel<true, true>), grid, dim3(RS_THREADS), p.lds_bytes, s, k);
     else
         hipLaunchKernelGGL((resample_kernel<false, true>), grid, dim3(RS_THREADS), p.lds_bytes, s, k);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return jsg_fail_hip(err, who);
-    return JSG_OK;
+    return finish_launch(who);
 }
 
 int jsg_resample_plan(int num_zeros, int per_zero, const jsg_resample_args* g, char* name, int name_len, int32_t* pass_outputs, int32_t* lds_bytes) {
     static const char* who = "jsg_resample_plan";
-    if (name && name_len < 24) return jsg_fail_who(JSG_ERR_INVALID, who, "bad argument");
+    if (const int rn = check_name_buffer(who, name, name_len, false); rn != JSG_OK) return rn;
     if (!table_size_ok(num_zeros, per_zero)) return jsg_fail_who(JSG_ERR_INVALID, who, "num_zeros and per_zero must be >= 1, their product <= 32768");
     RsCall c{};
     RsPath p{};
     const int rc = resample_resolve(num_zeros, per_zero, g, who, &c, &p);
     if (rc != JSG_OK) return rc;
-    if (name) std::strncpy(name, path_name(p), name_len);
+    put_path_name(name, name_len, path_name(p));
     if (pass_outputs) *pass_outputs = p.sub;
     if (lds_bytes) *lds_bytes = (int32_t)p.lds_bytes;
     return JSG_OK;
@@ -377,14 +370,14 @@ int jsg_resample_plan(int num_zeros, int per_zero, const jsg_resample_args* g, c
 
 int jsg_resample_kernel_name(const jsg_resampler* rs, const jsg_resample_args* g, char* out, int out_len) {
     static const char* who = "jsg_resample_kernel_name";
-    if (!out || out_len < 24) return jsg_fail_who(JSG_ERR_INVALID, who, "bad argument");
+    if (const int rn = check_name_buffer(who, out, out_len, true); rn != JSG_OK) return rn;
     if (g && !rs) return jsg_fail_who(JSG_ERR_INVALID, who, "null resampler");
     RsCall c{};
     RsPath p{};
     int rc = resample_check(g, who, &c);         // before the plan is read
     if (rc == JSG_OK) rc = resample_resolve(rs->Z, rs->P, g, who, &c, &p);
     if (rc != JSG_OK) return rc;
-    std::strncpy(out, path_name(p), out_len);
+    put_path_name(out, out_len, path_name(p));
     return JSG_OK;
 }
 

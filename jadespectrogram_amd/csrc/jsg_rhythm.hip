@@ -26,7 +26,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <climits>
 #include <cstdint>
 
@@ -330,27 +329,12 @@ __global__ __launch_bounds__(256) void tempo_kernel(const TpArgs a) {
 
 using namespace jsg;
 
-namespace {
-
-template <int NL>
-hipError_t tempogram_enqueue(const TgArgs& k, dim3 grid, size_t lds_bytes, hipStream_t s, bool first) {
-    // the kernel may ask for more than 48 KB of dynamic LDS: said once per device, before the first launch there
-    if (first) {
-        const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&tempogram_kernel<NL>), hipFuncAttributeMaxDynamicSharedMemorySize, kTgLdsOne * 4);
-        if (err != hipSuccess) return err;
-    }
-    hipLaunchKernelGGL((tempogram_kernel<NL>), grid, dim3(kTgThreads), lds_bytes, s, k);
-    return hipGetLastError();
-}
-
-}  // namespace
-
 extern "C" int jsg_onset_strength_launch(const jsg_onset_args* g, void* stream) {
     static const char* who = "jsg_onset_strength_launch";
-    const int rc = onset_check(g, who);
-    if (rc != JSG_OK) return rc;
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return jsg_fail_who(JSG_ERR_NO_DEVICE, who, "no HIP device");
+    int rc = onset_check(g, who);
+    if (rc == JSG_OK) rc = current_device(&dev, who);
+    if (rc != JSG_OK) return rc;
     // every refusal is behind us
     OnArgs k{};
     const bool multi = g->rows > 1;
@@ -372,21 +356,20 @@ extern "C" int jsg_onset_strength_launch(const jsg_onset_args* g, void* stream) 
     const int per = ON_K * (256 / k.W);
     k.groups = (g->n_frames + per - 1) / per;
     k.n_items = (long long)g->rows * k.groups;
-    const dim3 grid((unsigned)std::min<long long>(k.n_items, (long long)cu_count_of_device(dev) * 32));
+    const dim3 grid(resident_grid(k.n_items, dev, 32));
     if (g->max_size == 1)
         hipLaunchKernelGGL(onset_kernel<true>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k);
     else
         hipLaunchKernelGGL(onset_kernel<false>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? JSG_OK : jsg_fail_hip(err, who);
+    return finish_launch(who);
 }
 
 extern "C" int jsg_tempogram_launch(const jsg_tempogram_args* g, void* stream) {
     static const char* who = "jsg_tempogram_launch";
-    const int rc = tempogram_check(g, who);
-    if (rc != JSG_OK) return rc;
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return jsg_fail_who(JSG_ERR_NO_DEVICE, who, "no HIP device");
+    int rc = tempogram_check(g, who);
+    if (rc == JSG_OK) rc = current_device(&dev, who);
+    if (rc != JSG_OK) return rc;
     // every refusal is behind us
     TgPlan p{};
     tempogram_resolve(g, &p);
@@ -409,28 +392,20 @@ extern "C" int jsg_tempogram_launch(const jsg_tempogram_args* g, void* stream) {
     k.S = p.S;
     k.normalise = g->normalise;
     const size_t lds_bytes = sizeof(float) * (size_t)p.lds_floats;
-    const long long per_cu = std::max<long long>(1, std::min<long long>(8, kTgLdsOne / p.lds_floats));      // 2048 threads per compute unit
-    const dim3 grid((unsigned)std::min<long long>(k.n_items, (long long)cu_count_of_device(dev) * per_cu));
-    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    // one flag per device and path
-    static std::atomic<unsigned> told[64];
-    const unsigned bit = (unsigned)p.NL;
-    const bool first = dev < 0 || dev >= 64 || !(told[dev].load(std::memory_order_acquire) & bit);
-    const hipError_t err = p.NL == 1 ? tempogram_enqueue<1>(k, grid, lds_bytes, s, first)
-                         : p.NL == 2 ? tempogram_enqueue<2>(k, grid, lds_bytes, s, first)
-                         : p.NL == 4 ? tempogram_enqueue<4>(k, grid, lds_bytes, s, first)
-                                     : tempogram_enqueue<8>(k, grid, lds_bytes, s, first);
-    if (err != hipSuccess) return jsg_fail_hip(err, who);
-    if (first && dev >= 0 && dev < 64) told[dev].fetch_or(bit, std::memory_order_release);
-    return JSG_OK;
+    const dim3 grid(resident_grid(k.n_items, dev, per_cu_by_lds(kTgLdsOne, p.lds_floats, 8)));      // 2048 threads per compute unit
+    static void (*const kernels[4])(TgArgs) = {tempogram_kernel<1>, tempogram_kernel<2>, tempogram_kernel<4>, tempogram_kernel<8>};      // the code object holds them in this order
+    const int path = p.NL == 1 ? 0 : p.NL == 2 ? 1 : p.NL == 4 ? 2 : 3;
+    static OncePerDevice told;      // a bit per path
+    const hipError_t err = launch_large_lds(told, dev, 1u << path, kernels[path], kTgLdsOne * 4, grid, dim3(kTgThreads), lds_bytes, reinterpret_cast<hipStream_t>(stream), k);
+    return err == hipSuccess ? JSG_OK : jsg_fail_hip(err, who);
 }
 
 extern "C" int jsg_tempo_launch(const jsg_tempo_args* g, void* stream) {
     static const char* who = "jsg_tempo_launch";
-    const int rc = tempo_check(g, who);
-    if (rc != JSG_OK) return rc;
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return jsg_fail_who(JSG_ERR_NO_DEVICE, who, "no HIP device");
+    int rc = tempo_check(g, who);
+    if (rc == JSG_OK) rc = current_device(&dev, who);
+    if (rc != JSG_OK) return rc;
     // every refusal is behind us
     TpArgs k{};
     const bool multi = g->rows > 1;
@@ -446,6 +421,5 @@ extern "C" int jsg_tempo_launch(const jsg_tempo_args* g, void* stream) {
     k.Lg = g->lags;
     k.rate60 = 60.0f * g->frame_rate;
     hipLaunchKernelGGL(tempo_kernel, dim3((unsigned)g->rows), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), k);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? JSG_OK : jsg_fail_hip(err, who);
+    return finish_launch(who);
 }

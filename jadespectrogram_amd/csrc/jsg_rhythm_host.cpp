@@ -4,36 +4,28 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 
 #include "jsg_internal.h"
 
 namespace jsg {
 
-namespace {
-typedef __int128 i128;
-
-i128 addr(const void* p) { return (i128)reinterpret_cast<uintptr_t>(p); }
-bool overlap(i128 a0, i128 a_bytes, i128 b0, i128 b_bytes) { return a0 && b0 && a0 < b0 + b_bytes && b0 < a0 + a_bytes; }
-}  // namespace
-
 int onset_check(const jsg_onset_args* g, const char* who) {
     if (!g) return jsg_fail_who(JSG_ERR_INVALID, who, "null argument");
     if (!g->in) return jsg_fail_who(JSG_ERR_INVALID, who, "null in");
     if (!g->out) return jsg_fail_who(JSG_ERR_INVALID, who, "null out");
-    if (((reinterpret_cast<uintptr_t>(g->in) | reinterpret_cast<uintptr_t>(g->out)) & 3) != 0) return jsg_fail_who(JSG_ERR_INVALID, who, "pointers must be 4-byte aligned");
-    if (g->rows < 1 || g->rows > 65535) return jsg_fail_who(JSG_ERR_INVALID, who, "rows must be in 1..65535");
+    int rc = check_aligned4(who, g->in, g->out);
+    if (rc == JSG_OK) rc = check_rows(g->rows, who);
+    if (rc != JSG_OK) return rc;
     if (g->n_bands < 1 || g->n_bands > JSG_ONSET_MAX_BANDS) return jsg_fail_who(JSG_ERR_INVALID, who, "n_bands must be in 1..65536");
     if (g->n_frames < 1 || g->n_frames >= (1ll << 31)) return jsg_fail_who(JSG_ERR_INVALID, who, "n_frames must be in 1..2^31-1");
     if (g->lag < 1 || g->lag > JSG_ONSET_MAX_LAG) return jsg_fail_who(JSG_ERR_INVALID, who, "lag must be in 1..4096");
     if (g->max_size < 1 || g->max_size > JSG_ONSET_MAX_SIZE) return jsg_fail_who(JSG_ERR_INVALID, who, "max_size must be in 1..255");
     if (g->frame_pitch < g->n_bands) return jsg_fail_who(JSG_ERR_INVALID, who, "frame_pitch smaller than n_bands");
     const bool multi = g->rows > 1;
-    const i128 plane = (i128)(g->n_frames - 1) * g->frame_pitch + g->n_bands;
-    if (multi && (i128)g->row_pitch < plane) return jsg_fail_who(JSG_ERR_INVALID, who, "row_pitch smaller than (n_frames-1)*frame_pitch + n_bands");
+    const i128 in_plane = plane(g->n_frames, g->frame_pitch, g->n_bands);
+    if (multi && (i128)g->row_pitch < in_plane) return jsg_fail_who(JSG_ERR_INVALID, who, "row_pitch smaller than (n_frames-1)*frame_pitch + n_bands");
     if (multi && g->out_pitch < g->n_frames) return jsg_fail_who(JSG_ERR_INVALID, who, "out_pitch smaller than n_frames");
-    const i128 rows1 = g->rows - 1;
-    if (overlap(addr(g->in), 4 * (rows1 * (multi ? g->row_pitch : 0) + plane), addr(g->out), 4 * (rows1 * (multi ? g->out_pitch : 0) + g->n_frames)))
+    if (overlap(addr(g->in), span_bytes(g->rows, g->row_pitch, in_plane, 4), addr(g->out), span_bytes(g->rows, g->out_pitch, g->n_frames, 4)))
         return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps in");
     return JSG_OK;
 }
@@ -43,9 +35,9 @@ int tempogram_check(const jsg_tempogram_args* g, const char* who) {
     if (!g->in) return jsg_fail_who(JSG_ERR_INVALID, who, "null in");
     if (!g->window) return jsg_fail_who(JSG_ERR_INVALID, who, "null window");
     if (!g->out) return jsg_fail_who(JSG_ERR_INVALID, who, "null out");
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(g->in) | reinterpret_cast<uintptr_t>(g->window) | reinterpret_cast<uintptr_t>(g->out);
-    if ((bits & 3) != 0) return jsg_fail_who(JSG_ERR_INVALID, who, "pointers must be 4-byte aligned");
-    if (g->rows < 1 || g->rows > 65535) return jsg_fail_who(JSG_ERR_INVALID, who, "rows must be in 1..65535");
+    int rc = check_aligned4(who, g->in, g->window, g->out);
+    if (rc == JSG_OK) rc = check_rows(g->rows, who);
+    if (rc != JSG_OK) return rc;
     if (g->n_in < 1 || g->n_in >= (1ll << 31)) return jsg_fail_who(JSG_ERR_INVALID, who, "n_in must be in 1..2^31-1");
     if (g->win_length < 2 || g->win_length > JSG_TEMPOGRAM_MAX_WINDOW) return jsg_fail_who(JSG_ERR_INVALID, who, "win_length must be in 2..4096");
     if (g->lags < 1 || g->lags > g->win_length) return jsg_fail_who(JSG_ERR_INVALID, who, "lags must be in 1..win_length");
@@ -56,11 +48,10 @@ int tempogram_check(const jsg_tempogram_args* g, const char* who) {
     const bool multi = g->rows > 1;
     if (multi && g->in_pitch < g->n_in) return jsg_fail_who(JSG_ERR_INVALID, who, "in_pitch smaller than n_in");
     if (g->frame_pitch < g->lags) return jsg_fail_who(JSG_ERR_INVALID, who, "frame_pitch smaller than lags");
-    const i128 plane = (i128)(g->n_frames - 1) * g->frame_pitch + g->lags;
-    if (multi && (i128)g->row_pitch < plane) return jsg_fail_who(JSG_ERR_INVALID, who, "row_pitch smaller than (n_frames-1)*frame_pitch + lags");
-    const i128 rows1 = g->rows - 1;
-    const i128 out_bytes = 4 * (rows1 * (multi ? g->row_pitch : 0) + plane);
-    if (overlap(addr(g->in), 4 * (rows1 * (multi ? g->in_pitch : 0) + g->n_in), addr(g->out), out_bytes)) return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps in");
+    const i128 out_plane = plane(g->n_frames, g->frame_pitch, g->lags);
+    if (multi && (i128)g->row_pitch < out_plane) return jsg_fail_who(JSG_ERR_INVALID, who, "row_pitch smaller than (n_frames-1)*frame_pitch + lags");
+    const i128 out_bytes = span_bytes(g->rows, g->row_pitch, out_plane, 4);
+    if (overlap(addr(g->in), span_bytes(g->rows, g->in_pitch, g->n_in, 4), addr(g->out), out_bytes)) return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps in");
     if (overlap(addr(g->window), 4 * (i128)g->win_length, addr(g->out), out_bytes)) return jsg_fail_who(JSG_ERR_INVALID, who, "out overlaps window");
     return JSG_OK;
 }
@@ -97,23 +88,21 @@ int tempo_check(const jsg_tempo_args* g, const char* who) {
     if (!g->in) return jsg_fail_who(JSG_ERR_INVALID, who, "null in");
     if (!g->prior) return jsg_fail_who(JSG_ERR_INVALID, who, "null prior");
     if (!g->bpm && !g->lag && !g->profile) return jsg_fail_who(JSG_ERR_INVALID, who, "bpm, lag and profile are all null");
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(g->in) | reinterpret_cast<uintptr_t>(g->prior) | reinterpret_cast<uintptr_t>(g->bpm) |
-                           reinterpret_cast<uintptr_t>(g->lag) | reinterpret_cast<uintptr_t>(g->profile);
-    if ((bits & 3) != 0) return jsg_fail_who(JSG_ERR_INVALID, who, "pointers must be 4-byte aligned");
-    if (g->rows < 1 || g->rows > 65535) return jsg_fail_who(JSG_ERR_INVALID, who, "rows must be in 1..65535");
+    int rc = check_aligned4(who, g->in, g->prior, g->bpm, g->lag, g->profile);
+    if (rc == JSG_OK) rc = check_rows(g->rows, who);
+    if (rc != JSG_OK) return rc;
     if (g->lags < 2 || g->lags > JSG_TEMPOGRAM_MAX_WINDOW) return jsg_fail_who(JSG_ERR_INVALID, who, "lags must be in 2..4096");
     if (g->n_frames < 1 || g->n_frames >= (1ll << 31)) return jsg_fail_who(JSG_ERR_INVALID, who, "n_frames must be in 1..2^31-1");
     if (!std::isfinite(g->frame_rate) || !(g->frame_rate > 0.f)) return jsg_fail_who(JSG_ERR_INVALID, who, "frame_rate must be finite and > 0");
     if (g->frame_pitch < g->lags) return jsg_fail_who(JSG_ERR_INVALID, who, "frame_pitch smaller than lags");
     const bool multi = g->rows > 1;
-    const i128 plane = (i128)(g->n_frames - 1) * g->frame_pitch + g->lags;
-    if (multi && (i128)g->row_pitch < plane) return jsg_fail_who(JSG_ERR_INVALID, who, "row_pitch smaller than (n_frames-1)*frame_pitch + lags");
+    const i128 in_plane = plane(g->n_frames, g->frame_pitch, g->lags);
+    if (multi && (i128)g->row_pitch < in_plane) return jsg_fail_who(JSG_ERR_INVALID, who, "row_pitch smaller than (n_frames-1)*frame_pitch + lags");
     if (multi && g->profile && g->profile_pitch < g->lags) return jsg_fail_who(JSG_ERR_INVALID, who, "profile_pitch smaller than lags");
-    const i128 rows1 = g->rows - 1;
     const i128 src[2] = {addr(g->in), addr(g->prior)};
-    const i128 src_bytes[2] = {4 * (rows1 * (multi ? g->row_pitch : 0) + plane), 4 * (i128)g->lags};
+    const i128 src_bytes[2] = {span_bytes(g->rows, g->row_pitch, in_plane, 4), 4 * (i128)g->lags};
     const i128 dst[3] = {addr(g->bpm), addr(g->lag), addr(g->profile)};
-    const i128 dst_bytes[3] = {4 * (i128)g->rows, 4 * (i128)g->rows, 4 * (rows1 * (multi ? g->profile_pitch : 0) + g->lags)};
+    const i128 dst_bytes[3] = {4 * (i128)g->rows, 4 * (i128)g->rows, span_bytes(g->rows, g->profile_pitch, g->lags, 4)};
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 2; ++j)
             if (overlap(src[j], src_bytes[j], dst[i], dst_bytes[i])) return jsg_fail_who(JSG_ERR_INVALID, who, j == 0 ? "an output overlaps in" : "an output overlaps prior");
@@ -123,6 +112,21 @@ int tempo_check(const jsg_tempo_args* g, const char* who) {
 }  // namespace jsg
 
 using namespace jsg;
+
+namespace {
+// jsg_tempogram_plan (the name is optional) and jsg_tempogram_kernel_name (the name is all it gives)
+int tempogram_plan_call(const char* who, const jsg_tempogram_args* g, char* name, int name_len, bool need_name, int32_t* frames_per_item, int32_t* lds_bytes) {
+    int rc = check_name_buffer(who, name, name_len, need_name);
+    if (rc == JSG_OK) rc = tempogram_check(g, who);
+    if (rc != JSG_OK) return rc;
+    TgPlan p{};
+    tempogram_resolve(g, &p);
+    put_path_name(name, name_len, tempogram_path_name(p));
+    if (frames_per_item) *frames_per_item = p.F;
+    if (lds_bytes) *lds_bytes = 4 * p.lds_floats;
+    return JSG_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -134,27 +138,11 @@ int64_t jsg_tempogram_frames(int64_t n_in, int64_t hop) {
 }
 
 int jsg_tempogram_plan(const jsg_tempogram_args* g, char* name, int name_len, int32_t* frames_per_item, int32_t* lds_bytes) {
-    static const char* who = "jsg_tempogram_plan";
-    if (name && name_len < 24) return jsg_fail_who(JSG_ERR_INVALID, who, "bad argument");
-    const int rc = tempogram_check(g, who);
-    if (rc != JSG_OK) return rc;
-    TgPlan p{};
-    tempogram_resolve(g, &p);
-    if (name) std::strncpy(name, tempogram_path_name(p), name_len);
-    if (frames_per_item) *frames_per_item = p.F;
-    if (lds_bytes) *lds_bytes = 4 * p.lds_floats;
-    return JSG_OK;
+    return tempogram_plan_call("jsg_tempogram_plan", g, name, name_len, false, frames_per_item, lds_bytes);
 }
 
 int jsg_tempogram_kernel_name(const jsg_tempogram_args* g, char* out, int out_len) {
-    static const char* who = "jsg_tempogram_kernel_name";
-    if (!out || out_len < 24) return jsg_fail_who(JSG_ERR_INVALID, who, "bad argument");
-    const int rc = tempogram_check(g, who);
-    if (rc != JSG_OK) return rc;
-    TgPlan p{};
-    tempogram_resolve(g, &p);
-    std::strncpy(out, tempogram_path_name(p), out_len);
-    return JSG_OK;
+    return tempogram_plan_call("jsg_tempogram_kernel_name", g, out, out_len, true, nullptr, nullptr);
 }
 
 int jsg_tempo_prior_build(int32_t lags, double frame_rate, double start_bpm, double std_bpm, double max_bpm, float* out) {

@@ -374,10 +374,10 @@ void sp_enqueue(const SpArgs& k, const dim3 grid, hipStream_t s) {
 
 extern "C" int jsg_spectral_shape_launch(const jsg_spectral_args* g, void* stream) {
     static const char* who = "jsg_spectral_shape_launch";
-    const int rc = spectral_check(g, who);
-    if (rc != JSG_OK) return rc;
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return jsg_fail_who(JSG_ERR_NO_DEVICE, who, "no HIP device");
+    int rc = spectral_check(g, who);
+    if (rc == JSG_OK) rc = current_device(&dev, who);
+    if (rc != JSG_OK) return rc;
     // every refusal is behind us
     SpectralPlan p{};
     spectral_resolve(g, &p);
@@ -406,7 +406,7 @@ extern "C" int jsg_spectral_shape_launch(const jsg_spectral_args* g, void* strea
            | (g->flatness_db ? SP_FLATNESS : 0) | (g->crest ? SP_CREST : 0);
     // what a compute unit holds at a time by the registers of the path (tools/kernel_regs.py), two generations of it where that is 8
     const int per_cu = p.NC == kSpMaxRegs ? 2 : p.NC == 33 ? 3 : 8;
-    const dim3 grid((unsigned)std::min<long long>(k.n_items, (long long)cu_count_of_device(dev) * per_cu));
+    const dim3 grid(resident_grid(k.n_items, dev, per_cu));
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (p.NC) {
         case 1: sp_enqueue<1, 8>(k, grid, s); break;
@@ -418,6 +418,5 @@ extern "C" int jsg_spectral_shape_launch(const jsg_spectral_args* g, void* strea
         case kSpMaxRegs: sp_enqueue<kSpMaxRegs, 1>(k, grid, s); break;
         default: hipLaunchKernelGGL(spectral_stream_kernel, grid, dim3(kSpThreads), 0, s, k); break;
     }
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? JSG_OK : jsg_fail_hip(err, who);
+    return finish_launch(who);
 }

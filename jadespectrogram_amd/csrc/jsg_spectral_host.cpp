@@ -2,40 +2,29 @@
 // kernels and their launcher are in jsg_spectral.hip.
 #include <algorithm>
 #include <cstdint>
-#include <cstring>
 
 #include "jsg_internal.h"
 
 namespace jsg {
-
-namespace {
-typedef __int128 i128;
-
-i128 addr(const void* p) { return (i128)reinterpret_cast<uintptr_t>(p); }
-bool overlap(i128 a0, i128 a_bytes, i128 b0, i128 b_bytes) { return a0 && b0 && a0 < b0 + b_bytes && b0 < a0 + a_bytes; }
-}  // namespace
 
 int spectral_check(const jsg_spectral_args* g, const char* who) {
     if (!g) return jsg_fail_who(JSG_ERR_INVALID, who, "null argument");
     if (!g->in) return jsg_fail_who(JSG_ERR_INVALID, who, "null in");
     if (!g->freqs) return jsg_fail_who(JSG_ERR_INVALID, who, "null freqs");
     const void* outs[7] = {g->energy, g->centroid, g->spread, g->rolloff, g->rolloff_bin, g->flatness_db, g->crest};
-    uintptr_t bits = reinterpret_cast<uintptr_t>(g->in) | reinterpret_cast<uintptr_t>(g->freqs), any = 0;
-    for (const void* o : outs) any |= reinterpret_cast<uintptr_t>(o);
-    if (!any) return jsg_fail_who(JSG_ERR_INVALID, who, "all outputs null");
-    if (((bits | any) & 3) != 0) return jsg_fail_who(JSG_ERR_INVALID, who, "pointers must be 4-byte aligned");
-    if (g->rows < 1 || g->rows > 65535) return jsg_fail_who(JSG_ERR_INVALID, who, "rows must be in 1..65535");
+    if (std::all_of(outs, outs + 7, [](const void* o) { return !o; })) return jsg_fail_who(JSG_ERR_INVALID, who, "all outputs null");
+    int rc = check_aligned4(who, g->in, g->freqs, g->energy, g->centroid, g->spread, g->rolloff, g->rolloff_bin, g->flatness_db, g->crest);
+    if (rc == JSG_OK) rc = check_rows(g->rows, who);
+    if (rc != JSG_OK) return rc;
     if (g->n_bins < 1 || g->n_bins > JSG_SPECTRAL_MAX_BINS) return jsg_fail_who(JSG_ERR_INVALID, who, "n_bins must be in 1..65536");
     if (g->n_frames < 1 || g->n_frames >= (1ll << 31)) return jsg_fail_who(JSG_ERR_INVALID, who, "n_frames must be in 1..2^31-1");
     if (!(g->roll_percent > 0.f && g->roll_percent <= 1.f)) return jsg_fail_who(JSG_ERR_INVALID, who, "roll_percent must be in (0, 1]");
     if (g->frame_pitch < g->n_bins) return jsg_fail_who(JSG_ERR_INVALID, who, "frame_pitch smaller than n_bins");
     const bool multi = g->rows > 1;
-    const i128 plane = (i128)(g->n_frames - 1) * g->frame_pitch + g->n_bins;
-    if (multi && (i128)g->row_pitch < plane) return jsg_fail_who(JSG_ERR_INVALID, who, "row_pitch smaller than (n_frames-1)*frame_pitch + n_bins");
+    const i128 in_plane = plane(g->n_frames, g->frame_pitch, g->n_bins);
+    if (multi && (i128)g->row_pitch < in_plane) return jsg_fail_who(JSG_ERR_INVALID, who, "row_pitch smaller than (n_frames-1)*frame_pitch + n_bins");
     if (multi && g->out_pitch < g->n_frames) return jsg_fail_who(JSG_ERR_INVALID, who, "out_pitch smaller than n_frames");
-    const i128 rows1 = g->rows - 1;
-    const i128 in_bytes = 4 * (rows1 * (multi ? g->row_pitch : 0) + plane);
-    const i128 out_bytes = 4 * (rows1 * (multi ? g->out_pitch : 0) + g->n_frames);
+    const i128 in_bytes = span_bytes(g->rows, g->row_pitch, in_plane, 4), out_bytes = span_bytes(g->rows, g->out_pitch, g->n_frames, 4);
     for (const void* o : outs)
         if (overlap(addr(g->in), in_bytes, addr(o), out_bytes)) return jsg_fail_who(JSG_ERR_INVALID, who, "an output overlaps in");
     for (const void* o : outs)
@@ -79,31 +68,31 @@ const char* spectral_path_name(const SpectralPlan& p) {
 
 using namespace jsg;
 
-extern "C" {
-
-int jsg_spectral_shape_plan(const jsg_spectral_args* g, char* name, int name_len, int32_t* lanes_per_frame, int32_t* frames_per_group, int32_t* lds_bytes) {
-    static const char* who = "jsg_spectral_shape_plan";
-    if (name && name_len < 24) return jsg_fail_who(JSG_ERR_INVALID, who, "bad argument");
-    const int rc = spectral_check(g, who);
+namespace {
+// jsg_spectral_shape_plan (the name is optional) and jsg_spectral_shape_kernel_name (the name is all it gives)
+int spectral_plan_call(const char* who, const jsg_spectral_args* g, char* name, int name_len, bool need_name, int32_t* lanes_per_frame, int32_t* frames_per_group,
+                       int32_t* lds_bytes) {
+    int rc = check_name_buffer(who, name, name_len, need_name);
+    if (rc == JSG_OK) rc = spectral_check(g, who);
     if (rc != JSG_OK) return rc;
     SpectralPlan p{};
     spectral_resolve(g, &p);
-    if (name) std::strncpy(name, spectral_path_name(p), name_len);
+    put_path_name(name, name_len, spectral_path_name(p));
     if (lanes_per_frame) *lanes_per_frame = p.W;
     if (frames_per_group) *frames_per_group = p.FK;
     if (lds_bytes) *lds_bytes = 0;
     return JSG_OK;
 }
+}  // namespace
+
+extern "C" {
+
+int jsg_spectral_shape_plan(const jsg_spectral_args* g, char* name, int name_len, int32_t* lanes_per_frame, int32_t* frames_per_group, int32_t* lds_bytes) {
+    return spectral_plan_call("jsg_spectral_shape_plan", g, name, name_len, false, lanes_per_frame, frames_per_group, lds_bytes);
+}
 
 int jsg_spectral_shape_kernel_name(const jsg_spectral_args* g, char* out, int out_len) {
-    static const char* who = "jsg_spectral_shape_kernel_name";
-    if (!out || out_len < 24) return jsg_fail_who(JSG_ERR_INVALID, who, "bad argument");
-    const int rc = spectral_check(g, who);
-    if (rc != JSG_OK) return rc;
-    SpectralPlan p{};
-    spectral_resolve(g, &p);
-    std::strncpy(out, spectral_path_name(p), out_len);
-    return JSG_OK;
+    return spectral_plan_call("jsg_spectral_shape_kernel_name", g, out, out_len, true, nullptr, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -17,7 +17,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <climits>
 #include <cstdint>
 
@@ -194,27 +193,12 @@ __global__ __launch_bounds__(kYinThreads) void yin_kernel(const YnArgs a) {
 
 using namespace jsg;
 
-namespace {
-
-template <int NL>
-hipError_t yin_enqueue(const YnArgs& k, dim3 grid, size_t lds_bytes, hipStream_t s, bool first) {
-    // the kernel may ask for more than 48 KB of dynamic LDS: said once per device, before the first launch there
-    if (first) {
-        const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(&yin_kernel<NL>), hipFuncAttributeMaxDynamicSharedMemorySize, kYinLdsOne * 4);
-        if (err != hipSuccess) return err;
-    }
-    hipLaunchKernelGGL((yin_kernel<NL>), grid, dim3(kYinThreads), lds_bytes, s, k);
-    return hipGetLastError();
-}
-
-}  // namespace
-
 extern "C" int jsg_yin_launch(const jsg_yin_args* g, void* stream) {
     static const char* who = "jsg_yin_launch";
-    const int rc = yin_check(g, who);
-    if (rc != JSG_OK) return rc;
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return jsg_fail_who(JSG_ERR_NO_DEVICE, who, "no HIP device");
+    int rc = yin_check(g, who);
+    if (rc == JSG_OK) rc = current_device(&dev, who);
+    if (rc != JSG_OK) return rc;
     // every refusal is behind us
     YinPlan p{};
     yin_resolve(g, &p);
@@ -240,18 +224,10 @@ extern "C" int jsg_yin_launch(const jsg_yin_args* g, void* stream) {
     k.threshold = g->threshold;
     k.sample_rate = g->sample_rate;
     const size_t lds_bytes = sizeof(float) * (size_t)p.lds_floats;
-    const long long per_cu = std::max<long long>(1, std::min<long long>(8, kYinLdsOne / p.lds_floats));      // 2048 threads per compute unit
-    const dim3 grid((unsigned)std::min<long long>(k.n_items, (long long)cu_count_of_device(dev) * per_cu));
-    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    // one flag per device and path
-    static std::atomic<unsigned> told[64];
-    const unsigned bit = (unsigned)p.NL;
-    const bool first = dev < 0 || dev >= 64 || !(told[dev].load(std::memory_order_acquire) & bit);
-    const hipError_t err = p.NL == 1 ? yin_enqueue<1>(k, grid, lds_bytes, s, first)
-                         : p.NL == 2 ? yin_enqueue<2>(k, grid, lds_bytes, s, first)
-                         : p.NL == 4 ? yin_enqueue<4>(k, grid, lds_bytes, s, first)
-                                     : yin_enqueue<8>(k, grid, lds_bytes, s, first);
-    if (err != hipSuccess) return jsg_fail_hip(err, who);
-    if (first && dev >= 0 && dev < 64) told[dev].fetch_or(bit, std::memory_order_release);
-    return JSG_OK;
+    const dim3 grid(resident_grid(k.n_items, dev, per_cu_by_lds(kYinLdsOne, p.lds_floats, 8)));      // 2048 threads per compute unit
+    static void (*const kernels[4])(YnArgs) = {yin_kernel<1>, yin_kernel<2>, yin_kernel<4>, yin_kernel<8>};      // the code object holds them in this order
+    const int path = p.NL == 1 ? 0 : p.NL == 2 ? 1 : p.NL == 4 ? 2 : 3;
+    static OncePerDevice told;      // a bit per path
+    const hipError_t err = launch_large_lds(told, dev, 1u << path, kernels[path], kYinLdsOne * 4, grid, dim3(kYinThreads), lds_bytes, reinterpret_cast<hipStream_t>(stream), k);
+    return err == hipSuccess ? JSG_OK : jsg_fail_hip(err, who);
 }

@@ -3,15 +3,12 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 
 #include "jsg_internal.h"
 
 namespace jsg {
 
 namespace {
-typedef __int128 i128;
-
 long long yin_frame_count(long long L, int w, int tau_max, long long hop) {
     const long long span = (long long)w + tau_max;
     return L >= span ? 1 + (L - span) / hop : 0;
@@ -22,10 +19,9 @@ int yin_check(const jsg_yin_args* g, const char* who) {
     if (!g) return jsg_fail_who(JSG_ERR_INVALID, who, "null argument");
     if (!g->in) return jsg_fail_who(JSG_ERR_INVALID, who, "null in");
     if (!g->f0 && !g->aper && !g->cmnd) return jsg_fail_who(JSG_ERR_INVALID, who, "f0, aper and cmnd are all null");
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(g->in) | reinterpret_cast<uintptr_t>(g->f0) | reinterpret_cast<uintptr_t>(g->aper) |
-                           reinterpret_cast<uintptr_t>(g->cmnd);
-    if ((bits & 3) != 0) return jsg_fail_who(JSG_ERR_INVALID, who, "pointers must be 4-byte aligned");
-    if (g->rows < 1 || g->rows > 65535) return jsg_fail_who(JSG_ERR_INVALID, who, "rows must be in 1..65535");
+    int rc = check_aligned4(who, g->in, g->f0, g->aper, g->cmnd);
+    if (rc == JSG_OK) rc = check_rows(g->rows, who);
+    if (rc != JSG_OK) return rc;
     if (g->in_samples < 1 || g->in_samples >= (1ll << 31)) return jsg_fail_who(JSG_ERR_INVALID, who, "in_samples must be in 1..2^31-1");
     if (g->window < 1 || g->window > JSG_YIN_MAX_WINDOW) return jsg_fail_who(JSG_ERR_INVALID, who, "window must be in 1..8192");
     if (g->tau_max < 1 || g->tau_max > JSG_YIN_MAX_LAG) return jsg_fail_who(JSG_ERR_INVALID, who, "tau_max must be in 1..8192");
@@ -41,16 +37,14 @@ int yin_check(const jsg_yin_args* g, const char* who) {
     if (multi && (g->f0 || g->aper) && g->out_pitch < g->n_frames) return jsg_fail_who(JSG_ERR_INVALID, who, "out_pitch smaller than n_frames");
     const long long lags = (long long)g->tau_max + 1;
     if (g->cmnd && g->cmnd_frame_pitch < lags) return jsg_fail_who(JSG_ERR_INVALID, who, "cmnd_frame_pitch smaller than tau_max + 1");
-    const i128 plane = g->cmnd ? (i128)(g->n_frames - 1) * g->cmnd_frame_pitch + lags : 0;
-    if (multi && g->cmnd && (i128)g->cmnd_row_pitch < plane) return jsg_fail_who(JSG_ERR_INVALID, who, "cmnd_row_pitch smaller than (n_frames-1)*cmnd_frame_pitch + tau_max + 1");
+    const i128 cmnd_plane = g->cmnd ? plane(g->n_frames, g->cmnd_frame_pitch, lags) : 0;
+    if (multi && g->cmnd && (i128)g->cmnd_row_pitch < cmnd_plane) return jsg_fail_who(JSG_ERR_INVALID, who, "cmnd_row_pitch smaller than (n_frames-1)*cmnd_frame_pitch + tau_max + 1");
     // an output that overlaps the input
-    const i128 rows1 = g->rows - 1;
-    const i128 in0 = (i128)reinterpret_cast<uintptr_t>(g->in), in1 = in0 + 4 * (rows1 * (multi ? g->in_pitch : 0) + g->in_samples);
-    const i128 line = 4 * (rows1 * (multi ? g->out_pitch : 0) + g->n_frames);
-    const i128 lo[3] = {(i128)reinterpret_cast<uintptr_t>(g->f0), (i128)reinterpret_cast<uintptr_t>(g->aper), (i128)reinterpret_cast<uintptr_t>(g->cmnd)};
-    const i128 len[3] = {line, line, 4 * (rows1 * (multi ? g->cmnd_row_pitch : 0) + plane)};
+    const i128 in_bytes = span_bytes(g->rows, g->in_pitch, g->in_samples, 4), line = span_bytes(g->rows, g->out_pitch, g->n_frames, 4);
+    const void* out[3] = {g->f0, g->aper, g->cmnd};
+    const i128 len[3] = {line, line, span_bytes(g->rows, g->cmnd_row_pitch, cmnd_plane, 4)};
     for (int i = 0; i < 3; ++i)
-        if (lo[i] && in0 < lo[i] + len[i] && lo[i] < in1) return jsg_fail_who(JSG_ERR_INVALID, who, "an output overlaps in");
+        if (overlap(addr(g->in), in_bytes, addr(out[i]), len[i])) return jsg_fail_who(JSG_ERR_INVALID, who, "an output overlaps in");
     return JSG_OK;
 }
 
@@ -83,6 +77,21 @@ const char* yin_path_name(const YinPlan& p) { return p.NL == 1 ? "yin_lags1" : p
 
 using namespace jsg;
 
+namespace {
+// jsg_yin_plan (the name is optional) and jsg_yin_kernel_name (the name is all it gives)
+int yin_plan_call(const char* who, const jsg_yin_args* g, char* name, int name_len, bool need_name, int32_t* frames_per_item, int32_t* lds_bytes) {
+    int rc = check_name_buffer(who, name, name_len, need_name);
+    if (rc == JSG_OK) rc = yin_check(g, who);
+    if (rc != JSG_OK) return rc;
+    YinPlan p{};
+    yin_resolve(g, &p);
+    put_path_name(name, name_len, yin_path_name(p));
+    if (frames_per_item) *frames_per_item = p.F;
+    if (lds_bytes) *lds_bytes = 4 * p.lds_floats;
+    return JSG_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int64_t jsg_yin_frames(int64_t in_samples, int32_t window, int32_t tau_max, int64_t hop) {
@@ -95,27 +104,9 @@ int64_t jsg_yin_frames(int64_t in_samples, int32_t window, int32_t tau_max, int6
 }
 
 int jsg_yin_plan(const jsg_yin_args* g, char* name, int name_len, int32_t* frames_per_item, int32_t* lds_bytes) {
-    static const char* who = "jsg_yin_plan";
-    if (name && name_len < 24) return jsg_fail_who(JSG_ERR_INVALID, who, "bad argument");
-    const int rc = yin_check(g, who);
-    if (rc != JSG_OK) return rc;
-    YinPlan p{};
-    yin_resolve(g, &p);
-    if (name) std::strncpy(name, yin_path_name(p), name_len);
-    if (frames_per_item) *frames_per_item = p.F;
-    if (lds_bytes) *lds_bytes = 4 * p.lds_floats;
-    return JSG_OK;
+    return yin_plan_call("jsg_yin_plan", g, name, name_len, false, frames_per_item, lds_bytes);
 }
 
-int jsg_yin_kernel_name(const jsg_yin_args* g, char* out, int out_len) {
-    static const char* who = "jsg_yin_kernel_name";
-    if (!out || out_len < 24) return jsg_fail_who(JSG_ERR_INVALID, who, "bad argument");
-    const int rc = yin_check(g, who);
-    if (rc != JSG_OK) return rc;
-    YinPlan p{};
-    yin_resolve(g, &p);
-    std::strncpy(out, yin_path_name(p), out_len);
-    return JSG_OK;
-}
+int jsg_yin_kernel_name(const jsg_yin_args* g, char* out, int out_len) { return yin_plan_call("jsg_yin_kernel_name", g, out, out_len, true, nullptr, nullptr); }
 
 }  // extern "C"

@@ -122,6 +122,17 @@ def test_graph_capture_of_a_first_chain(jsg, torch_cuda):
     check_delta(Y, C, w, cr.INTERP, "capture")
 
 
+def test_first_mfcc_launch_of_a_path_with_more_than_48_kib_of_lds(jsg, torch_cuda):
+    """The first launch of the 16-coefficient path in this process (only the capture above precedes it, on another path) asks for more
+    dynamic LDS than a kernel may have without saying so: the launch itself has to say it."""
+    torch = torch_cuda
+    S = np.array(cr.planes()[:2, :3, :128])
+    D = cr.tables(128, 128)
+    name, _, lds = jsg.mfcc_plan(torch.from_numpy(S).cuda(), torch.from_numpy(np.array(D)).cuda(), torch.empty((2, 3, 128), dtype=torch.float32, device="cuda"))
+    assert name == "mfcc_block16" and lds > 49152, (name, lds)
+    check_projection(run_mfcc(jsg, torch, S, D, pad_frame=4, pad_out=1), S, D, "128 x 128, first on its path")
+
+
 # ---------------------------------------------------------------------------------------------------- the projection
 @pytest.mark.parametrize("B", [1, 2, 3, 31, 32, 33, 64, 65, 128, 257])
 def test_mfcc_bits_equal_the_restatement(jsg, torch_cuda, B):

@@ -157,6 +157,23 @@ def test_graph_capture_of_a_first_launch(jsg, torch_cuda):
     check_tg(tg, rr.tempogram(o, w, 100, 1, T, 1), "capture, Wn 100")
 
 
+def test_first_tempogram_launch_of_a_path_with_more_than_48_kib_of_lds(jsg, torch_cuda):
+    """The first launch of the eight-lags-per-lane path in this process (only the capture above precedes it, on another path) asks for
+    more dynamic LDS than a kernel may have without saying so: the launch itself has to say it."""
+    Wn, n_frames = 4096, 2
+    rng = np.random.default_rng(Wn)
+    o = (0.2 * np.abs(rng.standard_normal((1, Wn + 1)))).astype(np.float32)
+    o[0, ::7] += 1.0
+    w = rr.hann(Wn) + np.float32(0.01)
+    d_o, d_w, d_out = torch_cuda.zeros((1, Wn + 1), device="cuda"), torch_cuda.zeros(Wn, device="cuda"), torch_cuda.zeros((1, n_frames, Wn), device="cuda")
+    name, _, lds = jsg.tempogram_plan(d_o, d_w, d_out, lags=Wn, hop=1, n_frames=n_frames)
+    assert name == "tempogram_lags8" and lds > 49152, (name, lds)
+    shared = rr.sums(o, w, Wn, 1, n_frames)
+    for normalise in (0, 1):
+        got = run_tg(jsg, torch_cuda, o, w, Wn, 1, n_frames, normalise, pad_frame=1, offset=normalise)
+        check_tg(got, rr.tempogram(o, w, Wn, 1, n_frames, normalise, shared=shared), f"Wn = lags = {Wn}, first on its path, normalise {normalise}")
+
+
 # ---------------------------------------------------------------------------------------------------- onset strength
 @pytest.mark.parametrize("B", [1, 63, 64, 65, 128, 200])
 def test_onset_bits_equal_the_restatement(jsg, torch_cuda, B):

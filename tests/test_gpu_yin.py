@@ -141,6 +141,23 @@ def test_graph_capture_of_a_first_launch(jsg, torch_cuda):
     check(eager, yr.evaluate(x, 100, 3, 100, 50, n_frames, yr.THRESHOLD, yr.SR), lo=3, hi=100, thr=yr.THRESHOLD, sr=yr.SR, what="w 100, lags 3..100")
 
 
+def test_first_launch_of_a_path_with_more_than_48_kib_of_lds(jsg, torch_cuda):
+    """The first launch of the eight-lags-per-lane path in this process (only the capture above precedes it, on another path) asks for
+    more dynamic LDS than a kernel may have without saying so: the launch itself has to say it."""
+    size, hi, n_frames, hop = 8192, 2048, 2, 100
+    n = (n_frames - 1) * hop + size + hi
+    x = (0.4 * np.sin(2 * np.pi * np.arange(n) / 97.3) + 0.05 * np.random.default_rng(size).standard_normal(n)).astype(np.float32)[None]
+    d_x, d_f0 = torch_cuda.zeros((1, n), device="cuda"), torch_cuda.zeros((1, n_frames), device="cuda")
+    name, _, lds = jsg.yin_plan(d_x, size, 50, hi, hop, n_frames, 0.2, 48000.0, d_f0=d_f0)
+    assert name == "yin_lags8" and lds > 49152, (name, lds)
+    ref = yr.evaluate(x, size, 50, hi, hop, n_frames, 0.2, 48000.0)
+    out = run(jsg, torch_cuda, x, n_frames, w=size, lo=50, hi=hi, hop=hop, thr=0.2, sr=48000.0, offset=1)
+    check(out, ref, lo=50, hi=hi, thr=0.2, sr=48000.0, what=f"w {size}, tau_max {hi}, first on its path")
+    assert ref["decided"].all() and (np.abs(ref["tau64"] - 97) <= 1).all()
+    again = run(jsg, torch_cuda, x, n_frames, w=size, lo=50, hi=hi, hop=hop, thr=0.2, sr=48000.0, chunk_frames=1)
+    assert all(same(again[k], out[k]) for k in out)
+
+
 def test_accuracy_pitched_rows_at_an_odd_offset(jsg, torch_cuda):
     out = run(jsg, torch_cuda, yr.signals(), T, pad_in=5, pad_out=3, pad_frame=3, pad_row=7, offset=1, **SHARED)
     assert out["cmnd"].shape == (6, T, yr.TAU_MAX + 1) and out["f0"].shape == (6, T)

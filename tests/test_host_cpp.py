@@ -97,6 +97,17 @@ def test_host_math_entry_points_under_asan_ubsan(jsg):
     assert len(h_san) == 16 and h_san == h_lib
 
 
+def test_span_helpers_under_asan_ubsan():
+    """csrc/jsg_spans.h, which every feature unit's overlap refusals go through, alone in a CPU build under address + undefined-behaviour
+    sanitizers: a null pointer overlaps nothing, regions that touch do not overlap and regions that share a byte do, one row ignores its
+    row pitch, one frame's plane is its width, and a region that ends above 2^64 neither wraps nor overflows."""
+    exe = _cxx(["-O1", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                os.path.join(ROOT, "tests", "cpp", "spans_test.cpp")], os.path.join(tempfile.gettempdir(), "jsg_spans_san"))
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "spans: 0 failed" in r.stdout and "runtime error" not in r.stderr
+
+
 @pytest.mark.parametrize("flags", [["-fsanitize=thread"], ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]])
 def test_reblocker_resize_race_under_sanitizers(flags):
     """ADVICE (round 1): setFFTSize -> setDesiredBlockSizeSamples from the message thread while the audio thread is inside
