@@ -82,7 +82,13 @@ $(OBJ)/jsgx_beat_host.o: $(SRC)/jsgx_beat_host.cpp $(XDEPS)
 $(OBJ)/jsgx_dtw_host.o: $(SRC)/jsgx_dtw_host.cpp $(XDEPS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude -ffp-contract=off -D__HIP_PLATFORM_AMD__ -c $< -o $@
-$(OUTX): $(OBJ)/jsgx_beat.o $(OBJ)/jsgx_cdist.o $(OBJ)/jsgx_dtw.o $(OBJ)/jsgx_beat_host.o $(OBJ)/jsgx_dtw_host.o
+$(OBJ)/jsgx_viterbi.o: $(SRC)/jsgx_viterbi.hip $(XDEPS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(OBJ)/jsgx_viterbi_host.o: $(SRC)/jsgx_viterbi_host.cpp $(SRC)/jsg_spans.h $(XDEPS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude -ffp-contract=off -D__HIP_PLATFORM_AMD__ -c $< -o $@
+$(OUTX): $(OBJ)/jsgx_beat.o $(OBJ)/jsgx_cdist.o $(OBJ)/jsgx_dtw.o $(OBJ)/jsgx_viterbi.o $(OBJ)/jsgx_beat_host.o $(OBJ)/jsgx_dtw_host.o $(OBJ)/jsgx_viterbi_host.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^
 
 oracle:

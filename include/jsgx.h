@@ -341,6 +341,144 @@ JSGX_API int jsgx_dtw_launch(const jsgx_dtw_args* args, void* scratch, int64_t s
 JSGX_API int jsgx_dtw_plan(const jsgx_dtw_args* args, char* name, int name_len, int32_t* tile_rows, int32_t* tile_cols, int32_t* n_launches,
                            int32_t* threads, int32_t* lds_bytes);
 
+/* Section 4 was added to version 1 in the same way: sections 1 to 3, their structs and their constants are as they were. */
+
+/* ------------------------------------------------------------------------------------------------
+ * 4. Viterbi decoding of a hidden Markov model (the first function of librosa.sequence's second half): from frame-wise
+ *    log-likelihoods to the most likely state sequence.  A sequence q has T frames and S states; sequences are independent.  All
+ *    arithmetic is float32 and uncontracted (there are only additions and comparisons); fl(.) is one rounding to float32.  Every
+ *    input is a log-probability, and -inf (probability zero) is an ordinary value.  Nothing depends on seqs, on the pitches, on
+ *    which optional outputs are NULL or on the form of the kernel (jsgx_viterbi_plan).
+ *
+ *    Inputs.  Emissions b[t][s] = log_emit[q*emit_seq_pitch + t*emit_frame_pitch + s]: frame-major, the state fastest, the layout
+ *    the feature kernels of libjsg.so write.  The initial vector p0[s] = log_init[s] and the transition A(i, j), from the source
+ *    i to the destination j, are shared by all sequences.  A comes in one of two forms (trans_form):
+ *      JSGX_TRANS_DENSE:  A(i, j) = trans[i*trans_pitch + j], trans_pitch >= S; the sources of j are i = 0..S-1.
+ *      JSGX_TRANS_BAND with the half-width W = band_half, 0 <= W <= JSGX_VITERBI_MAX_BAND_HALF: the sources of j are
+ *          i = max(0, j-W) .. min(S-1, j+W), and A(i, j) = trans[(i - j + W)*trans_pitch + j]: diagonal-major, 2W+1 rows of S, so
+ *          that consecutive destinations are consecutive words.  An entry whose source would lie outside 0..S-1 is never read.
+ *          The band need not be Toeplitz: a locally normalised transition (librosa.sequence.transition_local,
+ *          jsgx_viterbi_band_build) fits, and so does pYIN's voiced/unvoiced x pitch product with the two kinds of state interleaved.
+ *
+ *    Recurrence.  V[0][s] = fl(p0[s] + b[0][s]).  For t >= 1 and every j, over the sources i of j:
+ *        v(i) = fl(V[t-1][i] + A(i, j));     w(i) = v(i), or -inf where v(i) is a NaN
+ *        i* = the source with the largest w, the lowest i among equal w (+0 and -0 are equal);   best = w(i*), with the bits of that w
+ *        V[t][j] = fl(best + b[t][j]);       psi[t][j] = i*
+ *    The selection is a reduction with the pair rule "(w, i) beats (w', i') iff w > w', or w == w' and i < i'".  The rule is a
+ *    total order on the pairs of one destination (the i are distinct), so its maximum is associative and commutative: the result
+ *    does not depend on how a kernel splits the sources among lanes or in which order it meets them.
+ *    End.  w_s = V[T-1][s], a NaN counted as -inf;  e = the lowest s among the largest w_s;  logp[q] = w_e.
+ *    Backtrace.  states[T-1] = e;  states[t-1] = psi[t][states[t]] for t = T-1 down to 1.
+ *    Outputs.  states[q*states_pitch + t] (int32);  logp[q] where given;  value[q*value_seq_pitch + t*value_frame_pitch + s] =
+ *    V[t][s] where given (a NaN of V is stored as it came out of the addition).
+ *    A path is always written.  logp = -inf says that no path has a probability above zero: the states are then what the tie
+ *    rule gives and mean nothing.  That is a result, not a refusal: the launch returns JSGX_OK, and only a refused argument returns
+ *    JSGX_ERR_INVALID.
+ *
+ *    NaN.  A NaN emission b[t][s] makes V[t][s] a NaN (value shows it); as a source of frame t+1 that state counts as -inf, and as
+ *    an end state too.  Nothing else is touched.  A NaN in A or p0 goes the same way: v is a NaN and counts as -inf.  +inf is
+ *    inside the contract only in so far as these operations define it (+inf + -inf is a NaN and counts as -inf).
+ *
+ *    Known answers.  All inputs +0 (S states, T frames, either form): every v is +0, every tie goes to the lowest source, V = +0
+ *    everywhere, psi = 0 (dense) or max(0, j-W) (band), e = 0, so states are all 0 and logp = +0.  A band with W = 0 and a finite
+ *    diagonal: psi[t][j] = j, so states are constant at the end state e.  A frame t whose emissions are all -inf: V[t'] = -inf for
+ *    every t' >= t, logp = -inf, e = 0, and the states follow the tie rule (dense: all 0).  A NaN emission at (t, s): above.
+ *
+ *    Error bound, for finite inputs that are all <= 0, against exact arithmetic on the same float32 inputs, u = 2^-24.  Every
+ *    addition is of two terms of one sign, so nothing cancels: a computed sum is the exact sum of its computed operands times
+ *    (1 + d), |d| <= u.  The maximum is monotone and exact: if every candidate has the relative error g, so has the largest
+ *    (all are <= 0).  V[0] carries one rounding; a frame t >= 1 adds one for v and one for V[t]: V[T-1], and so logp, carries at
+ *    most 2T - 1 roundings, a relative (1 + u)^(2T-1) - 1 <= (2T - 1) u + (2T u)^2 / 2 (1 + 2T u).  For T <= 4096 the second-order
+ *    part is at most 2^-23 (1 + 2^-11) < 3 u, so the whole is inside (2T + 2) u, which tests/test_viterbi_ref.py asserts against
+ *    float64 (whose own error is 2^-29 of that).  The states are exact where the exact optimum leads its runners-up by more than
+ *    this; elsewhere a different, nearly as likely path may come out.
+ *
+ *    Differences from librosa.sequence.viterbi: the inputs are logarithms (librosa takes probabilities and takes the logarithms
+ *    itself) and frame-major (librosa: [states][frames]); ties go to the lowest state (librosa: numpy's argmax, the same, but over
+ *    values computed in another order); log_init is required here (librosa's p_init defaults to the uniform vector; the Python
+ *    layer supplies that default).  Agreement with librosa has not been measured: librosa is not installed where this was built.
+ *
+ *    The kernels.  Time is serial, so "the forward kernel" decodes one sequence per workgroup from t = 0 to T-1; workgroups of
+ *    different sequences never wait for one another: no grid barrier, no ticket, no spin loop.  A lone sequence therefore uses one
+ *    compute unit; that is accepted.  V[t-1] and V[t] are two rows in LDS with one workgroup barrier per frame.  The workgroup has
+ *    threads = min(JSGX_VITERBI_THREADS, S*G rounded up to 64) lanes, G = the largest power of two <= 64 with S*G <=
+ *    JSGX_VITERBI_THREADS (1 where there is none): G lanes of one wavefront share a destination j, lane g of them takes the
+ *    sources lo + g, lo + g + G, ... (lo = the first source of j), and the G partial (w, i) are reduced with the pair rule by lane
+ *    moves (xor 1, 2, ..., G/2); by the paragraph on the rule the result is the one above.  Where S > JSGX_VITERBI_THREADS a lane
+ *    owns the destinations j and j + JSGX_VITERBI_THREADS.  V[t-1][i] is an LDS broadcast, A(i, j) for consecutive j is consecutive words, and
+ *    b[t+1][.] is loaded while frame t computes.  psi goes to the scratch as uint16.  The four forms are one templated kernel:
+ *      "viterbi_dense_lds"   dense, S <= JSGX_VITERBI_LDS_STATES: A staged once in LDS.         LDS bytes: 4 (S*S + 2 S)   (192: 148992)
+ *      "viterbi_dense_mem"   dense, larger S: A (at most 16 MiB) re-read every frame through L2 and the Infinity Cache.   8 S
+ *      "viterbi_band_lds"    band, 4 ((2W+1) S + 2 S) <= 163840: the band table staged once in LDS.   4 ((2W+1) S + 2 S)
+ *      "viterbi_band_mem"    band, where that does not fit: the table re-read from memory.            8 S
+ *    The backtrace is blocked over B = JSGX_VITERBI_BLOCK frames, n_blocks = ceil(T / B); block k ends at the frame
+ *    L_k = min((k+1) B, T) - 1.  "viterbi_jump" (seqs x blocks 1.., left out where n_blocks = 1): for every state s at L_k it follows psi
+ *    down to the state at L_(k-1): jump[k][s], uint16 in the scratch; all states and blocks in parallel.  "viterbi_ends" (a workgroup per
+ *    sequence): e and logp by the pair rule, then end[n_blocks-1] = e, end[k-1] = jump[k][end[k]]: T / B dependent steps.
+ *    "viterbi_trace" (seqs x blocks, a lane per block): from end[k] it walks its own frames and writes states.  Every psi value is
+ *    below S by construction and every loop is bounded by T or B.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSGX_TRANS_DENSE 0
+#define JSGX_TRANS_BAND 1
+#define JSGX_VITERBI_MAX_STATES 2048
+#define JSGX_VITERBI_MAX_FRAMES 1048576    /* 2^20 */
+#define JSGX_VITERBI_MAX_BAND_HALF 64
+#define JSGX_VITERBI_LDS_STATES 192        /* dense with A in LDS: 4 * (192 * 192 + 2 * 192) = 148992 bytes, inside 160 KiB */
+#define JSGX_VITERBI_THREADS 1024          /* the most lanes of a forward workgroup */
+#define JSGX_VITERBI_LDS_LIMIT 163840
+/* The block of the backtrace was chosen among 64, 256 and 1024 by measurement on an MI355X at T = 65536 (profiles/viterbi_bench.md). */
+#ifndef JSGX_VITERBI_BLOCK                 /* tools/viterbi_bench.py builds the other two for the comparison */
+#define JSGX_VITERBI_BLOCK 256
+#endif
+
+typedef struct jsgx_viterbi_args {
+    const float* log_emit;      /* device floats: b[q][t][s] */
+    int64_t emit_frame_pitch;   /* >= n_states */
+    int64_t emit_seq_pitch;     /* seqs > 1: >= (n_frames - 1) * emit_frame_pitch + n_states */
+    const float* log_init;      /* device floats [n_states] */
+    const float* trans;         /* device floats: dense [n_states][trans_pitch], band [2 * band_half + 1][trans_pitch] */
+    int64_t trans_pitch;        /* >= n_states */
+    int32_t trans_form;         /* JSGX_TRANS_DENSE or JSGX_TRANS_BAND */
+    int32_t band_half;          /* W: 0 with the dense form, 0..JSGX_VITERBI_MAX_BAND_HALF with the band form */
+    int32_t seqs;               /* 1..65535, independent */
+    int32_t n_states;           /* S, 1..JSGX_VITERBI_MAX_STATES */
+    int32_t n_frames;           /* T, 1..JSGX_VITERBI_MAX_FRAMES */
+    int32_t reserved0;          /* 0 */
+    int32_t* states;            /* device int32: states[q][t] at states[q*states_pitch + t] */
+    int64_t states_pitch;       /* seqs > 1: >= n_frames */
+    float* logp;                /* device floats [seqs] or NULL */
+    float* value;               /* device floats or NULL: V[q][t][s] at value[q*value_seq_pitch + t*value_frame_pitch + s] */
+    int64_t value_frame_pitch;  /* value given: >= n_states */
+    int64_t value_seq_pitch;    /* value given and seqs > 1: >= (n_frames - 1) * value_frame_pitch + n_states */
+} jsgx_viterbi_args;            /* 8-byte members and pairs of 4-byte ones: 120 bytes, no padding */
+
+/* The bytes of scratch the launch needs, with n_blocks = ceil(T / JSGX_VITERBI_BLOCK):
+ *     4 * seqs * S  (V[T-1])  +  4 * seqs * n_blocks  (end)  +  2 * seqs * T * S  (psi)  +  2 * seqs * n_blocks * S  (jump),
+ * rounded up to a multiple of 4, in this order.  Refused (a negative jsgx_status): what the launch refuses before it looks at the scratch. */
+JSGX_API int64_t jsgx_viterbi_scratch_bytes(const jsgx_viterbi_args* args);
+/* Enqueue only: no allocation, no synchronisation; capture works, a first launch included.  The kernels (forward, jump where
+ * T > JSGX_VITERBI_BLOCK, ends, trace) go onto the one stream as a plain chain.  The scratch is used only while they run.  Refused
+ * (JSGX_ERR_INVALID, nothing enqueued), in this order and before any device call: null args, a null log_emit, a null log_init, a null
+ * trans, a null states; a pointer that is not 4-byte aligned; seqs outside 1..65535, n_states outside 1..2048, n_frames outside
+ * 1..2^20; a trans_form other than the two; a non-zero band_half with the dense form, a band_half outside 0..64 with the band form; a
+ * non-zero reserved0; emit_frame_pitch below n_states, emit_seq_pitch that does not cover a sequence (seqs > 1), trans_pitch below
+ * n_states, states_pitch below n_frames (seqs > 1), value_frame_pitch below n_states (value given), value_seq_pitch that does not
+ * cover a sequence (value given, seqs > 1); an output (states, logp, value) overlapping log_emit, one overlapping log_init, one
+ * overlapping trans, an output overlapping another output; a null scratch, a scratch that is not 4-byte aligned, scratch_bytes below
+ * jsgx_viterbi_scratch_bytes.  Then JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_viterbi_launch(const jsgx_viterbi_args* args, void* scratch, int64_t scratch_bytes, void* stream);
+/* What the launch enqueues, without a device: the form of the forward kernel (above), the lanes of its workgroup, the bytes of LDS
+ * it holds (dynamic; <= JSGX_VITERBI_LDS_LIMIT) and the number of kernels (3 where T <= JSGX_VITERBI_BLOCK, else 4).  Any output
+ * pointer may be NULL (name: else name_len >= 24).  Refused: a name_len below 24 with a name, then what the scratch size refuses. */
+JSGX_API int jsgx_viterbi_plan(const jsgx_viterbi_args* args, char* name, int name_len, int32_t* threads, int32_t* lds_bytes, int32_t* n_launches);
+/* A locally normalised band transition on the host (no device; librosa.sequence.transition_local with a given window): for every
+ * source i the weights are window[j - i + W] over the j = max(0, i-W)..min(S-1, i+W); their sum is taken in double, j ascending;
+ * out[(i - j + W)*out_pitch + j] = (float)log(weight / sum), the logarithm in double and rounded once; a zero weight gives -inf.
+ * The entries whose source lies outside the matrix are written as -inf (the launch never reads them).  out has 2W+1 rows of out_pitch.
+ * JSGX_ERR_INVALID, in this order: a null window, a null out; n_states outside 1..2048; band_half outside 0..64; a window entry that is
+ * negative or not finite; window[W] <= 0 (so that no row sums to zero); out_pitch below n_states. */
+JSGX_API int jsgx_viterbi_band_build(int32_t n_states, int32_t band_half, const double* window, float* out, int64_t out_pitch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,8 +28,8 @@ UNIT_FLAGS = {"jsg_stft_a.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 ARCH = "gfx950"
 # the companion library (include/jsgx.h): its own units and headers, the same flags, nothing shared with libjsg.so
 LIBX = os.path.join(PKG, "libjsgx.so")
-SOURCES_X = ["jsgx_beat.hip", "jsgx_cdist.hip", "jsgx_dtw.hip", "jsgx_beat_host.cpp", "jsgx_dtw_host.cpp"]
-HEADERS_X = ["jsgx_internal.h", os.path.join(ROOT, "include", "jsgx.h")]
+SOURCES_X = ["jsgx_beat.hip", "jsgx_cdist.hip", "jsgx_dtw.hip", "jsgx_viterbi.hip", "jsgx_beat_host.cpp", "jsgx_dtw_host.cpp", "jsgx_viterbi_host.cpp"]
+HEADERS_X = ["jsgx_internal.h", "jsg_spans.h", os.path.join(ROOT, "include", "jsgx.h")]
 
 
 def _hipcc() -> str:

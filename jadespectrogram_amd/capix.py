@@ -50,6 +50,18 @@ class DtwArgs(C.Structure):
                 ("path_pitch", C.c_int64), ("max_path", C.c_int32), ("path_len", C.c_void_p), ("total", C.c_void_p)]
 
 
+TRANS_DENSE, TRANS_BAND = 0, 1
+VITERBI_MAX_STATES, VITERBI_MAX_FRAMES, VITERBI_MAX_BAND_HALF = 2048, 1 << 20, 64
+VITERBI_LDS_STATES, VITERBI_THREADS, VITERBI_LDS_LIMIT, VITERBI_BLOCK = 192, 1024, 163840, 256
+
+
+class ViterbiArgs(C.Structure):
+    _fields_ = [("log_emit", C.c_void_p), ("emit_frame_pitch", C.c_int64), ("emit_seq_pitch", C.c_int64), ("log_init", C.c_void_p), ("trans", C.c_void_p),
+                ("trans_pitch", C.c_int64), ("trans_form", C.c_int32), ("band_half", C.c_int32), ("seqs", C.c_int32), ("n_states", C.c_int32),
+                ("n_frames", C.c_int32), ("reserved0", C.c_int32), ("states", C.c_void_p), ("states_pitch", C.c_int64), ("logp", C.c_void_p),
+                ("value", C.c_void_p), ("value_frame_pitch", C.c_int64), ("value_seq_pitch", C.c_int64)]
+
+
 # every symbol include/jsgx.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -64,6 +76,10 @@ SIGNATURES = {
     "jsgx_dtw_scratch_bytes": (C.c_int64, [C.POINTER(DtwArgs)]),
     "jsgx_dtw_launch": (C.c_int, [C.POINTER(DtwArgs), _P, C.c_int64, _P]),
     "jsgx_dtw_plan": (C.c_int, [C.POINTER(DtwArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 5),
+    "jsgx_viterbi_scratch_bytes": (C.c_int64, [C.POINTER(ViterbiArgs)]),
+    "jsgx_viterbi_launch": (C.c_int, [C.POINTER(ViterbiArgs), _P, C.c_int64, _P]),
+    "jsgx_viterbi_plan": (C.c_int, [C.POINTER(ViterbiArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 3),
+    "jsgx_viterbi_band_build": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int64]),
 }
 
 _lib = None

@@ -8,6 +8,8 @@
 
 #if defined(__HIPCC__)      // hipcc compiles the host unit as HIP too
 #include <hip/hip_runtime.h>
+
+#include <atomic>
 #define JSGX_HD __host__ __device__ __forceinline__
 #else
 #define JSGX_HD static inline
@@ -27,8 +29,42 @@ int cdist_check(const jsgx_cdist_args* g, const char* who);
 int dtw_check(const jsgx_dtw_args* g, const char* who);
 int64_t dtw_scratch_bytes(const jsgx_dtw_args* g);
 int dtw_launches(const jsgx_dtw_args* g);          // the kernels jsgx_dtw_launch enqueues
+// section 4 (jsgx_viterbi_host.cpp): every refusal that does not look at the scratch, in the header's order
+int viterbi_check(const jsgx_viterbi_args* g, const char* who);
 
-constexpr int kBeatRing = 4096;                                  // >= 2 * JSGX_BEAT_MAX_PERIOD + JSGX_BEAT_THREADS, a power of two
+// How the forward kernel of section 4 serves a shape (include/jsgx.h, "The kernels"), and where the parts of the scratch lie.
+struct ViterbiPlan {
+    const char* name;
+    bool band, table_in_lds;
+    int G, threads, lds_bytes;
+    int n_blocks, n_launches;
+    long long off_end, off_psi, off_jump;          // byte offsets in the scratch; V[T-1] is at 0
+    long long scratch_bytes;
+};
+ViterbiPlan viterbi_plan(const jsgx_viterbi_args* g);
+
+#if defined(__HIPCC__)
+// Launches a kernel that may ask for more than 64 KiB of dynamic LDS, up to lds_max bytes.  The runtime has to be told once per
+// device and kernel before the first such launch; *told keeps a bit per device (a device index outside 0..63 is told every time).
+// Telling is no stream operation, so a first launch under capture works.  The bit is set after the launch has succeeded.
+template <class Args>
+hipError_t launch_large_lds(std::atomic<unsigned long long>* told, int dev, void (*kernel)(Args), int lds_max, dim3 grid, dim3 block, size_t lds_bytes,
+                            hipStream_t s, const Args& k) {
+    const unsigned long long bit = dev >= 0 && dev < 64 ? 1ull << dev : 0;
+    const bool first = !(told->load(std::memory_order_acquire) & bit);
+    if (first) {
+        const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        if (err != hipSuccess) return err;
+    }
+    void* args[] = {const_cast<Args*>(&k)};
+    (void)hipLaunchKernel(reinterpret_cast<const void*>(kernel), grid, block, args, lds_bytes, s);
+    const hipError_t err = hipGetLastError();
+    if (err == hipSuccess && first) told->fetch_or(bit, std::memory_order_release);
+    return err;
+}
+#endif
+
+constexpr int kBeatRing = 4096;                                 // >= 2 * JSGX_BEAT_MAX_PERIOD + JSGX_BEAT_THREADS, a power of two
 constexpr int kBeatPen = 2 * JSGX_BEAT_MAX_PERIOD + 4;           // pen[tau], tau <= 2P
 constexpr int kBeatG = JSGX_BEAT_MAX_PERIOD + 4;                 // g[k], k <= P
 

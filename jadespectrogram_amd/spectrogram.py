@@ -1966,6 +1966,100 @@ def dtw(X=None, Y=None, *, C=None, metric="euclidean", weights_mul=None, weights
 
 
 # --------------------------------------------------------------------------------------------------
+# Viterbi decoding of hidden Markov models (include/jsgx.h, section 4: libjsgx.so)
+# --------------------------------------------------------------------------------------------------
+def _viterbi_args(d_log_emit, d_log_init, d_log_trans, d_states, band_half, d_logp, d_value) -> capix.ViterbiArgs:
+    import torch
+    b = _planes(d_log_emit, "d_log_emit")
+    Q, T, S = b.shape
+    band = band_half is not None
+    rows = 2 * int(band_half) + 1 if band else S
+    a = d_log_trans
+    assert a.is_cuda and a.dtype == torch.float32 and a.dim() == 2 and tuple(a.shape) == (rows, S) and (a.stride(1) == 1 or S == 1), \
+        "d_log_trans: float32 CUDA [states][states], or [2 * band_half + 1][states] with band_half"
+    assert d_log_init.is_cuda and d_log_init.dtype == torch.float32 and d_log_init.dim() == 1 and d_log_init.shape[0] == S and d_log_init.is_contiguous(), \
+        "d_log_init: float32 CUDA [states]"
+    st = d_states[None] if d_states.dim() == 1 else d_states
+    assert st.is_cuda and st.dtype == torch.int32 and st.dim() == 2 and tuple(st.shape) == (Q, T) and (st.stride(1) == 1 or T == 1), "d_states: int32 CUDA [seqs][frames]"
+    assert d_logp is None or (d_logp.is_cuda and d_logp.dtype == torch.float32 and d_logp.dim() == 1 and d_logp.shape[0] >= Q and d_logp.is_contiguous()), \
+        "d_logp: float32 CUDA [seqs]"
+    v = None if d_value is None else _planes(d_value, "d_value")
+    assert v is None or tuple(v.shape) == (Q, T, S), "d_value: the shape of d_log_emit"
+    ptr = lambda t: None if t is None else t.data_ptr()
+    return capix.ViterbiArgs(b.data_ptr(), b.stride(1), b.stride(0), d_log_init.data_ptr(), a.data_ptr(), a.stride(0) if rows > 1 else max(S, a.stride(0)),
+                             capix.TRANS_BAND if band else capix.TRANS_DENSE, int(band_half) if band else 0, Q, S, T, 0, st.data_ptr(), st.stride(0), ptr(d_logp),
+                             ptr(v), 0 if v is None else v.stride(1), 0 if v is None else v.stride(0))
+
+
+def viterbi_scratch_bytes(d_log_emit, d_log_init, d_log_trans, d_states, *, band_half: int | None = None, d_logp=None, d_value=None) -> int:
+    """jsgx_viterbi_scratch_bytes: the bytes of scratch viterbi_launch needs for these arguments."""
+    a = _viterbi_args(d_log_emit, d_log_init, d_log_trans, d_states, band_half, d_logp, d_value)
+    return int(capix.check(capix.lib().jsgx_viterbi_scratch_bytes(C.byref(a))))
+
+
+def viterbi_launch(d_log_emit, d_log_init, d_log_trans, d_states, *, band_half: int | None = None, d_logp=None, d_value=None, d_scratch=None,
+                   stream: int | None = None):
+    """jsgx_viterbi_launch: d_log_emit float32 [frames][states] or [seqs][frames][states] (log-likelihoods, frame-major), d_log_init float32
+    [states], d_log_trans float32 [states][states] (source, destination) or, with band_half = W, the diagonal-major band table
+    [2W + 1][states] of viterbi_band_transition -> d_states int32 [seqs][frames] (the most likely path), and where given d_logp float32
+    [seqs] (its log-probability; -inf: no path has a probability above zero) and d_value float32, the shape of d_log_emit (V).
+    d_scratch: a contiguous CUDA tensor of at least viterbi_scratch_bytes bytes (None: one is allocated with torch for this call).
+    Enqueue only: the forward kernel, then the blocked backtrace."""
+    import torch
+    a = _viterbi_args(d_log_emit, d_log_init, d_log_trans, d_states, band_half, d_logp, d_value)
+    d_scratch, stream = _scratch_and_stream(d_scratch, stream, d_log_emit, lambda: capix.check(capix.lib().jsgx_viterbi_scratch_bytes(C.byref(a))) // 4, torch.int32,
+                                            any_dtype=True)
+    capix.check(capix.lib().jsgx_viterbi_launch(C.byref(a), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), stream))
+
+
+def viterbi_plan(n_states: int, n_frames: int, seqs: int = 1, band_half: int | None = None):
+    """jsgx_viterbi_plan: (form of the forward kernel, lanes per workgroup, bytes of LDS per workgroup, kernel launches) for this shape:
+    "viterbi_dense_lds" / "viterbi_dense_mem" without band_half, "viterbi_band_lds" / "viterbi_band_mem" with it.  Needs no device."""
+    S, T = int(n_states), int(n_frames)
+    a = capix.ViterbiArgs(log_emit=1 << 44, emit_frame_pitch=S, emit_seq_pitch=S * T, log_init=2 << 44, trans=3 << 44, trans_pitch=S,
+                          trans_form=capix.TRANS_DENSE if band_half is None else capix.TRANS_BAND, band_half=0 if band_half is None else int(band_half),
+                          seqs=int(seqs), n_states=S, n_frames=T, states=4 << 44, states_pitch=T)      # never dereferenced
+    name, out = C.create_string_buffer(32), [C.c_int32() for _ in range(3)]
+    capix.check(capix.lib().jsgx_viterbi_plan(C.byref(a), name, 32, *[C.byref(o) for o in out]))
+    return (name.value.decode(),) + tuple(o.value for o in out)
+
+
+def viterbi_band_transition(n_states: int, window) -> np.ndarray:
+    """jsgx_viterbi_band_build: the locally normalised band transition of a window of 2W + 1 non-negative weights (window[W] > 0), as
+    float32 [2W + 1][n_states], diagonal-major: row i - j + W, column j holds log(window[j - i + W] / the sum of the window over the
+    destinations of i inside the matrix), -inf where the source lies outside.  What viterbi_launch takes with band_half = W."""
+    w = np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
+    if w.size % 2 != 1:
+        raise JsgError(capix.JSGX_ERR_INVALID, "viterbi_band_transition: the window has 2 * band_half + 1 entries")
+    out = np.empty((w.size, int(n_states)), dtype=np.float32)
+    capix.check(capix.lib().jsgx_viterbi_band_build(int(n_states), w.size // 2, w.ctypes.data, out.ctypes.data, int(n_states)))
+    return out
+
+
+def viterbi(log_emit, log_trans, log_init=None, *, band_half=None):
+    """The most likely state sequence of a hidden Markov model (librosa.sequence.viterbi, in logarithms): log_emit [T, S] or [Q, T, S]
+    (frame-major log-likelihoods), log_trans [S, S] (source, destination) or with band_half = W the band table [2W + 1, S], log_init [S]
+    (None: uniform, log(1 / S)); numpy arrays or float32 CUDA tensors -> (states int32 [T] or [Q, T], logp float32 [] or [Q]) as CUDA
+    tensors.  logp = -inf: no path has a probability above zero.  Differences from librosa are listed in include/jsgx.h."""
+    import torch
+    b, _ = _to_cuda(log_emit)
+    assert b.dim() in (2, 3), "viterbi: log_emit [T, S] or [Q, T, S]"
+    batched = b.dim() == 3
+    b3 = (b if batched else b[None]).contiguous()
+    Q, T, S = b3.shape
+    a = _to_cuda(log_trans)[0].to(b.device).contiguous()
+    if log_init is None:
+        p0 = torch.full((S,), float(np.float32(np.log(1.0 / S))), dtype=torch.float32, device=b.device)
+    else:
+        p0 = _to_cuda(log_init)[0].to(b.device).contiguous()
+    states = torch.empty((Q, T), dtype=torch.int32, device=b.device)
+    logp = torch.empty((Q,), dtype=torch.float32, device=b.device)
+    with torch.cuda.device(_device_index(b)):
+        viterbi_launch(b3, p0, a, states, band_half=band_half, d_logp=logp)
+    return (states, logp) if batched else (states[0], logp[0])
+
+
+# --------------------------------------------------------------------------------------------------
 # cepstral coefficients and delta features (include/jsg.h, section 2k)
 # --------------------------------------------------------------------------------------------------
 _NORMS = {"ortho": capi.DCT_NORM_ORTHO, None: capi.DCT_NORM_NONE, "none": capi.DCT_NORM_NONE}
