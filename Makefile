@@ -10,85 +10,36 @@ OBJ   := jadespectrogram_amd/build
 .PHONY: lib oracle test-cpp clean
 lib: $(OUT) $(OUTX)
 
-HIPFLAGS := -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude --offload-arch=$(ARCH) -fno-slp-vectorize -mllvm -amdgpu-kernarg-preload-count=16
-KDEPS    := $(SRC)/jsg_stft_kernel.h $(SRC)/jsg_runs_grid.h $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h $(SRC)/jsg_exact_math.h include/jsg.h
+HIPFLAGS  := -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude --offload-arch=$(ARCH) -fno-slp-vectorize -mllvm -amdgpu-kernarg-preload-count=16
+HOSTFLAGS := -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude -ffp-contract=off -D__HIP_PLATFORM_AMD__
 
-$(OBJ)/jsg_kernels.o: $(SRC)/jsg_kernels.hip $(KDEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+# the units of each library, in link order, and the headers that all units of a kind depend on
+HIP_UNITS   := jsg_kernels jsg_stft_a jsg_stft_b jsg_filterbank jsg_display_axis jsg_cstft jsg_pvoc jsg_hpss jsg_resample jsg_cqt jsg_yin jsg_rhythm jsg_cepstral jsg_spectral
+HOST_UNITS  := jsg_engine jsg_host_math jsg_filterbank_host jsg_display_axis_host jsg_cqt_host jsg_yin_host jsg_rhythm_host jsg_cepstral_host jsg_spectral_host
+XHIP_UNITS  := jsgx_beat jsgx_cdist jsgx_dtw jsgx_viterbi
+XHOST_UNITS := jsgx_beat_host jsgx_dtw_host jsgx_viterbi_host
+# jsg_spans.h and jsg_launch.h have no state; they are all that the two libraries share
+SHARED := $(SRC)/jsg_spans.h $(SRC)/jsg_launch.h
+KDEPS  := $(SRC)/jsg_stft_kernel.h $(SRC)/jsg_runs_grid.h $(SRC)/jsg_internal.h $(SRC)/jsg_exact_math.h $(SHARED) include/jsg.h
+HDEPS  := $(SRC)/jsg_internal.h $(SRC)/jsg_block_queue.h $(SRC)/jsg_exact_math.h $(SRC)/jsg_colormap_tables.inc $(SHARED) include/jsg.h
+XDEPS  := $(SRC)/jsgx_internal.h $(SHARED) include/jsgx.h
+
+$(HIP_UNITS:%=$(OBJ)/%.o): $(KDEPS)
+$(HOST_UNITS:%=$(OBJ)/%.o): $(HDEPS)
+$(XHIP_UNITS:%=$(OBJ)/%.o) $(XHOST_UNITS:%=$(OBJ)/%.o): $(XDEPS)
 # the 512 / 1024 / 2048 / 8192-point kernels: ILP-first machine scheduler (see the unit's header comment)
-$(OBJ)/jsg_stft_a.o: $(SRC)/jsg_stft_a.hip $(KDEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -mllvm -amdgpu-sched-strategy=max-ilp -c $< -o $@
-$(OBJ)/jsg_stft_b.o: $(SRC)/jsg_stft_b.hip $(KDEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_filterbank.o: $(SRC)/jsg_filterbank.hip $(KDEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_display_axis.o: $(SRC)/jsg_display_axis.hip $(KDEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_cstft.o: $(SRC)/jsg_cstft.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_pvoc.o: $(SRC)/jsg_pvoc.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_hpss.o: $(SRC)/jsg_hpss.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_resample.o: $(SRC)/jsg_resample.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_cqt.o: $(SRC)/jsg_cqt.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_yin.o: $(SRC)/jsg_yin.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_rhythm.o: $(SRC)/jsg_rhythm.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_cepstral.o: $(SRC)/jsg_cepstral.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h include/jsg.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsg_spectral.o: $(SRC)/jsg_spectral.hip $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h $(SRC)/jsg_exact_math.h include/jsg.h
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(OBJ)/jsg_stft_a.o: UNITFLAGS := -mllvm -amdgpu-sched-strategy=max-ilp
 
-$(OBJ)/%.o: $(SRC)/%.cpp $(SRC)/jsg_internal.h $(SRC)/jsg_spans.h $(SRC)/jsg_block_queue.h $(SRC)/jsg_exact_math.h $(SRC)/jsg_colormap_tables.inc include/jsg.h
+$(HIP_UNITS:%=$(OBJ)/%.o) $(XHIP_UNITS:%=$(OBJ)/%.o): $(OBJ)/%.o: $(SRC)/%.hip
 	@mkdir -p $(OBJ)
-	$(HIPCC) -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude -ffp-contract=off -D__HIP_PLATFORM_AMD__ -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) $(UNITFLAGS) -c $< -o $@
+$(HOST_UNITS:%=$(OBJ)/%.o) $(XHOST_UNITS:%=$(OBJ)/%.o): $(OBJ)/%.o: $(SRC)/%.cpp
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
 
-$(OUT): $(OBJ)/jsg_kernels.o $(OBJ)/jsg_stft_a.o $(OBJ)/jsg_stft_b.o $(OBJ)/jsg_filterbank.o $(OBJ)/jsg_display_axis.o $(OBJ)/jsg_cstft.o $(OBJ)/jsg_pvoc.o $(OBJ)/jsg_hpss.o $(OBJ)/jsg_resample.o $(OBJ)/jsg_cqt.o $(OBJ)/jsg_yin.o $(OBJ)/jsg_rhythm.o $(OBJ)/jsg_cepstral.o $(OBJ)/jsg_spectral.o $(OBJ)/jsg_engine.o \
-        $(OBJ)/jsg_host_math.o $(OBJ)/jsg_filterbank_host.o $(OBJ)/jsg_display_axis_host.o $(OBJ)/jsg_cqt_host.o $(OBJ)/jsg_yin_host.o $(OBJ)/jsg_rhythm_host.o $(OBJ)/jsg_cepstral_host.o $(OBJ)/jsg_spectral_host.o
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^
-
-# the companion library: its own units and headers, the same flags, nothing of libjsg.so
-XDEPS := $(SRC)/jsgx_internal.h include/jsgx.h
-$(OBJ)/jsgx_beat.o: $(SRC)/jsgx_beat.hip $(XDEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsgx_cdist.o: $(SRC)/jsgx_cdist.hip $(XDEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsgx_dtw.o: $(SRC)/jsgx_dtw.hip $(XDEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsgx_beat_host.o: $(SRC)/jsgx_beat_host.cpp $(XDEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude -ffp-contract=off -D__HIP_PLATFORM_AMD__ -c $< -o $@
-$(OBJ)/jsgx_dtw_host.o: $(SRC)/jsgx_dtw_host.cpp $(XDEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude -ffp-contract=off -D__HIP_PLATFORM_AMD__ -c $< -o $@
-$(OBJ)/jsgx_viterbi.o: $(SRC)/jsgx_viterbi.hip $(XDEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJ)/jsgx_viterbi_host.o: $(SRC)/jsgx_viterbi_host.cpp $(SRC)/jsg_spans.h $(XDEPS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) -std=c++17 -O3 -fPIC -fvisibility=hidden -fvisibility-inlines-hidden -Iinclude -ffp-contract=off -D__HIP_PLATFORM_AMD__ -c $< -o $@
-$(OUTX): $(OBJ)/jsgx_beat.o $(OBJ)/jsgx_cdist.o $(OBJ)/jsgx_dtw.o $(OBJ)/jsgx_viterbi.o $(OBJ)/jsgx_beat_host.o $(OBJ)/jsgx_dtw_host.o $(OBJ)/jsgx_viterbi_host.o
+$(OUT): $(HIP_UNITS:%=$(OBJ)/%.o) $(HOST_UNITS:%=$(OBJ)/%.o)
+$(OUTX): $(XHIP_UNITS:%=$(OBJ)/%.o) $(XHOST_UNITS:%=$(OBJ)/%.o)
+$(OUT) $(OUTX):
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^
 
 oracle:

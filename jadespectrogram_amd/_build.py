@@ -14,7 +14,7 @@ LIB = os.path.join(PKG, "libjsg.so")
 
 SOURCES = ["jsg_kernels.hip", "jsg_stft_a.hip", "jsg_stft_b.hip", "jsg_filterbank.hip", "jsg_display_axis.hip", "jsg_cstft.hip", "jsg_pvoc.hip", "jsg_hpss.hip", "jsg_resample.hip", "jsg_cqt.hip", "jsg_yin.hip", "jsg_rhythm.hip", "jsg_cepstral.hip", "jsg_spectral.hip", "jsg_engine.cpp", "jsg_host_math.cpp", "jsg_filterbank_host.cpp",
            "jsg_display_axis_host.cpp", "jsg_cqt_host.cpp", "jsg_yin_host.cpp", "jsg_rhythm_host.cpp", "jsg_cepstral_host.cpp", "jsg_spectral_host.cpp"]
-HEADERS = ["jsg_internal.h", "jsg_spans.h", "jsg_block_queue.h", "jsg_exact_math.h", "jsg_stft_kernel.h", "jsg_runs_grid.h", "jsg_colormap_tables.inc", os.path.join(ROOT, "include", "jsg.h")]
+HEADERS = ["jsg_internal.h", "jsg_spans.h", "jsg_launch.h", "jsg_block_queue.h", "jsg_exact_math.h", "jsg_stft_kernel.h", "jsg_runs_grid.h", "jsg_colormap_tables.inc", os.path.join(ROOT, "include", "jsg.h")]
 # device-compile flags of every .hip unit:
 #   -fno-slp-vectorize: the kernel packs its complex arithmetic into v_pk_*_f32 by hand (re, im in one register pair); the automatic
 #       SLP pass pairs unrelated scalars and pays ~140 register moves per FFT
@@ -26,10 +26,11 @@ VISIBILITY = ["-fvisibility=hidden", "-fvisibility-inlines-hidden"]
 # gives the measurements); the 4096-point kernels (jsg_stft_b.hip) keep the default one
 UNIT_FLAGS = {"jsg_stft_a.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 ARCH = "gfx950"
-# the companion library (include/jsgx.h): its own units and headers, the same flags, nothing shared with libjsg.so
+# the companion library (include/jsgx.h): its own units, the same flags; of libjsg.so it takes two headers without state (jsg_spans.h,
+# jsg_launch.h), no object code
 LIBX = os.path.join(PKG, "libjsgx.so")
 SOURCES_X = ["jsgx_beat.hip", "jsgx_cdist.hip", "jsgx_dtw.hip", "jsgx_viterbi.hip", "jsgx_beat_host.cpp", "jsgx_dtw_host.cpp", "jsgx_viterbi_host.cpp"]
-HEADERS_X = ["jsgx_internal.h", "jsg_spans.h", os.path.join(ROOT, "include", "jsgx.h")]
+HEADERS_X = ["jsgx_internal.h", "jsg_spans.h", "jsg_launch.h", os.path.join(ROOT, "include", "jsgx.h")]
 
 
 def _hipcc() -> str:

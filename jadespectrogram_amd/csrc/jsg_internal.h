@@ -3,13 +3,13 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/jsg.h"
+#include "jsg_launch.h"      // OncePerDevice, launch_large_lds
 #include "jsg_spans.h"
 
 namespace jsg {
@@ -88,7 +88,7 @@ inline int check_rows(long long rows, const char* who) {
 }
 template <class... P>
 int check_aligned4(const char* who, const P*... p) {
-    return ((reinterpret_cast<uintptr_t>(p) | ...) & 3) == 0 ? JSG_OK : jsg_fail_who(JSG_ERR_INVALID, who, "pointers must be 4-byte aligned");
+    return aligned4(p...) ? JSG_OK : jsg_fail_who(JSG_ERR_INVALID, who, "pointers must be 4-byte aligned");
 }
 
 // The two ends of a ..._plan or ..._kernel_name call: the refusal of a name buffer below 24 bytes, before any other (a plan call may
@@ -114,36 +114,6 @@ inline long long per_cu_by_lds(long long limit, long long lds, long long cap) { 
 inline int finish_launch(const char* who) {
     const hipError_t err = hipGetLastError();
     return err == hipSuccess ? JSG_OK : jsg_fail_hip(err, who);
-}
-
-// What has been said once per device, a bit per path of a unit.  A device index outside 0..63 has no slot: there every call is the
-// first.  done() after the step has succeeded, so that a failed first attempt is made again.
-class OncePerDevice {
-public:
-    bool first(int dev, unsigned bit) const { return dev < 0 || dev >= 64 || !(told_[dev].load(std::memory_order_acquire) & bit); }
-    void done(int dev, unsigned bit) {
-        if (dev >= 0 && dev < 64) told_[dev].fetch_or(bit, std::memory_order_release);
-    }
-
-private:
-    std::atomic<unsigned> told_[64] = {};
-};
-
-// Launches a kernel that may ask for more than 48 KB of dynamic LDS, up to lds_max bytes.  It has to be said once per device before
-// the first launch there; `once` and the path's bit remember it, so it is said at the first launch of a path on a device.
-template <class Args>
-hipError_t launch_large_lds(OncePerDevice& once, int dev, unsigned bit, void (*kernel)(Args), int lds_max, dim3 grid, dim3 block, size_t lds_bytes,
-                            hipStream_t s, const Args& k) {
-    const bool first = once.first(dev, bit);
-    if (first) {
-        const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-        if (err != hipSuccess) return err;
-    }
-    void* args[] = {const_cast<Args*>(&k)};
-    (void)hipLaunchKernel(reinterpret_cast<const void*>(kernel), grid, block, args, lds_bytes, s);
-    const hipError_t err = hipGetLastError();
-    if (err == hipSuccess && first) once.done(dev, bit);
-    return err;
 }
 
 // jsg_yin_host.cpp: the refusals of jsg_yin_args and how a call that passes is served (jsg_yin.hip launches by it).  A work item is a

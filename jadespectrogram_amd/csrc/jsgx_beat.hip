@@ -14,7 +14,6 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdio>
 
 #include "jsgx_internal.h"
 
@@ -288,13 +287,11 @@ using namespace jsgx;
 
 extern "C" int jsgx_beat_launch(const jsgx_beat_args* g, void* scratch, int64_t scratch_bytes, void* stream) {
     static const char* who = "jsgx_beat_launch";
-    const int rc = beat_check(g, who);
+    int rc = beat_check(g, who);
+    if (rc == JSGX_OK) rc = check_scratch(who, scratch, scratch_bytes, beat_scratch_bytes(g), "jsgx_beat_scratch_bytes");
     if (rc != JSGX_OK) return rc;
-    if (!scratch) return fail(JSGX_ERR_INVALID, who, "null scratch");
-    if ((reinterpret_cast<uintptr_t>(scratch) & 3) != 0) return fail(JSGX_ERR_INVALID, who, "scratch must be 4-byte aligned");
-    if (scratch_bytes < beat_scratch_bytes(g)) return fail(JSGX_ERR_INVALID, who, "scratch smaller than jsgx_beat_scratch_bytes");
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(JSGX_ERR_NO_DEVICE, who, "no HIP device");
+    if ((rc = current_device(&dev, who)) != JSGX_OK) return rc;
     // every refusal is behind us
     BeatArgs k{};
     const bool multi = g->rows > 1;
@@ -318,11 +315,5 @@ extern "C" int jsgx_beat_launch(const jsgx_beat_args* g, void* scratch, int64_t 
     k.max_beats = g->max_beats;
     k.tightness = g->tightness;
     hipLaunchKernelGGL(beat_kernel, dim3((unsigned)g->rows), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), k);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        char what[160];
-        std::snprintf(what, sizeof what, "HIP error %d (%s)", (int)err, hipGetErrorString(err));
-        return fail(JSGX_ERR_HIP, who, what);
-    }
-    return JSGX_OK;
+    return finish_launch(who, hipGetLastError());
 }

@@ -1,5 +1,6 @@
 // libjsgx.so, beat tracking (include/jsgx.h section 1): the error text, the refusals, the scratch size, the plan of a period and the
-// logarithm table, on the host and without a device.  The kernel and its launcher are in jsgx_beat.hip.
+// logarithm table, on the host and without a device.  The kernel and its launcher are in jsgx_beat.hip.  jsgx::fail lives here for
+// all units; the span and overlap arithmetic is jsg_spans.h, a header without state that both libraries take.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -10,11 +11,9 @@
 namespace jsgx {
 
 namespace {
-typedef __int128 i128;
+using jsg::addr;
+using jsg::i128;
 thread_local char g_error[192] = "";
-
-i128 addr(const void* p) { return (i128)reinterpret_cast<uintptr_t>(p); }
-bool overlap(i128 a0, i128 a_bytes, i128 b0, i128 b_bytes) { return a0 && b0 && a0 < b0 + b_bytes && b0 < a0 + a_bytes; }
 }  // namespace
 
 int fail(int code, const char* who, const char* what) {
@@ -28,10 +27,7 @@ int beat_check(const jsgx_beat_args* g, const char* who) {
     if (!g->log_table) return fail(JSGX_ERR_INVALID, who, "null log_table");
     if (!g->beats) return fail(JSGX_ERR_INVALID, who, "null beats");
     if (!g->n_beats) return fail(JSGX_ERR_INVALID, who, "null n_beats");
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(g->in) | reinterpret_cast<uintptr_t>(g->period) | reinterpret_cast<uintptr_t>(g->log_table) |
-                           reinterpret_cast<uintptr_t>(g->beats) | reinterpret_cast<uintptr_t>(g->n_beats) | reinterpret_cast<uintptr_t>(g->local_score) |
-                           reinterpret_cast<uintptr_t>(g->cum_score);
-    if ((bits & 3) != 0) return fail(JSGX_ERR_INVALID, who, "pointers must be 4-byte aligned");
+    if (!jsg::aligned4(g->in, g->period, g->log_table, g->beats, g->n_beats, g->local_score, g->cum_score)) return fail(JSGX_ERR_INVALID, who, "pointers must be 4-byte aligned");
     if (g->rows < 1 || g->rows > 65535) return fail(JSGX_ERR_INVALID, who, "rows must be in 1..65535");
     if (g->n_frames < 1 || g->n_frames > JSGX_BEAT_MAX_FRAMES) return fail(JSGX_ERR_INVALID, who, "n_frames must be in 1..2^24");
     if (!g->period && (g->period_all < 1 || g->period_all > JSGX_BEAT_MAX_PERIOD)) return fail(JSGX_ERR_INVALID, who, "period_all must be in 1..1024 (period is null)");
@@ -45,16 +41,16 @@ int beat_check(const jsgx_beat_args* g, const char* who) {
     if (multi && g->beats_pitch < g->max_beats) return fail(JSGX_ERR_INVALID, who, "beats_pitch smaller than max_beats");
     if (multi && g->local_score && g->local_pitch < g->n_frames) return fail(JSGX_ERR_INVALID, who, "local_pitch smaller than n_frames");
     if (multi && g->cum_score && g->cum_pitch < g->n_frames) return fail(JSGX_ERR_INVALID, who, "cum_pitch smaller than n_frames");
-    const i128 rows1 = g->rows - 1, T = g->n_frames;
+    const long long R = g->rows, T = g->n_frames;
     const i128 src[3] = {addr(g->in), addr(g->period), addr(g->log_table)};
-    const i128 src_bytes[3] = {4 * (rows1 * (multi ? g->in_pitch : 0) + T), 4 * (i128)g->rows, 4 * (i128)(2 * JSGX_BEAT_MAX_PERIOD + 1)};
+    const i128 src_bytes[3] = {jsg::span_bytes(R, g->in_pitch, T, 4), 4 * (i128)R, 4 * (i128)(2 * JSGX_BEAT_MAX_PERIOD + 1)};
     const i128 dst[4] = {addr(g->beats), addr(g->n_beats), addr(g->local_score), addr(g->cum_score)};
-    const i128 dst_bytes[4] = {4 * (rows1 * (multi ? g->beats_pitch : 0) + g->max_beats), 4 * (i128)g->rows, 4 * (rows1 * (multi ? g->local_pitch : 0) + T),
-                               4 * (rows1 * (multi ? g->cum_pitch : 0) + T)};
+    const i128 dst_bytes[4] = {jsg::span_bytes(R, g->beats_pitch, g->max_beats, 4), 4 * (i128)R, jsg::span_bytes(R, g->local_pitch, T, 4),
+                               jsg::span_bytes(R, g->cum_pitch, T, 4)};
     static const char* const what[3] = {"an output overlaps in", "an output overlaps period", "an output overlaps log_table"};
     for (int j = 0; j < 3; ++j)         // input by input, in the header's order
         for (int i = 0; i < 4; ++i)
-            if (overlap(src[j], src_bytes[j], dst[i], dst_bytes[i])) return fail(JSGX_ERR_INVALID, who, what[j]);
+            if (jsg::overlap(src[j], src_bytes[j], dst[i], dst_bytes[i])) return fail(JSGX_ERR_INVALID, who, what[j]);
     return JSGX_OK;
 }
 
@@ -86,11 +82,11 @@ int64_t jsgx_beat_scratch_bytes(const jsgx_beat_args* g) {
 
 int jsgx_beat_plan(const jsgx_beat_args* g, int32_t period, char* name, int name_len, int32_t* threads, int32_t* lds_bytes) {
     static const char* who = "jsgx_beat_plan";
-    if (name && name_len < 16) return fail(JSGX_ERR_INVALID, who, "bad argument");
-    const int rc = beat_check(g, who);
+    int rc = check_name_buffer(who, name, name_len, 16);
+    if (rc == JSGX_OK) rc = beat_check(g, who);
     if (rc != JSGX_OK) return rc;
     if (period < 1 || period > JSGX_BEAT_MAX_PERIOD) return fail(JSGX_ERR_INVALID, who, "period must be in 1..1024");
-    if (name) std::strncpy(name, beat_form(period).G == 1 ? "beat_frames" : "beat_split", name_len);
+    put_name(name, name_len, beat_form(period).G == 1 ? "beat_frames" : "beat_split");
     if (threads) *threads = JSGX_BEAT_THREADS;
     if (lds_bytes) *lds_bytes = JSGX_BEAT_LDS_BYTES;
     return JSGX_OK;

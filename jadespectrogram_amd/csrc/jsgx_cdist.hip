@@ -11,8 +11,6 @@
 // terms.  A row of the tile goes out as 16 lanes x 16 bytes = one 256-byte line (as 16-byte stores where cost is so aligned).
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
 #include "jsgx_internal.h"
 
 namespace jsgx {
@@ -116,10 +114,10 @@ using namespace jsgx;
 
 extern "C" int jsgx_cdist_launch(const jsgx_cdist_args* g, void* stream) {
     static const char* who = "jsgx_cdist_launch";
-    const int rc = cdist_check(g, who);
+    int rc = cdist_check(g, who);
     if (rc != JSGX_OK) return rc;
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(JSGX_ERR_NO_DEVICE, who, "no HIP device");
+    if ((rc = current_device(&dev, who)) != JSGX_OK) return rc;
     // every refusal is behind us
     CdistArgs k{};
     k.x = g->x;
@@ -144,11 +142,5 @@ extern "C" int jsgx_cdist_launch(const jsgx_cdist_args* g, void* stream) {
         hipLaunchKernelGGL(cdist_kernel<JSGX_METRIC_EUCLIDEAN>, grid, dim3(JSGX_CDIST_THREADS), 0, s, k);
     else
         hipLaunchKernelGGL(cdist_kernel<JSGX_METRIC_COSINE>, grid, dim3(JSGX_CDIST_THREADS), 0, s, k);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        char what[160];
-        std::snprintf(what, sizeof what, "HIP error %d (%s)", (int)err, hipGetErrorString(err));
-        return fail(JSGX_ERR_HIP, who, what);
-    }
-    return JSGX_OK;
+    return finish_launch(who, hipGetLastError());
 }

@@ -26,7 +26,6 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdio>
 
 #include "jsgx_internal.h"
 
@@ -322,16 +321,12 @@ using namespace jsgx;
 
 extern "C" int jsgx_dtw_launch(const jsgx_dtw_args* g, void* scratch, int64_t scratch_bytes, void* stream) {
     static const char* who = "jsgx_dtw_launch";
-    const int rc = dtw_check(g, who);
+    int rc = dtw_check(g, who);
     if (rc != JSGX_OK) return rc;
     const int64_t need = dtw_scratch_bytes(g);
-    if (need > 0) {
-        if (!scratch) return fail(JSGX_ERR_INVALID, who, "null scratch");
-        if ((reinterpret_cast<uintptr_t>(scratch) & 3) != 0) return fail(JSGX_ERR_INVALID, who, "scratch must be 4-byte aligned");
-        if (scratch_bytes < need) return fail(JSGX_ERR_INVALID, who, "scratch smaller than jsgx_dtw_scratch_bytes");
-    }
+    if (need > 0 && (rc = check_scratch(who, scratch, scratch_bytes, need, "jsgx_dtw_scratch_bytes")) != JSGX_OK) return rc;
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(JSGX_ERR_NO_DEVICE, who, "no HIP device");
+    if ((rc = current_device(&dev, who)) != JSGX_OK) return rc;
     // every refusal is behind us
     const bool multi = g->pairs > 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -348,9 +343,9 @@ extern "C" int jsgx_dtw_launch(const jsgx_dtw_args* g, void* scratch, int64_t sc
     k.band = g->band;
     k.wm0 = g->weights_mul[0], k.wm1 = g->weights_mul[1], k.wm2 = g->weights_mul[2];
     k.wa0 = g->weights_add[0], k.wa1 = g->weights_add[1], k.wa2 = g->weights_add[2];
-    const int tiles_i = (g->n + kRows - 1) / kRows, tiles_j = (g->m + kCols - 1) / kCols;
-    for (int d = 0; d < tiles_i + tiles_j - 1; ++d) {
-        const int first = d - (tiles_j - 1) > 0 ? d - (tiles_j - 1) : 0, last = d < tiles_i - 1 ? d : tiles_i - 1;
+    const DtwTiles tiles = dtw_tiles(g->n, g->m);
+    for (int d = 0; d < tiles.diagonals(); ++d) {
+        const int first = d - (tiles.j - 1) > 0 ? d - (tiles.j - 1) : 0, last = d < tiles.i - 1 ? d : tiles.i - 1;
         k.diagonal = d;
         k.ti_first = first;
         hipLaunchKernelGGL(dtw_kernel, dim3((unsigned)(last - first + 1), (unsigned)g->pairs), dim3(kLanes), 0, s, k);
@@ -369,11 +364,5 @@ extern "C" int jsgx_dtw_launch(const jsgx_dtw_args* g, void* scratch, int64_t sc
         b.scratch = need > 0 ? static_cast<int*>(scratch) : nullptr;
         hipLaunchKernelGGL(dtw_backtrace_kernel, dim3((unsigned)g->pairs), dim3(kLanes), 0, s, b);
     }
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        char what[160];
-        std::snprintf(what, sizeof what, "HIP error %d (%s)", (int)err, hipGetErrorString(err));
-        return fail(JSGX_ERR_HIP, who, what);
-    }
-    return JSGX_OK;
+    return finish_launch(who, hipGetLastError());
 }

@@ -1,20 +1,24 @@
-// libjsgx.so, what its units share (include/jsgx.h): the error text, the argument check and the float32 routines whose every
-// operation the header states.  Nothing of libjsg.so is used here.
+// libjsgx.so, what its units share (include/jsgx.h): the error text, the argument checks, the refusals that every unit words alike, the
+// launchers' two ends and the float32 routines whose every operation the header states.  Of libjsg.so it takes two headers without
+// state, jsg_spans.h (spans, overlap, alignment) and jsg_launch.h (OncePerDevice, launch_large_lds): the two libraries share that
+// text, no object code and no state.  The first part needs no HIP header: plain g++ builds the host units for the sanitizer drivers.
 #pragma once
 
 #include <cstdint>
+#include <cstdio>
+#include <cstring>
 
+#include "jsg_spans.h"
 #include "jsgx.h"
 
 #if defined(__HIPCC__)      // hipcc compiles the host unit as HIP too
 #include <hip/hip_runtime.h>
 
-#include <atomic>
+#include "jsg_launch.h"
 #define JSGX_HD __host__ __device__ __forceinline__
 #else
 #define JSGX_HD static inline
 #include <cmath>
-#include <cstring>
 #endif
 
 namespace jsgx {
@@ -43,24 +47,43 @@ struct ViterbiPlan {
 };
 ViterbiPlan viterbi_plan(const jsgx_viterbi_args* g);
 
+// The three refusals of a launch's scratch buffer, in this order; `sizer` names the call that states `need`.
+inline int check_scratch(const char* who, const void* scratch, int64_t scratch_bytes, int64_t need, const char* sizer) {
+    if (!scratch) return fail(JSGX_ERR_INVALID, who, "null scratch");
+    if (!jsg::aligned4(scratch)) return fail(JSGX_ERR_INVALID, who, "scratch must be 4-byte aligned");
+    if (scratch_bytes >= need) return JSGX_OK;
+    char what[96];
+    std::snprintf(what, sizeof what, "scratch smaller than %s", sizer);
+    return fail(JSGX_ERR_INVALID, who, what);
+}
+
+// The two ends of a ..._plan call's name buffer: the refusal of one below min_len bytes, before any other (a call may pass none), and
+// the kernel's name into it once the call has passed.
+inline int check_name_buffer(const char* who, const char* buf, int len, int min_len) {
+    return buf && len < min_len ? fail(JSGX_ERR_INVALID, who, "bad argument") : JSGX_OK;
+}
+inline void put_name(char* buf, int len, const char* name) {
+    if (buf) std::strncpy(buf, name, len);
+}
+
+// The tiles of an n x m plane of section 3, down and across.  A launch takes one anti-diagonal of them.
+struct DtwTiles {
+    int i, j;
+    int diagonals() const { return i + j - 1; }
+};
+inline DtwTiles dtw_tiles(int n, int m) { return {(n + JSGX_DTW_TILE_ROWS - 1) / JSGX_DTW_TILE_ROWS, (m + JSGX_DTW_TILE_COLS - 1) / JSGX_DTW_TILE_COLS}; }
+
 #if defined(__HIPCC__)
-// Launches a kernel that may ask for more than 64 KiB of dynamic LDS, up to lds_max bytes.  The runtime has to be told once per
-// device and kernel before the first such launch; *told keeps a bit per device (a device index outside 0..63 is told every time).
-// Telling is no stream operation, so a first launch under capture works.  The bit is set after the launch has succeeded.
-template <class Args>
-hipError_t launch_large_lds(std::atomic<unsigned long long>* told, int dev, void (*kernel)(Args), int lds_max, dim3 grid, dim3 block, size_t lds_bytes,
-                            hipStream_t s, const Args& k) {
-    const unsigned long long bit = dev >= 0 && dev < 64 ? 1ull << dev : 0;
-    const bool first = !(told->load(std::memory_order_acquire) & bit);
-    if (first) {
-        const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-        if (err != hipSuccess) return err;
-    }
-    void* args[] = {const_cast<Args*>(&k)};
-    (void)hipLaunchKernel(reinterpret_cast<const void*>(kernel), grid, block, args, lds_bytes, s);
-    const hipError_t err = hipGetLastError();
-    if (err == hipSuccess && first) told->fetch_or(bit, std::memory_order_release);
-    return err;
+// the device a launch goes to
+inline int current_device(int* dev, const char* who) {
+    return hipGetDevice(dev) == hipSuccess ? JSGX_OK : fail(JSGX_ERR_NO_DEVICE, who, "no HIP device");
+}
+// after the last launch of a call: what the launches left (hipGetLastError(), or what launch_large_lds returned), as the call's return code
+inline int finish_launch(const char* who, hipError_t err) {
+    if (err == hipSuccess) return JSGX_OK;
+    char what[160];
+    std::snprintf(what, sizeof what, "HIP error %d (%s)", (int)err, hipGetErrorString(err));
+    return fail(JSGX_ERR_HIP, who, what);
 }
 #endif
 

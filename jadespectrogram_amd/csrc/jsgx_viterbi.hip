@@ -17,7 +17,6 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdio>
 
 #include "jsgx_internal.h"
 
@@ -226,7 +225,7 @@ __global__ __launch_bounds__(kTraceThreads) void viterbi_trace_kernel(BackArgs a
 }
 
 namespace {
-std::atomic<unsigned long long> g_told[4];      // per form: the devices that know its LDS limit
+jsg::OncePerDevice g_told;      // a bit per form: the devices that know its LDS limit
 }
 
 }  // namespace jsgx
@@ -235,14 +234,12 @@ using namespace jsgx;
 
 extern "C" int jsgx_viterbi_launch(const jsgx_viterbi_args* g, void* scratch, int64_t scratch_bytes, void* stream) {
     static const char* who = "jsgx_viterbi_launch";
-    const int rc = viterbi_check(g, who);
+    int rc = viterbi_check(g, who);
     if (rc != JSGX_OK) return rc;
     const ViterbiPlan p = viterbi_plan(g);
-    if (!scratch) return fail(JSGX_ERR_INVALID, who, "null scratch");
-    if ((reinterpret_cast<uintptr_t>(scratch) & 3) != 0) return fail(JSGX_ERR_INVALID, who, "scratch must be 4-byte aligned");
-    if (scratch_bytes < p.scratch_bytes) return fail(JSGX_ERR_INVALID, who, "scratch smaller than jsgx_viterbi_scratch_bytes");
+    if ((rc = check_scratch(who, scratch, scratch_bytes, p.scratch_bytes, "jsgx_viterbi_scratch_bytes")) != JSGX_OK) return rc;
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(JSGX_ERR_NO_DEVICE, who, "no HIP device");
+    if ((rc = current_device(&dev, who)) != JSGX_OK) return rc;
     // every refusal is behind us
     const bool multi = g->seqs > 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -263,7 +260,7 @@ extern "C" int jsgx_viterbi_launch(const jsgx_viterbi_args* g, void* scratch, in
     void (*const forms[4])(ForwardArgs) = {viterbi_forward_kernel<false, false>, viterbi_forward_kernel<false, true>, viterbi_forward_kernel<true, false>,
                                            viterbi_forward_kernel<true, true>};
     const int form = (p.band ? 2 : 0) + (p.table_in_lds ? 1 : 0);
-    hipError_t err = launch_large_lds(&g_told[form], dev, forms[form], JSGX_VITERBI_LDS_LIMIT, dim3((unsigned)g->seqs), dim3((unsigned)p.threads), (size_t)p.lds_bytes, s, f);
+    hipError_t err = jsg::launch_large_lds(g_told, dev, 1u << form, forms[form], JSGX_VITERBI_LDS_LIMIT, dim3((unsigned)g->seqs), dim3((unsigned)p.threads), (size_t)p.lds_bytes, s, f);
     if (err == hipSuccess) {
         BackArgs b{};
         b.psi = f.psi;
@@ -279,10 +276,5 @@ extern "C" int jsgx_viterbi_launch(const jsgx_viterbi_args* g, void* scratch, in
         hipLaunchKernelGGL(viterbi_trace_kernel, dim3((unsigned)((p.n_blocks + kTraceThreads - 1) / kTraceThreads), (unsigned)g->seqs), dim3(kTraceThreads), 0, s, b);
         err = hipGetLastError();
     }
-    if (err != hipSuccess) {
-        char what[160];
-        std::snprintf(what, sizeof what, "HIP error %d (%s)", (int)err, hipGetErrorString(err));
-        return fail(JSGX_ERR_HIP, who, what);
-    }
-    return JSGX_OK;
+    return finish_launch(who, err);
 }

@@ -3,16 +3,13 @@
 // (jsgx::fail) is in jsgx_beat_host.cpp.  The span and overlap arithmetic is jsg_spans.h, a header without state that both libraries take.
 #include <cmath>
 #include <cstdint>
-#include <cstring>
 
-#include "jsg_spans.h"
 #include "jsgx_internal.h"
 
 namespace jsgx {
 
 namespace {
 using jsg::i128;
-uintptr_t bits_of(const void* p) { return reinterpret_cast<uintptr_t>(p); }
 }  // namespace
 
 int viterbi_check(const jsgx_viterbi_args* g, const char* who) {
@@ -21,7 +18,7 @@ int viterbi_check(const jsgx_viterbi_args* g, const char* who) {
     if (!g->log_init) return fail(JSGX_ERR_INVALID, who, "null log_init");
     if (!g->trans) return fail(JSGX_ERR_INVALID, who, "null trans");
     if (!g->states) return fail(JSGX_ERR_INVALID, who, "null states");
-    if (((bits_of(g->log_emit) | bits_of(g->log_init) | bits_of(g->trans) | bits_of(g->states) | bits_of(g->logp) | bits_of(g->value)) & 3) != 0)
+    if (!jsg::aligned4(g->log_emit, g->log_init, g->trans, g->states, g->logp, g->value))
         return fail(JSGX_ERR_INVALID, who, "pointers must be 4-byte aligned");
     if (g->seqs < 1 || g->seqs > 65535) return fail(JSGX_ERR_INVALID, who, "seqs must be in 1..65535");
     if (g->n_states < 1 || g->n_states > JSGX_VITERBI_MAX_STATES) return fail(JSGX_ERR_INVALID, who, "n_states must be in 1..2048");
@@ -89,11 +86,11 @@ int64_t jsgx_viterbi_scratch_bytes(const jsgx_viterbi_args* g) {
 
 int jsgx_viterbi_plan(const jsgx_viterbi_args* g, char* name, int name_len, int32_t* threads, int32_t* lds_bytes, int32_t* n_launches) {
     static const char* who = "jsgx_viterbi_plan";
-    if (name && name_len < 24) return fail(JSGX_ERR_INVALID, who, "bad argument");
-    const int rc = viterbi_check(g, who);
+    int rc = check_name_buffer(who, name, name_len, 24);
+    if (rc == JSGX_OK) rc = viterbi_check(g, who);
     if (rc != JSGX_OK) return rc;
     const ViterbiPlan p = viterbi_plan(g);
-    if (name) std::strncpy(name, p.name, name_len);
+    put_name(name, name_len, p.name);
     if (threads) *threads = p.threads;
     if (lds_bytes) *lds_bytes = p.lds_bytes;
     if (n_launches) *n_launches = p.n_launches;

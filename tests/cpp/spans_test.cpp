@@ -1,4 +1,4 @@
-// CPU-only: the span and overlap helpers that the refusals of the feature units share (csrc/jsg_spans.h), built alone under
+// CPU-only: the span, overlap and alignment helpers that the refusals of both libraries' units share (csrc/jsg_spans.h), built alone under
 // -fsanitize=address,undefined (tests/test_host_cpp.py).  No pointer here is ever dereferenced: they are addresses only.
 #include <cstdint>
 #include <cstdio>
@@ -68,6 +68,53 @@ int main() {
     CHECK(!overlap(addr(at(top)), huge, addr(at(top - 64)), 64));
     CHECK(overlap(addr(at(4096)), huge, addr(at(top)), 16));
     CHECK(overlap(addr(at(top)), huge, addr(at(top)), huge));
+
+    // aligned4: no pointer at all; every pointer aligned; one misaligned pointer among several, at each place and by each of 1, 2, 3
+    CHECK(aligned4());
+    CHECK(aligned4(at(4096)));
+    CHECK(aligned4(at(4096), at(8), at(1 << 20)));
+    for (uintptr_t off : {1, 2, 3}) {
+        CHECK(!aligned4(at(4096 + off)));
+        CHECK(!aligned4(at(4096 + off), at(8), at(1 << 20)));
+        CHECK(!aligned4(at(4096), at(8 + off), at(1 << 20)));
+        CHECK(!aligned4(at(4096), at(8), at((1 << 20) + off)));
+    }
+    // pointers of different types in one call; null pointers (outputs that were not asked for) count as aligned
+    CHECK(aligned4(static_cast<const float*>(nullptr), static_cast<int*>(nullptr), at(64)));
+    CHECK(aligned4(static_cast<const void*>(nullptr)));
+    CHECK(!aligned4(static_cast<const float*>(nullptr), at(66), static_cast<int*>(nullptr)));
+    // an address near 2^64: the low bits decide, nothing is narrowed on the way
+    CHECK(aligned4(at(UINTPTR_MAX - 3)));
+    CHECK(aligned4(at(UINTPTR_MAX - 3), at(4)));
+    CHECK(!aligned4(at(UINTPTR_MAX - 2), at(4)));
+    CHECK(!aligned4(at(4), at(UINTPTR_MAX)));
+    CHECK(!aligned4(at(((uintptr_t)1 << 63) + 2)));
+
+    // What libjsgx.so wrote out by hand before it took this header, restated as plain arithmetic, against span_bytes(plane(...)).
+    // dtw: 4 * extent(P, pp, rows, pitch, cols), extent = (P - 1) * pp + (rows - 1) * pitch + cols, called with pp as the field
+    // holds it for x and y (0 = a broadcast sequence) and with "P > 1 ? pp : 0" for the planes.  beat: 4 * (rows1 * (multi ? pitch
+    // : 0) + T).  pairs 1 and 3; pair pitch 0, exact and padded; n, m, K at 1 and at their maxima; a pitch near 2^62.
+    for (long long P : {1ll, 3ll})
+        for (long long rows : {1ll, 65536ll})
+            for (long long cols : {1ll, 1024ll, 65536ll})
+                for (long long pitch : {cols, cols + 7, ((long long)1 << 62) - 3}) {
+                    const i128 one = (i128)(rows - 1) * pitch + cols;        // the floats of one plane, as extent(1, 0, ...) had them
+                    CHECK(plane(rows, pitch, cols) == one);
+                    const long long exact = one < ((i128)1 << 62) ? (long long)one : (long long)1 << 62;
+                    for (long long pp : {0ll, exact, exact + 13, ((long long)1 << 62) - 1}) {
+                        const i128 old_as_held = 4 * ((i128)(P - 1) * pp + (i128)(rows - 1) * pitch + cols);
+                        const i128 old_guarded = 4 * ((i128)(P - 1) * (P > 1 ? pp : 0) + (i128)(rows - 1) * pitch + cols);
+                        CHECK(span_bytes(P, pp, plane(rows, pitch, cols), 4) == old_as_held);
+                        CHECK(span_bytes(P, pp, plane(rows, pitch, cols), 4) == old_guarded);
+                    }
+                }
+    for (long long rows : {1ll, 3ll, 65535ll})
+        for (long long T : {1ll, 1000ll, (long long)1 << 24})
+            for (long long pitch : {0ll, T, T + 5, ((long long)1 << 62) - 3}) {
+                const bool multi = rows > 1;
+                const i128 rows1 = rows - 1;
+                CHECK(span_bytes(rows, pitch, T, 4) == 4 * (rows1 * (multi ? pitch : 0) + T));
+            }
 
     std::printf("spans: %d failed\n", failed);
     return failed ? 1 : 0;
