@@ -45,6 +45,12 @@ def form(P):
     return a, G, min(LANES // G, a)
 
 
+# The periods of the GPU test over the kernel's forms (tests/test_gpu_beat.py): every (G, F) and plan name that a period in 1..1024 gives, and
+# both periods wherever one of them changes (3, 5, 7, 15, 31, 63, 127, 255, 511); 1, 16, 33, 64, 100, 200, 257 and 1024 lie inside a form.
+# tests/test_jsgx_forms_host.py derives the forms from form() and jsgx_beat_plan and fails where this list misses one.
+FORM_PERIODS = (1, 2, 3, 4, 5, 6, 7, 14, 15, 16, 30, 31, 33, 62, 63, 64, 100, 126, 127, 200, 254, 255, 257, 510, 511, 1024)
+
+
 # ---------------------------------------------------------------------------------------------------- jsgx_exp
 def exp32(x):
     """jsgx_exp of an array of float32 x <= 0, operation by operation."""

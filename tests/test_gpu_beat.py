@@ -1,8 +1,9 @@
 """The beat tracker of libjsgx.so on the GPU (include/jsgx.h section 1) against tests/beat_ref.py, bit for bit: graph capture of a first
-launch; beats, their number, the local and the cumulative score over the periods and lengths at which the kernel changes its form, its
-step or its ring use, with smoothing and normalisation on and off, on zero, constant, random and impulse-train rows; periods read from a
-device buffer (bad ones among them); pitched buffers with guard elements; a NaN row between good rows; max_beats below the length of the
-chain; and the Python layer down to beat_track_audio on a click track."""
+launch; beats, their number, the local and the cumulative score over beat_ref.FORM_PERIODS (every (G, F) of the kernel and both periods at
+each of the nine boundaries between them, which tests/test_jsgx_forms_host.py holds complete) at the lengths around one step, with
+smoothing and normalisation on and off, on zero, constant, random and impulse-train rows; rows longer than the ring of 4096 frames with
+64, 32, 16, 8, 4, 2 lanes and one lane per frame; periods read from a device buffer (bad ones among them); pitched buffers with guard elements; a NaN row between good rows; max_beats below the length of the chain; and the Python
+layer down to beat_track_audio on a click track."""
 import numpy as np
 import pytest
 
@@ -13,7 +14,6 @@ pytestmark = pytest.mark.gpu
 SENTINEL = np.float32(-7.25e11)
 ISENTINEL = np.int32(-77777)
 KINDS = ("zero", "const", "random", "train")
-PERIODS = (1, 2, 3, 4, 7, 16, 33, 64, 100, 257, 1024)
 
 
 @pytest.fixture(scope="module")
@@ -108,14 +108,16 @@ def test_captured_first_launch_replays(jsg, torch_cuda, d_log):
         assert n[r] == want[r]["n"] and (beats[r, :n[r]] == want[r]["beats"]).all() and (beats[r, n[r]:] == ISENTINEL).all()
 
 
-@pytest.mark.parametrize("P", PERIODS)
+@pytest.mark.parametrize("P", br.FORM_PERIODS)
 def test_periods_and_lengths_to_the_bit(jsg, torch_cuda, d_log, P):
     """Four rows (zero, constant, random, impulse train) per launch; the lengths around a = (P + 1) // 2 (one step of the recurrence), 2P and
-    5P + 3 (the ring of 4096 frames wraps for P = 1024 only; the look-back leaves the row at the start); P = 1, 2: one frame per step; 3..510: the split form with
-    64, 32, ... 2 lanes per frame; 1024: one lane per frame, 256 frames per step, two tiles of smoothing staged with the widest halo."""
+    5P + 3 (the ring of 4096 frames wraps for P = 1024 only; the look-back leaves the row at the start); P = 1, 2: one frame per step; 3..6:
+    two and three; 7..14: four frames of 64 lanes; then 32, 16, 8, 4 and 2 lanes per frame, each from its first period (15, 31, 63, 127,
+    255) to its last; 511 and 1024: one lane per frame, 256 frames per step, at 1024 two tiles of smoothing staged with the widest halo."""
     a = (P + 1) // 2
     lengths = sorted({1, max(1, a - 1), a, a + 1, 2 * P, 2 * P + 1, 5 * P + 3} | ({3000} if P == 33 else set()))
     assert jsg.beat_plan(P)[0] == ("beat_frames" if P >= 511 else "beat_split")
+    assert br.form(P)[1] * br.form(P)[2] <= 256 and (br.form(P)[1] == 4) == (127 <= P <= 254)
     for T in lengths:
         o = np.stack([br.envelope(kind, T, P) for kind in KINDS])
         for smooth in (False, True):
@@ -125,28 +127,33 @@ def test_periods_and_lengths_to_the_bit(jsg, torch_cuda, d_log, P):
                 check_rows(got, want, (P, T, smooth, normalise))
 
 
-@pytest.mark.parametrize("P", [5, 6, 47])
+@pytest.mark.parametrize("P", [5, 6, 20, 47, 100, 200, 255])
 def test_long_rows(jsg, torch_cuda, d_log, P):
-    """Rows longer than the ring of 4096 frames, so that it wraps: three frames per step (P = 5, 6: a step count that is no power of two) over
-    4500 frames, and the benchmark's period 47 over 9000 frames with chains of more than 150 beats, whole and cut at max_beats."""
+    """Rows longer than the ring of 4096 frames, so that it wraps, in every split of a frame over lanes (one lane per frame wraps at P = 1024
+    above): three frames per step (P = 5, 6: a step count that is no power of two) over 4500 frames, the benchmark's period 47 over 9000
+    frames with chains of more than 150 beats, whole and cut at max_beats, and 32, 8, 4 and 2 lanes per frame (P = 20, 100, 200, 255) over
+    4500 frames; at P = 200 the backtrace walks 15 links or more."""
     T = 9000 if P == 47 else 4500
-    assert br.form(P)[2] == (16 if P == 47 else 3)
+    assert br.form(P)[1:] == {5: (64, 3), 6: (64, 3), 20: (32, 8), 47: (16, 16), 100: (8, 32), 200: (4, 64), 255: (2, 128)}[P]
     o = np.stack([br.envelope(kind, T, P) for kind in KINDS])
     for smooth in (False, True):
         want = br.beat32_rows(o, P, smooth=smooth)
         assert P != 47 or min(w["n"] for w in want) > 150
+        assert P != 200 or min(w["n"] for w in want) >= 15
         check_rows(run(jsg, torch_cuda, d_log, o, period=P, smooth=smooth), want, (P, smooth))
         if P == 47:
             check_rows(run(jsg, torch_cuda, d_log, o, period=P, smooth=smooth, max_beats=100), want, (P, smooth, 100), max_beats=100)
 
 
 def test_periods_from_a_device_buffer(jsg, torch_cuda, d_log):
-    """Eight rows, eight periods in device memory as tempo_launch leaves them, -1 (its NaN row) and 1025 among them; every buffer pitched."""
-    periods = (7, -1, 100, 1025, 1, 257, 33, 600)
+    """Nine rows, nine periods in device memory as tempo_launch leaves them, -1 (its NaN row) and 1025 among them, each good one in another
+    form of the kernel (190: four lanes per frame); every buffer pitched."""
+    periods = (7, -1, 100, 1025, 1, 257, 33, 600, 190)
     T = 1300
-    o = np.stack([br.envelope(KINDS[2 + r % 2], T, 40 + r) for r in range(8)])
+    assert sorted(br.form(P)[1] for P in periods if 1 <= P <= 1024) == [1, 2, 4, 8, 16, 64, 64]
+    o = np.stack([br.envelope(KINDS[2 + r % 2], T, 40 + r) for r in range(9)])
     want = [br.beat32(o[r], P) for r, P in enumerate(periods)]
-    assert [w["n"] < 0 for w in want] == [False, True, False, True, False, False, False, False]
+    assert [w["n"] < 0 for w in want] == [False, True, False, True, False, False, False, False, False]
     got = run(jsg, torch_cuda, d_log, o, periods=periods, pads=(5, 3, 7, 1))
     check_rows(got, want, "device periods")
     # ... and a row does not depend on its neighbours, on the pitches or on the number of rows

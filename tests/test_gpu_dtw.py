@@ -1,8 +1,9 @@
 """The pairwise cost and dynamic time warping of libjsgx.so on the GPU (include/jsgx.h sections 2 and 3) against tests/dtw_ref.py, bit for
 bit (NaN positions equal, all other bits equal): D, the path, its length and the total over shapes around the tile edges on costs with
 many ties and with none; weights, subseq and bands on both sides of the connectivity rule; three pairs in pitched buffers with poisoned
-padding; a NaN cell that stays in its pair; graph capture of a first launch; the cost kernel per metric around its own tile edges, with a
-shared sequence and a zero vector; and the Python layer end to end."""
+padding; a NaN cell that stays in its pair; graph capture of a first launch; the total alone under subseq, without a scratch; the cost
+kernel per metric around its own tile edges, with 16-byte stores beside a scalar tail, feature counts around its panel and at the limit,
+three pairs in one pitched plane, a shared sequence and a zero vector; and the Python layer end to end."""
 import functools
 
 import numpy as np
@@ -222,6 +223,28 @@ def test_forward_alone_needs_no_scratch(jsg, torch_cuda):
     assert dr.same_bits(d_total.cpu().numpy(), np.asarray([want[3]]))
 
 
+def test_total_alone_under_subseq_needs_no_scratch(jsg, torch_cuda, tiles):
+    """d_total without paths and without a path length, subseq on: the backtrace kernel reduces the last row to its lowest minimal column
+    and walks without recording, so the scratch is 0 bytes and none is passed.  Integer costs: the minimum of the last row is tied."""
+    torch = torch_cuda
+    TR, TC = tiles
+    N, M = 3, 2 * TC + 5
+    C, D, path, total = reference("integers", N, M, 40, 0, True, 0)
+    assert path is not None and (D[N - 1] == D[N - 1].min()).sum() > 1 and path[-1][1] == int(np.argmin(D[N - 1])) < M - 1
+    d_cost = torch.from_numpy(np.array(C)).cuda()
+    d_acc = torch.full((N, M), float(SENTINEL), dtype=torch.float32, device="cuda")
+    d_total = torch.full((3,), float(SENTINEL), dtype=torch.float32, device="cuda")
+    assert jsg.dtw_scratch_bytes(d_cost, d_acc, subseq=True, d_total=d_total[1:2]) == 0
+    assert jsg.dtw_plan(N, M, backtrack=False)[3] + 1 == jsg.dtw_plan(N, M)[3]
+    none = torch.empty((0,), dtype=torch.int32, device="cuda")
+    assert none.numel() == 0
+    jsg.dtw_launch(d_cost, d_acc, subseq=True, d_total=d_total[1:2], d_scratch=none)
+    torch.cuda.synchronize()
+    t = d_total.cpu().numpy()
+    assert t[0] == t[2] == SENTINEL and dr.same_bits(t[1:2], np.asarray([total])), (t, total)
+    assert dr.same_bits(d_acc.cpu().numpy(), D)
+
+
 # ---------------------------------------------------------------------------------------------------- the cost kernel
 def features(N, K, seed):
     return np.random.default_rng(seed).standard_normal((N, K)).astype(np.float32)
@@ -247,6 +270,83 @@ def test_cdist_per_metric_around_its_tile_edges(jsg, torch_cuda, metric, K):
             torch.cuda.synchronize()
             assert untouched(fc, d_cost, SENTINEL, offset), "a guard element was written"
             assert dr.same_bits(d_cost[0].cpu().numpy(), dr.cost32(X, Y, metric)), (metric, K, N, M, pad)
+
+
+def aligned_planes(torch, planes, rows, cols, offset):
+    """A flat buffer full of SENTINEL and the view [planes][rows][cols] inside it whose every row starts on a 16-byte boundary: the row pitch
+    is cols rounded up to a multiple of 4, the plane pitch a multiple of 4 with two guard rows of 4 behind the plane, `offset` (0 or 4)
+    elements in front."""
+    pitch = -(-cols // 4) * 4
+    plane = rows * pitch + 8
+    flat = torch.full((offset + planes * plane + 8,), float(SENTINEL), dtype=torch.float32, device="cuda")
+    view = torch.as_strided(flat, (planes, rows, cols), (plane, pitch, 1), storage_offset=offset)
+    assert view.data_ptr() % 16 == 0 and pitch % 4 == 0 and plane % 4 == 0
+    return flat, view
+
+
+@pytest.mark.parametrize("metric", list(dr.METRICS))
+def test_cdist_16_byte_stores_beside_a_scalar_tail(jsg, torch_cuda, metric):
+    """Planes aligned to 16 bytes whose m is no multiple of 4: a row goes out as 16-byte stores up to its last whole group of four and as
+    single stores behind it (3, 2 and 3 of them), in the tile's last lanes, in a second tile, and in a third; the guard elements that
+    close each row's pitch stay."""
+    torch = torch_cuda
+    T, K = jsg.capix.CDIST_TILE, 12
+    for N, M in ((5, T - 1), (T + 1, T + 2), (3, 2 * T + 3)):
+        assert M % 4 != 0
+        X, Y = features(N, K, 10 + N), features(M, K, 2000 + M)
+        want = dr.cost32(X, Y, metric)
+        d_x, d_y = torch.from_numpy(X).cuda(), torch.from_numpy(Y).cuda()
+        for offset in (0, 4):
+            fc, d_cost = aligned_planes(torch, 1, N, M, offset)
+            jsg.cdist_launch(d_x, d_y, d_cost[0], metric=metric)
+            torch.cuda.synchronize()
+            assert untouched(fc, d_cost, SENTINEL, offset), ("a guard element was written", metric, N, M, offset)
+            assert dr.same_bits(d_cost[0].cpu().numpy(), want), (metric, N, M, offset)
+
+
+@pytest.mark.parametrize("K", [31, 32, 33, 64, 1024])
+def test_cdist_feature_counts_around_the_panel(jsg, torch_cuda, K):
+    """K one below, at and one above the panel of 32 features, two whole panels, and the limit 1024 (32 panels: the longest fmaf chain)."""
+    torch = torch_cuda
+    T = jsg.capix.CDIST_TILE
+    assert K <= jsg.capix.CDIST_MAX_FEATURES
+    N, M = T + 1, T - 1
+    X, Y = features(N, K, 3000 + K), features(M, K, 4000 + K)
+    d_x, d_y = torch.from_numpy(X).cuda(), torch.from_numpy(Y).cuda()
+    for metric in dr.METRICS:
+        fc, d_cost = guarded(torch, 1, N, M, 5, torch.float32, float(SENTINEL), 3)
+        jsg.cdist_launch(d_x, d_y, d_cost[0], metric=metric)
+        torch.cuda.synchronize()
+        assert untouched(fc, d_cost, SENTINEL, 3), "a guard element was written"
+        assert dr.same_bits(d_cost[0].cpu().numpy(), dr.cost32(X, Y, metric)), (metric, K)
+
+
+@pytest.mark.parametrize("aligned", [False, True])
+def test_cdist_three_pairs_in_one_pitched_guarded_plane(jsg, torch_cuda, aligned):
+    """pairs = 3 written into one pitched buffer full of sentinels, with single stores (an odd offset and pitch) and with 16-byte stores
+    beside a scalar tail (every row of every plane on a 16-byte boundary); X is one sequence for every pair (a pair pitch of 0), Y is
+    padded per frame and per pair with poison."""
+    torch = torch_cuda
+    T, K = jsg.capix.CDIST_TILE, 12
+    N, M = T + 5, T + 9
+    X, Ys = features(N, K, 21), np.stack([features(M, K, s) for s in (22, 23, 24)])
+    d_x = torch.from_numpy(X).cuda()
+    fy, d_y = guarded(torch, 3, M, K, 3, torch.float32, float("nan"), 2)
+    d_y.copy_(torch.from_numpy(Ys))
+    for metric in dr.METRICS:
+        if aligned:
+            offset = 4
+            fc, d_cost = aligned_planes(torch, 3, N, M, offset)
+        else:
+            offset = 3
+            fc, d_cost = guarded(torch, 3, N, M, 5, torch.float32, float(SENTINEL), offset)
+        jsg.cdist_launch(d_x, d_y, d_cost, metric=metric)
+        torch.cuda.synchronize()
+        assert untouched(fc, d_cost, SENTINEL, offset), ("a guard element was written", metric)
+        assert untouched(fy, d_y, float("nan"), 2) and dr.same_bits(d_y.cpu().numpy(), Ys), "y was written"
+        got = d_cost.cpu().numpy()
+        for p in range(3):
+            assert dr.same_bits(got[p], dr.cost32(X, Ys[p], metric)), (metric, p, aligned)
 
 
 def test_cdist_with_a_shared_sequence_and_pairs(jsg, torch_cuda):

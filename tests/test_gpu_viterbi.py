@@ -1,8 +1,11 @@
 """Viterbi decoding of libjsgx.so on the GPU (include/jsgx.h section 4) against tests/viterbi_ref.py, bit for bit (NaN positions equal, all
-other bits equal): V, the states and logp over state counts around every lane-split group, both dense forms and a lane's second state; band
-shapes in both band forms with the never-read entries poisoned; frame counts around the block edges of the backtrace; three sequences in
-pitched buffers full of sentinels; missing optional outputs; a NaN emission and a dead frame that stay in their sequence; an exact scratch
-with a guard behind it; graph capture of a first launch of a large-LDS form; and the Python layer end to end."""
+other bits equal): V, the states and logp over viterbi_ref.FORM_STATES (every lane split G = 64 ... 1 in both dense forms with both state
+counts at each of the seven boundaries, which tests/test_jsgx_forms_host.py holds complete, and a lane's second state), with maxima tied
+across the lanes of a destination; viterbi_ref.FORM_BANDS (for every G a band narrower than, next to and wider than the lane split, both
+band forms on both sides of the LDS limit, the never-read entries poisoned); frame counts around the block edges of the backtrace and over
+several blocks; three sequences in pitched buffers full of sentinels; missing optional outputs; a NaN emission and a dead frame that stay
+in their sequence, dense and band; an exact scratch with a guard behind it; graph capture of a first launch of a large-LDS form and a
+first launch of the band form at its largest LDS; and the Python layer end to end."""
 import functools
 
 import numpy as np
@@ -15,8 +18,6 @@ pytestmark = pytest.mark.gpu
 SENTINEL = np.float32(-7.25e11)
 ISENTINEL = np.int32(-77777)
 T_SHAPES = 37
-DENSE_STATES = [1, 2, 3, 63, 64, 65, 191, 192, 193, 255, 256, 257, 1023, 1024, 1025, 2048]
-BANDS = [(1, 0), (5, 0), (5, 4), (64, 3), (300, 25), (1200, 25), (2048, 64), (40, 64)]
 KINDS = ["eighths", "floats"]
 
 
@@ -139,24 +140,58 @@ def test_graph_capture_of_a_first_launch_of_a_large_lds_form(jsg, torch_cuda, bl
         check_seq(got, 1, (None, None, None, V, states, logp), ("replay", seeds, 1))
 
 
+# the second test of the file: no other has launched a band form before it
+def test_first_launch_of_the_band_form_at_its_largest_lds(jsg, torch_cuda):
+    """"viterbi_band_lds" at S = 312, W = 64 holds 163488 of the 163840 bytes of LDS: the first launch of the form tells the device the limit."""
+    S, W = 312, 64
+    assert jsg.viterbi_plan(S, T_SHAPES, band_half=W) == ("viterbi_band_lds", 640, 163488, 3)
+    want = reference("floats", T_SHAPES, S, 200 + S + W, W)
+    assert len(np.unique(want[4])) > 3 and np.isfinite(want[5])
+    check_seq(run(jsg, torch_cuda, [want[0]], want[1], want[2], W=W), 0, want, (S, W, "first launch"))
+
+
+def ties_across_lanes(want, G):
+    """The number of (t, j), t >= 1, whose maximum over the sources is attained by sources that different lanes of the G hold (i % G differs),
+    from the reference's V and the dense matrix."""
+    b, p0, A, V, states, logp = want
+    count = 0
+    with np.errstate(invalid="ignore"):
+        for t in range(1, V.shape[0]):
+            w = V[t - 1][:, None] + A                                    # [i][j]
+            w = np.where(np.isnan(w), vr.NEG_INF, w)
+            at_top = w == w.max(axis=0)[None, :]
+            lanes = np.zeros((G, A.shape[1]), bool)
+            np.logical_or.at(lanes, np.arange(A.shape[0]) % G, at_top)
+            count += int((lanes.sum(axis=0) > 1).sum())
+    return count
+
+
 @pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("S", DENSE_STATES)
+@pytest.mark.parametrize("S", vr.FORM_STATES)
 def test_dense_over_state_counts(jsg, torch_cuda, S, kind):
-    """Every lane-split group (64 lanes per destination at S <= 16 down to 1 above 512), both dense forms (192 | 193) and a lane owning a
-    second destination (1025, 2048), on inputs with many ties and -inf and on inputs with none."""
+    """Every lane split (64 lanes per destination at S <= 16, 32 up to 32, ... 1 above 512) from its first state count to its last, both
+    dense forms (192 | 193) and a lane owning a second destination (1025, 2048), on inputs with many ties and -inf and on inputs with
+    none.  From S = 16 on, wherever G > 1, the eighths tie the maximum of 20 destinations or more across lanes (28 at S = 16, 3163 at 512),
+    so that the xor reduction has to apply the pair rule."""
     name, threads, lds, launches = jsg.viterbi_plan(S, T_SHAPES)
-    assert name == ("viterbi_dense_lds" if S <= 192 else "viterbi_dense_mem") and launches == 3 and threads <= 1024
+    assert name == ("viterbi_dense_lds" if S <= 192 else "viterbi_dense_mem") and launches == 3 and threads == vr.form(S)[1] <= 1024
     want = reference(kind, T_SHAPES, S, 100 + S)
+    G = vr.form(S)[0]
+    if kind == "eighths" and S >= 16 and G > 1:
+        tied = ties_across_lanes(want, G)
+        print(f"S={S} G={G}: {tied} destinations with a maximum tied across lanes")
+        assert tied >= 20, (S, G, tied)
     check_seq(run(jsg, torch_cuda, [want[0]], want[1], want[2]), 0, want, (S, kind))
 
 
 @pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("S, W", BANDS)
+@pytest.mark.parametrize("S, W", vr.FORM_BANDS)
 def test_band_shapes(jsg, torch_cuda, S, W, kind):
-    """Both band forms, W = 0, a band as wide as the matrix and one wider; the entries of the table whose source lies outside the matrix
-    hold 1e30 and must not show."""
+    """Both band forms on both sides of the LDS limit (312 | 313 at W = 64); for every lane split G a band with fewer sources per destination
+    than lanes, one next to G and one with more; W = 0, a band as wide as the matrix and one wider; the entries of the table whose source
+    lies outside the matrix hold 1e30 and must not show."""
     name = jsg.viterbi_plan(S, T_SHAPES, band_half=W)[0]
-    assert name == ("viterbi_band_mem" if (S, W) in ((1200, 25), (2048, 64)) else "viterbi_band_lds")
+    assert name == ("viterbi_band_mem" if (S, W) in ((1200, 25), (2048, 64), (313, 64)) else "viterbi_band_lds")
     want = reference(kind, T_SHAPES, S, 200 + S + W, W)
     assert W == 0 or (want[2] == np.float32(1e30)).any()
     check_seq(run(jsg, torch_cuda, [want[0]], want[1], want[2], W=W), 0, want, (S, W, kind))
@@ -224,6 +259,38 @@ def test_a_nan_emission_and_a_dead_frame_stay_in_their_sequence(jsg, torch_cuda,
     got = run(jsg, torch_cuda, [w[0] for w in wants], p0, A)
     for q, want in enumerate(wants):
         check_seq(got, q, want, q)
+
+
+def test_a_dead_frame_in_the_band_form(jsg, torch_cuda, block):
+    """S = 24 (32 lanes per destination, 7 sources at the most: most lanes of a destination hold no source), W = 3, the table of the
+    builder from a window with zero weights, so that the table itself holds -inf inside the band; one frame of one sequence all -inf.
+    From there on every source of a destination ties at -inf and the lowest one inside the band wins, max(0, j - W)."""
+    T, S, W = block + 20, 24, 3
+    band = jsg.viterbi_band_transition(S, [0.0, 0.5, 0.0, 1.0, 0.25, 0.0, 0.125])
+    assert band.shape == (2 * W + 1, S) and np.isneginf(band[[1, 4, 6]]).all() and np.isfinite(band[3]).all()      # row r holds window[2W - r]
+    b, p0, _ = vr.inputs("floats", T, S, 75)
+    dead = b.copy()
+    dead[T // 2] = -np.inf
+    wants = []
+    for e in (b, dead, b):
+        Ve, psi, se, le = vr.viterbi32(e, p0, band, band_half=W)
+        wants.append((e, p0, band, Ve, se, le))
+    assert np.isfinite(wants[0][5]) and len(np.unique(wants[0][4])) > 3
+    assert wants[1][5] == -np.inf and np.isneginf(wants[1][3][T // 2:]).all() and np.isfinite(wants[1][3][:T // 2]).all()
+    assert (wants[1][4][T // 2:] == 0).all() and (wants[1][4][:T // 2] != 0).any()      # from the end state 0 down max(0, j - W) = 0
+    got = run(jsg, torch_cuda, [w[0] for w in wants], p0, band, W=W)
+    for q, want in enumerate(wants):
+        check_seq(got, q, want, q)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_several_backtrace_blocks_in_the_32_lane_form(jsg, torch_cuda, block, kind):
+    """S = 24 over 3 B + 5 frames: four blocks with a short last one; the jump kernel composes psi of the form with 32 lanes per destination."""
+    T, S = 3 * block + 5, 24
+    assert vr.form(S)[0] == 32 and jsg.viterbi_plan(S, T)[3] == 4
+    want = reference(kind, T, S, 330)
+    assert kind == "eighths" or len(np.unique(want[4])) > 3
+    check_seq(run(jsg, torch_cuda, [want[0]], want[1], want[2]), 0, want, (T, S, kind))
 
 
 def test_all_zero_inputs(jsg, torch_cuda, block):

@@ -1,8 +1,35 @@
 """The numpy restatement of include/jsgx.h section 4 (Viterbi decoding), operation by operation in float32: both transition forms, V, psi,
-the states and logp; the input makers of the tests; and the bit comparison."""
+the states and logp; the lane split of the forward kernel and the shapes that run every form of it; the input makers of the tests; and
+the bit comparison."""
 import numpy as np
 
 NEG_INF = np.float32(-np.inf)
+THREADS = 1024                # JSGX_VITERBI_THREADS of include/jsgx.h
+
+
+def form(S):
+    """(G, threads) of include/jsgx.h, "The kernels": G the largest power of two <= 64 with S * G <= 1024 (1 where there is none),
+    S * G lanes rounded up to whole wavefronts, 1024 at the most."""
+    G = 64
+    while G > 1 and S * G > THREADS:
+        G //= 2
+    return G, min(THREADS, -(-S * G // 64) * 64)
+
+
+# The state counts of the dense GPU test (tests/test_gpu_viterbi.py): every (plan name, G) that a state count in 1..2048 gives and both
+# counts wherever one of them changes (17, 33, 65, 129, 193, 257, 513); 1025 and 2048 give a lane its second destination.
+FORM_STATES = (1, 2, 3, 16, 17, 24, 32, 33, 63, 64, 65, 128, 129, 191, 192, 193, 255, 256, 257, 512, 513, 1023, 1024, 1025, 2048)
+
+# (S, W) of the band GPU test: for every G a band with fewer sources per destination than G lanes (2W + 1 < G; none for G = 1), one next
+# to G (2W + 1 = G - 1 or G + 1; 1 for G = 1) and one with more (2W + 1 > G); W = 0, a band as wide as the matrix and one wider; and
+# both sides of the LDS limit of the band table at W = 64 (312 | 313).  tests/test_jsgx_forms_host.py checks the list against form().
+FORM_BANDS = ((1, 0), (5, 0), (5, 4), (16, 31), (16, 32),                  # G = 64
+              (24, 3), (24, 15), (32, 16), (17, 40),                         # G = 32
+              (64, 3), (40, 7), (33, 8), (40, 64),                           # G = 16
+              (70, 1), (100, 3), (128, 4), (65, 30),                         # G = 8
+              (129, 0), (200, 1), (256, 2), (192, 10),                       # G = 4
+              (257, 0), (512, 1), (300, 25), (312, 64), (313, 64),           # G = 2
+              (513, 0), (1200, 25), (2048, 64))                              # G = 1
 
 
 def same_bits(a, b) -> bool:
