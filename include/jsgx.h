@@ -479,6 +479,217 @@ JSGX_API int jsgx_viterbi_plan(const jsgx_viterbi_args* args, char* name, int na
  * negative or not finite; window[W] <= 0 (so that no row sums to zero); out_pitch below n_states. */
 JSGX_API int jsgx_viterbi_band_build(int32_t n_states, int32_t band_half, const double* window, float* out, int64_t out_pitch);
 
+/* Section 5 was added to version 1 in the same way: sections 1 to 4, their structs and their constants are as they were. */
+
+/* ------------------------------------------------------------------------------------------------
+ * 5. pYIN (Mauch and Dixon 2014; librosa.pyin): from the d' plane of jsg_yin_launch (include/jsg.h section 2i, its cmnd output) to
+ *    the emissions of a hidden Markov model over P pitch bins x {voiced, unvoiced}, and the decoding of that model with its
+ *    transition in factored form.  The state s = u P + p, u = 0 voiced and u = 1 unvoiced, p the pitch bin: librosa's order.  A row
+ *    (a sequence) is one signal; rows and frames are independent in the observation, sequences in the decoder.  All device arithmetic
+ *    is float32 and uncontracted; fl(.) is one rounding to float32; the divides are correctly rounded.  Nothing depends on the number
+ *    of rows, on the pitches, on which optional outputs are NULL or on the form of a kernel.
+ *
+ *    5a. The tables, built on the host in double and rounded to float32 once (no device).
+ *      prior (jsgx_pyin_prior_build):  out[k] = I((k+1)/N; a, b) - I(k/N; a, b), k = 0..N-1, I the regularised incomplete beta function
+ *        (its continued fraction by Lentz's method on the side x < (a+1)/(a+b+2), the other side by symmetry, the front factor from
+ *        lgamma).  librosa: np.diff(beta.cdf(linspace(0, 1, N+1), a, b)) with (a, b) = (2, 18), N = 100.
+ *      decay, norm (jsgx_pyin_boltzmann_build):  decay[i] = exp(-lambda i), i = 0..n-1;  norm[0] = 0, norm[m] = (1 - exp(-lambda)) /
+ *        (1 - exp(-lambda m)), m = 1..n.  The truncated Boltzmann pmf of the position i among m troughs is norm[m] * decay[i].
+ *      edges, freqs (jsgx_pyin_bins_build):  freqs[b] = fmin 2^(b / (12 bps)), b = 0..P-1;  edges[b] = sample_rate / (fmin 2^((b - 0.5) /
+ *        (12 bps))), b = 0..P: a descending table of PERIODS.  The device finds a candidate's bin by comparing with this table and takes
+ *        no logarithm, so the bin is reproducible bit for bit.
+ *      log_window, src_offset, log_switch (jsgx_pyin_transition_build):  log_window[k] = log(window[k]), -inf for 0, k = 0..2W;
+ *        src_offset[p] = -log(the sum of window[p' - p + W] over p' = max(0, p-W)..min(P-1, p+W), p' ascending): the local normalisation
+ *        of jsgx_viterbi_band_build kept as a term of the source;  log_switch[2u + u'] = log(u == u' ? 1 - switch_prob : switch_prob),
+ *        -inf for 0.
+ *
+ *    5b. The observation (jsgx_pyin_observe_launch).  Per frame, with h[tau] = d'[tau] = cmnd[r*cmnd_row_pitch + t*cmnd_frame_pitch + tau]:
+ *      1. Troughs.  tau_min is a trough iff h[tau_min] < h[tau_min+1];  tau_min < tau < tau_max iff h[tau-1] > h[tau] <= h[tau+1];  tau_max
+ *         never is, and with tau_min == tau_max there is none.  No two neighbouring lags are troughs: there are at most
+ *         (tau_max - tau_min + 1) / 2 of them (integer division).  Trough j = 0, 1, ... in ascending lag order, h_j = h[tau_j].
+ *      2. Thresholds.  th_k = (float)((k+1) / (double)N), k = 0..N-1.  Trough j lies below threshold k iff h_j < th_k (strict), so for all
+ *         k >= k0(j), k0(j) = N where there is none.  n_k = the number of troughs below threshold k;  pos_jk = the number of troughs i < j
+ *         below threshold k (the rank of j among them by ascending lag, from 0).
+ *      3. Probability.  term_jk = fl(prior[k] * fl(norm[n_k] * decay[pos_jk])) for k >= k0(j), +0 for k < k0(j).  The sum over k is the lane
+ *         sum of 64 lanes: lane l adds term_jk for k = l, l+64, l+128, l+192 (those below N) ascending with plain adds from +0; then a
+ *         halving tree: for m = 32, 16, ..., 1:  acc_l = acc_l + acc_(l+m) for l < m;  prob_j = acc_0.  The lowest trough g (the lowest h_j,
+ *         the lowest lag among equal ones) gets in addition:  prob_g = fl(prob_g + fl(no_trough_prob * q)), q = the same lane sum of
+ *         (k < k0(g) ? prior[k] : +0).
+ *      4. Period and bin.  a, b, c = h[tau_j - 1], h[tau_j], h[tau_j + 1];  den = (a - b) + (c - b);  if den > 0:  s = (0.5f * (a - c)) / den,
+ *         kept if |s| <= 1, else 0; in every other case (a NaN h[tau_min - 1] included) s = 0:  step 4 of jsg.h section 2i.
+ *         period_j = (float)tau_j + s.  bin_j = the number of b in 1..P-1 with period_j <= edges[b]: a period above edges[1] is in bin 0,
+ *         one at or below edges[P-1] in bin P-1, so both ends are clamped (edges[0] and edges[P] are the outer rims and are not read).  The
+ *         kernel finds the number by bisection, which is that number for a descending table; for any other table it is some bin in 0..P-1.
+ *      5. Accumulation.  obs[b] = the sum of prob_j over the troughs with bin_j = b, in ascending lag order with plain adds from +0.
+ *         total = the lane sum of 64 lanes of obs[b] (lane l adds b = l, l+64, ... ascending from +0, then the halving tree above);
+ *         voiced = 1 where total > 1, else total;  unv = fl(fl(1 - voiced) / (float)P).
+ *      6. Emissions.  log_emit[p] = L(obs[p]);  log_emit[P + p] = L(unv), p = 0..P-1, at log_emit[r*emit_row_pitch + t*emit_frame_pitch + s].
+ *         obs[r][t][p] and voiced_prob[r][t] = voiced where these are given.
+ *      7. NaN.  If any h[tau], tau_min <= tau <= tau_max, is a NaN the frame is unobserved: obs = +0, voiced_prob = NaN, the voiced emissions
+ *         are -inf and the unvoiced ones L(fl(1 / (float)P)).  No other frame is touched, and the decoder goes through such a frame.
+ *
+ *      L(x), the natural logarithm from plain float32 adds and multiplies and one divide, no fmaf, no hardware logarithm (the reduction
+ *      and the polynomial of the freely available fdlibm e_logf.c, evaluated in this order):
+ *          x == 0: -inf;   x < 0 or a NaN: NaN;   x == +inf: +inf
+ *          k = 0;   x < 2^-126:  x = x * 2^24 (exact), k = -24
+ *          i = (the bits of x) + 0x004afb0d;   k = k + (i >> 23) - 127;   m = the float with the bits (i & 0x007fffff) + 0x3f3504f3
+ *              (x = m 2^k, sqrt(1/2) <= m < sqrt(2))
+ *          f = m - 1;   s = f / (2 + f);   z = s * s;   w = z * z
+ *          t1 = w * (0.40000972152 + w * 0.24279078841);   t2 = z * (0.66666662693 + w * 0.28498786688)        (floats: 0xccce13p-25,
+ *              0xf89e26p-26, 0xaaaaaap-24, 0x91e9eep-25; every product and sum rounded)
+ *          r = t2 + t1;   hfsq = (0.5f * f) * f;   dk = (float)k
+ *          L = (((s * (hfsq + r) + dk * 9.0580006145e-06f) - hfsq) + f) + dk * 6.9313812256e-01f          (ln 2 = hi + lo)
+ *      L(1) = +0.  |L(x) - ln x| <= JSGX_LOG_ABS_BOUND * max(1, |ln x|) over every float32 x in (0, 1] against log in double (measured:
+ *      profiles/pyin_accuracy.md).
+ *
+ *      Known answers.  A silent frame (d' = 1 everywhere) has no trough: obs = +0, voiced_prob = +0, unv = fl(1 / (float)P), the voiced
+ *      emissions are -inf.  A frame whose only trough has h >= 1 lies below no threshold (th_(N-1) = 1): prob = +0 + fl(no_trough_prob *
+ *      (the lane sum of prior)) goes into that trough's bin and nothing else.
+ *      Error bound, for tables that are >= 0, against exact arithmetic on the same float32 tables and the same troughs, bins and
+ *      thresholds, u = 2^-24: a term carries two roundings, the lane sum of at most 4 + 6 additions of non-negative numbers ten more, the
+ *      no-trough part at most 12 and one more for its addition, the sum into obs[b] one per trough of the bin: obs[b] is relative
+ *      (13 + c_b) u to first order, c_b the troughs of bin b after the first (0 where the bins do not collide); against a float64 evaluation
+ *      with unrounded tables three more (prior, norm, decay): tests/test_pyin_ref.py asserts 18 u on frames without collisions.  voiced adds ceil(P / 64) + 6 roundings.
+ *      Differences from librosa.pyin, on purpose: candidates that fall into one bin add (librosa's fancy assignment keeps the last);
+ *      both ends of the bin index clamp (librosa clips to P, which lands in the unvoiced half and is overwritten); the parabola is
+ *      section 2i's; the troughs are defined on d' above.  Agreement with librosa has not been measured.
+ *      The kernel ("pyin_observe"): one wavefront per frame (a workgroup of JSGX_PYIN_OBSERVE_THREADS lanes, one frame per workgroup),
+ *      nobody waits for anybody.  d' of the frame is staged in LDS; the troughs are packed by a ballot; a lane owns four thresholds; the
+ *      troughs are met in lag order, each with one xor tree over the lanes.  LDS: 4 (tau_max + 1 + 3 (max troughs + 1) + P) bytes.
+ *
+ *    5c. The decoder (jsgx_pyin_decode_launch).  Inputs as section 4: b[t][s] = log_emit[q*emit_seq_pitch + t*emit_frame_pitch + s],
+ *      S = 2P states; p0 = log_init[2P]; the transition is A((u, p), (u', p')) = src_offset[p] + log_window[p' - p + W] + log_switch[2u + u']
+ *      for |p - p'| <= W = band_half, and only these sources exist.
+ *      Recurrence.  V[0][s] = fl(p0[s] + b[0][s]).  For t >= 1:
+ *          U[u][p] = fl(V[t-1][uP + p] + src_offset[p])
+ *          for every p' and u, over p = max(0, p'-W)..min(P-1, p'+W):   w(p) = fl(U[u][p] + log_window[p' - p + W]), a NaN counted as -inf;
+ *              p*_u = the p with the largest w, the lowest p among equal w;   m_u = w(p*_u)
+ *          for every u':   c_u = fl(m_u + log_switch[2u + u']), a NaN counted as -inf;   the winner is the larger c_u, u = 0 on ties;
+ *              psi[t][u'P + p'] = uP + p*_u;     V[t][u'P + p'] = fl(c_u + b[t][u'P + p'])
+ *      The selection over p is the pair rule of section 4, so it does not depend on how the lanes split the sources.  End, backtrace,
+ *      outputs (states, logp, value), the meaning of logp = -inf and the NaN rules are section 4's with S = 2P, and the backtrace is
+ *      section 4's three kernels.
+ *      Against section 4 on the dense matrix A: the same maximisation, with the three terms of A added to V in another association.
+ *      Where every sum is exact (multiples of 1/8 in a small range) and every destination has a source above -inf the two give the same
+ *      bits; where all sources of a destination are -inf the lowest source inside the pitch band wins here, u = 0 and p = max(0, p'-W).
+ *      Known answers.  All inputs +0: every w ties, V = +0, psi[t][u'P + p'] = max(0, p'-W), e = 0, the states are all 0 and logp = +0.
+ *      A frame whose emissions are all -inf: logp = -inf with JSGX_OK.
+ *      Error bound, for finite inputs that are all <= 0, u = 2^-24: as section 4, with four same-sign additions per frame instead of two
+ *      (U, w, c, V): logp carries at most 4T - 3 roundings, inside (4T + 2) u relative for T <= 4096, which tests/test_pyin_ref.py
+ *      asserts against float64.
+ *      The kernel ("pyin_decode"): one workgroup per sequence, nobody waits across workgroups.  U of both u lies in LDS, two copies
+ *      swapped by the parity of t, every row padded with W words of -inf at both ends: the inner loop has no bounds test.  m_0 and m_1
+ *      are computed once per p' and serve both u'.  G lanes of one wavefront share a p' and take the offsets g, g + G, ...; they are
+ *      joined with the pair rule by xor lane moves.  G = the largest power of two <= 64 with 8 G <= 2W + 1 (a lane has eight offsets
+ *      at the least) and P*G <= 512, 1 where there is none; the workgroup has P*G lanes rounded up to 64.  The rule was chosen by
+ *      measurement (profiles/pyin_bench.md): with as many lanes per bin as 1024 lanes hold, the joins cost more than the split saves.  U of frame t is
+ *      written where V[t] is: one barrier per frame.  U is kept as pairs (U[0][p], U[1][p]) that a lane reads 8 bytes at a time.  The
+ *      emissions of frame t + 1 are loaded while frame t computes.  psi is uint16 in the scratch in section 4's layout.  LDS: 4 (4 (P + 2W) + 2W + 1) bytes.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSGX_PYIN_MAX_BINS 1024
+#define JSGX_PYIN_MAX_BAND_HALF 128
+#define JSGX_PYIN_MAX_THRESHOLDS 256
+#define JSGX_PYIN_MAX_LAG 4096
+#define JSGX_PYIN_OBSERVE_THREADS 64
+#define JSGX_PYIN_THREADS 1024             /* the most lanes of a forward workgroup of the decoder */
+#define JSGX_LOG_ABS_BOUND 1.0e-7          /* L against log in double over every float32 in (0, 1] (measured 8.07e-8: profiles/pyin_accuracy.md) */
+
+/* out[k], k = 0..n_thresholds-1 (5a).  JSGX_ERR_INVALID, in this order: a null out; n_thresholds outside 1..256; a or b not finite and > 0. */
+JSGX_API int jsgx_pyin_prior_build(int32_t n_thresholds, double a, double b, float* out);
+/* decay[0..n-1] and norm[0..n] (5a).  JSGX_ERR_INVALID, in this order: a null decay, a null norm; lambda not finite and > 0; n outside
+ * 1..JSGX_PYIN_MAX_LAG. */
+JSGX_API int jsgx_pyin_boltzmann_build(double lambda, int32_t n, float* decay, float* norm);
+/* edges[0..n_bins] and freqs[0..n_bins-1] (5a).  JSGX_ERR_INVALID, in this order: a null edges, a null freqs; sample_rate not finite and
+ * > 0; fmin not finite and > 0; bins_per_semitone outside 1..1024; n_bins outside 1..JSGX_PYIN_MAX_BINS. */
+JSGX_API int jsgx_pyin_bins_build(double sample_rate, double fmin, int32_t bins_per_semitone, int32_t n_bins, float* edges, float* freqs);
+/* log_window[0..2W], src_offset[0..n_bins-1], log_switch[0..3] (5a).  JSGX_ERR_INVALID, in this order: a null window, a null log_window,
+ * a null src_offset, a null log_switch; n_bins outside 1..1024; band_half outside 0..JSGX_PYIN_MAX_BAND_HALF; a window entry that is
+ * negative or not finite; window[W] <= 0; switch_prob outside [0, 1]. */
+JSGX_API int jsgx_pyin_transition_build(int32_t n_bins, int32_t band_half, const double* window, double switch_prob, float* log_window, float* src_offset,
+                                        float* log_switch);
+
+typedef struct jsgx_pyin_observe_args {
+    const float* cmnd;          /* device floats: d'[r][t][tau] at cmnd[r*cmnd_row_pitch + t*cmnd_frame_pitch + tau], tau = 0..tau_max */
+    int64_t cmnd_frame_pitch;   /* >= tau_max + 1 */
+    int64_t cmnd_row_pitch;     /* rows > 1: >= (n_frames - 1) * cmnd_frame_pitch + tau_max + 1 */
+    int32_t rows;               /* 1..65535, independent */
+    int32_t n_frames;           /* 1..JSGX_VITERBI_MAX_FRAMES */
+    int32_t tau_min;            /* 1..tau_max */
+    int32_t tau_max;            /* 1..JSGX_PYIN_MAX_LAG */
+    const float* prior;         /* device floats [n_thresholds] */
+    const float* decay;         /* device floats [boltz_len] */
+    const float* norm;          /* device floats [boltz_len + 1] */
+    const float* edges;         /* device floats [n_bins + 1], descending */
+    int32_t n_thresholds;       /* N, 1..JSGX_PYIN_MAX_THRESHOLDS */
+    int32_t boltz_len;          /* max(1, (tau_max - tau_min + 1) / 2)..JSGX_PYIN_MAX_LAG: the most troughs of a frame at the least */
+    int32_t n_bins;             /* P, 1..JSGX_PYIN_MAX_BINS */
+    float no_trough_prob;       /* in [0, 1] */
+    float* log_emit;            /* device floats: [r][t][2P] at log_emit[r*emit_row_pitch + t*emit_frame_pitch + s] */
+    int64_t emit_frame_pitch;   /* >= 2 * n_bins */
+    int64_t emit_row_pitch;     /* rows > 1: >= (n_frames - 1) * emit_frame_pitch + 2 * n_bins */
+    float* obs;                 /* device floats or NULL: [r][t][P] at obs[r*obs_row_pitch + t*obs_frame_pitch + p] */
+    int64_t obs_frame_pitch;    /* obs given: >= n_bins */
+    int64_t obs_row_pitch;      /* obs given and rows > 1: >= (n_frames - 1) * obs_frame_pitch + n_bins */
+    float* voiced_prob;         /* device floats or NULL: [r][t] at voiced_prob[r*voiced_pitch + t] */
+    int64_t voiced_pitch;       /* voiced_prob given and rows > 1: >= n_frames */
+} jsgx_pyin_observe_args;       /* 152 bytes, no padding */
+
+/* Enqueue only (one kernel, no scratch): no allocation, no synchronisation; capture works, a first launch included.  Refused
+ * (JSGX_ERR_INVALID, nothing enqueued), in this order and before any device call: null args, a null cmnd, a null prior, a null decay, a
+ * null norm, a null edges, a null log_emit; a pointer that is not 4-byte aligned; rows outside 1..65535, n_frames outside 1..2^20,
+ * tau_max outside 1..4096, tau_min outside 1..tau_max, n_thresholds outside 1..256, n_bins outside 1..1024, boltz_len outside
+ * max(1, (tau_max - tau_min + 1) / 2)..4096, no_trough_prob outside [0, 1]; cmnd_frame_pitch below tau_max + 1, cmnd_row_pitch that does
+ * not cover a row (rows > 1), emit_frame_pitch below 2 * n_bins, emit_row_pitch that does not cover a row (rows > 1), obs_frame_pitch
+ * below n_bins (obs given), obs_row_pitch that does not cover a row (obs given, rows > 1), voiced_pitch below n_frames (voiced_prob
+ * given, rows > 1); an output (log_emit, obs, voiced_prob) overlapping cmnd, one overlapping prior, decay, norm, edges in this order,
+ * an output overlapping another output.  Then JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_pyin_observe_launch(const jsgx_pyin_observe_args* args, void* stream);
+/* The kernel of these arguments, without a device: its name ("pyin_observe"), the lanes of a workgroup, the bytes of LDS it holds
+ * (dynamic, <= 65536) and the frames a workgroup takes (1).  Any output pointer may be NULL (name: else name_len >= 16).  Refused: a
+ * name_len below 16 with a name, then what the launch refuses. */
+JSGX_API int jsgx_pyin_observe_plan(const jsgx_pyin_observe_args* args, char* name, int name_len, int32_t* threads, int32_t* lds_bytes,
+                                    int32_t* frames_per_workgroup);
+
+typedef struct jsgx_pyin_decode_args {
+    const float* log_emit;      /* device floats: b[q][t][s], s = u*n_bins + p */
+    int64_t emit_frame_pitch;   /* >= 2 * n_bins */
+    int64_t emit_seq_pitch;     /* seqs > 1: >= (n_frames - 1) * emit_frame_pitch + 2 * n_bins */
+    const float* log_init;      /* device floats [2 * n_bins] */
+    const float* log_window;    /* device floats [2 * band_half + 1] */
+    const float* src_offset;    /* device floats [n_bins] */
+    const float* log_switch;    /* device floats [4] */
+    int32_t n_bins;             /* P, 1..JSGX_PYIN_MAX_BINS */
+    int32_t band_half;          /* W, 0..JSGX_PYIN_MAX_BAND_HALF */
+    int32_t seqs;               /* 1..65535, independent */
+    int32_t n_frames;           /* T, 1..JSGX_VITERBI_MAX_FRAMES */
+    int32_t* states;            /* device int32: states[q][t] at states[q*states_pitch + t] */
+    int64_t states_pitch;       /* seqs > 1: >= n_frames */
+    float* logp;                /* device floats [seqs] or NULL */
+    float* value;               /* device floats or NULL: V[q][t][s] at value[q*value_seq_pitch + t*value_frame_pitch + s] */
+    int64_t value_frame_pitch;  /* value given: >= 2 * n_bins */
+    int64_t value_seq_pitch;    /* value given and seqs > 1: >= (n_frames - 1) * value_frame_pitch + 2 * n_bins */
+} jsgx_pyin_decode_args;        /* 120 bytes, no padding */
+
+/* The bytes of scratch the launch needs: the formula of jsgx_viterbi_scratch_bytes with S = 2 * n_bins.  Refused (a negative jsgx_status):
+ * what the launch refuses before it looks at the scratch. */
+JSGX_API int64_t jsgx_pyin_decode_scratch_bytes(const jsgx_pyin_decode_args* args);
+/* Enqueue only: no allocation, no synchronisation; capture works, a first launch included.  The kernels (forward, then section 4's jump
+ * where T > JSGX_VITERBI_BLOCK, ends, trace) go onto the one stream as a plain chain.  Refused (JSGX_ERR_INVALID, nothing enqueued), in
+ * this order and before any device call: null args, a null log_emit, a null log_init, a null log_window, a null src_offset, a null
+ * log_switch, a null states; a pointer that is not 4-byte aligned; seqs outside 1..65535, n_bins outside 1..1024, band_half outside
+ * 0..128, n_frames outside 1..2^20; emit_frame_pitch below 2 * n_bins, emit_seq_pitch that does not cover a sequence (seqs > 1),
+ * states_pitch below n_frames (seqs > 1), value_frame_pitch below 2 * n_bins (value given), value_seq_pitch that does not cover a
+ * sequence (value given, seqs > 1); an output (states, logp, value) overlapping log_emit, one overlapping log_init, log_window,
+ * src_offset, log_switch in this order, an output overlapping another output; a null scratch, a scratch that is not 4-byte aligned,
+ * scratch_bytes below jsgx_pyin_decode_scratch_bytes.  Then JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_pyin_decode_launch(const jsgx_pyin_decode_args* args, void* scratch, int64_t scratch_bytes, void* stream);
+/* What the launch enqueues, without a device: the name of the forward kernel ("pyin_decode"), G (the lanes that share a pitch bin), the
+ * lanes of its workgroup, the bytes of LDS it holds (dynamic, <= 65536) and the number of kernels (3 where T <= JSGX_VITERBI_BLOCK, else
+ * 4).  Any output pointer may be NULL (name: else name_len >= 16).  Refused: a name_len below 16 with a name, then what the scratch
+ * size refuses. */
+JSGX_API int jsgx_pyin_decode_plan(const jsgx_pyin_decode_args* args, char* name, int name_len, int32_t* lanes_per_bin, int32_t* threads, int32_t* lds_bytes,
+                                   int32_t* n_launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ from .spectrogram import (CColorPalette, Filterbank, FreqAxis, Plan, Spectrogram
                           beat_launch, beat_log_table, beat_plan, beat_scratch_bytes, beat_track, beat_track_audio,
                           cdist, cdist_launch, cdist_plan, dtw, dtw_launch, dtw_plan, dtw_scratch_bytes,
                           viterbi, viterbi_band_transition, viterbi_launch, viterbi_plan, viterbi_scratch_bytes,
+                          pyin, pyin_geometry, pyin_decode_launch, pyin_decode_plan, pyin_decode_scratch_bytes, pyin_observe_launch, pyin_observe_plan, pyin_prior, pyin_tables,
                           delta, delta_launch, delta_weights, mfcc, mfcc_audio, mfcc_kernel_name, mfcc_launch, mfcc_plan, mfcc_table, mfcc_to_mel_db,
                           fft_frequencies, spectral_bandwidth, spectral_centroid, spectral_crest, spectral_flatness, spectral_rolloff, spectral_shape,
                           spectral_shape_audio, spectral_shape_kernel_name, spectral_shape_launch, spectral_shape_plan)
@@ -37,6 +38,7 @@ __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_d
            "capix", "beat_log_table", "beat_scratch_bytes", "beat_launch", "beat_plan", "beat_track", "beat_track_audio",
            "cdist", "cdist_launch", "cdist_plan", "dtw", "dtw_launch", "dtw_scratch_bytes", "dtw_plan",
            "viterbi_scratch_bytes", "viterbi_launch", "viterbi_plan", "viterbi_band_transition", "viterbi",
+           "pyin_prior", "pyin_tables", "pyin_observe_launch", "pyin_observe_plan", "pyin_decode_launch", "pyin_decode_scratch_bytes", "pyin_decode_plan", "pyin_geometry", "pyin",
            "mfcc_table", "mfcc_launch", "mfcc_plan", "mfcc_kernel_name", "delta_weights", "delta_launch", "mfcc", "mfcc_to_mel_db", "delta", "mfcc_audio",
            "spectral_shape_launch", "spectral_shape_plan", "spectral_shape_kernel_name", "fft_frequencies", "spectral_shape", "spectral_centroid",
            "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "spectral_crest", "spectral_shape_audio"]

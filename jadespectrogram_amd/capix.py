@@ -62,6 +62,26 @@ class ViterbiArgs(C.Structure):
                 ("value", C.c_void_p), ("value_frame_pitch", C.c_int64), ("value_seq_pitch", C.c_int64)]
 
 
+PYIN_MAX_BINS, PYIN_MAX_BAND_HALF, PYIN_MAX_THRESHOLDS, PYIN_MAX_LAG = 1024, 128, 256, 4096
+PYIN_OBSERVE_THREADS, PYIN_THREADS = 64, 1024
+LOG_ABS_BOUND = 1.0e-7
+
+
+class PyinObserveArgs(C.Structure):
+    _fields_ = [("cmnd", C.c_void_p), ("cmnd_frame_pitch", C.c_int64), ("cmnd_row_pitch", C.c_int64), ("rows", C.c_int32), ("n_frames", C.c_int32),
+                ("tau_min", C.c_int32), ("tau_max", C.c_int32), ("prior", C.c_void_p), ("decay", C.c_void_p), ("norm", C.c_void_p), ("edges", C.c_void_p),
+                ("n_thresholds", C.c_int32), ("boltz_len", C.c_int32), ("n_bins", C.c_int32), ("no_trough_prob", C.c_float), ("log_emit", C.c_void_p),
+                ("emit_frame_pitch", C.c_int64), ("emit_row_pitch", C.c_int64), ("obs", C.c_void_p), ("obs_frame_pitch", C.c_int64), ("obs_row_pitch", C.c_int64),
+                ("voiced_prob", C.c_void_p), ("voiced_pitch", C.c_int64)]
+
+
+class PyinDecodeArgs(C.Structure):
+    _fields_ = [("log_emit", C.c_void_p), ("emit_frame_pitch", C.c_int64), ("emit_seq_pitch", C.c_int64), ("log_init", C.c_void_p), ("log_window", C.c_void_p),
+                ("src_offset", C.c_void_p), ("log_switch", C.c_void_p), ("n_bins", C.c_int32), ("band_half", C.c_int32), ("seqs", C.c_int32), ("n_frames", C.c_int32),
+                ("states", C.c_void_p), ("states_pitch", C.c_int64), ("logp", C.c_void_p), ("value", C.c_void_p), ("value_frame_pitch", C.c_int64),
+                ("value_seq_pitch", C.c_int64)]
+
+
 # every symbol include/jsgx.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -80,6 +100,15 @@ SIGNATURES = {
     "jsgx_viterbi_launch": (C.c_int, [C.POINTER(ViterbiArgs), _P, C.c_int64, _P]),
     "jsgx_viterbi_plan": (C.c_int, [C.POINTER(ViterbiArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 3),
     "jsgx_viterbi_band_build": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int64]),
+    "jsgx_pyin_prior_build": (C.c_int, [C.c_int32, C.c_double, C.c_double, _P]),
+    "jsgx_pyin_boltzmann_build": (C.c_int, [C.c_double, C.c_int32, _P, _P]),
+    "jsgx_pyin_bins_build": (C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_int32, _P, _P]),
+    "jsgx_pyin_transition_build": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_double, _P, _P, _P]),
+    "jsgx_pyin_observe_launch": (C.c_int, [C.POINTER(PyinObserveArgs), _P]),
+    "jsgx_pyin_observe_plan": (C.c_int, [C.POINTER(PyinObserveArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 3),
+    "jsgx_pyin_decode_scratch_bytes": (C.c_int64, [C.POINTER(PyinDecodeArgs)]),
+    "jsgx_pyin_decode_launch": (C.c_int, [C.POINTER(PyinDecodeArgs), _P, C.c_int64, _P]),
+    "jsgx_pyin_decode_plan": (C.c_int, [C.POINTER(PyinDecodeArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 4),
 }
 
 _lib = None

@@ -46,6 +46,28 @@ struct ViterbiPlan {
     long long scratch_bytes;
 };
 ViterbiPlan viterbi_plan(const jsgx_viterbi_args* g);
+// The parts of the scratch behind V[T-1] for Q sequences of T frames and S states, and the blocks of the backtrace: what sections 4 and 5 share.
+inline void viterbi_layout(long long Q, long long S, long long T, ViterbiPlan* p) {
+    p->n_blocks = (int)((T + JSGX_VITERBI_BLOCK - 1) / JSGX_VITERBI_BLOCK);
+    p->off_end = 4 * Q * S;
+    p->off_psi = p->off_end + 4 * Q * p->n_blocks;
+    p->off_jump = p->off_psi + 2 * Q * T * S;
+    p->scratch_bytes = (p->off_jump + 2 * Q * p->n_blocks * S + 3) / 4 * 4;
+}
+
+// section 5 (jsgx_pyin_host.cpp): every refusal that does not look at the scratch, in the header's order
+int pyin_observe_check(const jsgx_pyin_observe_args* g, const char* who);
+int pyin_decode_check(const jsgx_pyin_decode_args* g, const char* who);
+// The most troughs a frame can hold: no two lags next to each other are troughs and tau_max never is one.
+inline int pyin_max_troughs(int tau_min, int tau_max) { return (tau_max - tau_min + 1) / 2; }
+// The words of LDS of the observation kernel: d' of the frame, then lag, probability and bin of every trough, then obs.
+inline int pyin_observe_lds_bytes(int tau_min, int tau_max, int P) { return 4 * (tau_max + 1 + 3 * (pyin_max_troughs(tau_min, tau_max) + 1) + P); }
+// How the forward kernel of section 5 serves a shape: G lanes per pitch bin, and the scratch of section 4 with S = 2P (psi, jump, end, V[T-1]).
+struct PyinDecodePlan {
+    int G, threads, lds_bytes;
+    ViterbiPlan back;
+};
+PyinDecodePlan pyin_decode_plan(const jsgx_pyin_decode_args* g);
 
 // The three refusals of a launch's scratch buffer, in this order; `sizer` names the call that states `need`.
 inline int check_scratch(const char* who, const void* scratch, int64_t scratch_bytes, int64_t need, const char* sizer) {
@@ -85,6 +107,10 @@ inline int finish_launch(const char* who, hipError_t err) {
     std::snprintf(what, sizeof what, "HIP error %d (%s)", (int)err, hipGetErrorString(err));
     return fail(JSGX_ERR_HIP, who, what);
 }
+// The blocked backtrace of section 4 (jsgx_viterbi.hip: jump where n_blocks > 1, ends, trace) onto the stream, from psi and V[T-1] in the
+// scratch `base` laid out by viterbi_layout: what jsgx_viterbi_launch and jsgx_pyin_decode_launch enqueue behind their forward kernels.
+// states_pitch is 0 for one sequence.  Returns hipGetLastError().
+hipError_t viterbi_backtrace_enqueue(char* base, const ViterbiPlan& p, int seqs, int S, int T, int* states, long long states_pitch, float* logp, hipStream_t s);
 #endif
 
 constexpr int kBeatRing = 4096;                                 // >= 2 * JSGX_BEAT_MAX_PERIOD + JSGX_BEAT_THREADS, a power of two
@@ -129,6 +155,44 @@ JSGX_HD float exp_neg(float x) {
     p = __builtin_fmaf(p, r, 1.0f);
     p = __builtin_fmaf(p, r, 1.0f);
     return p * float_of_bits((unsigned)((int)n + 127) << 23);
+}
+
+JSGX_HD unsigned bits_of_float(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __float_as_uint(v);
+#else
+    unsigned b;
+    memcpy(&b, &v, 4);
+    return b;
+#endif
+}
+
+// L(x), the natural logarithm as include/jsgx.h section 5 states it, operation by operation: plain float32 adds, multiplies and one
+// correctly rounded divide, no fmaf and no hardware logarithm
+JSGX_HD float log_pos(float x) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    if (!(x > 0.f)) return x == 0.f ? -__builtin_inff() : __builtin_nanf("");
+    if (x == __builtin_inff()) return x;
+    int k = 0;
+    if (x < 1.1754943508222875e-38f) {           // below 2^-126: scaled by 2^24, exactly
+        x = x * 16777216.0f;
+        k = -24;
+    }
+    unsigned ix = bits_of_float(x) + (0x3f800000u - 0x3f3504f3u);
+    k += (int)(ix >> 23) - 127;
+    const float m = float_of_bits((ix & 0x007fffffu) + 0x3f3504f3u);        // x = m 2^k, sqrt(1/2) <= m < sqrt(2)
+    const float f = m - 1.0f;
+    const float s = f / (2.0f + f);
+    const float z = s * s;
+    const float w = z * z;
+    const float t1 = w * (0xccce13.0p-25f + w * 0xf89e26.0p-26f);
+    const float t2 = z * (0xaaaaaa.0p-24f + w * 0x91e9ee.0p-25f);
+    const float r = t2 + t1;
+    const float hfsq = (0.5f * f) * f;
+    const float dk = (float)k;
+    return (((s * (hfsq + r) + dk * 9.0580006145e-06f) - hfsq) + f) + dk * 6.9313812256e-01f;
 }
 
 }  // namespace jsgx

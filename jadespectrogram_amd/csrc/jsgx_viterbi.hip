@@ -228,6 +228,22 @@ namespace {
 jsg::OncePerDevice g_told;      // a bit per form: the devices that know its LDS limit
 }
 
+hipError_t viterbi_backtrace_enqueue(char* base, const ViterbiPlan& p, int seqs, int S, int T, int* states, long long states_pitch, float* logp, hipStream_t s) {
+    BackArgs b{};
+    b.psi = reinterpret_cast<const unsigned short*>(base + p.off_psi);
+    b.jump = reinterpret_cast<unsigned short*>(base + p.off_jump);
+    b.end = reinterpret_cast<int*>(base + p.off_end);
+    b.vlast = reinterpret_cast<const float*>(base);
+    b.S = S, b.T = T, b.n_blocks = p.n_blocks;
+    b.states = states;
+    b.states_pitch = states_pitch;
+    b.logp = logp;
+    if (p.n_blocks > 1) hipLaunchKernelGGL(viterbi_jump_kernel, dim3((unsigned)(p.n_blocks - 1), (unsigned)seqs), dim3(kJumpThreads), 0, s, b);
+    hipLaunchKernelGGL(viterbi_ends_kernel, dim3((unsigned)seqs), dim3(kEndsThreads), 0, s, b);
+    hipLaunchKernelGGL(viterbi_trace_kernel, dim3((unsigned)((p.n_blocks + kTraceThreads - 1) / kTraceThreads), (unsigned)seqs), dim3(kTraceThreads), 0, s, b);
+    return hipGetLastError();
+}
+
 }  // namespace jsgx
 
 using namespace jsgx;
@@ -261,20 +277,6 @@ extern "C" int jsgx_viterbi_launch(const jsgx_viterbi_args* g, void* scratch, in
                                            viterbi_forward_kernel<true, true>};
     const int form = (p.band ? 2 : 0) + (p.table_in_lds ? 1 : 0);
     hipError_t err = jsg::launch_large_lds(g_told, dev, 1u << form, forms[form], JSGX_VITERBI_LDS_LIMIT, dim3((unsigned)g->seqs), dim3((unsigned)p.threads), (size_t)p.lds_bytes, s, f);
-    if (err == hipSuccess) {
-        BackArgs b{};
-        b.psi = f.psi;
-        b.jump = reinterpret_cast<unsigned short*>(base + p.off_jump);
-        b.end = reinterpret_cast<int*>(base + p.off_end);
-        b.vlast = f.vlast;
-        b.S = g->n_states, b.T = g->n_frames, b.n_blocks = p.n_blocks;
-        b.states = g->states;
-        b.states_pitch = multi ? g->states_pitch : 0;
-        b.logp = g->logp;
-        if (p.n_blocks > 1) hipLaunchKernelGGL(viterbi_jump_kernel, dim3((unsigned)(p.n_blocks - 1), (unsigned)g->seqs), dim3(kJumpThreads), 0, s, b);
-        hipLaunchKernelGGL(viterbi_ends_kernel, dim3((unsigned)g->seqs), dim3(kEndsThreads), 0, s, b);
-        hipLaunchKernelGGL(viterbi_trace_kernel, dim3((unsigned)((p.n_blocks + kTraceThreads - 1) / kTraceThreads), (unsigned)g->seqs), dim3(kTraceThreads), 0, s, b);
-        err = hipGetLastError();
-    }
+    if (err == hipSuccess) err = viterbi_backtrace_enqueue(base, p, g->seqs, g->n_states, g->n_frames, g->states, multi ? g->states_pitch : 0, g->logp, s);
     return finish_launch(who, err);
 }

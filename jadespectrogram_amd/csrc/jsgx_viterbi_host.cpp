@@ -64,12 +64,8 @@ ViterbiPlan viterbi_plan(const jsgx_viterbi_args* g) {
     while (p.G < 64 && S * p.G * 2 <= JSGX_VITERBI_THREADS) p.G *= 2;
     const long long lanes = (S * p.G + 63) / 64 * 64;
     p.threads = (int)(lanes < JSGX_VITERBI_THREADS ? lanes : JSGX_VITERBI_THREADS);
-    p.n_blocks = (int)((T + JSGX_VITERBI_BLOCK - 1) / JSGX_VITERBI_BLOCK);
+    viterbi_layout(Q, S, T, &p);
     p.n_launches = p.n_blocks > 1 ? 4 : 3;
-    p.off_end = 4 * Q * S;
-    p.off_psi = p.off_end + 4 * Q * p.n_blocks;
-    p.off_jump = p.off_psi + 2 * Q * T * S;
-    p.scratch_bytes = (p.off_jump + 2 * Q * p.n_blocks * S + 3) / 4 * 4;
     return p;
 }
 

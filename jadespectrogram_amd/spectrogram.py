@@ -2060,6 +2060,201 @@ def viterbi(log_emit, log_trans, log_init=None, *, band_half=None):
 
 
 # --------------------------------------------------------------------------------------------------
+# pYIN pitch tracking (include/jsgx.h, section 5: libjsgx.so)
+# --------------------------------------------------------------------------------------------------
+def pyin_prior(n_thresholds: int = 100, beta_parameters=(2, 18)) -> np.ndarray:
+    """jsgx_pyin_prior_build: the prior over the n_thresholds thresholds (k + 1) / n_thresholds, float32 [n_thresholds]: the mass of the
+    Beta(a, b) distribution between k / N and (k + 1) / N.  Needs no device."""
+    out = np.empty((int(n_thresholds),) if 1 <= int(n_thresholds) <= capix.PYIN_MAX_THRESHOLDS else (1,), dtype=np.float32)
+    capix.check(capix.lib().jsgx_pyin_prior_build(int(n_thresholds), float(beta_parameters[0]), float(beta_parameters[1]), out.ctypes.data))
+    return out
+
+
+def pyin_tables(sr: float, fmin: float, n_bins: int, bins_per_semitone: int, band_half: int, window, tau_min: int, tau_max: int,
+                n_thresholds: int = 100, beta_parameters=(2, 18), boltzmann_parameter: float = 2.0, switch_prob: float = 0.01) -> dict:
+    """Every table of pyin_observe_launch and pyin_decode_launch as float32 numpy arrays, from the four host builders of include/jsgx.h
+    section 5a: prior [N], decay [n], norm [n + 1] with n = max(1, (tau_max - tau_min + 1) // 2) (the most troughs of a frame), edges
+    [n_bins + 1] (descending periods), freqs [n_bins], log_window [2 * band_half + 1], src_offset [n_bins], log_switch [4] and log_init
+    [2 * n_bins] (-inf on the voiced states, log(1 / n_bins) on the unvoiced ones).  window: 2 * band_half + 1 non-negative weights.
+    Needs no device."""
+    l = capix.lib()
+    P, W = int(n_bins), int(band_half)
+    w = np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
+    if w.size != 2 * W + 1:
+        raise JsgError(capix.JSGX_ERR_INVALID, "pyin_tables: the window has 2 * band_half + 1 entries")
+    n = max(1, (int(tau_max) - int(tau_min) + 1) // 2)
+    sized = lambda count, limit: np.empty((count if 1 <= count <= limit else 1,), dtype=np.float32)      # a refused size is refused by the builder
+    t = dict(prior=pyin_prior(n_thresholds, beta_parameters), decay=sized(n, capix.PYIN_MAX_LAG), norm=sized(n + 1, capix.PYIN_MAX_LAG + 1),
+             edges=sized(P + 1, capix.PYIN_MAX_BINS + 1), freqs=sized(P, capix.PYIN_MAX_BINS),
+             log_window=np.empty((w.size,), np.float32), src_offset=sized(P, capix.PYIN_MAX_BINS), log_switch=np.empty((4,), np.float32))
+    capix.check(l.jsgx_pyin_boltzmann_build(float(boltzmann_parameter), n, t["decay"].ctypes.data, t["norm"].ctypes.data))
+    capix.check(l.jsgx_pyin_bins_build(float(sr), float(fmin), int(bins_per_semitone), P, t["edges"].ctypes.data, t["freqs"].ctypes.data))
+    capix.check(l.jsgx_pyin_transition_build(P, W, w.ctypes.data, float(switch_prob), t["log_window"].ctypes.data, t["src_offset"].ctypes.data,
+                                             t["log_switch"].ctypes.data))
+    t["log_init"] = np.concatenate([np.full(P, -np.inf, np.float32), np.full(P, np.float32(np.log(1.0 / P)), np.float32)])
+    return t
+
+
+def _pyin_vector(t, count: int, what: str):
+    import torch
+    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.shape[0] >= count and t.is_contiguous(), f"{what}: float32 CUDA [>= {count}]"
+    return t.data_ptr()
+
+
+def _pyin_observe_args(d_cmnd, tau_min, tau_max, d_prior, d_decay, d_norm, d_edges, no_trough_prob, d_log_emit, d_obs, d_voiced_prob) -> capix.PyinObserveArgs:
+    import torch
+    c = _planes(d_cmnd, "d_cmnd")
+    R, T, lags = c.shape
+    assert lags >= int(tau_max) + 1, "d_cmnd: float32 CUDA [rows][frames][>= tau_max + 1]"
+    e = _planes(d_log_emit, "d_log_emit")
+    assert e.shape[0] == R and e.shape[1] == T and e.shape[2] % 2 == 0, "d_log_emit: float32 CUDA [rows][frames][2 * n_bins]"
+    P = e.shape[2] // 2
+    o = None if d_obs is None else _planes(d_obs, "d_obs")
+    assert o is None or tuple(o.shape) == (R, T, P), "d_obs: float32 CUDA [rows][frames][n_bins]"
+    v = None
+    if d_voiced_prob is not None:
+        v = d_voiced_prob[None] if d_voiced_prob.dim() == 1 else d_voiced_prob
+        assert v.is_cuda and v.dtype == torch.float32 and v.dim() == 2 and tuple(v.shape) == (R, T) and (v.stride(1) == 1 or T == 1), \
+            "d_voiced_prob: float32 CUDA [rows][frames]"
+    n = d_decay.shape[0]
+    ptr = lambda t: None if t is None else t.data_ptr()
+    return capix.PyinObserveArgs(c.data_ptr(), c.stride(1), c.stride(0), R, T, int(tau_min), int(tau_max), _pyin_vector(d_prior, 1, "d_prior"),
+                                 _pyin_vector(d_decay, 1, "d_decay"), _pyin_vector(d_norm, n + 1, "d_norm"), _pyin_vector(d_edges, P + 1, "d_edges"),
+                                 d_prior.shape[0], n, P, float(no_trough_prob), e.data_ptr(), e.stride(1), e.stride(0), ptr(o), 0 if o is None else o.stride(1),
+                                 0 if o is None else o.stride(0), ptr(v), 0 if v is None else v.stride(0))
+
+
+def pyin_observe_launch(d_cmnd, tau_min: int, tau_max: int, d_prior, d_decay, d_norm, d_edges, d_log_emit, *, no_trough_prob: float = 0.01, d_obs=None,
+                        d_voiced_prob=None, stream: int | None = None):
+    """jsgx_pyin_observe_launch: d_cmnd float32 [rows][frames][>= tau_max + 1] (the d' plane of yin_launch) and the tables of pyin_tables
+    (d_prior [N], d_decay [n], d_norm [n + 1], d_edges [n_bins + 1]) -> d_log_emit float32 [rows][frames][2 * n_bins] (state u * n_bins + p,
+    u = 0 voiced), and where given d_obs float32 [rows][frames][n_bins] (the voiced probabilities) and d_voiced_prob float32 [rows][frames].
+    Enqueue only: one kernel, no scratch."""
+    a = _pyin_observe_args(d_cmnd, tau_min, tau_max, d_prior, d_decay, d_norm, d_edges, no_trough_prob, d_log_emit, d_obs, d_voiced_prob)
+    capix.check(capix.lib().jsgx_pyin_observe_launch(C.byref(a), _stream_handle(stream, d_cmnd)))
+
+
+def pyin_observe_plan(tau_min: int, tau_max: int, n_bins: int, n_frames: int = 1, rows: int = 1, n_thresholds: int = 100):
+    """jsgx_pyin_observe_plan: (kernel name, lanes per workgroup, bytes of LDS per workgroup, frames per workgroup).  Needs no device."""
+    P, T, lags = int(n_bins), int(n_frames), int(tau_max) + 1
+    a = capix.PyinObserveArgs(cmnd=1 << 44, cmnd_frame_pitch=lags, cmnd_row_pitch=lags * T, rows=int(rows), n_frames=T, tau_min=int(tau_min), tau_max=int(tau_max),
+                              prior=2 << 44, decay=3 << 44, norm=4 << 44, edges=5 << 44, n_thresholds=int(n_thresholds),
+                              boltz_len=max(1, (int(tau_max) - int(tau_min) + 1) // 2), n_bins=P, no_trough_prob=0.01, log_emit=6 << 44, emit_frame_pitch=2 * P,
+                              emit_row_pitch=2 * P * T)      # never dereferenced
+    name, out = C.create_string_buffer(32), [C.c_int32() for _ in range(3)]
+    capix.check(capix.lib().jsgx_pyin_observe_plan(C.byref(a), name, 32, *[C.byref(o) for o in out]))
+    return (name.value.decode(),) + tuple(o.value for o in out)
+
+
+def _pyin_decode_args(d_log_emit, d_log_init, d_log_window, d_src_offset, d_log_switch, d_states, d_logp, d_value) -> capix.PyinDecodeArgs:
+    import torch
+    b = _planes(d_log_emit, "d_log_emit")
+    Q, T, S = b.shape
+    assert S % 2 == 0, "d_log_emit: float32 CUDA [seqs][frames][2 * n_bins]"
+    P = S // 2
+    assert d_log_window.dim() == 1 and d_log_window.shape[0] % 2 == 1, "d_log_window: float32 CUDA [2 * band_half + 1]"
+    W = d_log_window.shape[0] // 2
+    st = d_states[None] if d_states.dim() == 1 else d_states
+    assert st.is_cuda and st.dtype == torch.int32 and st.dim() == 2 and tuple(st.shape) == (Q, T) and (st.stride(1) == 1 or T == 1), "d_states: int32 CUDA [seqs][frames]"
+    assert d_logp is None or (d_logp.is_cuda and d_logp.dtype == torch.float32 and d_logp.dim() == 1 and d_logp.shape[0] >= Q and d_logp.is_contiguous()), \
+        "d_logp: float32 CUDA [seqs]"
+    v = None if d_value is None else _planes(d_value, "d_value")
+    assert v is None or tuple(v.shape) == (Q, T, S), "d_value: the shape of d_log_emit"
+    ptr = lambda t: None if t is None else t.data_ptr()
+    return capix.PyinDecodeArgs(b.data_ptr(), b.stride(1), b.stride(0), _pyin_vector(d_log_init, S, "d_log_init"), _pyin_vector(d_log_window, 2 * W + 1, "d_log_window"),
+                                _pyin_vector(d_src_offset, P, "d_src_offset"), _pyin_vector(d_log_switch, 4, "d_log_switch"), P, W, Q, T, st.data_ptr(), st.stride(0),
+                                ptr(d_logp), ptr(v), 0 if v is None else v.stride(1), 0 if v is None else v.stride(0))
+
+
+def pyin_decode_scratch_bytes(d_log_emit, d_log_init, d_log_window, d_src_offset, d_log_switch, d_states, *, d_logp=None, d_value=None) -> int:
+    """jsgx_pyin_decode_scratch_bytes: the bytes of scratch pyin_decode_launch needs for these arguments."""
+    a = _pyin_decode_args(d_log_emit, d_log_init, d_log_window, d_src_offset, d_log_switch, d_states, d_logp, d_value)
+    return int(capix.check(capix.lib().jsgx_pyin_decode_scratch_bytes(C.byref(a))))
+
+
+def pyin_decode_launch(d_log_emit, d_log_init, d_log_window, d_src_offset, d_log_switch, d_states, *, d_logp=None, d_value=None, d_scratch=None,
+                       stream: int | None = None):
+    """jsgx_pyin_decode_launch: d_log_emit float32 [frames][2P] or [seqs][frames][2P] (state u * P + p), d_log_init float32 [2P] and the
+    factored transition of pyin_tables (d_log_window [2W + 1], d_src_offset [P], d_log_switch [4]) -> d_states int32 [seqs][frames], and
+    where given d_logp float32 [seqs] and d_value float32, the shape of d_log_emit (V).  d_scratch: a contiguous CUDA tensor of at least
+    pyin_decode_scratch_bytes bytes (None: one is allocated with torch for this call).  Enqueue only: the forward kernel, then the blocked
+    backtrace of viterbi_launch."""
+    import torch
+    a = _pyin_decode_args(d_log_emit, d_log_init, d_log_window, d_src_offset, d_log_switch, d_states, d_logp, d_value)
+    d_scratch, stream = _scratch_and_stream(d_scratch, stream, d_log_emit, lambda: capix.check(capix.lib().jsgx_pyin_decode_scratch_bytes(C.byref(a))) // 4,
+                                            torch.int32, any_dtype=True)
+    capix.check(capix.lib().jsgx_pyin_decode_launch(C.byref(a), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), stream))
+
+
+def pyin_decode_plan(n_bins: int, band_half: int, n_frames: int, seqs: int = 1):
+    """jsgx_pyin_decode_plan: (name of the forward kernel, lanes that share a pitch bin, lanes per workgroup, bytes of LDS per workgroup,
+    kernel launches) for this shape.  Needs no device."""
+    P, T = int(n_bins), int(n_frames)
+    a = capix.PyinDecodeArgs(log_emit=1 << 44, emit_frame_pitch=2 * P, emit_seq_pitch=2 * P * T, log_init=2 << 44, log_window=3 << 44, src_offset=4 << 44,
+                             log_switch=5 << 44, n_bins=P, band_half=int(band_half), seqs=int(seqs), n_frames=T, states=6 << 44, states_pitch=T)      # never dereferenced
+    name, out = C.create_string_buffer(32), [C.c_int32() for _ in range(4)]
+    capix.check(capix.lib().jsgx_pyin_decode_plan(C.byref(a), name, 32, *[C.byref(o) for o in out]))
+    return (name.value.decode(),) + tuple(o.value for o in out)
+
+
+def pyin_geometry(sr: float, fmin: float, fmax: float, frame_length: int = 2048, hop_length: int | None = None, resolution: float = 0.1,
+                  max_transition_rate: float = 35.92):
+    """The model pyin decodes for these arguments, as librosa.pyin lays it out: (bins_per_semitone, n_bins, band_half, tau_min, tau_max).
+    bins_per_semitone = ceil(1 / resolution); n_bins = floor(12 bps log2(fmax / fmin)) + 1; the pitch transition is a triangle of
+    round(max_transition_rate * 12 * hop / sr) * bps + 1 points (the width librosa passes to transition_local), so its half-width is
+    band_half = (round(...) * bps) // 2: 50 at the defaults (hop 512 at 22 050 Hz, 0.1 semitone); tau_min = max(1, floor(sr / fmax)) and
+    tau_max = ceil(sr / fmin) are yin's.  Needs no device and refuses nothing: pyin refuses what the library does not serve."""
+    import math
+    hop = int(frame_length) // 4 if hop_length is None else int(hop_length)
+    bps = int(math.ceil(1.0 / float(resolution)))
+    P = int(math.floor(12 * bps * math.log2(float(fmax) / float(fmin)))) + 1
+    W = (int(round(float(max_transition_rate) * 12 * hop / float(sr))) * bps) // 2
+    return bps, P, W, max(1, int(math.floor(float(sr) / float(fmax)))), int(math.ceil(float(sr) / float(fmin)))
+
+
+def pyin(x, sr: float, fmin: float, fmax: float, frame_length: int = 2048, hop_length: int | None = None, n_thresholds: int = 100, beta_parameters=(2, 18),
+         boltzmann_parameter: float = 2, resolution: float = 0.1, max_transition_rate: float = 35.92, switch_prob: float = 0.01, no_trough_prob: float = 0.01,
+         fill_na=float("nan"), center: bool = True):
+    """Probabilistic YIN on the GPU (librosa.pyin): x [..., L] (numpy array or float32 CUDA tensor) -> (f0 float32 [..., frames], voiced_flag
+    bool [..., frames], voiced_prob float32 [..., frames]); numpy arrays for numpy input.  The framing is yin's; the d' plane of yin_launch
+    goes through pyin_observe_launch and pyin_decode_launch, and nothing returns to the host between the audio and the states.  The
+    geometry is librosa's (pyin_geometry): bins_per_semitone = ceil(1 / resolution), n_bins = floor(12 bps log2(fmax / fmin)) + 1, the pitch
+    transition is a triangle of round(max_transition_rate * 12 * hop / sr) * bps + 1 points without zero ends (half-width 50 at the
+    defaults), the initial distribution is unvoiced and uniform.  f0
+    of an unvoiced frame is fill_na (None: the frequency of the decoded bin).  The differences from librosa are listed in
+    include/jsgx.h section 5; agreement with it has not been measured."""
+    import math
+    import torch
+    frame_length = int(frame_length)
+    hop = frame_length // 4 if hop_length is None else int(hop_length)
+    bps, P, W, tau_min, tau_max = pyin_geometry(sr, fmin, fmax, frame_length, hop, resolution, max_transition_rate)
+    if P < 1 or P > capix.PYIN_MAX_BINS:
+        raise JsgError(capix.JSGX_ERR_INVALID, f"pyin: {P} pitch bins between fmin and fmax at this resolution; 1..{capix.PYIN_MAX_BINS} are served")
+    if W > capix.PYIN_MAX_BAND_HALF:
+        raise JsgError(capix.JSGX_ERR_INVALID, f"pyin: a pitch transition of half-width {W} bins; at most {capix.PYIN_MAX_BAND_HALF} are served")
+    if tau_max > capix.PYIN_MAX_LAG:
+        raise JsgError(capix.JSGX_ERR_INVALID, f"pyin: tau_max {tau_max} (= ceil(sr / fmin)); at most {capix.PYIN_MAX_LAG} is served")
+    window = np.concatenate([np.arange(1, W + 2), np.arange(W, 0, -1)]).astype(np.float64)        # a triangle of 2W + 1 points without zero ends
+    tables = pyin_tables(sr, fmin, P, bps, W, window, tau_min, tau_max, n_thresholds, beta_parameters, boltzmann_parameter, switch_prob)
+    plane, _, batch, was_numpy = _yin_rows(x, sr, fmin, fmax, frame_length, hop, 0.1, center, True)
+    R, T = plane.shape[0], plane.shape[1]
+    dev = plane.device
+    with torch.cuda.device(_device_index(plane)):
+        d = {k: torch.from_numpy(v).to(dev) for k, v in tables.items()}
+        emit = torch.empty((R, T, 2 * P), dtype=torch.float32, device=dev)
+        voiced_prob = torch.empty((R, T), dtype=torch.float32, device=dev)
+        states = torch.empty((R, T), dtype=torch.int32, device=dev)
+        pyin_observe_launch(plane, tau_min, tau_max, d["prior"], d["decay"], d["norm"], d["edges"], emit, no_trough_prob=no_trough_prob, d_voiced_prob=voiced_prob)
+        pyin_decode_launch(emit, d["log_init"], d["log_window"], d["src_offset"], d["log_switch"], states)
+        voiced_flag = states < P
+        f0 = d["freqs"][(states % P).long()]
+        if fill_na is not None:
+            f0 = torch.where(voiced_flag, f0, torch.full_like(f0, float(fill_na)))
+    f0, voiced_flag, voiced_prob = (v.reshape(*batch, -1) for v in (f0, voiced_flag, voiced_prob))
+    return (f0.cpu().numpy(), voiced_flag.cpu().numpy(), voiced_prob.cpu().numpy()) if was_numpy else (f0, voiced_flag, voiced_prob)
+
+
+# --------------------------------------------------------------------------------------------------
 # cepstral coefficients and delta features (include/jsg.h, section 2k)
 # --------------------------------------------------------------------------------------------------
 _NORMS = {"ortho": capi.DCT_NORM_ORTHO, None: capi.DCT_NORM_NONE, "none": capi.DCT_NORM_NONE}
