@@ -690,6 +690,205 @@ JSGX_API int jsgx_pyin_decode_launch(const jsgx_pyin_decode_args* args, void* sc
 JSGX_API int jsgx_pyin_decode_plan(const jsgx_pyin_decode_args* args, char* name, int name_len, int32_t* lanes_per_bin, int32_t* threads, int32_t* lds_bytes,
                                    int32_t* n_launches);
 
+/* Sections 6 to 8 were added to version 1 in the same way: sections 1 to 5, their structs and their constants are as they were. */
+
+/* ------------------------------------------------------------------------------------------------
+ * 6. The k nearest frames (the selection behind librosa.segment.recurrence_matrix and cross_similarity): for every frame i of x the k
+ *    frames j of y with the lowest cost, without the N x M plane ever reaching memory.  x, y, their pitches, pairs, n_features, n, m and
+ *    metric are those of jsgx_cdist_args with the same limits; a pair pitch of 0 is a shared sequence; c(i, j) is the cost of section 2
+ *    bit for bit: the same k-ascending fmaf chain per output.
+ *
+ *    Definition.  The candidates of row i are the j in 0..M-1 with |i - j| >= width and c(i, j) not a NaN (width 0 excludes nothing,
+ *    width 1 only the main diagonal, as in librosa).  They are ordered by the key (c, j): the float comparison on c, so -0 == +0, then
+ *    the lower j: a total order, the j being distinct.  With cnt = min(k, the number of candidates):
+ *        nn_index[p*index_pair_pitch + i*index_pitch + r], nn_dist[p*dist_pair_pitch + i*dist_pitch + r], r < cnt:  j and c(i, j) of the
+ *        cnt smallest candidates in that order;   r = cnt..k-1:  index -1 and distance +inf.
+ *    A +inf cost is a candidate like any other.  Nothing behind entry k-1 of a row is written.  The result is a set of exact
+ *    comparisons on section 2's costs: it does not depend on pairs, on the pitches, on split or on how the kernel finds it.
+ *
+ *    Against librosa.  librosa takes the k + 2 width nearest of every frame from sklearn's NearestNeighbors, drops the band |i - j| <
+ *    width from them and keeps the nearest k of the rest.  A band holds at most 2 width - 1 frames, so the k nearest outside the band
+ *    are among the k + 2 width nearest of all: the two selections are the same set in the same order wherever the costs are distinct.
+ *    The differences: ties go to the lower j here (sklearn: whatever its partial sort leaves); a NaN cost is no candidate here (sklearn
+ *    refuses NaN input); a zero vector under the cosine metric costs 1 as in section 2 (scipy: NaN); the costs are section 2's float32
+ *    chain (sklearn: float64, euclidean by the expanded form); k is at most JSGX_KNN_MAX_K: a larger k is out of scope.  Agreement with
+ *    librosa has not been measured: librosa is not installed where this was built.
+ *
+ *    The kernel ("knn_64"): a workgroup of JSGX_KNN_THREADS lanes owns a strip of JSGX_KNN_STRIP rows of one pair and sweeps its column
+ *    tiles of JSGX_KNN_TILE columns in ascending order with the inner loop of "cdist_64x64": the same staging, the same order.  Each
+ *    tile of costs is dropped into the LDS the panels have left (64 rows of 68 words).  Every row keeps its running sorted list in LDS:
+ *    k float costs and k 16-bit indices (M <= 65536), 6 k bytes a row.  A wavefront serves 16 rows of the strip; its lane l holds
+ *    candidate j0 + l of the row.  A candidate survives if the list is not full or c is below the k-th cost, as the row's last merge
+ *    left it and as the row keeps it in a word of its own (an equal cost loses: every j of the list is lower).  A tile whose 64 candidates of a row all fail costs one ballot and nothing else.  Survivors are appended
+ *    (a prefix count over the ballot) to the row's 64 pending places in LDS and merged only when the next tile's survivors no longer fit,
+ *    and at the end of the sweep: a merge serves up to 64 survivors instead of a tile's few, and a survivor that a later, lower k-th cost
+ *    has overtaken falls away in the merge.  The merge is by rank: a candidate's rank among the candidates is counted with lane reads (equal
+ *    costs: the earlier, which has the lower j) and their costs are laid down sorted; a candidate's place is its rank + the list entries
+ *    with cost <= its own (bisection of the list), a list entry's place is its index + the candidates with cost < its own (bisection of
+ *    the candidates); places >= k fall away.  The places are a permutation, so every lane reads first and writes afterwards, with no second
+ *    copy of the list.
+ *    LDS: JSGX_KNN_LDS_STATIC + 6 * JSGX_KNN_STRIP * k bytes (the second part dynamic), 142080 at k = 256, inside 160 KiB.
+ *    Column splits.  T = ceil(M / 64) column tiles are divided among S = min(split, T) workgroups per strip, workgroup s taking the tiles
+ *    floor(s T / S) .. floor((s + 1) T / S) - 1.  S = 1 writes the outputs; S > 1 writes partial lists (cost and int32 index, 8 k S bytes
+ *    a row) to the scratch and "knn_merge" (one wavefront per row, the same merge by rank over the S lists in ascending s) writes the
+ *    outputs.  Selecting the k smallest of a total order is associative: the outputs are the same bits for every split.  split = 0 is
+ *    automatic: the smallest S in {1, 2, 4, 8, 16} with pairs * ceil(N / 64) * S >= the compute units of the device; where there is none,
+ *    or a workgroup would be left without a tile, the largest S of the set that is <= T.
+ *    The accumulation order is stated, so this runs on the vector pipe, not on MFMA.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSGX_KNN_MAX_K 256
+#define JSGX_KNN_MAX_SPLIT 16
+#define JSGX_KNN_STRIP 64
+#define JSGX_KNN_TILE 64
+#define JSGX_KNN_THREADS 256
+#define JSGX_KNN_LDS_STATIC 43776          /* the panels and then the tile 17408, 64 pending survivors a row 24576, the sorted costs of four merges 1024, lengths and k-th costs 768 */
+#define JSGX_KNN_LDS_LIMIT 163840
+#define JSGX_KNN_MERGE_THREADS 256         /* "knn_merge": four rows a workgroup */
+
+typedef struct jsgx_knn_args {
+    const float* x;             /* device floats, as jsgx_cdist_args */
+    int64_t x_frame_pitch;      /* >= n_features */
+    int64_t x_pair_pitch;       /* 0 (shared), or >= (n - 1) * x_frame_pitch + n_features */
+    const float* y;             /* device floats */
+    int64_t y_frame_pitch;      /* >= n_features */
+    int64_t y_pair_pitch;       /* 0 (shared), or >= (m - 1) * y_frame_pitch + n_features */
+    int32_t pairs;              /* 1..65535 */
+    int32_t n_features;         /* K, 1..JSGX_CDIST_MAX_FEATURES */
+    int32_t n;                  /* N, 1..JSGX_DTW_MAX_LEN */
+    int32_t m;                  /* M, 1..JSGX_DTW_MAX_LEN */
+    int32_t metric;             /* JSGX_METRIC_* */
+    int32_t k;                  /* 1..JSGX_KNN_MAX_K */
+    int32_t width;              /* >= 0 */
+    int32_t split;              /* 0 (automatic), or 1..JSGX_KNN_MAX_SPLIT */
+    int32_t* nn_index;          /* device int32: [p][i][r] */
+    int64_t index_pitch;        /* >= k */
+    int64_t index_pair_pitch;   /* pairs > 1: >= (n - 1) * index_pitch + k */
+    float* nn_dist;             /* device floats: [p][i][r] */
+    int64_t dist_pitch;         /* >= k */
+    int64_t dist_pair_pitch;    /* pairs > 1: >= (n - 1) * dist_pitch + k */
+} jsgx_knn_args;                /* 128 bytes, no padding */
+
+/* The bytes of scratch the launch needs: 8 * pairs * n * k * S for the partial lists where S > 1, else 0; S = min(split, ceil(m / 64)),
+ * and for split = 0 the largest S the automatic rule can give (the largest of 1, 2, 4, 8, 16 that is <= ceil(m / 64)), since the device is not asked here.  Refused (a
+ * negative jsgx_status): what the launch refuses before it looks at the scratch. */
+JSGX_API int64_t jsgx_knn_scratch_bytes(const jsgx_knn_args* args);
+/* Enqueue only ("knn_64", then "knn_merge" where S > 1): no allocation, no synchronisation; capture works, a first launch included.
+ * The scratch is used only while the kernels run.  Refused (JSGX_ERR_INVALID, nothing enqueued), in this order and before any device
+ * call: null args, a null x, a null y, a null nn_index, a null nn_dist; a pointer that is not 4-byte aligned; pairs outside 1..65535,
+ * n_features outside 1..1024, n outside 1..65536, m outside 1..65536, a metric outside 0..2, k outside 1..256, a negative width, split
+ * outside 0..16; x_frame_pitch below n_features, y_frame_pitch below n_features, a non-zero x_pair_pitch that does not cover a sequence,
+ * the same for y_pair_pitch, index_pitch below k, index_pair_pitch that does not cover a plane (pairs > 1), dist_pitch below k,
+ * dist_pair_pitch that does not cover a plane (pairs > 1); an output (nn_index, nn_dist) overlapping x, one overlapping y, nn_index
+ * overlapping nn_dist; a null scratch, a scratch that is not 4-byte aligned, scratch_bytes below jsgx_knn_scratch_bytes (each only
+ * where that size is not 0).  Then JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_knn_launch(const jsgx_knn_args* args, void* scratch, int64_t scratch_bytes, void* stream);
+/* What the launch enqueues on a device of n_cu compute units, without a device: the name of the forward kernel ("knn_64"), the rows of a
+ * strip, S (as the launch resolves it: split = 0 by the automatic rule for n_cu), JSGX_KNN_THREADS and the bytes of LDS of a workgroup
+ * (JSGX_KNN_LDS_STATIC + 384 k <= JSGX_KNN_LDS_LIMIT).  Any output pointer may be NULL (name: else name_len >= 16).  Refused: a name_len
+ * below 16 with a name, then what the scratch size refuses, then an n_cu below 1. */
+JSGX_API int jsgx_knn_plan(const jsgx_knn_args* args, int32_t n_cu, char* name, int name_len, int32_t* strip_rows, int32_t* split, int32_t* threads,
+                           int32_t* lds_bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * 7. The dense recurrence plane from the lists of section 6 (librosa.segment.recurrence_matrix and cross_similarity, their modes):
+ *    out[p*out_pair_pitch + i*out_pitch + j], i < N, j < M, float32.  list(i) = the entries r < k of row i of nn_index that lie in 0..M-1.
+ *        link(i, j) holds where j is in list(i); with sym = 1 (refused unless n == m) i must also be in list(j): mutual neighbours,
+ *        librosa's minimum(rec, rec.T).
+ *        The value of a link, d = nn_dist of row i at the entry that holds j:
+ *            JSGX_REC_CONNECTIVITY:  1.0f                                (nn_dist is not read and may be NULL)
+ *            JSGX_REC_DISTANCE:      d
+ *            JSGX_REC_AFFINITY:      jsgx_exp(-fl(d / bw)), bw = bandwidth[p] read on the device (nothing returns to the host): section 1's
+ *                                    routine, restated on the device operation by operation; NaN where !(bw > 0) or d is a NaN.
+ *                                    (A cosine cost a rounding below zero gives an argument a rounding above zero: the same operations.)
+ *        Every other element is +0.  With diag = 1, out[i][i] (i < min(N, M)) is 1.0f in connectivity and affinity mode and 0.0f in
+ *        distance mode, link or not.  Every element of the plane is written; nothing outside it is written.
+ *    A list of section 6 holds every j at most once.  A list from elsewhere that holds a j twice gives one of the two values.
+ *    Symmetry.  For x == y the costs of sections 2 and 6 are bitwise symmetric: for (sq)euclidean fl(a - b) = -fl(b - a) and the chain of
+ *    squares is the same; for cosine the products commute.  So sym = 1 loses nothing by keeping row i's distance, and out is symmetric.
+ *    Orientation.  Query-major: row i holds the neighbours of frame i.  librosa documents the transpose (rec[i, j] non-zero where i is a
+ *    neighbour of j); with sym the two are the same.  Sparse outputs are out of scope: the lists are the sparse form.
+ *    The kernel ("recurrence_rows"): a workgroup of JSGX_REC_THREADS lanes per row; the row is built in LDS in pieces of JSGX_REC_CHUNK
+ *    columns (zeros, then the links of the piece, then the diagonal) and goes out as whole lines: every element is stored once.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSGX_REC_CONNECTIVITY 0
+#define JSGX_REC_DISTANCE 1
+#define JSGX_REC_AFFINITY 2
+#define JSGX_REC_THREADS 256
+#define JSGX_REC_CHUNK 4096
+#define JSGX_REC_LDS_BYTES 18432           /* static: the piece 16384, the row's list 256 x (index, value) */
+
+typedef struct jsgx_recurrence_args {
+    const int32_t* nn_index;    /* device int32: [p][i][r] */
+    int64_t index_pitch;        /* >= k */
+    int64_t index_pair_pitch;   /* pairs > 1: >= (n - 1) * index_pitch + k */
+    const float* nn_dist;       /* device floats [p][i][r]; NULL allowed in connectivity mode */
+    int64_t dist_pitch;         /* nn_dist given: >= k */
+    int64_t dist_pair_pitch;    /* nn_dist given and pairs > 1: >= (n - 1) * dist_pitch + k */
+    const float* bandwidth;     /* device floats [pairs]; affinity mode only, else not read and may be NULL */
+    int32_t pairs;              /* 1..65535 */
+    int32_t n;                  /* N, 1..JSGX_DTW_MAX_LEN */
+    int32_t m;                  /* M, 1..JSGX_DTW_MAX_LEN */
+    int32_t k;                  /* 1..JSGX_KNN_MAX_K */
+    int32_t mode;               /* JSGX_REC_* */
+    int32_t sym;                /* 0 or 1; 1 needs n == m */
+    int32_t diag;               /* 0 or 1 */
+    int32_t reserved0;          /* 0 */
+    float* out;                 /* device floats: [p][i][j] */
+    int64_t out_pitch;          /* >= m */
+    int64_t out_pair_pitch;     /* pairs > 1: >= (n - 1) * out_pitch + m */
+} jsgx_recurrence_args;         /* 112 bytes, no padding */
+
+/* Enqueue only (one kernel, no scratch); capture works, a first launch included.  Refused (JSGX_ERR_INVALID, nothing enqueued), in this
+ * order and before any device call: null args, a null nn_index, a null out; a pointer that is not 4-byte aligned; pairs outside
+ * 1..65535, n outside 1..65536, m outside 1..65536, k outside 1..256, a mode outside 0..2, sym other than 0 or 1, diag other than 0 or
+ * 1; a non-zero reserved0; sym with n != m; a null nn_dist in distance or affinity mode, a null bandwidth in affinity mode;
+ * index_pitch below k, index_pair_pitch that does not cover a plane (pairs > 1), the same for dist_pitch and dist_pair_pitch (nn_dist
+ * given), out_pitch below m, out_pair_pitch that does not cover a plane (pairs > 1); out overlapping nn_index, out overlapping nn_dist,
+ * out overlapping bandwidth.  Then JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_recurrence_launch(const jsgx_recurrence_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 8. Neighbour aggregation of a plane (librosa.decompose.nn_filter with the mean or a weighted mean; square only: the neighbours of
+ *    frame i are frames of the same plane).  S[j][f] = s[p*s_pair_pitch + j*s_frame_pitch + f], j < N, f < F, frame-major.  For row i
+ *    let r ascend over the entries r < k of nn_index whose index is in 0..N-1, cnt their number:
+ *        mean (weights NULL):  acc = fl(acc + S[idx][f]) from +0;   out[i][f] = fl(acc / (float)cnt)
+ *        weighted:  w = weights[p*weights_pair_pitch + i*weights_pitch + r];   num = fmaf(w, S[idx][f], num);  den = fl(den + w), both
+ *                   from +0;   out[i][f] = fl(num / den)
+ *        a row with cnt == 0, or a weighted row with den == 0, takes S[i][f]: librosa's rule for a frame without neighbours.
+ *    out[p*out_pair_pitch + i*out_frame_pitch + f]; nothing else is written.  The median aggregate (librosa's default) is out of scope.
+ *    The kernel ("nn_filter_rows"): one wavefront per row; lane l takes the features l, l + 64, ...; the index and the weight of an
+ *    entry are one broadcast read each, the reads of S run along f.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSGX_NNF_MAX_FEATURES 65536
+#define JSGX_NNF_THREADS 64
+
+typedef struct jsgx_nn_filter_args {
+    const float* s;             /* device floats: S[p][j][f] */
+    int64_t s_frame_pitch;      /* >= n_features */
+    int64_t s_pair_pitch;       /* pairs > 1: >= (n - 1) * s_frame_pitch + n_features */
+    const int32_t* nn_index;    /* device int32: [p][i][r] */
+    int64_t index_pitch;        /* >= k */
+    int64_t index_pair_pitch;   /* pairs > 1: >= (n - 1) * index_pitch + k */
+    const float* weights;       /* device floats [p][i][r], or NULL: the mean */
+    int64_t weights_pitch;      /* weights given: >= k */
+    int64_t weights_pair_pitch; /* weights given and pairs > 1: >= (n - 1) * weights_pitch + k */
+    int32_t pairs;              /* 1..65535 */
+    int32_t n;                  /* N, 1..JSGX_DTW_MAX_LEN */
+    int32_t n_features;         /* F, 1..JSGX_NNF_MAX_FEATURES */
+    int32_t k;                  /* 1..JSGX_KNN_MAX_K */
+    float* out;                 /* device floats: out[p][i][f] */
+    int64_t out_frame_pitch;    /* >= n_features */
+    int64_t out_pair_pitch;     /* pairs > 1: >= (n - 1) * out_frame_pitch + n_features */
+} jsgx_nn_filter_args;          /* 112 bytes, no padding */
+
+/* Enqueue only (one kernel, no scratch); capture works, a first launch included.  Refused (JSGX_ERR_INVALID, nothing enqueued), in this
+ * order and before any device call: null args, a null s, a null nn_index, a null out; a pointer that is not 4-byte aligned; pairs
+ * outside 1..65535, n outside 1..65536, n_features outside 1..65536, k outside 1..256; s_frame_pitch below n_features, s_pair_pitch that
+ * does not cover a plane (pairs > 1), index_pitch below k, index_pair_pitch that does not cover a plane (pairs > 1), the same for
+ * weights_pitch and weights_pair_pitch (weights given), out_frame_pitch below n_features, out_pair_pitch that does not cover a plane
+ * (pairs > 1); out overlapping s, out overlapping nn_index, out overlapping weights.  Then JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_nn_filter_launch(const jsgx_nn_filter_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

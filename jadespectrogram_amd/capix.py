@@ -82,6 +82,32 @@ class PyinDecodeArgs(C.Structure):
                 ("value_seq_pitch", C.c_int64)]
 
 
+KNN_MAX_K, KNN_MAX_SPLIT, KNN_STRIP, KNN_TILE, KNN_THREADS, KNN_LDS_STATIC, KNN_LDS_LIMIT, KNN_MERGE_THREADS = 256, 16, 64, 64, 256, 43776, 163840, 256
+REC_CONNECTIVITY, REC_DISTANCE, REC_AFFINITY = 0, 1, 2
+REC_THREADS, REC_CHUNK, REC_LDS_BYTES = 256, 4096, 18432
+NNF_MAX_FEATURES, NNF_THREADS = 65536, 64
+
+
+class KnnArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_frame_pitch", C.c_int64), ("x_pair_pitch", C.c_int64), ("y", C.c_void_p), ("y_frame_pitch", C.c_int64),
+                ("y_pair_pitch", C.c_int64), ("pairs", C.c_int32), ("n_features", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("metric", C.c_int32),
+                ("k", C.c_int32), ("width", C.c_int32), ("split", C.c_int32), ("nn_index", C.c_void_p), ("index_pitch", C.c_int64),
+                ("index_pair_pitch", C.c_int64), ("nn_dist", C.c_void_p), ("dist_pitch", C.c_int64), ("dist_pair_pitch", C.c_int64)]
+
+
+class RecurrenceArgs(C.Structure):
+    _fields_ = [("nn_index", C.c_void_p), ("index_pitch", C.c_int64), ("index_pair_pitch", C.c_int64), ("nn_dist", C.c_void_p), ("dist_pitch", C.c_int64),
+                ("dist_pair_pitch", C.c_int64), ("bandwidth", C.c_void_p), ("pairs", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("k", C.c_int32),
+                ("mode", C.c_int32), ("sym", C.c_int32), ("diag", C.c_int32), ("reserved0", C.c_int32), ("out", C.c_void_p), ("out_pitch", C.c_int64),
+                ("out_pair_pitch", C.c_int64)]
+
+
+class NnFilterArgs(C.Structure):
+    _fields_ = [("s", C.c_void_p), ("s_frame_pitch", C.c_int64), ("s_pair_pitch", C.c_int64), ("nn_index", C.c_void_p), ("index_pitch", C.c_int64),
+                ("index_pair_pitch", C.c_int64), ("weights", C.c_void_p), ("weights_pitch", C.c_int64), ("weights_pair_pitch", C.c_int64), ("pairs", C.c_int32),
+                ("n", C.c_int32), ("n_features", C.c_int32), ("k", C.c_int32), ("out", C.c_void_p), ("out_frame_pitch", C.c_int64), ("out_pair_pitch", C.c_int64)]
+
+
 # every symbol include/jsgx.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -109,6 +135,11 @@ SIGNATURES = {
     "jsgx_pyin_decode_scratch_bytes": (C.c_int64, [C.POINTER(PyinDecodeArgs)]),
     "jsgx_pyin_decode_launch": (C.c_int, [C.POINTER(PyinDecodeArgs), _P, C.c_int64, _P]),
     "jsgx_pyin_decode_plan": (C.c_int, [C.POINTER(PyinDecodeArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 4),
+    "jsgx_knn_scratch_bytes": (C.c_int64, [C.POINTER(KnnArgs)]),
+    "jsgx_knn_launch": (C.c_int, [C.POINTER(KnnArgs), _P, C.c_int64, _P]),
+    "jsgx_knn_plan": (C.c_int, [C.POINTER(KnnArgs), C.c_int32, C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 4),
+    "jsgx_recurrence_launch": (C.c_int, [C.POINTER(RecurrenceArgs), _P]),
+    "jsgx_nn_filter_launch": (C.c_int, [C.POINTER(NnFilterArgs), _P]),
 }
 
 _lib = None

@@ -69,6 +69,18 @@ struct PyinDecodePlan {
 };
 PyinDecodePlan pyin_decode_plan(const jsgx_pyin_decode_args* g);
 
+// sections 6 to 8 (jsgx_knn_host.cpp): every refusal that does not look at the scratch, in the header's order
+int knn_check(const jsgx_knn_args* g, const char* who);
+int recurrence_check(const jsgx_recurrence_args* g, const char* who);
+int nn_filter_check(const jsgx_nn_filter_args* g, const char* who);
+// How section 6 serves a shape on a device of n_cu compute units: the column tiles, the workgroups S that share a strip (split = 0: the
+// automatic rule; n_cu = 0: its largest answer, which is what the scratch is sized for), the dynamic LDS and the bytes of the partial lists.
+struct KnnPlan {
+    int tiles, S, lds_dynamic;
+    long long scratch_bytes;
+};
+KnnPlan knn_plan(const jsgx_knn_args* g, int n_cu);
+
 // The three refusals of a launch's scratch buffer, in this order; `sizer` names the call that states `need`.
 inline int check_scratch(const char* who, const void* scratch, int64_t scratch_bytes, int64_t need, const char* sizer) {
     if (!scratch) return fail(JSGX_ERR_INVALID, who, "null scratch");

@@ -2255,6 +2255,203 @@ def pyin(x, sr: float, fmin: float, fmax: float, frame_length: int = 2048, hop_l
 
 
 # --------------------------------------------------------------------------------------------------
+# k nearest frames, recurrence planes and neighbour aggregation (include/jsgx.h, sections 6 to 8: libjsgx.so)
+# --------------------------------------------------------------------------------------------------
+_REC_MODES = {"connectivity": capix.REC_CONNECTIVITY, "distance": capix.REC_DISTANCE, "affinity": capix.REC_AFFINITY}
+
+
+def _pair_pitch(t) -> int:
+    return 0 if t.shape[0] == 1 else t.stride(0)      # one plane for every pair: a pair pitch of 0
+
+
+def _knn_args(d_x, d_y, d_index, d_dist, width, metric, split) -> capix.KnnArgs:
+    import torch
+    ix, ds = _planes(d_index, "d_index", torch.int32), _planes(d_dist, "d_dist")
+    P, N, k = ix.shape
+    x, y = _planes(d_x, "d_x"), _planes(d_y, "d_y")
+    K, M = x.shape[2], y.shape[1]
+    assert tuple(ds.shape) == (P, N, k) and x.shape[1] == N and y.shape[2] == K and x.shape[0] in (1, P) and y.shape[0] in (1, P), \
+        "d_x [pairs or 1][n][features], d_y [pairs or 1][m][features], d_index int32 and d_dist float32 [pairs][n][k]"
+    return capix.KnnArgs(x.data_ptr(), x.stride(1), _pair_pitch(x), y.data_ptr(), y.stride(1), _pair_pitch(y), P, K, N, M, _named(_METRICS, metric, "metric"),
+                         k, int(width), int(split), ix.data_ptr(), ix.stride(1), ix.stride(0), ds.data_ptr(), ds.stride(1), ds.stride(0))
+
+
+def knn_scratch_bytes(d_x, d_y, d_index, d_dist, *, width: int = 0, metric: str = "euclidean", split: int = 0) -> int:
+    """jsgx_knn_scratch_bytes: the bytes of scratch knn_launch needs for these arguments (0 where one workgroup sweeps all columns of a strip)."""
+    a = _knn_args(d_x, d_y, d_index, d_dist, width, metric, split)
+    return int(capix.check(capix.lib().jsgx_knn_scratch_bytes(C.byref(a))))
+
+
+def knn_launch(d_x, d_y, d_index, d_dist, *, width: int = 0, metric: str = "euclidean", split: int = 0, d_scratch=None, stream: int | None = None):
+    """jsgx_knn_launch: d_x float32 [n][features] or [pairs][n][features], d_y likewise with m frames (a 2-D tensor or a leading 1 is one
+    sequence shared by every pair) -> d_index int32 and d_dist float32 [n][k] or [pairs][n][k]: for every frame of x the k frames j of y
+    with |i - j| >= width and the lowest cost, ascending by (cost, j); -1 and +inf behind the last candidate.  k is the last axis of the
+    outputs, 1..256.  split: 0 (automatic) or the workgroups 1..16 that share the columns of a strip; the result does not depend on it.
+    Enqueue only."""
+    import torch
+    a = _knn_args(d_x, d_y, d_index, d_dist, width, metric, split)
+    d_scratch, stream = _scratch_and_stream(d_scratch, stream, d_index, lambda: max(1, capix.check(capix.lib().jsgx_knn_scratch_bytes(C.byref(a))) // 4), torch.int32,
+                                            any_dtype=True)
+    capix.check(capix.lib().jsgx_knn_launch(C.byref(a), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), stream))
+
+
+def knn_plan(n: int, m: int, n_features: int, k: int, pairs: int = 1, metric: str = "euclidean", split: int = 0, n_cu: int = 256):
+    """jsgx_knn_plan: (kernel name, rows of a strip, workgroups per strip S, lanes per workgroup, bytes of LDS per workgroup) for this
+    shape on a device of n_cu compute units.  Needs no device."""
+    a = capix.KnnArgs(1 << 44, int(n_features), int(n) * int(n_features), 2 << 44, int(n_features), int(m) * int(n_features), int(pairs), int(n_features),
+                      int(n), int(m), _named(_METRICS, metric, "metric"), int(k), 0, int(split), 3 << 44, int(k), int(n) * int(k), 4 << 44, int(k),
+                      int(n) * int(k))      # never dereferenced
+    name, out = C.create_string_buffer(32), [C.c_int32() for _ in range(4)]
+    capix.check(capix.lib().jsgx_knn_plan(C.byref(a), int(n_cu), name, 32, *[C.byref(o) for o in out]))
+    return (name.value.decode(),) + tuple(o.value for o in out)
+
+
+def knn_default_k(n: int, width: int = 0) -> int:
+    """librosa's default number of neighbours, 2 * ceil(sqrt(n - 2 * width + 1)), clamped to 1..256 (the clamp is a difference: librosa
+    has no upper limit, and none below either where the root is of a number below 1)."""
+    import math
+    t = int(n) - 2 * int(width) + 1
+    root = 0 if t <= 0 else math.isqrt(t - 1) + 1      # ceil(sqrt(t)), exactly
+    return max(1, min(capix.KNN_MAX_K, 2 * root))
+
+
+def knn(x, y=None, k=None, *, width: int = 0, metric: str = "euclidean", split: int = 0):
+    """The k nearest frames: x [N, K] and y [M, K] (numpy arrays or float32 CUDA tensors, frame-major; a leading axis of P pairs on either
+    or both; y None: x itself) -> (index int32, dist float32) as CUDA tensors [N, k] or [P, N, k].  Row i holds the k frames j of y with
+    |i - j| >= width and the lowest cost under `metric`, ascending by (cost, j), and their costs; -1 and +inf behind the last candidate.
+    k None: knn_default_k(M, width).  Every operation is as include/jsgx.h section 6 states it."""
+    import torch
+    x, _ = _to_cuda(x)
+    y = x if y is None else _to_cuda(y)[0]
+    assert x.dim() in (2, 3) and y.dim() in (2, 3), "knn: x [N, K] or [P, N, K], y [M, K] or [P, M, K]"
+    x, y = x.contiguous(), y.contiguous()
+    batched = x.dim() == 3 or y.dim() == 3
+    P = max(x.shape[0] if x.dim() == 3 else 1, y.shape[0] if y.dim() == 3 else 1)
+    k = knn_default_k(y.shape[-2], width) if k is None else int(k)
+    shape = ((P,) if batched else ()) + (x.shape[-2], max(k, 1))
+    index = torch.empty(shape, dtype=torch.int32, device=x.device)
+    dist = torch.empty(shape, dtype=torch.float32, device=x.device)
+    if k < 1:
+        raise JsgError(capix.JSGX_ERR_INVALID, "knn: k must be in 1..256")
+    with torch.cuda.device(_device_index(x)):
+        knn_launch(x, y, index, dist, width=width, metric=metric, split=split)
+    return index, dist
+
+
+def recurrence_launch(d_index, d_dist, d_out, *, mode: str = "connectivity", sym: bool = False, diag: bool = False, d_bandwidth=None, stream: int | None = None):
+    """jsgx_recurrence_launch: the lists d_index int32 and d_dist float32 [n][k] or [pairs][n][k] (d_dist may be None in connectivity mode)
+    -> d_out float32 [n][m] or [pairs][n][m], every element written: the value of a link where j is in the list of i (with sym: and i in
+    the list of j; n == m), +0 elsewhere.  mode "connectivity": 1; "distance": the list's distance; "affinity": exp(-d / bw) with
+    bw = d_bandwidth float32 [pairs] read on the device (NaN where bw is not > 0).  diag: the main diagonal is 1 (distance mode: 0).
+    Query-major: row i holds the neighbours of frame i (librosa documents the transpose).  Enqueue only."""
+    import torch
+    ix, o = _planes(d_index, "d_index", torch.int32), _planes(d_out, "d_out")
+    P, N, k = ix.shape
+    M = o.shape[2]
+    assert o.shape[0] == P and o.shape[1] == N, "d_out [pairs][n][m]"
+    ds = None if d_dist is None else _planes(d_dist, "d_dist")
+    assert ds is None or tuple(ds.shape) == (P, N, k), "d_dist: the shape of d_index"
+    bw = d_bandwidth
+    assert bw is None or (bw.is_cuda and bw.dtype == torch.float32 and bw.dim() == 1 and bw.shape[0] >= P and bw.is_contiguous()), "d_bandwidth: float32 CUDA [pairs]"
+    a = capix.RecurrenceArgs(ix.data_ptr(), ix.stride(1), ix.stride(0), None if ds is None else ds.data_ptr(), 0 if ds is None else ds.stride(1),
+                             0 if ds is None else ds.stride(0), None if bw is None else bw.data_ptr(), P, N, M, k, _named(_REC_MODES, mode, "mode"), int(bool(sym)),
+                             int(bool(diag)), 0, o.data_ptr(), o.stride(1), o.stride(0))
+    capix.check(capix.lib().jsgx_recurrence_launch(C.byref(a), _stream_handle(stream, d_out)))
+
+
+def _median_k_bandwidth(dist):
+    """librosa's med_k_scalar bandwidth per pair, on the device and without a host synchronisation: of the finite dist[p][i][k-1] (a row
+    with fewer than k candidates has +inf there and does not count), sorted ascending as v[0..c-1], bw = 0.5f * (v[(c-1)//2] + v[c//2]) in
+    float32: the median, the mean of the two middle ones for an even count.  No finite entry at all: +inf."""
+    import torch
+    last = dist[:, :, -1]
+    finite = torch.isfinite(last)
+    v, _ = torch.sort(torch.where(finite, last, torch.full_like(last, float("inf"))), dim=1)
+    c = finite.sum(dim=1, keepdim=True)
+    lo, hi = torch.clamp((c - 1) // 2, min=0), c // 2
+    hi = torch.clamp(hi, max=last.shape[1] - 1)
+    return (0.5 * (torch.gather(v, 1, lo) + torch.gather(v, 1, hi)))[:, 0].contiguous()
+
+
+def _recurrence(x, y, k, width, metric, sym, mode, bandwidth, diag, what):
+    import torch
+    index, dist = knn(x, y, k, width=width, metric=metric)
+    batched = index.dim() == 3
+    ix, ds = (index, dist) if batched else (index[None], dist[None])
+    P, N, _ = ix.shape
+    M = N if y is None else (y.shape[-2])
+    bw = None
+    if _named(_REC_MODES, mode, "mode") == capix.REC_AFFINITY:
+        if bandwidth is None:
+            bw = _median_k_bandwidth(ds)
+        elif hasattr(bandwidth, "is_cuda"):
+            bw = bandwidth.to(device=ix.device, dtype=torch.float32).reshape(-1).expand(P).contiguous() if bandwidth.numel() == 1 else bandwidth.to(torch.float32).contiguous()
+        else:
+            bw = torch.full((P,), float(bandwidth), dtype=torch.float32, device=ix.device)
+    out = torch.empty((P, N, M), dtype=torch.float32, device=ix.device)
+    with torch.cuda.device(_device_index(ix)):
+        recurrence_launch(ix, ds, out, mode=mode, sym=sym, diag=diag, d_bandwidth=bw)
+    return out if batched else out[0]
+
+
+def recurrence_matrix(data, k=None, width: int = 1, metric: str = "euclidean", sym: bool = False, mode: str = "connectivity", bandwidth=None, self: bool = False):
+    """librosa.segment.recurrence_matrix on the GPU: data [N, K] or [P, N, K] (frame-major; numpy array or float32 CUDA tensor) -> a
+    float32 CUDA tensor [N, N] or [P, N, N].  rec[i, j] is non-zero where j is one of the k nearest frames of i outside |i - j| < width
+    (sym: and i one of j's): 1 ("connectivity"), the distance ("distance") or exp(-distance / bandwidth) ("affinity").  k None:
+    knn_default_k(N, width).  bandwidth None: librosa's med_k_scalar, the median over the frames of the distance to the k-th neighbour,
+    computed with torch on the device without a host synchronisation (of the finite dist[i][k-1] sorted ascending, c of them,
+    0.5f * (v[(c-1)//2] + v[c//2])); a number or a float32 CUDA tensor [P] is taken as given.  self: the main diagonal is set (1; 0 in
+    distance mode).  Differences from librosa: query-major (librosa returns the transpose unless sym), a dense float32 plane, ties to the
+    lower frame, k at most 256; include/jsgx.h sections 6 and 7 state every operation.  Agreement with librosa has not been measured."""
+    x, _ = _to_cuda(data)
+    return _recurrence(x, None, k, width, metric, sym, mode, bandwidth, self, "recurrence_matrix")
+
+
+def cross_similarity(data, data_ref, k=None, metric: str = "euclidean", mode: str = "connectivity", bandwidth=None):
+    """librosa.segment.cross_similarity on the GPU: data [N, K] and data_ref [M, K] (a leading axis of P pairs on either or both) -> a
+    float32 CUDA tensor [N, M] or [P, N, M]: row i marks the k frames of data_ref nearest to frame i of data (query-major; librosa
+    returns the transpose).  k None: librosa's min(M, 2 * ceil(sqrt(M))), clamped to 256.  mode and bandwidth as recurrence_matrix."""
+    import math
+    x, _ = _to_cuda(data)
+    y, _ = _to_cuda(data_ref)
+    M = y.shape[-2]
+    if k is None:
+        k = max(1, min(M, 2 * (math.isqrt(M - 1) + 1 if M > 0 else 0), capix.KNN_MAX_K))
+    return _recurrence(x, y, k, 0, metric, False, mode, bandwidth, False, "cross_similarity")
+
+
+def nn_filter_launch(d_s, d_index, d_out, *, d_weights=None, stream: int | None = None):
+    """jsgx_nn_filter_launch: d_s float32 [n][features] or [pairs][n][features] and the lists d_index int32 [n][k] or [pairs][n][k] ->
+    d_out, the shape of d_s: every frame replaced by the mean of its neighbours, or with d_weights float32 (the shape of d_index) by
+    their weighted mean; a frame without neighbours (or with a zero weight sum) keeps its own values.  Enqueue only."""
+    import torch
+    s, o, ix = _planes(d_s, "d_s"), _planes(d_out, "d_out"), _planes(d_index, "d_index", torch.int32)
+    P, N, F = s.shape
+    k = ix.shape[2]
+    assert tuple(o.shape) == (P, N, F) and ix.shape[0] == P and ix.shape[1] == N, "d_out: the shape of d_s; d_index [pairs][n][k]"
+    w = None if d_weights is None else _planes(d_weights, "d_weights")
+    assert w is None or tuple(w.shape) == (P, N, k), "d_weights: the shape of d_index"
+    a = capix.NnFilterArgs(s.data_ptr(), s.stride(1), s.stride(0), ix.data_ptr(), ix.stride(1), ix.stride(0), None if w is None else w.data_ptr(),
+                           0 if w is None else w.stride(1), 0 if w is None else w.stride(0), P, N, F, k, o.data_ptr(), o.stride(1), o.stride(0))
+    capix.check(capix.lib().jsgx_nn_filter_launch(C.byref(a), _stream_handle(stream, d_out)))
+
+
+def nn_filter(S, index, weights=None):
+    """librosa.decompose.nn_filter with aggregate = mean (weights None) or a weighted mean, on the GPU: S [N, F] or [P, N, F] (frame-major;
+    numpy array or float32 CUDA tensor), index int32 [N, k] or [P, N, k] (what knn returns; -1 marks no neighbour) -> a float32 CUDA
+    tensor of the shape of S.  A frame without neighbours keeps its own values.  The median aggregate, librosa's default, is not served."""
+    import torch
+    s, _ = _to_cuda(S)
+    s = s.contiguous()
+    ix = index if hasattr(index, "is_cuda") else torch.from_numpy(np.ascontiguousarray(index, dtype=np.int32)).to(s.device)
+    w = None if weights is None else _to_cuda(weights)[0].contiguous()
+    out = torch.empty_like(s)
+    with torch.cuda.device(_device_index(s)):
+        nn_filter_launch(s, ix.contiguous(), out, d_weights=w)
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
 # cepstral coefficients and delta features (include/jsg.h, section 2k)
 # --------------------------------------------------------------------------------------------------
 _NORMS = {"ortho": capi.DCT_NORM_ORTHO, None: capi.DCT_NORM_NONE, "none": capi.DCT_NORM_NONE}
