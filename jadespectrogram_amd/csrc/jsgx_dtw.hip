@@ -38,20 +38,15 @@ static_assert(kCols % 64 == 0, "a row pitch that is a multiple of 64 words keeps
 static_assert((kRows * kCols + kTop) * 4 == JSGX_DTW_LDS_BYTES, "include/jsgx.h states the LDS");
 
 struct DtwArgs {
-    const float* cost;
-    long long cost_pitch, cost_pair_pitch;
-    float* acc;
-    long long acc_pitch, acc_pair_pitch;
+    Plane<const float> cost;
+    Plane<float> acc;
     int n, m, subseq, band;
     float wm0, wm1, wm2, wa0, wa1, wa2;
     int diagonal, ti_first;         // this launch: the tiles (ti_first + blockIdx.x, diagonal - ti)
 };
 
 struct BacktraceArgs {
-    const float* cost;
-    long long cost_pitch, cost_pair_pitch;
-    const float* acc;
-    long long acc_pitch, acc_pair_pitch;
+    Plane<const float> cost, acc;
     int n, m, subseq;
     float wm0, wm1, wm2, wa0, wa1, wa2;
     int* path_i;
@@ -140,9 +135,9 @@ __global__ __launch_bounds__(kLanes) void dtw_kernel(DtwArgs a) {
     const int i0 = ti * kRows, j0 = tj * kCols;
     const int rows = a.n - i0 < kRows ? a.n - i0 : kRows, cols = a.m - j0 < kCols ? a.m - j0 : kCols;
     const float inf = __builtin_inff();
-    const float* C = a.cost + blockIdx.y * a.cost_pair_pitch + (long long)i0 * a.cost_pitch + j0;
-    float* Dp = a.acc + blockIdx.y * a.acc_pair_pitch;             // the pair's plane
-    float* D = Dp + (long long)i0 * a.acc_pitch + j0;              // the tile
+    const float* C = a.cost.row(blockIdx.y, i0) + j0;
+    float* Dp = a.acc.row(blockIdx.y, 0);                          // the pair's plane
+    float* D = a.acc.row(blockIdx.y, i0) + j0;                     // the tile
     const long long n1 = a.n - 1, m1 = a.m - 1, lim = (long long)a.band * (n1 > 1 ? n1 : 1);
     const bool banded = a.band != 0;
     if (banded) {
@@ -150,13 +145,13 @@ __global__ __launch_bounds__(kLanes) void dtw_kernel(DtwArgs a) {
         const long long hi = (long long)(j0 + cols - 1) * n1 - (long long)i0 * m1, lo = (long long)j0 * n1 - (long long)(i0 + rows - 1) * m1;
         if (lo > lim || hi < -lim) {
             for (int r = 0; r < rows; ++r)
-                for (int c = l; c < cols; c += kLanes) D[(long long)r * a.acc_pitch + c] = inf;
+                for (int c = l; c < cols; c += kLanes) D[(long long)r * a.acc.pitch + c] = inf;
             return;
         }
     }
     // every load below is issued without a branch, from an address kept inside the matrix, and what lies outside is replaced afterwards:
     // the loads of a batch are in flight together.  Tile cells outside the matrix hold copies of cells inside; no step that is used reads them.
-    const long long ap = a.acc_pitch;
+    const long long ap = a.acc.pitch;
     const int row_above = i0 > 0 ? i0 - 1 : 0, col_before = j0 > 0 ? j0 - 1 : 0;
     const float corner_value = Dp[row_above * ap + col_before];
     const float left_value = D[(long long)(l < rows ? l : rows - 1) * ap + (col_before - j0)];
@@ -168,7 +163,7 @@ __global__ __launch_bounds__(kLanes) void dtw_kernel(DtwArgs a) {
         for (int r0 = 0; r0 < kRows; r0 += 16) {
             float v[16];
 #pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = C[(long long)(r0 + q < rows ? r0 + q : rows - 1) * a.cost_pitch + c];
+            for (int q = 0; q < 16; ++q) v[q] = C[(long long)(r0 + q < rows ? r0 + q : rows - 1) * a.cost.pitch + c];
 #pragma unroll
             for (int q = 0; q < 16; ++q) tile[(r0 + q) * kCols + c0 + l] = v[q];
         }
@@ -189,7 +184,7 @@ __global__ __launch_bounds__(kLanes) void dtw_kernel(DtwArgs a) {
     __syncthreads();
 #pragma unroll 8
     for (int r = 0; r < rows; ++r)
-        for (int c = l; c < cols; c += kLanes) D[(long long)r * a.acc_pitch + c] = tile[r * kCols + c];
+        for (int c = l; c < cols; c += kLanes) D[(long long)r * a.acc.pitch + c] = tile[r * kCols + c];
 }
 
 constexpr int kWin = 32;                  // the window of the backtrace: kWin x kWin cells of D and of C, 16 loads of each per lane
@@ -201,15 +196,15 @@ __global__ __launch_bounds__(kLanes) void dtw_backtrace_kernel(BacktraceArgs a) 
     __shared__ int state[4];            // i, j, the cells recorded, 0 walking / 1 at the start / -1 no path
     const int l = threadIdx.x, p = blockIdx.x;
     const float inf = __builtin_inff();
-    const float* C = a.cost + p * a.cost_pair_pitch;
-    const float* D = a.acc + p * a.acc_pair_pitch;
+    const float* C = a.cost.row(p, 0);
+    const float* D = a.acc.row(p, 0);
     const int longest = a.n + a.m - 1;
     int* rev_i = a.scratch ? a.scratch + (long long)p * 2 * longest : nullptr;
     int* rev_j = rev_i ? rev_i + longest : nullptr;
     // ---- the end cell
     int end_j = a.m - 1, no_path = 0;
     if (a.subseq) {
-        const float* last_row = D + (long long)(a.n - 1) * a.acc_pitch;
+        const float* last_row = D + (long long)(a.n - 1) * a.acc.pitch;
         float best = inf;
         int best_j = INT_MAX, nan = 0;
         for (int j = l; j < a.m; j += kLanes) {             // j ascends: a strict comparison keeps the lowest
@@ -257,7 +252,7 @@ __global__ __launch_bounds__(kLanes) void dtw_backtrace_kernel(BacktraceArgs a) 
             const int gi = i - (kWin - 1) + q / kWin, gj = j - (kWin - 1) + q % kWin;
             const bool in = gi >= 0 && gj >= 0;             // gi <= i < n and gj <= j < m
             const long long ri = gi < 0 ? 0 : gi, rj = gj < 0 ? 0 : gj;
-            const float dv = D[ri * a.acc_pitch + rj], cv = C[ri * a.cost_pitch + rj];
+            const float dv = D[ri * a.acc.pitch + rj], cv = C[ri * a.cost.pitch + rj];
             wd[q] = in ? dv : inf;
             wc[q] = cv;
         }
@@ -311,7 +306,7 @@ __global__ __launch_bounds__(kLanes) void dtw_backtrace_kernel(BacktraceArgs a) 
     }
     if (l == 0) {
         if (a.path_len) a.path_len[p] = L;
-        if (a.total) a.total[p] = D[(long long)(a.n - 1) * a.acc_pitch + end_j];
+        if (a.total) a.total[p] = D[(long long)(a.n - 1) * a.acc.pitch + end_j];
     }
 }
 
@@ -328,15 +323,10 @@ extern "C" int jsgx_dtw_launch(const jsgx_dtw_args* g, void* scratch, int64_t sc
     int dev = -1;
     if ((rc = current_device(&dev, who)) != JSGX_OK) return rc;
     // every refusal is behind us
-    const bool multi = g->pairs > 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     DtwArgs k{};
-    k.cost = g->cost;
-    k.cost_pitch = g->cost_pitch;
-    k.cost_pair_pitch = multi ? g->cost_pair_pitch : 0;
-    k.acc = g->acc;
-    k.acc_pitch = g->acc_pitch;
-    k.acc_pair_pitch = multi ? g->acc_pair_pitch : 0;
+    k.cost = plane_of(g->cost, g->cost_pitch, g->cost_pair_pitch, g->pairs);
+    k.acc = plane_of(g->acc, g->acc_pitch, g->acc_pair_pitch, g->pairs);
     k.n = g->n;
     k.m = g->m;
     k.subseq = g->subseq;
@@ -352,13 +342,13 @@ extern "C" int jsgx_dtw_launch(const jsgx_dtw_args* g, void* scratch, int64_t sc
     }
     if (g->path_len || g->total) {
         BacktraceArgs b{};
-        b.cost = k.cost, b.cost_pitch = k.cost_pitch, b.cost_pair_pitch = k.cost_pair_pitch;
-        b.acc = k.acc, b.acc_pitch = k.acc_pitch, b.acc_pair_pitch = k.acc_pair_pitch;
+        b.cost = k.cost;
+        b.acc = plane_of<const float>(g->acc, g->acc_pitch, g->acc_pair_pitch, g->pairs);
         b.n = g->n, b.m = g->m, b.subseq = g->subseq;
         b.wm0 = k.wm0, b.wm1 = k.wm1, b.wm2 = k.wm2, b.wa0 = k.wa0, b.wa1 = k.wa1, b.wa2 = k.wa2;
         b.path_i = g->path_i;
         b.path_j = g->path_j;
-        b.path_pitch = multi ? g->path_pitch : 0;
+        b.path_pitch = g->pairs > 1 ? g->path_pitch : 0;
         b.path_len = g->path_len;
         b.total = g->total;
         b.scratch = need > 0 ? static_cast<int*>(scratch) : nullptr;

@@ -12,7 +12,6 @@ namespace {
 using jsg::addr;
 using jsg::i128;
 using jsg::overlap;
-using jsg::plane;
 using jsg::span_bytes;
 }  // namespace
 
@@ -28,16 +27,12 @@ int cdist_check(const jsgx_cdist_args* g, const char* who) {
     if (g->m < 1 || g->m > JSGX_DTW_MAX_LEN) return fail(JSGX_ERR_INVALID, who, "m must be in 1..65536");
     if (g->metric < JSGX_METRIC_SQEUCLIDEAN || g->metric > JSGX_METRIC_COSINE) return fail(JSGX_ERR_INVALID, who, "metric must be in 0..2");
     if (g->reserved0 != 0) return fail(JSGX_ERR_INVALID, who, "reserved0 must be 0");
-    const long long K = g->n_features, N = g->n, M = g->m, P = g->pairs;
-    if (g->x_frame_pitch < K) return fail(JSGX_ERR_INVALID, who, "x_frame_pitch smaller than n_features");
-    if (g->y_frame_pitch < K) return fail(JSGX_ERR_INVALID, who, "y_frame_pitch smaller than n_features");
-    if (g->x_pair_pitch != 0 && g->x_pair_pitch < plane(N, g->x_frame_pitch, K)) return fail(JSGX_ERR_INVALID, who, "x_pair_pitch does not cover a sequence");
-    if (g->y_pair_pitch != 0 && g->y_pair_pitch < plane(M, g->y_frame_pitch, K)) return fail(JSGX_ERR_INVALID, who, "y_pair_pitch does not cover a sequence");
-    if (g->cost_pitch < M) return fail(JSGX_ERR_INVALID, who, "cost_pitch smaller than m");
-    if (P > 1 && g->cost_pair_pitch < plane(N, g->cost_pitch, M)) return fail(JSGX_ERR_INVALID, who, "cost_pair_pitch does not cover a plane");
-    const i128 cost_bytes = span_bytes(P, g->cost_pair_pitch, plane(N, g->cost_pitch, M), 4);
-    if (overlap(addr(g->cost), cost_bytes, addr(g->x), span_bytes(P, g->x_pair_pitch, plane(N, g->x_frame_pitch, K), 4))) return fail(JSGX_ERR_INVALID, who, "cost overlaps x");
-    if (overlap(addr(g->cost), cost_bytes, addr(g->y), span_bytes(P, g->y_pair_pitch, plane(M, g->y_frame_pitch, K), 4))) return fail(JSGX_ERR_INVALID, who, "cost overlaps y");
+    i128 x_bytes, y_bytes, cost_bytes;
+    int rc = check_xy(g, who, &x_bytes, &y_bytes);
+    if (rc == JSGX_OK) rc = check_plane(who, "cost", "", "m", g->n, g->m, g->cost_pitch, g->cost_pair_pitch, g->pairs, &cost_bytes);
+    if (rc != JSGX_OK) return rc;
+    if (overlap(addr(g->cost), cost_bytes, addr(g->x), x_bytes)) return fail(JSGX_ERR_INVALID, who, "cost overlaps x");
+    if (overlap(addr(g->cost), cost_bytes, addr(g->y), y_bytes)) return fail(JSGX_ERR_INVALID, who, "cost overlaps y");
     return JSGX_OK;
 }
 
@@ -59,15 +54,13 @@ int dtw_check(const jsgx_dtw_args* g, const char* who) {
     if (g->reserved0 != 0) return fail(JSGX_ERR_INVALID, who, "reserved0 must be 0");
     if (g->band != 0 && g->subseq) return fail(JSGX_ERR_INVALID, who, "band and subseq exclude each other");
     const long long N = g->n, M = g->m, P = g->pairs;
-    const bool multi = g->pairs > 1;
     if (g->path_i && g->max_path < N + M - 1) return fail(JSGX_ERR_INVALID, who, "max_path smaller than n + m - 1");
-    if (g->cost_pitch < M) return fail(JSGX_ERR_INVALID, who, "cost_pitch smaller than m");
-    if (multi && g->cost_pair_pitch < plane(N, g->cost_pitch, M)) return fail(JSGX_ERR_INVALID, who, "cost_pair_pitch does not cover a plane");
-    if (g->acc_pitch < M) return fail(JSGX_ERR_INVALID, who, "acc_pitch smaller than m");
-    if (multi && g->acc_pair_pitch < plane(N, g->acc_pitch, M)) return fail(JSGX_ERR_INVALID, who, "acc_pair_pitch does not cover a plane");
-    if (multi && g->path_i && g->path_pitch < g->max_path) return fail(JSGX_ERR_INVALID, who, "path_pitch smaller than max_path");
-    const i128 cost0 = addr(g->cost), cost_bytes = span_bytes(P, g->cost_pair_pitch, plane(N, g->cost_pitch, M), 4);
-    const i128 acc0 = addr(g->acc), acc_bytes = span_bytes(P, g->acc_pair_pitch, plane(N, g->acc_pitch, M), 4);
+    i128 cost_bytes, acc_bytes;
+    int rc = check_plane(who, "cost", "", "m", N, M, g->cost_pitch, g->cost_pair_pitch, P, &cost_bytes);
+    if (rc == JSGX_OK) rc = check_plane(who, "acc", "", "m", N, M, g->acc_pitch, g->acc_pair_pitch, P, &acc_bytes);
+    if (rc != JSGX_OK) return rc;
+    if (P > 1 && g->path_i && g->path_pitch < g->max_path) return fail(JSGX_ERR_INVALID, who, "path_pitch smaller than max_path");
+    const i128 cost0 = addr(g->cost), acc0 = addr(g->acc);
     const i128 path_bytes = g->path_i ? span_bytes(P, g->path_pitch, g->max_path, 4) : 0;
     const i128 out[4] = {addr(g->path_i), addr(g->path_j), addr(g->path_len), addr(g->total)};
     const i128 out_bytes[4] = {path_bytes, path_bytes, 4 * (i128)P, 4 * (i128)P};

@@ -91,6 +91,40 @@ inline int check_scratch(const char* who, const void* scratch, int64_t scratch_b
     return fail(JSGX_ERR_INVALID, who, what);
 }
 
+// One plane per pair, `rows` rows of `cols` elements of 4 bytes: its two refusals in the words every unit uses, "<name><row>_pitch smaller
+// than <cols_name>" (row: "" or "_frame") and then "<name>_pair_pitch does not cover a plane", and its bytes for the overlap refusals.
+inline int check_plane(const char* who, const char* name, const char* row, const char* cols_name, long long rows, long long cols, long long pitch,
+                       long long pair_pitch, long long pairs, jsg::i128* bytes) {
+    char what[96];
+    const jsg::i128 one = jsg::plane(rows, pitch, cols);
+    *bytes = jsg::span_bytes(pairs, pair_pitch, one, 4);
+    if (pitch < cols)
+        std::snprintf(what, sizeof what, "%s%s_pitch smaller than %s", name, row, cols_name);
+    else if (pairs > 1 && pair_pitch < one)
+        std::snprintf(what, sizeof what, "%s_pair_pitch does not cover a plane", name);
+    else
+        return JSGX_OK;
+    return fail(JSGX_ERR_INVALID, who, what);
+}
+// Its sibling for a sequence of `frames` frames that the pairs may share (a pair pitch of 0), behind the refusal of its frame pitch.
+inline int check_sequence(const char* who, const char* name, long long frames, long long K, long long frame_pitch, long long pair_pitch, long long pairs,
+                          jsg::i128* bytes) {
+    const jsg::i128 one = jsg::plane(frames, frame_pitch, K);
+    *bytes = jsg::span_bytes(pairs, pair_pitch, one, 4);
+    if (pair_pitch == 0 || pair_pitch >= one) return JSGX_OK;
+    char what[96];
+    std::snprintf(what, sizeof what, "%s_pair_pitch does not cover a sequence", name);
+    return fail(JSGX_ERR_INVALID, who, what);
+}
+// x and y of sections 2 and 6, whose argument blocks name them alike: both frame pitches, then both pair pitches.
+template <class Args>
+int check_xy(const Args* g, const char* who, jsg::i128* x_bytes, jsg::i128* y_bytes) {
+    if (g->x_frame_pitch < g->n_features) return fail(JSGX_ERR_INVALID, who, "x_frame_pitch smaller than n_features");
+    if (g->y_frame_pitch < g->n_features) return fail(JSGX_ERR_INVALID, who, "y_frame_pitch smaller than n_features");
+    const int rc = check_sequence(who, "x", g->n, g->n_features, g->x_frame_pitch, g->x_pair_pitch, g->pairs, x_bytes);
+    return rc != JSGX_OK ? rc : check_sequence(who, "y", g->m, g->n_features, g->y_frame_pitch, g->y_pair_pitch, g->pairs, y_bytes);
+}
+
 // The two ends of a ..._plan call's name buffer: the refusal of one below min_len bytes, before any other (a call may pass none), and
 // the kernel's name into it once the call has passed.
 inline int check_name_buffer(const char* who, const char* buf, int len, int min_len) {
@@ -118,6 +152,23 @@ inline int finish_launch(const char* who, hipError_t err) {
     char what[160];
     std::snprintf(what, sizeof what, "HIP error %d (%s)", (int)err, hipGetErrorString(err));
     return fail(JSGX_ERR_HIP, who, what);
+}
+// A pitched plane per pair as a kernel takes it: the pointer, the elements between its rows and between the pairs' planes.
+template <class T>
+struct Plane {
+    T* p;
+    long long pitch, pair_pitch;
+    __device__ __forceinline__ T* row(long long pair, long long i) const { return p + pair * pair_pitch + i * pitch; }
+};
+// of a call's arguments: one pair has no pair pitch, whatever the field holds ...
+template <class T>
+Plane<T> plane_of(T* p, long long pitch, long long pair_pitch, int pairs) {
+    return {p, pitch, pairs > 1 ? pair_pitch : 0};
+}
+// ... and a sequence's pair pitch is the caller's, 0 for one that every pair shares
+template <class T>
+Plane<T> sequence_of(T* p, long long frame_pitch, long long pair_pitch) {
+    return {p, frame_pitch, pair_pitch};
 }
 // The blocked backtrace of section 4 (jsgx_viterbi.hip: jump where n_blocks > 1, ends, trace) onto the stream, from psi and V[T-1] in the
 // scratch `base` laid out by viterbi_layout: what jsgx_viterbi_launch and jsgx_pyin_decode_launch enqueue behind their forward kernels.

@@ -1,10 +1,9 @@
 // libjsgx.so, the k nearest frames, the recurrence plane and the neighbour aggregation (include/jsgx.h sections 6 to 8): the kernels and
 // their launchers.  The refusals, the plan and the scratch size are in jsgx_knn_host.cpp.
 //
-// "knn_64" is the cost loop of jsgx_cdist.hip (the same staging, the same order of accumulation: the costs are the same bits) with the
-// selection behind it.  A workgroup owns 64 rows of one pair and sweeps its share of the column tiles in ascending order.  The LDS:
-//   panels   2 x 32 features x 68 words, as in "cdist_64x64"; once a tile's costs are in registers the same 17408 bytes take the tile,
-//            64 rows of 68 words
+// "knn_64" is the cost tile of jsgx_cost_tile.h, the function that "cdist_64x64" stores (one function: the costs are the same bits), with
+// the selection behind it.  A workgroup owns 64 rows of one pair and sweeps its share of the column tiles in ascending order.  The LDS:
+//   panels   the two of the cost tile; once a tile's costs are in registers the same 17408 bytes take the tile, 64 rows of 68 words
 //   lists    per row k float costs, then per row k 16-bit indices: the k best of the columns swept so far, ascending by (c, j)
 //   pending  per row up to 64 survivors (cost, 16-bit index) that wait for their merge, in the order they came: ascending j
 //   sorted   per wavefront 64 costs: those of the candidates of one merge in their order
@@ -13,26 +12,20 @@
 // does alone, so the rows need no workgroup barrier; the two barriers per tile are those around the tile itself.
 #include <hip/hip_runtime.h>
 
-#include "jsgx_internal.h"
+#include "jsgx_cost_tile.h"
 
 namespace jsgx {
 
 struct KnnArgs {
-    const float* x;
-    long long x_frame_pitch, x_pair_pitch;
-    const float* y;
-    long long y_frame_pitch, y_pair_pitch;
-    int* nn_index;
-    long long index_pitch, index_pair_pitch;
-    float* nn_dist;
-    long long dist_pitch, dist_pair_pitch;
+    Plane<const float> x, y;
+    Plane<int> nn_index;
+    Plane<float> nn_dist;
     float* part_dist;           // S > 1: [p][i][s][r]
     int* part_index;
     int n, m, K, k, width, S, tiles;
 };
 
-constexpr int kTile = JSGX_KNN_TILE, kPanel = 32, kPitch = kTile + 4, kRowsPerWave = JSGX_KNN_STRIP / (JSGX_KNN_THREADS / 64), kPending = 64;
-static_assert(JSGX_KNN_TILE == JSGX_CDIST_TILE && JSGX_KNN_THREADS == JSGX_CDIST_THREADS && JSGX_KNN_STRIP == kTile, "the inner loop is that of cdist_64x64");
+constexpr int kRowsPerWave = JSGX_KNN_STRIP / (JSGX_KNN_THREADS / 64), kPending = 64;
 static_assert(2 * kPanel * kPitch * 4 + 4 * 64 * 4 + 12 * JSGX_KNN_STRIP + 6 * kPending * JSGX_KNN_STRIP == JSGX_KNN_LDS_STATIC, "include/jsgx.h states the LDS");
 static_assert(JSGX_KNN_LDS_STATIC + 6 * JSGX_KNN_STRIP * JSGX_KNN_MAX_K <= JSGX_KNN_LDS_LIMIT, "the lists of the largest k fit");
 static_assert(JSGX_KNN_MAX_K <= 4 * 64, "a lane holds four entries of a list");
@@ -112,82 +105,28 @@ __global__ __launch_bounds__(JSGX_KNN_THREADS) void knn_kernel(KnnArgs a) {
     __shared__ float pend_c[JSGX_KNN_STRIP * kPending];
     __shared__ unsigned short pend_j[JSGX_KNN_STRIP * kPending];
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
-    float* xs = panels;
-    float* ys = panels + kPanel * kPitch;
     float* ct = panels;                                            // the tile, once the panels are spent
     float* list_c = reinterpret_cast<float*>(dyn);                 // [64][k]
     unsigned short* list_j = reinterpret_cast<unsigned short*>(dyn + 4 * JSGX_KNN_STRIP * a.k);
     const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15, lane = tid & 63, wave = tid >> 6;
     const int i0 = blockIdx.y * kTile, s_part = blockIdx.x, k = a.k;
     const int t_begin = (int)((long long)s_part * a.tiles / a.S), t_end = (int)((long long)(s_part + 1) * a.tiles / a.S);
-    const float* x = a.x + blockIdx.z * a.x_pair_pitch;
-    const float* y = a.y + blockIdx.z * a.y_pair_pitch;
+    const CostTileArgs seqs{a.x.row(blockIdx.z, 0), a.x.pitch, a.y.row(blockIdx.z, 0), a.y.pitch, a.n, a.m, a.K, panels, panels + kPanel * kPitch};
     if (tid < JSGX_KNN_STRIP) {
         lens[tid] = pends[tid] = 0;
         kth[tid] = __builtin_nanf("");
     }
-    const int kk = tid & 31, f0 = tid >> 5;
     for (int t = t_begin; t < t_end; ++t) {
         const int j0 = t * kTile;
-        float acc[4][4], nx[4], ny[4];
-        for (int r = 0; r < 4; ++r) {
-            nx[r] = ny[r] = 0.f;
-            for (int c = 0; c < 4; ++c) acc[r][c] = 0.f;
-        }
-        for (int k0 = 0; k0 < a.K; k0 += kPanel) {
-            const int kc = a.K - k0 < kPanel ? a.K - k0 : kPanel;
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int f = f0 + 8 * r;
-                const bool k_in = kk < kc;
-                xs[kk * kPitch + f] = (k_in && i0 + f < a.n) ? x[(long long)(i0 + f) * a.x_frame_pitch + k0 + kk] : 0.f;
-                ys[kk * kPitch + f] = (k_in && j0 + f < a.m) ? y[(long long)(j0 + f) * a.y_frame_pitch + k0 + kk] : 0.f;
-            }
-            __syncthreads();
-            for (int kf = 0; kf < kc; ++kf) {
-                const float4 xq = *reinterpret_cast<const float4*>(&xs[kf * kPitch + 4 * ti]);
-                const float4 yq = *reinterpret_cast<const float4*>(&ys[kf * kPitch + 4 * tj]);
-                const float xv[4] = {xq.x, xq.y, xq.z, xq.w}, yv[4] = {yq.x, yq.y, yq.z, yq.w};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        if (METRIC == JSGX_METRIC_COSINE) {
-                            acc[r][c] = __builtin_fmaf(xv[r], yv[c], acc[r][c]);
-                        } else {
-                            const float d = xv[r] - yv[c];
-                            acc[r][c] = __builtin_fmaf(d, d, acc[r][c]);
-                        }
-                    }
-                }
-                if (METRIC == JSGX_METRIC_COSINE) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        nx[r] = __builtin_fmaf(xv[r], xv[r], nx[r]);
-                        ny[r] = __builtin_fmaf(yv[r], yv[r], ny[r]);
-                    }
-                }
-            }
-        }
+        const CostTile tile = cost_tile<METRIC>(seqs, i0, j0);
         __syncthreads();                                           // the panels are spent: the tile takes their place
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float c4[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                if (METRIC == JSGX_METRIC_SQEUCLIDEAN) {
-                    c4[c] = acc[r][c];
-                } else if (METRIC == JSGX_METRIC_EUCLIDEAN) {
-                    c4[c] = sqrtf(acc[r][c]);
-                } else {
-                    const float den = sqrtf(nx[r]) * sqrtf(ny[c]);
-                    c4[c] = den == 0.f ? 1.0f : 1.0f - acc[r][c] / den;
-                }
-            }
-            *reinterpret_cast<float4*>(&ct[(4 * ti + r) * kPitch + 4 * tj]) = make_float4(c4[0], c4[1], c4[2], c4[3]);
-        }
+        for (int r = 0; r < 4; ++r)
+            *reinterpret_cast<float4*>(&ct[(4 * ti + r) * kPitch + 4 * tj]) = make_float4(tile.c[r][0], tile.c[r][1], tile.c[r][2], tile.c[r][3]);
         __syncthreads();
+        // The selection is one wavefront per SIMD waiting on its own LDS reads, and its loops are sensitive to where they lie in a 64-byte
+        // fetch line: 20 bytes more in front of them cost 2.8 % (profiles/knn_bench.md).  It starts on a line, whatever the cost tile takes.
+        asm volatile(".p2align 6");
         const int j = j0 + lane;
         // every row of the wavefront first: one read of the cost and of the row's k-th cost, one ballot; `todo` keeps the rows with a survivor.
         // kth is a NaN while a list is not full, and then every candidate passes; an equal cost loses: every j of the list is lower
@@ -253,8 +192,8 @@ __global__ __launch_bounds__(JSGX_KNN_THREADS) void knn_kernel(KnnArgs a) {
         float* od;
         int* oi;
         if (a.S == 1) {
-            od = a.nn_dist + blockIdx.z * a.dist_pair_pitch + (long long)i * a.dist_pitch;
-            oi = a.nn_index + blockIdx.z * a.index_pair_pitch + (long long)i * a.index_pitch;
+            od = a.nn_dist.row(blockIdx.z, i);
+            oi = a.nn_index.row(blockIdx.z, i);
         } else {
             const long long at = (((long long)blockIdx.z * a.n + i) * a.S + s_part) * k;
             od = a.part_dist + at;
@@ -270,10 +209,8 @@ __global__ __launch_bounds__(JSGX_KNN_THREADS) void knn_kernel(KnnArgs a) {
 struct KnnMergeArgs {
     const float* part_dist;     // [row][s][r]
     const int* part_index;
-    int* nn_index;
-    long long index_pitch, index_pair_pitch;
-    float* nn_dist;
-    long long dist_pitch, dist_pair_pitch;
+    Plane<int> nn_index;
+    Plane<float> nn_dist;
     long long rows;             // pairs * n
     int n, k, S;
 };
@@ -302,9 +239,8 @@ __global__ __launch_bounds__(JSGX_KNN_MERGE_THREADS) void knn_merge_kernel(KnnMe
             len = merge_by_rank(Lc, Lj, len, k, sorted_c + 64 * wave, lane, c, j, mask);
         }
     }
-    const long long p = row / a.n, i = row % a.n;
-    float* od = a.nn_dist + p * a.dist_pair_pitch + i * a.dist_pitch;
-    int* oi = a.nn_index + p * a.index_pair_pitch + i * a.index_pitch;
+    float* od = a.nn_dist.row(row / a.n, row % a.n);
+    int* oi = a.nn_index.row(row / a.n, row % a.n);
     for (int r = lane; r < k; r += 64) {
         od[r] = r < len ? Lc[r] : __builtin_inff();
         oi[r] = r < len ? (int)Lj[r] : -1;
@@ -312,13 +248,10 @@ __global__ __launch_bounds__(JSGX_KNN_MERGE_THREADS) void knn_merge_kernel(KnnMe
 }
 
 struct RecArgs {
-    const int* nn_index;
-    long long index_pitch, index_pair_pitch;
-    const float* nn_dist;
-    long long dist_pitch, dist_pair_pitch;
+    Plane<const int> nn_index;
+    Plane<const float> nn_dist;
     const float* bandwidth;
-    float* out;
-    long long out_pitch, out_pair_pitch;
+    Plane<float> out;
     int n, m, k, mode, sym, diag;
 };
 
@@ -332,19 +265,18 @@ __global__ __launch_bounds__(JSGX_REC_THREADS) void recurrence_kernel(RecArgs a)
     __shared__ int link_j[JSGX_KNN_MAX_K];
     __shared__ float link_v[JSGX_KNN_MAX_K];
     const int tid = threadIdx.x, i = blockIdx.x;
-    const int* idx = a.nn_index + blockIdx.y * a.index_pair_pitch;
     if (tid < JSGX_KNN_MAX_K) {
-        int j = tid < a.k ? idx[(long long)i * a.index_pitch + tid] : -1;
+        int j = tid < a.k ? a.nn_index.row(blockIdx.y, i)[tid] : -1;
         if (j < 0 || j >= a.m || (a.diag && j == i)) j = -1;      // the diagonal is written by its own rule
         if (j >= 0 && a.sym) {
-            const int* other = idx + (long long)j * a.index_pitch;
+            const int* other = a.nn_index.row(blockIdx.y, j);
             bool mutual = false;
             for (int r = 0; r < a.k; ++r) mutual = mutual || other[r] == i;
             if (!mutual) j = -1;
         }
         float v = 1.0f;
         if (j >= 0 && a.mode != JSGX_REC_CONNECTIVITY) {
-            v = a.nn_dist[blockIdx.y * a.dist_pair_pitch + (long long)i * a.dist_pitch + tid];
+            v = a.nn_dist.row(blockIdx.y, i)[tid];
             if (a.mode == JSGX_REC_AFFINITY) {
                 const float bw = a.bandwidth[blockIdx.y];
                 v = (!(bw > 0.f) || v != v) ? __builtin_nanf("") : exp_neg(-(v / bw));
@@ -353,7 +285,7 @@ __global__ __launch_bounds__(JSGX_REC_THREADS) void recurrence_kernel(RecArgs a)
         link_j[tid] = j;
         link_v[tid] = v;
     }
-    float* out = a.out + blockIdx.y * a.out_pair_pitch + (long long)i * a.out_pitch;
+    float* out = a.out.row(blockIdx.y, i);
     for (int c0 = 0; c0 < a.m; c0 += JSGX_REC_CHUNK) {
         const int width = a.m - c0 < JSGX_REC_CHUNK ? a.m - c0 : JSGX_REC_CHUNK;
         __syncthreads();
@@ -370,14 +302,10 @@ __global__ __launch_bounds__(JSGX_REC_THREADS) void recurrence_kernel(RecArgs a)
 }
 
 struct NnfArgs {
-    const float* s;
-    long long s_frame_pitch, s_pair_pitch;
-    const int* nn_index;
-    long long index_pitch, index_pair_pitch;
-    const float* weights;
-    long long weights_pitch, weights_pair_pitch;
-    float* out;
-    long long out_frame_pitch, out_pair_pitch;
+    Plane<const float> s;
+    Plane<const int> nn_index;
+    Plane<const float> weights;
+    Plane<float> out;
     int n, F, k;
 };
 
@@ -385,17 +313,16 @@ struct NnfArgs {
 __global__ __launch_bounds__(JSGX_NNF_THREADS) void nn_filter_kernel(NnfArgs a) {
 #pragma clang fp contract(off)
     const int i = blockIdx.x, lane = threadIdx.x;
-    const float* s = a.s + blockIdx.y * a.s_pair_pitch;
-    const int* idx = a.nn_index + blockIdx.y * a.index_pair_pitch + (long long)i * a.index_pitch;
-    const float* w = a.weights ? a.weights + blockIdx.y * a.weights_pair_pitch + (long long)i * a.weights_pitch : nullptr;
-    float* out = a.out + blockIdx.y * a.out_pair_pitch + (long long)i * a.out_frame_pitch;
+    const int* idx = a.nn_index.row(blockIdx.y, i);
+    const float* w = a.weights.p ? a.weights.row(blockIdx.y, i) : nullptr;
+    float* out = a.out.row(blockIdx.y, i);
     for (int f = lane; f < a.F; f += JSGX_NNF_THREADS) {
         float acc = 0.f, den = 0.f;
         int cnt = 0;
         for (int r = 0; r < a.k; ++r) {
             const int j = idx[r];
             if (j < 0 || j >= a.n) continue;
-            const float v = s[(long long)j * a.s_frame_pitch + f];
+            const float v = a.s.row(blockIdx.y, j)[f];
             ++cnt;
             if (w) {
                 acc = __builtin_fmaf(w[r], v, acc);
@@ -405,7 +332,7 @@ __global__ __launch_bounds__(JSGX_NNF_THREADS) void nn_filter_kernel(NnfArgs a) 
             }
         }
         if (!w) den = (float)cnt;
-        out[f] = (cnt == 0 || den == 0.f) ? s[(long long)i * a.s_frame_pitch + f] : acc / den;
+        out[f] = (cnt == 0 || den == 0.f) ? a.s.row(blockIdx.y, i)[f] : acc / den;
     }
 }
 
@@ -440,20 +367,11 @@ extern "C" int jsgx_knn_launch(const jsgx_knn_args* g, void* scratch, int64_t sc
     if ((rc = current_device(&dev, who)) != JSGX_OK) return rc;
     // every refusal is behind us
     const KnnPlan p = knn_plan(g, g->split != 0 ? 1 : cu_count(dev));
-    const bool multi = g->pairs > 1;
     KnnArgs k{};
-    k.x = g->x;
-    k.x_frame_pitch = g->x_frame_pitch;
-    k.x_pair_pitch = g->x_pair_pitch;
-    k.y = g->y;
-    k.y_frame_pitch = g->y_frame_pitch;
-    k.y_pair_pitch = g->y_pair_pitch;
-    k.nn_index = g->nn_index;
-    k.index_pitch = g->index_pitch;
-    k.index_pair_pitch = multi ? g->index_pair_pitch : 0;
-    k.nn_dist = g->nn_dist;
-    k.dist_pitch = g->dist_pitch;
-    k.dist_pair_pitch = multi ? g->dist_pair_pitch : 0;
+    k.x = sequence_of(g->x, g->x_frame_pitch, g->x_pair_pitch);
+    k.y = sequence_of(g->y, g->y_frame_pitch, g->y_pair_pitch);
+    k.nn_index = plane_of(g->nn_index, g->index_pitch, g->index_pair_pitch, g->pairs);
+    k.nn_dist = plane_of(g->nn_dist, g->dist_pitch, g->dist_pair_pitch, g->pairs);
     const long long entries = (long long)g->pairs * g->n * g->k * p.S;
     k.part_dist = p.S > 1 ? static_cast<float*>(scratch) : nullptr;
     k.part_index = p.S > 1 ? static_cast<int*>(scratch) + entries : nullptr;
@@ -479,11 +397,7 @@ extern "C" int jsgx_knn_launch(const jsgx_knn_args* g, void* scratch, int64_t sc
         q.part_dist = k.part_dist;
         q.part_index = k.part_index;
         q.nn_index = k.nn_index;
-        q.index_pitch = k.index_pitch;
-        q.index_pair_pitch = k.index_pair_pitch;
         q.nn_dist = k.nn_dist;
-        q.dist_pitch = k.dist_pitch;
-        q.dist_pair_pitch = k.dist_pair_pitch;
         q.rows = (long long)g->pairs * g->n;
         q.n = g->n;
         q.k = g->k;
@@ -500,18 +414,11 @@ extern "C" int jsgx_recurrence_launch(const jsgx_recurrence_args* g, void* strea
     if (rc != JSGX_OK) return rc;
     int dev = -1;
     if ((rc = current_device(&dev, who)) != JSGX_OK) return rc;
-    const bool multi = g->pairs > 1;
     RecArgs k{};
-    k.nn_index = g->nn_index;
-    k.index_pitch = g->index_pitch;
-    k.index_pair_pitch = multi ? g->index_pair_pitch : 0;
-    k.nn_dist = g->nn_dist;
-    k.dist_pitch = g->dist_pitch;
-    k.dist_pair_pitch = multi ? g->dist_pair_pitch : 0;
+    k.nn_index = plane_of(g->nn_index, g->index_pitch, g->index_pair_pitch, g->pairs);
+    k.nn_dist = plane_of(g->nn_dist, g->dist_pitch, g->dist_pair_pitch, g->pairs);
     k.bandwidth = g->bandwidth;
-    k.out = g->out;
-    k.out_pitch = g->out_pitch;
-    k.out_pair_pitch = multi ? g->out_pair_pitch : 0;
+    k.out = plane_of(g->out, g->out_pitch, g->out_pair_pitch, g->pairs);
     k.n = g->n;
     k.m = g->m;
     k.k = g->k;
@@ -528,20 +435,11 @@ extern "C" int jsgx_nn_filter_launch(const jsgx_nn_filter_args* g, void* stream)
     if (rc != JSGX_OK) return rc;
     int dev = -1;
     if ((rc = current_device(&dev, who)) != JSGX_OK) return rc;
-    const bool multi = g->pairs > 1;
     NnfArgs k{};
-    k.s = g->s;
-    k.s_frame_pitch = g->s_frame_pitch;
-    k.s_pair_pitch = multi ? g->s_pair_pitch : 0;
-    k.nn_index = g->nn_index;
-    k.index_pitch = g->index_pitch;
-    k.index_pair_pitch = multi ? g->index_pair_pitch : 0;
-    k.weights = g->weights;
-    k.weights_pitch = g->weights_pitch;
-    k.weights_pair_pitch = multi ? g->weights_pair_pitch : 0;
-    k.out = g->out;
-    k.out_frame_pitch = g->out_frame_pitch;
-    k.out_pair_pitch = multi ? g->out_pair_pitch : 0;
+    k.s = plane_of(g->s, g->s_frame_pitch, g->s_pair_pitch, g->pairs);
+    k.nn_index = plane_of(g->nn_index, g->index_pitch, g->index_pair_pitch, g->pairs);
+    k.weights = plane_of(g->weights, g->weights_pitch, g->weights_pair_pitch, g->pairs);
+    k.out = plane_of(g->out, g->out_frame_pitch, g->out_pair_pitch, g->pairs);
     k.n = g->n;
     k.F = g->n_features;
     k.k = g->k;

@@ -11,8 +11,6 @@ namespace {
 using jsg::addr;
 using jsg::i128;
 using jsg::overlap;
-using jsg::plane;
-using jsg::span_bytes;
 }  // namespace
 
 int knn_check(const jsgx_knn_args* g, const char* who) {
@@ -30,18 +28,12 @@ int knn_check(const jsgx_knn_args* g, const char* who) {
     if (g->k < 1 || g->k > JSGX_KNN_MAX_K) return fail(JSGX_ERR_INVALID, who, "k must be in 1..256");
     if (g->width < 0) return fail(JSGX_ERR_INVALID, who, "width must be >= 0");
     if (g->split < 0 || g->split > JSGX_KNN_MAX_SPLIT) return fail(JSGX_ERR_INVALID, who, "split must be in 0..16");
-    const long long K = g->n_features, N = g->n, M = g->m, P = g->pairs, k = g->k;
-    if (g->x_frame_pitch < K) return fail(JSGX_ERR_INVALID, who, "x_frame_pitch smaller than n_features");
-    if (g->y_frame_pitch < K) return fail(JSGX_ERR_INVALID, who, "y_frame_pitch smaller than n_features");
-    if (g->x_pair_pitch != 0 && g->x_pair_pitch < plane(N, g->x_frame_pitch, K)) return fail(JSGX_ERR_INVALID, who, "x_pair_pitch does not cover a sequence");
-    if (g->y_pair_pitch != 0 && g->y_pair_pitch < plane(M, g->y_frame_pitch, K)) return fail(JSGX_ERR_INVALID, who, "y_pair_pitch does not cover a sequence");
-    if (g->index_pitch < k) return fail(JSGX_ERR_INVALID, who, "index_pitch smaller than k");
-    if (P > 1 && g->index_pair_pitch < plane(N, g->index_pitch, k)) return fail(JSGX_ERR_INVALID, who, "index_pair_pitch does not cover a plane");
-    if (g->dist_pitch < k) return fail(JSGX_ERR_INVALID, who, "dist_pitch smaller than k");
-    if (P > 1 && g->dist_pair_pitch < plane(N, g->dist_pitch, k)) return fail(JSGX_ERR_INVALID, who, "dist_pair_pitch does not cover a plane");
-    const i128 x_bytes = span_bytes(P, g->x_pair_pitch, plane(N, g->x_frame_pitch, K), 4), y_bytes = span_bytes(P, g->y_pair_pitch, plane(M, g->y_frame_pitch, K), 4);
+    i128 x_bytes, y_bytes, out_bytes[2];
+    int rc = check_xy(g, who, &x_bytes, &y_bytes);
+    if (rc == JSGX_OK) rc = check_plane(who, "index", "", "k", g->n, g->k, g->index_pitch, g->index_pair_pitch, g->pairs, &out_bytes[0]);
+    if (rc == JSGX_OK) rc = check_plane(who, "dist", "", "k", g->n, g->k, g->dist_pitch, g->dist_pair_pitch, g->pairs, &out_bytes[1]);
+    if (rc != JSGX_OK) return rc;
     const i128 out[2] = {addr(g->nn_index), addr(g->nn_dist)};
-    const i128 out_bytes[2] = {span_bytes(P, g->index_pair_pitch, plane(N, g->index_pitch, k), 4), span_bytes(P, g->dist_pair_pitch, plane(N, g->dist_pitch, k), 4)};
     for (int i = 0; i < 2; ++i)
         if (overlap(out[i], out_bytes[i], addr(g->x), x_bytes)) return fail(JSGX_ERR_INVALID, who, "an output overlaps x");
     for (int i = 0; i < 2; ++i)
@@ -84,17 +76,15 @@ int recurrence_check(const jsgx_recurrence_args* g, const char* who) {
     if (g->sym && g->n != g->m) return fail(JSGX_ERR_INVALID, who, "sym needs n == m");
     if (g->mode != JSGX_REC_CONNECTIVITY && !g->nn_dist) return fail(JSGX_ERR_INVALID, who, "null nn_dist");
     if (g->mode == JSGX_REC_AFFINITY && !g->bandwidth) return fail(JSGX_ERR_INVALID, who, "null bandwidth");
-    const long long N = g->n, M = g->m, P = g->pairs, k = g->k;
-    if (g->index_pitch < k) return fail(JSGX_ERR_INVALID, who, "index_pitch smaller than k");
-    if (P > 1 && g->index_pair_pitch < plane(N, g->index_pitch, k)) return fail(JSGX_ERR_INVALID, who, "index_pair_pitch does not cover a plane");
-    if (g->nn_dist && g->dist_pitch < k) return fail(JSGX_ERR_INVALID, who, "dist_pitch smaller than k");
-    if (g->nn_dist && P > 1 && g->dist_pair_pitch < plane(N, g->dist_pitch, k)) return fail(JSGX_ERR_INVALID, who, "dist_pair_pitch does not cover a plane");
-    if (g->out_pitch < M) return fail(JSGX_ERR_INVALID, who, "out_pitch smaller than m");
-    if (P > 1 && g->out_pair_pitch < plane(N, g->out_pitch, M)) return fail(JSGX_ERR_INVALID, who, "out_pair_pitch does not cover a plane");
-    const i128 out0 = addr(g->out), out_bytes = span_bytes(P, g->out_pair_pitch, plane(N, g->out_pitch, M), 4);
-    if (overlap(out0, out_bytes, addr(g->nn_index), span_bytes(P, g->index_pair_pitch, plane(N, g->index_pitch, k), 4))) return fail(JSGX_ERR_INVALID, who, "out overlaps nn_index");
-    if (g->nn_dist && overlap(out0, out_bytes, addr(g->nn_dist), span_bytes(P, g->dist_pair_pitch, plane(N, g->dist_pitch, k), 4)))
-        return fail(JSGX_ERR_INVALID, who, "out overlaps nn_dist");
+    const long long N = g->n, P = g->pairs;
+    i128 index_bytes, dist_bytes = 0, out_bytes;
+    int rc = check_plane(who, "index", "", "k", N, g->k, g->index_pitch, g->index_pair_pitch, P, &index_bytes);
+    if (rc == JSGX_OK && g->nn_dist) rc = check_plane(who, "dist", "", "k", N, g->k, g->dist_pitch, g->dist_pair_pitch, P, &dist_bytes);
+    if (rc == JSGX_OK) rc = check_plane(who, "out", "", "m", N, g->m, g->out_pitch, g->out_pair_pitch, P, &out_bytes);
+    if (rc != JSGX_OK) return rc;
+    const i128 out0 = addr(g->out);
+    if (overlap(out0, out_bytes, addr(g->nn_index), index_bytes)) return fail(JSGX_ERR_INVALID, who, "out overlaps nn_index");
+    if (g->nn_dist && overlap(out0, out_bytes, addr(g->nn_dist), dist_bytes)) return fail(JSGX_ERR_INVALID, who, "out overlaps nn_dist");
     if (g->mode == JSGX_REC_AFFINITY && overlap(out0, out_bytes, addr(g->bandwidth), 4 * (i128)P)) return fail(JSGX_ERR_INVALID, who, "out overlaps bandwidth");
     return JSGX_OK;
 }
@@ -109,20 +99,17 @@ int nn_filter_check(const jsgx_nn_filter_args* g, const char* who) {
     if (g->n < 1 || g->n > JSGX_DTW_MAX_LEN) return fail(JSGX_ERR_INVALID, who, "n must be in 1..65536");
     if (g->n_features < 1 || g->n_features > JSGX_NNF_MAX_FEATURES) return fail(JSGX_ERR_INVALID, who, "n_features must be in 1..65536");
     if (g->k < 1 || g->k > JSGX_KNN_MAX_K) return fail(JSGX_ERR_INVALID, who, "k must be in 1..256");
-    const long long N = g->n, F = g->n_features, P = g->pairs, k = g->k;
-    if (g->s_frame_pitch < F) return fail(JSGX_ERR_INVALID, who, "s_frame_pitch smaller than n_features");
-    if (P > 1 && g->s_pair_pitch < plane(N, g->s_frame_pitch, F)) return fail(JSGX_ERR_INVALID, who, "s_pair_pitch does not cover a plane");
-    if (g->index_pitch < k) return fail(JSGX_ERR_INVALID, who, "index_pitch smaller than k");
-    if (P > 1 && g->index_pair_pitch < plane(N, g->index_pitch, k)) return fail(JSGX_ERR_INVALID, who, "index_pair_pitch does not cover a plane");
-    if (g->weights && g->weights_pitch < k) return fail(JSGX_ERR_INVALID, who, "weights_pitch smaller than k");
-    if (g->weights && P > 1 && g->weights_pair_pitch < plane(N, g->weights_pitch, k)) return fail(JSGX_ERR_INVALID, who, "weights_pair_pitch does not cover a plane");
-    if (g->out_frame_pitch < F) return fail(JSGX_ERR_INVALID, who, "out_frame_pitch smaller than n_features");
-    if (P > 1 && g->out_pair_pitch < plane(N, g->out_frame_pitch, F)) return fail(JSGX_ERR_INVALID, who, "out_pair_pitch does not cover a plane");
-    const i128 out0 = addr(g->out), out_bytes = span_bytes(P, g->out_pair_pitch, plane(N, g->out_frame_pitch, F), 4);
-    if (overlap(out0, out_bytes, addr(g->s), span_bytes(P, g->s_pair_pitch, plane(N, g->s_frame_pitch, F), 4))) return fail(JSGX_ERR_INVALID, who, "out overlaps s");
-    if (overlap(out0, out_bytes, addr(g->nn_index), span_bytes(P, g->index_pair_pitch, plane(N, g->index_pitch, k), 4))) return fail(JSGX_ERR_INVALID, who, "out overlaps nn_index");
-    if (g->weights && overlap(out0, out_bytes, addr(g->weights), span_bytes(P, g->weights_pair_pitch, plane(N, g->weights_pitch, k), 4)))
-        return fail(JSGX_ERR_INVALID, who, "out overlaps weights");
+    const long long N = g->n, F = g->n_features, P = g->pairs;
+    i128 s_bytes, index_bytes, weights_bytes = 0, out_bytes;
+    int rc = check_plane(who, "s", "_frame", "n_features", N, F, g->s_frame_pitch, g->s_pair_pitch, P, &s_bytes);
+    if (rc == JSGX_OK) rc = check_plane(who, "index", "", "k", N, g->k, g->index_pitch, g->index_pair_pitch, P, &index_bytes);
+    if (rc == JSGX_OK && g->weights) rc = check_plane(who, "weights", "", "k", N, g->k, g->weights_pitch, g->weights_pair_pitch, P, &weights_bytes);
+    if (rc == JSGX_OK) rc = check_plane(who, "out", "_frame", "n_features", N, F, g->out_frame_pitch, g->out_pair_pitch, P, &out_bytes);
+    if (rc != JSGX_OK) return rc;
+    const i128 out0 = addr(g->out);
+    if (overlap(out0, out_bytes, addr(g->s), s_bytes)) return fail(JSGX_ERR_INVALID, who, "out overlaps s");
+    if (overlap(out0, out_bytes, addr(g->nn_index), index_bytes)) return fail(JSGX_ERR_INVALID, who, "out overlaps nn_index");
+    if (g->weights && overlap(out0, out_bytes, addr(g->weights), weights_bytes)) return fail(JSGX_ERR_INVALID, who, "out overlaps weights");
     return JSGX_OK;
 }
 

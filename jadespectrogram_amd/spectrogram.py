@@ -1835,6 +1835,15 @@ def _planes(t, what: str, dtype=None):
     return t
 
 
+def _pair_pitch(t) -> int:
+    return 0 if t.shape[0] == 1 else t.stride(0)      # one plane for every pair: a pair pitch of 0
+
+
+def _plan_xy(n, m, n_features):
+    """The x and y of a ..._plan call's argument block, dense and per pair; never dereferenced."""
+    return 1 << 44, int(n_features), int(n) * int(n_features), 2 << 44, int(n_features), int(m) * int(n_features)
+
+
 def _cdist_args(d_x, d_y, d_cost, metric) -> capix.CdistArgs:
     c = _planes(d_cost, "d_cost")
     P, N, M = c.shape
@@ -1842,8 +1851,7 @@ def _cdist_args(d_x, d_y, d_cost, metric) -> capix.CdistArgs:
     K = x.shape[2]
     assert x.shape[1] == N and y.shape[1] == M and y.shape[2] == K and x.shape[0] in (1, P) and y.shape[0] in (1, P), \
         "d_x [pairs or 1][n][features], d_y [pairs or 1][m][features], d_cost [pairs][n][m]"
-    pair = lambda t: 0 if t.shape[0] == 1 else t.stride(0)      # one sequence for every pair: a pair pitch of 0
-    return capix.CdistArgs(x.data_ptr(), x.stride(1), pair(x), y.data_ptr(), y.stride(1), pair(y), P, K, N, M, _named(_METRICS, metric, "metric"), 0,
+    return capix.CdistArgs(x.data_ptr(), x.stride(1), _pair_pitch(x), y.data_ptr(), y.stride(1), _pair_pitch(y), P, K, N, M, _named(_METRICS, metric, "metric"), 0,
                            c.data_ptr(), c.stride(1), c.stride(0))
 
 
@@ -1857,8 +1865,8 @@ def cdist_launch(d_x, d_y, d_cost, *, metric: str = "euclidean", stream: int | N
 
 def cdist_plan(n: int, m: int, n_features: int, pairs: int = 1, metric: str = "euclidean"):
     """jsgx_cdist_plan: (kernel name, lanes per workgroup, bytes of LDS per workgroup) for this shape.  Needs no device."""
-    a = capix.CdistArgs(1 << 44, int(n_features), int(n) * int(n_features), 2 << 44, int(n_features), int(m) * int(n_features), int(pairs), int(n_features),
-                        int(n), int(m), _named(_METRICS, metric, "metric"), 0, 3 << 44, int(m), int(n) * int(m))      # never dereferenced
+    a = capix.CdistArgs(*_plan_xy(n, m, n_features), int(pairs), int(n_features), int(n), int(m), _named(_METRICS, metric, "metric"), 0,
+                        3 << 44, int(m), int(n) * int(m))      # never dereferenced
     name, threads, lds = C.create_string_buffer(32), C.c_int32(), C.c_int32()
     capix.check(capix.lib().jsgx_cdist_plan(C.byref(a), name, 32, C.byref(threads), C.byref(lds)))
     return name.value.decode(), threads.value, lds.value
@@ -2260,10 +2268,6 @@ def pyin(x, sr: float, fmin: float, fmax: float, frame_length: int = 2048, hop_l
 _REC_MODES = {"connectivity": capix.REC_CONNECTIVITY, "distance": capix.REC_DISTANCE, "affinity": capix.REC_AFFINITY}
 
 
-def _pair_pitch(t) -> int:
-    return 0 if t.shape[0] == 1 else t.stride(0)      # one plane for every pair: a pair pitch of 0
-
-
 def _knn_args(d_x, d_y, d_index, d_dist, width, metric, split) -> capix.KnnArgs:
     import torch
     ix, ds = _planes(d_index, "d_index", torch.int32), _planes(d_dist, "d_dist")
@@ -2298,9 +2302,8 @@ def knn_launch(d_x, d_y, d_index, d_dist, *, width: int = 0, metric: str = "eucl
 def knn_plan(n: int, m: int, n_features: int, k: int, pairs: int = 1, metric: str = "euclidean", split: int = 0, n_cu: int = 256):
     """jsgx_knn_plan: (kernel name, rows of a strip, workgroups per strip S, lanes per workgroup, bytes of LDS per workgroup) for this
     shape on a device of n_cu compute units.  Needs no device."""
-    a = capix.KnnArgs(1 << 44, int(n_features), int(n) * int(n_features), 2 << 44, int(n_features), int(m) * int(n_features), int(pairs), int(n_features),
-                      int(n), int(m), _named(_METRICS, metric, "metric"), int(k), 0, int(split), 3 << 44, int(k), int(n) * int(k), 4 << 44, int(k),
-                      int(n) * int(k))      # never dereferenced
+    a = capix.KnnArgs(*_plan_xy(n, m, n_features), int(pairs), int(n_features), int(n), int(m), _named(_METRICS, metric, "metric"), int(k), 0, int(split),
+                      3 << 44, int(k), int(n) * int(k), 4 << 44, int(k), int(n) * int(k))      # never dereferenced
     name, out = C.create_string_buffer(32), [C.c_int32() for _ in range(4)]
     capix.check(capix.lib().jsgx_knn_plan(C.byref(a), int(n_cu), name, 32, *[C.byref(o) for o in out]))
     return (name.value.decode(),) + tuple(o.value for o in out)

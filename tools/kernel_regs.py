@@ -13,7 +13,8 @@ instruction-mix counts from the disassembly.  CPU only (llvm-objcopy / clang-off
                                                                jsg_spectral.o the spectral shape kernels;
                                                                jsgx_beat.o, of libjsgx.so, the beat tracker, jsgx_cdist.o the
                                                                pairwise cost, jsgx_dtw.o the time warping, jsgx_viterbi.o
-                                                               the Viterbi kernels and jsgx_pyin.o the pYIN kernels: name them)
+                                                               the Viterbi kernels, jsgx_pyin.o the pYIN kernels and jsgx_knn.o
+                                                               the nearest-frame, recurrence and nn_filter kernels: name them)
 """
 import os
 import re
@@ -73,7 +74,8 @@ def main():
                 if not any(k in name for k in ("stft_db_kernel", "fb_band_kernel", "colormap_axis_kernel", "cstft_fwd_kernel", "istft_c2r_kernel", "istft_ola_kernel", "pvoc_walk_kernel",
                                                "pvoc_scan_kernel", "hpss_freq_kernel", "hpss_time_kernel", "resample_kernel", "cqt_kernel", "yin_kernel", "onset_kernel", "tempogram_kernel", "tempo_kernel", "mfcc_kernel", "delta_kernel", "spectral_regs_kernel",
                                                "spectral_stream_kernel", "beat_kernel", "cdist_kernel", "dtw_kernel", "dtw_backtrace_kernel", "viterbi_forward_kernel",
-                                               "viterbi_jump_kernel", "viterbi_ends_kernel", "viterbi_trace_kernel", "pyin_observe_kernel", "pyin_forward_kernel")):
+                                               "viterbi_jump_kernel", "viterbi_ends_kernel", "viterbi_trace_kernel", "pyin_observe_kernel", "pyin_forward_kernel",
+                                               "knn_kernel", "knn_merge_kernel", "recurrence_kernel", "nn_filter_kernel")):
                     continue
                 mx = mix.get(name, {})
                 valu = sum(c for o, c in mx.items() if o.startswith("v_"))
