@@ -889,6 +889,119 @@ typedef struct jsgx_nn_filter_args {
  * (pairs > 1); out overlapping s, out overlapping nn_index, out overlapping weights.  Then JSGX_ERR_NO_DEVICE without a HIP device. */
 JSGX_API int jsgx_nn_filter_launch(const jsgx_nn_filter_args* args, void* stream);
 
+/* Section 9 was added to version 1 in the same way: sections 1 to 8, their structs and their constants are as they were. */
+
+/* ------------------------------------------------------------------------------------------------
+ * 9. Recurrence quantification alignment (librosa.sequence.rqa, the third function of librosa.sequence): the best-scoring aligned run
+ *    through a similarity plane, with gaps and, optionally, knight moves.  R[i][j] = sim[p*sim_pair_pitch + i*sim_pitch + j], i < N,
+ *    j < M: a plane of section 7 (affinity mode, or cross-similarity) or any plane the caller filled.  Pairs are independent.  All
+ *    arithmetic is float32 and uncontracted (there are only additions, subtractions and comparisons); fl(.) is one rounding to float32.
+ *
+ *    Links.  A cell is a link iff R[i][j] > 0, the comparison as written: a NaN, a zero or a negative value is no link.
+ *    Steps, as (di, dj):  k = 0: (1, 1),  k = 1: (1, 2),  k = 2: (2, 1).  With knight = 0 only k = 0 is a step.  The candidates of a cell
+ *    are the steps whose predecessor pred_k = (i - di, j - dj) lies inside the matrix; for i, j >= 1, k = 0 always is one.
+ *
+ *    Border cells (i == 0 or j == 0):  S = R, with its bits;  step = -2 where the cell is a link, else -1.
+ *    Every other cell, over its candidates in ascending k:
+ *        link cell:      v_k = S[pred_k]
+ *        non-link cell:  v_k = fl(S[pred_k] - pen_k),  pen_k = gap_onset where pred_k is a link, else gap_extend
+ *        best = v of the lowest candidate;  for each later candidate:  if (v_k > best) best = v_k;      k* = the k that was kept
+ *        link cell:      S = fl(best + R[i][j]);  step = k*
+ *        non-link cell:  if (best > 0) { S = best; step = k*; } else { S = +0; step = -1; }
+ *    The comparison is strict: the lowest k wins ties, a NaN v_k never replaces best, a NaN first candidate stays, and a NaN best
+ *    resets a non-link cell.  S[i][j] is a function of the plane alone: it does not depend on the tile sizes, on pairs, on the pitches
+ *    or on which outputs are NULL.
+ *
+ *    End cell.  Among the cells with S > 0 the one with the largest S; among equal S the lowest i, then the lowest j: numpy's flat
+ *    argmax order, stated as a total order on (S, i, j), so its maximum is associative and commutative and does not depend on how a
+ *    kernel splits the cells.  Where no cell has S > 0:  path_len[p] = 0, total[p] = +0, end[p] = (-1, -1) and no path is written: a
+ *    result, not a refusal.
+ *    Backtrace.  No step plane is kept for it: as in section 3 the step of the current cell is recomputed from S and R with the same
+ *    operations and the same selection.  At each cell:  step -1: stop, the cell is not part of the path.  Otherwise the cell is part of
+ *    the path;  step -2: stop;  otherwise move to pred_k*.  Every step lowers both i and j, so a path has at most min(N, M) cells.
+ *    Outputs.  score[p*score_pair_pitch + i*score_pitch + j] = S, required.  step[p*step_pair_pitch + i*step_pitch + j]: the int8
+ *    values above, optional.  path_i and path_j at [p*path_pitch + n], n < path_len[p], ascending, the start first.  end[2p], end[2p+1] =
+ *    (i, j) of the end cell.  total[p] = S there.
+ *
+ *    Known answers.  An all-zero plane: S = +0 everywhere, every step is -1, path_len is 0.  The N x N identity, either knight: the
+ *    path is the main diagonal, total = N exactly, and the end cell is unique.  The identity with R[g][g] and R[g+1][g+1] cleared,
+ *    2 <= g, knight = 0:  total = N - 2 - gap_onset - gap_extend and the path is still the whole diagonal, the two gap cells having
+ *    S > 0 (N = 70, g = 2, penalties 0.5 and 0.25: 67.25); with knight = 1 the same plane is bridged by a knight move: total 67.5,
+ *    69 cells.
+ *
+ *    Differences from librosa.sequence.rqa: a link is R > 0 everywhere (librosa tests truthiness on the border); the NaN and tie rules
+ *    are the ones above; score is float32.  Agreement with librosa has not been measured: librosa is not installed where this was
+ *    built.  No error bound is claimed, since gaps subtract; on planes and penalties that are small integers or dyadic fractions every
+ *    operation is exact.
+ *
+ *    The kernels.  The three predecessors lie in an earlier row AND an earlier column, so the cells of one row are independent of each
+ *    other and the skewed sweep of section 3 is not needed.  S is cut into the tiles of section 3 (JSGX_DTW_TILE_ROWS x
+ *    JSGX_DTW_TILE_COLS) and "rqa_tiles" is launched once per tile anti-diagonal over pairs x (tiles on it), one wavefront per tile.  A
+ *    tile reads its halo from score itself -- the two rows above, the two columns to the left and the corner between them, which
+ *    earlier launches on the stream wrote -- and the matching cells of sim; no workgroup waits for another.  Inside the tile lane l
+ *    owns column l and the rows are walked top to bottom, 64 steps: S(i-1, j-1) is one DPP wave shift of the row above (lane 0 takes
+ *    the left halo), S(i-1, j-2) a second shift of that, S(i-2, j-1) the first shift of the step before; the penalties of the
+ *    predecessors travel the same way.  R comes in and S goes out through LDS in whole lines, and a step's LDS operands are read two
+ *    steps ahead.  The forms with and without knight moves and with and without a step plane are separate kernels, and the tiles that
+ *    hold row 0 or column 0 take a form of their own, so the border rule is not in the hot one.  Where path_len, end or total is given
+ *    a tile also reduces its best (S, i, j) by the key above into the scratch (8 bytes a tile: S and i * 65536 + j), and
+ *    "rqa_backtrace", one wavefront per pair, reduces those entries, so the plane is not read a second time for the end cell; it then
+ *    fetches JSGX_RQA_WINDOW x JSGX_RQA_WINDOW windows of S and R that end at the current cell and walks inside each while two rows
+ *    and two columns of halo remain (at least 15 steps per round trip to memory), writes the path backwards into the scratch and copies
+ *    it out reversed.  Every loop is bounded by min(N, M).
+ * ------------------------------------------------------------------------------------------------ */
+#define JSGX_RQA_THREADS 64
+#define JSGX_RQA_LDS_BYTES 17408           /* static, of the forward kernels: the tile 64 x 64 words, the left halo 64 x 4 words */
+#define JSGX_RQA_WINDOW 32
+
+typedef struct jsgx_rqa_args {
+    const float* sim;           /* device floats: R */
+    int64_t sim_pitch;          /* >= m */
+    int64_t sim_pair_pitch;     /* pairs > 1: >= (n - 1) * sim_pitch + m */
+    int32_t pairs;              /* 1..65535 */
+    int32_t n;                  /* N, 1..JSGX_DTW_MAX_LEN */
+    int32_t m;                  /* M, 1..JSGX_DTW_MAX_LEN */
+    int32_t knight;             /* 0 or 1 */
+    float gap_onset;            /* finite, >= 0 */
+    float gap_extend;           /* finite, >= 0 */
+    int32_t reserved0;          /* 0 */
+    int32_t max_path;           /* paths given: >= min(n, m) */
+    float* score;               /* device floats: S, required */
+    int64_t score_pitch;        /* >= m */
+    int64_t score_pair_pitch;   /* pairs > 1: >= (n - 1) * score_pitch + m */
+    int8_t* step;               /* device int8 or NULL */
+    int64_t step_pitch;         /* step given: >= m */
+    int64_t step_pair_pitch;    /* step given and pairs > 1: >= (n - 1) * step_pitch + m */
+    int32_t* path_i;            /* device int32 or NULL (then path_j NULL too) */
+    int32_t* path_j;
+    int64_t path_pitch;         /* pairs > 1 and paths given: >= max_path */
+    int32_t* path_len;          /* device int32 [pairs]; required with the paths, else optional */
+    int32_t* end;               /* device int32 [pairs][2] or NULL */
+    float* total;               /* device floats [pairs] or NULL */
+} jsgx_rqa_args;                /* 152 bytes, no padding */
+
+/* The bytes of scratch the launch needs: 8 * pairs * tiles for the tiles' best cells where path_len, end or total is given (tiles =
+ * ceil(n / JSGX_DTW_TILE_ROWS) * ceil(m / JSGX_DTW_TILE_COLS)), plus 8 * pairs * min(n, m) where the paths are given; else 0.  Refused
+ * (a negative jsgx_status): what the launch refuses before it looks at the scratch. */
+JSGX_API int64_t jsgx_rqa_scratch_bytes(const jsgx_rqa_args* args);
+/* Enqueue only: no allocation, no synchronisation; capture works, a first launch included.  The kernels (one per tile anti-diagonal,
+ * then the backtrace where path_len, end or total is given) go onto the one stream as a plain chain.  Refused (JSGX_ERR_INVALID,
+ * nothing enqueued), in this order and before any device call: null args, a null sim, a null score, one of path_i and path_j without
+ * the other, paths without path_len; a float or int32 pointer that is not 4-byte aligned; pairs outside 1..65535, n outside 1..65536,
+ * m outside 1..65536, knight other than 0 or 1, a gap_onset that is not finite and >= 0, the same for gap_extend; a non-zero
+ * reserved0; max_path below min(n, m) (paths given); sim_pitch below m, sim_pair_pitch that does not cover a plane (pairs > 1), the
+ * same for score_pitch and score_pair_pitch and (step given) for step_pitch and step_pair_pitch, path_pitch below max_path (pairs > 1,
+ * paths given); score overlapping sim, another output (step, path_i, path_j, path_len, end, total) overlapping sim, two outputs
+ * (score among them) overlapping each other; a null scratch, a scratch that is not 4-byte aligned, scratch_bytes below the size above
+ * (each only where that size is not 0).  Then JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_rqa_launch(const jsgx_rqa_args* args, void* scratch, int64_t scratch_bytes, void* stream);
+/* What the launch enqueues, without a device: the name of the forward kernel ("rqa_tiles"), the tile sizes, the number of kernel
+ * launches (the tile anti-diagonals, ceil(n / tile_rows) + ceil(m / tile_cols) - 1, plus one for "rqa_backtrace" where path_len, end or
+ * total is given), JSGX_RQA_THREADS and JSGX_RQA_LDS_BYTES.  Any output pointer may be NULL (name: else name_len >= 16).  Refused: a
+ * name_len below 16 with a name, then what the scratch size refuses. */
+JSGX_API int jsgx_rqa_plan(const jsgx_rqa_args* args, char* name, int name_len, int32_t* tile_rows, int32_t* tile_cols, int32_t* n_launches,
+                           int32_t* threads, int32_t* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif

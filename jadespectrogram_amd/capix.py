@@ -108,6 +108,17 @@ class NnFilterArgs(C.Structure):
                 ("n", C.c_int32), ("n_features", C.c_int32), ("k", C.c_int32), ("out", C.c_void_p), ("out_frame_pitch", C.c_int64), ("out_pair_pitch", C.c_int64)]
 
 
+RQA_THREADS, RQA_LDS_BYTES, RQA_WINDOW = 64, 17408, 32
+
+
+class RqaArgs(C.Structure):
+    _fields_ = [("sim", C.c_void_p), ("sim_pitch", C.c_int64), ("sim_pair_pitch", C.c_int64), ("pairs", C.c_int32), ("n", C.c_int32), ("m", C.c_int32),
+                ("knight", C.c_int32), ("gap_onset", C.c_float), ("gap_extend", C.c_float), ("reserved0", C.c_int32), ("max_path", C.c_int32),
+                ("score", C.c_void_p), ("score_pitch", C.c_int64), ("score_pair_pitch", C.c_int64), ("step", C.c_void_p), ("step_pitch", C.c_int64),
+                ("step_pair_pitch", C.c_int64), ("path_i", C.c_void_p), ("path_j", C.c_void_p), ("path_pitch", C.c_int64), ("path_len", C.c_void_p),
+                ("end", C.c_void_p), ("total", C.c_void_p)]
+
+
 # every symbol include/jsgx.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -140,6 +151,9 @@ SIGNATURES = {
     "jsgx_knn_plan": (C.c_int, [C.POINTER(KnnArgs), C.c_int32, C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 4),
     "jsgx_recurrence_launch": (C.c_int, [C.POINTER(RecurrenceArgs), _P]),
     "jsgx_nn_filter_launch": (C.c_int, [C.POINTER(NnFilterArgs), _P]),
+    "jsgx_rqa_scratch_bytes": (C.c_int64, [C.POINTER(RqaArgs)]),
+    "jsgx_rqa_launch": (C.c_int, [C.POINTER(RqaArgs), _P, C.c_int64, _P]),
+    "jsgx_rqa_plan": (C.c_int, [C.POINTER(RqaArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 5),
 }
 
 _lib = None

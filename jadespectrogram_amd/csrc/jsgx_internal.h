@@ -81,6 +81,16 @@ struct KnnPlan {
 };
 KnnPlan knn_plan(const jsgx_knn_args* g, int n_cu);
 
+// section 9 (jsgx_rqa_host.cpp): every refusal that does not look at the scratch, in the header's order
+int rqa_check(const jsgx_rqa_args* g, const char* who);
+// Where the parts of the scratch of section 9 lie: the tiles' best cells at 0 (8 bytes a tile), the reversed paths behind them.
+struct RqaScratch {
+    long long tiles;               // of one pair
+    long long off_paths, bytes;
+};
+RqaScratch rqa_scratch(const jsgx_rqa_args* g);
+int rqa_launches(const jsgx_rqa_args* g);          // the kernels jsgx_rqa_launch enqueues
+
 // The three refusals of a launch's scratch buffer, in this order; `sizer` names the call that states `need`.
 inline int check_scratch(const char* who, const void* scratch, int64_t scratch_bytes, int64_t need, const char* sizer) {
     if (!scratch) return fail(JSGX_ERR_INVALID, who, "null scratch");

@@ -1974,6 +1974,91 @@ def dtw(X=None, Y=None, *, C=None, metric="euclidean", weights_mul=None, weights
 
 
 # --------------------------------------------------------------------------------------------------
+# recurrence quantification alignment (include/jsgx.h, section 9: libjsgx.so)
+# --------------------------------------------------------------------------------------------------
+def _rqa_args(d_sim, d_score, gap_onset, gap_extend, knight_moves, d_step, d_path_i, d_path_j, d_path_len, d_end, d_total) -> capix.RqaArgs:
+    import torch
+    r, s = _planes(d_sim, "d_sim"), _planes(d_score, "d_score")
+    P, N, M = r.shape
+    assert tuple(s.shape) == (P, N, M), "d_score: the shape of d_sim"
+    ptr = lambda t: None if t is None else t.data_ptr()
+    step_ptr, step_pitch, step_pair_pitch = None, 0, 0
+    if d_step is not None:
+        st = _planes(d_step, "d_step", torch.int8)
+        assert tuple(st.shape) == (P, N, M), "d_step: int8, the shape of d_sim"
+        step_ptr, step_pitch, step_pair_pitch = st.data_ptr(), st.stride(1), st.stride(0)
+    path_pitch = max_path = 0
+    if d_path_i is not None and d_path_j is not None:
+        pi, pj = (t[None] if t.dim() == 1 else t for t in (d_path_i, d_path_j))
+        for t in (pi, pj):
+            assert t.is_cuda and t.dtype == torch.int32 and t.dim() == 2 and t.shape[0] == P and (t.stride(1) == 1 or t.shape[1] == 1), "d_path_i, d_path_j: int32 CUDA [pairs][max_path]"
+        assert pi.shape == pj.shape and pi.stride(0) == pj.stride(0), "d_path_i and d_path_j: one shape and pitch"
+        path_pitch, max_path = pi.stride(0), pi.shape[1]
+    for t, dtype, count, what in ((d_path_len, torch.int32, P, "d_path_len: int32 CUDA [pairs]"), (d_end, torch.int32, 2 * P, "d_end: int32 CUDA [pairs][2]"),
+                                  (d_total, torch.float32, P, "d_total: float32 CUDA [pairs]")):
+        assert t is None or (t.is_cuda and t.dtype == dtype and t.numel() >= count and t.is_contiguous()), what
+    return capix.RqaArgs(r.data_ptr(), r.stride(1), r.stride(0), P, N, M, int(bool(knight_moves)), float(gap_onset), float(gap_extend), 0, max_path,
+                         s.data_ptr(), s.stride(1), s.stride(0), step_ptr, step_pitch, step_pair_pitch, ptr(d_path_i), ptr(d_path_j), path_pitch,
+                         ptr(d_path_len), ptr(d_end), ptr(d_total))
+
+
+def rqa_scratch_bytes(d_sim, d_score, *, gap_onset: float = 1.0, gap_extend: float = 1.0, knight_moves: bool = True, d_step=None, d_path_i=None,
+                      d_path_j=None, d_path_len=None, d_end=None, d_total=None) -> int:
+    """jsgx_rqa_scratch_bytes: the bytes of scratch rqa_launch needs for these arguments (0 for the score alone)."""
+    a = _rqa_args(d_sim, d_score, gap_onset, gap_extend, knight_moves, d_step, d_path_i, d_path_j, d_path_len, d_end, d_total)
+    return int(capix.check(capix.lib().jsgx_rqa_scratch_bytes(C.byref(a))))
+
+
+def rqa_launch(d_sim, d_score, *, gap_onset: float = 1.0, gap_extend: float = 1.0, knight_moves: bool = True, d_step=None, d_path_i=None,
+               d_path_j=None, d_path_len=None, d_end=None, d_total=None, d_scratch=None, stream: int | None = None):
+    """jsgx_rqa_launch: d_sim float32 [n][m] or [pairs][n][m] (a cell is a link where it is > 0) -> d_score (S, the same shape), and where
+    given d_step int8 (the step of every cell: 0, 1, 2, -1 no step, -2 a start on the border), d_path_i, d_path_j int32
+    [pairs][max_path >= min(n, m)] (the best aligned run, ascending), d_path_len int32 [pairs] (its length; 0: no cell with S > 0),
+    d_end int32 [pairs][2] (its last cell, or -1, -1) and d_total float32 [pairs] (S there).  Enqueue only: one kernel per tile
+    anti-diagonal, then the backtrace."""
+    import torch
+    a = _rqa_args(d_sim, d_score, gap_onset, gap_extend, knight_moves, d_step, d_path_i, d_path_j, d_path_len, d_end, d_total)
+    d_scratch, stream = _scratch_and_stream(d_scratch, stream, d_sim, lambda: max(1, capix.check(capix.lib().jsgx_rqa_scratch_bytes(C.byref(a))) // 4), torch.int32,
+                                            any_dtype=True)
+    capix.check(capix.lib().jsgx_rqa_launch(C.byref(a), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), stream))
+
+
+def rqa_plan(n: int, m: int, pairs: int = 1, backtrack: bool = True):
+    """jsgx_rqa_plan: (kernel name, tile rows, tile columns, kernel launches, lanes per workgroup, bytes of LDS per workgroup) for this
+    shape: one launch per tile anti-diagonal and one for the backtrace.  Needs no device."""
+    a = capix.RqaArgs(sim=1 << 44, sim_pitch=int(m), sim_pair_pitch=int(n) * int(m), pairs=int(pairs), n=int(n), m=int(m), knight=1, gap_onset=1.0, gap_extend=1.0,
+                      score=2 << 44, score_pitch=int(m), score_pair_pitch=int(n) * int(m), path_len=(3 << 44) if backtrack else None)      # never dereferenced
+    name, out = C.create_string_buffer(32), [C.c_int32() for _ in range(5)]
+    capix.check(capix.lib().jsgx_rqa_plan(C.byref(a), name, 32, *[C.byref(o) for o in out]))
+    return (name.value.decode(),) + tuple(o.value for o in out)
+
+
+def rqa(sim, gap_onset=1.0, gap_extend=1.0, knight_moves=True, backtrack=True):
+    """librosa.sequence.rqa on the GPU: from a similarity plane sim [N, M] (a numpy array or a float32 CUDA tensor; recurrence_matrix in
+    affinity mode and cross_similarity make one) -> (score, path): the alignment score of every cell [N, M] and the best aligned run,
+    int32 [L, 2] ascending, as CUDA tensors; backtrack False: score alone.  A plane without a positive score has an empty path.  A leading
+    axis of P pairs is allowed: score is [P, N, M] and path a list.  Reading the path lengths is the one host synchronisation.  A cell
+    is a link where sim > 0; the differences from librosa are listed in include/jsgx.h section 9."""
+    import torch
+    s, _ = _to_cuda(sim)
+    assert s.dim() in (2, 3), "rqa: sim [N, M] or [P, N, M]"
+    s = s.contiguous()
+    batched = s.dim() == 3
+    s3 = s if batched else s[None]
+    P, N, M = s3.shape
+    score = torch.empty_like(s3)
+    with torch.cuda.device(_device_index(s)):
+        if not backtrack:
+            rqa_launch(s3, score, gap_onset=gap_onset, gap_extend=gap_extend, knight_moves=knight_moves)
+            return score if batched else score[0]
+        path = torch.empty((2, P, min(N, M)), dtype=torch.int32, device=s.device)
+        length = torch.empty((P,), dtype=torch.int32, device=s.device)
+        rqa_launch(s3, score, gap_onset=gap_onset, gap_extend=gap_extend, knight_moves=knight_moves, d_path_i=path[0], d_path_j=path[1], d_path_len=length)
+    wp = [torch.stack((path[0, p, :L], path[1, p, :L]), dim=1) for p, L in enumerate(length.tolist())]           # the one host synchronisation
+    return (score, wp) if batched else (score[0], wp[0])
+
+
+# --------------------------------------------------------------------------------------------------
 # Viterbi decoding of hidden Markov models (include/jsgx.h, section 4: libjsgx.so)
 # --------------------------------------------------------------------------------------------------
 def _viterbi_args(d_log_emit, d_log_init, d_log_trans, d_states, band_half, d_logp, d_value) -> capix.ViterbiArgs:
