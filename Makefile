@@ -22,7 +22,7 @@ XHOST_UNITS := jsgx_beat_host jsgx_dtw_host jsgx_viterbi_host jsgx_pyin_host jsg
 SHARED := $(SRC)/jsg_spans.h $(SRC)/jsg_launch.h
 KDEPS  := $(SRC)/jsg_stft_kernel.h $(SRC)/jsg_runs_grid.h $(SRC)/jsg_internal.h $(SRC)/jsg_exact_math.h $(SHARED) include/jsg.h
 HDEPS  := $(SRC)/jsg_internal.h $(SRC)/jsg_block_queue.h $(SRC)/jsg_exact_math.h $(SRC)/jsg_colormap_tables.inc $(SHARED) include/jsg.h
-XDEPS  := $(SRC)/jsgx_internal.h $(SRC)/jsgx_cost_tile.h $(SHARED) include/jsgx.h
+XDEPS  := $(SRC)/jsgx_internal.h $(SRC)/jsgx_cost_tile.h $(SRC)/jsgx_plane_tiles.h $(SHARED) include/jsgx.h
 
 $(HIP_UNITS:%=$(OBJ)/%.o): $(KDEPS)
 $(HOST_UNITS:%=$(OBJ)/%.o): $(HDEPS)

@@ -31,7 +31,7 @@ ARCH = "gfx950"
 LIBX = os.path.join(PKG, "libjsgx.so")
 SOURCES_X = ["jsgx_beat.hip", "jsgx_cdist.hip", "jsgx_dtw.hip", "jsgx_viterbi.hip", "jsgx_pyin.hip", "jsgx_knn.hip", "jsgx_rqa.hip", "jsgx_beat_host.cpp", "jsgx_dtw_host.cpp", "jsgx_viterbi_host.cpp",
              "jsgx_pyin_host.cpp", "jsgx_knn_host.cpp", "jsgx_rqa_host.cpp"]
-HEADERS_X = ["jsgx_internal.h", "jsgx_cost_tile.h", "jsg_spans.h", "jsg_launch.h", os.path.join(ROOT, "include", "jsgx.h")]
+HEADERS_X = ["jsgx_internal.h", "jsgx_cost_tile.h", "jsgx_plane_tiles.h", "jsg_spans.h", "jsg_launch.h", os.path.join(ROOT, "include", "jsgx.h")]
 
 
 def _hipcc() -> str:

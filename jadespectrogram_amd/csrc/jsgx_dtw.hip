@@ -1,40 +1,32 @@
 // libjsgx.so, dynamic time warping over a cost plane (include/jsgx.h section 3): the two kernels and their launcher.  The refusals, the
-// scratch size and the plan are in jsgx_dtw_host.cpp.
+// scratch size and the plan are in jsgx_dtw_host.cpp; the tiles, their launches, the staging, the lane move and the backtrace's window and
+// path output are jsgx_plane_tiles.h, shared with jsgx_rqa.hip.
 //
-// dtw_kernel.  D is cut into tiles of 64 x 64; the launcher enqueues one launch per tile anti-diagonal over pairs x (tiles on it),
-// one wavefront per tile.  A tile depends on the tiles above, left and above-left of it, all on earlier anti-diagonals, so it reads
-// its top row, left column and corner from D in global memory and never waits for another workgroup.  Inside the tile the sweep is
-// skewed: lane l owns row l and at step s computes column c = s - l.  Its three neighbours are
+// dtw_kernel.  A tile reads its top row, left column and corner from D in global memory.  Inside the tile the sweep is skewed: lane l
+// owns row l and at step s computes column c = s - l.  Its three neighbours are
 //     left  (l, c-1)     its own value of the step before
-//     up    (l-1, c)     what lane l-1 computed in the step before: one wave shift per step
+//     up    (l-1, c)     what lane l-1 computed in the step before: one lane move per step
 //     diag  (l-1, c-1)   the `up` of the step before
-// and for lane 0 the top row (top[0] is the corner), for column 0 the left column.  The shift is a DPP wave_shr:1 (one v_mov with
-// a DPP modifier on the dependent chain, whose old operand hands lane 0 its top-row value; built with -DJSGX_DTW_SHFL it is
-// __shfl_up, a ds_bpermute through the LDS pipe, for the comparison that profiles/dtw_bench.md reports).
-//   tile[64][64]    C on the way in, D on the way out, in place (a cell's C is read before the step that writes its D); the global
-//                   accesses are whole 256-byte lines; lane l reads word l * 64 + s - l: 64 different banks
+// and for lane 0 the top row (top[0] is the corner), for column 0 the left column.
+//   tile[64][64]    C on the way in, D on the way out (a cell's C is read before the step that writes its D); lane l reads word
+//                   l * 64 + s - l: 64 different banks
 //   top[65 + 3]     D of the row above the tile, from the corner on; +inf outside the matrix
 // The tile is as wide as it is high because the chain of dependent steps decides the time: a tile takes cols + 63 steps and the tiles
 // of one tile row follow each other, so N x M costs about (N / 64 + M / cols) (cols + 63) steps, least near cols = 64 (measured:
 // profiles/dtw_bench.md).
 // A tile wholly outside the band is filled with +inf and C is not read.
 //
-// dtw_backtrace_kernel.  One wavefront per pair.  The walk is serial, so the wavefront fetches the 32 x 32 window of D and C whose
-// last cell is the current one (one round trip to memory, 16 loads of each per lane), lane 0 walks inside it while the three predecessors
-// are in the window (at least 31 steps), and the window is fetched again around the cell the walk stands on.  The path is written backwards
-// into the scratch and copied out reversed by all lanes.
+// dtw_backtrace_kernel.  The window holds D (+inf outside the matrix) and C; lane 0 walks inside it while the three predecessors are in
+// the window (at least 31 steps).
 #include <hip/hip_runtime.h>
 
 #include <climits>
 
-#include "jsgx_internal.h"
+#include "jsgx_plane_tiles.h"
 
 namespace jsgx {
 
-constexpr int kRows = JSGX_DTW_TILE_ROWS, kCols = JSGX_DTW_TILE_COLS, kLanes = JSGX_DTW_THREADS;
 constexpr int kTop = kCols + 4;
-static_assert(kRows == kLanes && kLanes == 64, "lane l owns row l of a tile: one wavefront");
-static_assert(kCols % 64 == 0, "a row pitch that is a multiple of 64 words keeps the skewed reads on 64 banks");
 static_assert((kRows * kCols + kTop) * 4 == JSGX_DTW_LDS_BYTES, "include/jsgx.h states the LDS");
 
 struct DtwArgs {
@@ -42,30 +34,16 @@ struct DtwArgs {
     Plane<float> acc;
     int n, m, subseq, band;
     float wm0, wm1, wm2, wa0, wa1, wa2;
-    int diagonal, ti_first;         // this launch: the tiles (ti_first + blockIdx.x, diagonal - ti)
+    TileDiagonal at;
 };
 
 struct BacktraceArgs {
     Plane<const float> cost, acc;
     int n, m, subseq;
     float wm0, wm1, wm2, wa0, wa1, wa2;
-    int* path_i;
-    int* path_j;
-    long long path_pitch;
-    int* path_len;
+    PathOut out;                    // longest: n + m - 1
     float* total;
-    int* scratch;                   // [pairs][2][n + m - 1], or null without paths
 };
-
-// the value of lane l - 1; lane 0 receives `lane0` (it has no source lane: the DPP move leaves its old value)
-__device__ __forceinline__ float from_lane_below(float v, float lane0) {
-#if defined(JSGX_DTW_SHFL)
-    const float shifted = __shfl_up(v, 1);
-    return threadIdx.x == 0 ? lane0 : shifted;
-#else
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane0), __float_as_int(v), 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
-#endif
-}
 
 // D of a cell that is not an initial one, from its cost and its three predecessors (include/jsgx.h, "Recurrence"); *k: the step taken
 __device__ __forceinline__ float dtw_cell(float c, float diag, float left, float up, float wm0, float wm1, float wm2, float wa0, float wa1, float wa2, int* k) {
@@ -131,7 +109,9 @@ __global__ __launch_bounds__(kLanes) void dtw_kernel(DtwArgs a) {
     __shared__ float tile[kRows * kCols];
     __shared__ float top[kTop];
     const int l = threadIdx.x;
-    const int ti = a.ti_first + blockIdx.x, tj = a.diagonal - ti;
+    // a.at.place(a.n, a.m), spelled out: through the struct the sweep keeps its instructions and gets other registers, and one tile alone
+    // takes 19.66 us instead of 19.37 us (profiles/dtw_bench.md)
+    const int ti = a.at.ti_first + blockIdx.x, tj = a.at.diagonal - ti;
     const int i0 = ti * kRows, j0 = tj * kCols;
     const int rows = a.n - i0 < kRows ? a.n - i0 : kRows, cols = a.m - j0 < kCols ? a.m - j0 : kCols;
     const float inf = __builtin_inff();
@@ -144,31 +124,19 @@ __global__ __launch_bounds__(kLanes) void dtw_kernel(DtwArgs a) {
         // j (N-1) - i (M-1) is largest at the tile's top right cell and smallest at its bottom left one
         const long long hi = (long long)(j0 + cols - 1) * n1 - (long long)i0 * m1, lo = (long long)j0 * n1 - (long long)(i0 + rows - 1) * m1;
         if (lo > lim || hi < -lim) {
-            for (int r = 0; r < rows; ++r)
-                for (int c = l; c < cols; c += kLanes) D[(long long)r * a.acc.pitch + c] = inf;
+            if (l < cols)
+                for (int r = 0; r < rows; ++r) D[(long long)r * a.acc.pitch + l] = inf;
             return;
         }
     }
-    // every load below is issued without a branch, from an address kept inside the matrix, and what lies outside is replaced afterwards:
-    // the loads of a batch are in flight together.  Tile cells outside the matrix hold copies of cells inside; no step that is used reads them.
+    // the halo is loaded as the tile is: without a branch, from addresses kept inside the matrix, and what lies outside is replaced afterwards
     const long long ap = a.acc.pitch;
     const int row_above = i0 > 0 ? i0 - 1 : 0, col_before = j0 > 0 ? j0 - 1 : 0;
     const float corner_value = Dp[row_above * ap + col_before];
     const float left_value = D[(long long)(l < rows ? l : rows - 1) * ap + (col_before - j0)];
-#pragma unroll
-    for (int c0 = 0; c0 < kCols; c0 += kLanes) {
-        const int c = c0 + l < cols ? c0 + l : cols - 1;
-        const float top_value = Dp[row_above * ap + j0 + c];
-#pragma unroll
-        for (int r0 = 0; r0 < kRows; r0 += 16) {
-            float v[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = C[(long long)(r0 + q < rows ? r0 + q : rows - 1) * a.cost.pitch + c];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) tile[(r0 + q) * kCols + c0 + l] = v[q];
-        }
-        top[1 + c0 + l] = (i0 > 0 && c0 + l < cols) ? top_value : inf;
-    }
+    const float top_value = Dp[row_above * ap + j0 + (l < cols ? l : cols - 1)];
+    stage_tile(tile, C, a.cost.pitch, rows, cols, l);
+    top[1 + l] = (i0 > 0 && l < cols) ? top_value : inf;
     if (l == 0) top[0] = (i0 > 0 && j0 > 0) ? corner_value : inf;
     const float left_edge = (j0 > 0 && l < rows) ? left_value : inf;
     __syncthreads();
@@ -182,25 +150,19 @@ __global__ __launch_bounds__(kLanes) void dtw_kernel(DtwArgs a) {
     else
         dtw_sweep<false, false>(tile, top, a, l, i0, j0, rows, cols, left_edge, diag_edge, n1, m1, lim);
     __syncthreads();
-#pragma unroll 8
-    for (int r = 0; r < rows; ++r)
-        for (int c = l; c < cols; c += kLanes) D[(long long)r * a.acc.pitch + c] = tile[r * kCols + c];
+    store_tile(D, a.acc.pitch, tile, rows, cols, l);
 }
-
-constexpr int kWin = 32;                  // the window of the backtrace: kWin x kWin cells of D and of C, 16 loads of each per lane
 
 __global__ __launch_bounds__(kLanes) void dtw_backtrace_kernel(BacktraceArgs a) {
 #pragma clang fp contract(off)
     __shared__ float wd[kWin * kWin], wc[kWin * kWin], red_v[kLanes];
     __shared__ int red_j[kLanes], red_nan[kLanes];
-    __shared__ int state[4];            // i, j, the cells recorded, 0 walking / 1 at the start / -1 no path
+    __shared__ int state[4];            // set_walk(); the status: 0 walking / 1 at the start / -1 no path
     const int l = threadIdx.x, p = blockIdx.x;
     const float inf = __builtin_inff();
     const float* C = a.cost.row(p, 0);
     const float* D = a.acc.row(p, 0);
-    const int longest = a.n + a.m - 1;
-    int* rev_i = a.scratch ? a.scratch + (long long)p * 2 * longest : nullptr;
-    int* rev_j = rev_i ? rev_i + longest : nullptr;
+    int* rev = a.out.reversed(p);
     // ---- the end cell
     int end_j = a.m - 1, no_path = 0;
     if (a.subseq) {
@@ -235,27 +197,14 @@ __global__ __launch_bounds__(kLanes) void dtw_backtrace_kernel(BacktraceArgs a) 
         no_path = state[1];
         __syncthreads();
     }
-    if (l == 0) {
-        state[0] = a.n - 1;
-        state[1] = end_j;
-        state[2] = 0;
-        state[3] = no_path ? -1 : 0;
-    }
+    if (l == 0) set_walk(state, a.n - 1, end_j, 0, no_path ? -1 : 0);
     // ---- the walk, window by window
     for (;;) {
         __syncthreads();
         const int i = state[0], j = state[1], status = state[3];
         if (status != 0) break;
-#pragma unroll
-        for (int u = 0; u < kWin * kWin / kLanes; ++u) {    // unconditional loads from addresses kept inside the matrix: all in flight together
-            const int q = u * kLanes + l;
-            const int gi = i - (kWin - 1) + q / kWin, gj = j - (kWin - 1) + q % kWin;
-            const bool in = gi >= 0 && gj >= 0;             // gi <= i < n and gj <= j < m
-            const long long ri = gi < 0 ? 0 : gi, rj = gj < 0 ? 0 : gj;
-            const float dv = D[ri * a.acc.pitch + rj], cv = C[ri * a.cost.pitch + rj];
-            wd[q] = in ? dv : inf;
-            wc[q] = cv;
-        }
+        fetch_window<true>(wd, D, a.acc.pitch, i, j, l);
+        fetch_window<false>(wc, C, a.cost.pitch, i, j, l);
         __syncthreads();
         if (l == 0) {
             int r = kWin - 1, c = kWin - 1, ci = i, cj = j, count = state[2], st = 0;
@@ -265,15 +214,11 @@ __global__ __launch_bounds__(kLanes) void dtw_backtrace_kernel(BacktraceArgs a) 
                 const float diag = wd[(r - 1) * kWin + c - 1], left = wd[r * kWin + c - 1], up = wd[(r - 1) * kWin + c];
                 int k;
                 dtw_cell(cost, diag, left, up, a.wm0, a.wm1, a.wm2, a.wa0, a.wa1, a.wa2, &k);
-                if (d != d || d == inf || count >= longest) {
+                if (d != d || d == inf || count >= a.out.longest) {
                     st = -1;
                     break;
                 }
-                if (rev_i) {
-                    rev_i[count] = ci;
-                    rev_j[count] = cj;
-                }
-                ++count;
+                a.out.record(rev, count++, ci, cj);
                 if (ci == 0 && (a.subseq || cj == 0)) {
                     st = 1;
                     break;
@@ -285,27 +230,17 @@ __global__ __launch_bounds__(kLanes) void dtw_backtrace_kernel(BacktraceArgs a) 
                     break;
                 }
             }
-            state[0] = ci;
-            state[1] = cj;
-            state[2] = count;
-            state[3] = st;
+            set_walk(state, ci, cj, count, st);
         }
     }
     const int L = state[2];
     if (state[3] < 0) {
-        if (l == 0 && a.path_len) a.path_len[p] = -1;
+        if (l == 0 && a.out.path_len) a.out.path_len[p] = -1;
         return;
     }
-    if (a.path_i) {
-        int* out_i = a.path_i + p * a.path_pitch;
-        int* out_j = a.path_j + p * a.path_pitch;
-        for (int q = l; q < L; q += kLanes) {
-            out_i[q] = rev_i[L - 1 - q];
-            out_j[q] = rev_j[L - 1 - q];
-        }
-    }
+    a.out.copy_out(rev, p, L, l);
     if (l == 0) {
-        if (a.path_len) a.path_len[p] = L;
+        if (a.out.path_len) a.out.path_len[p] = L;
         if (a.total) a.total[p] = D[(long long)(a.n - 1) * a.acc.pitch + end_j];
     }
 }
@@ -333,25 +268,15 @@ extern "C" int jsgx_dtw_launch(const jsgx_dtw_args* g, void* scratch, int64_t sc
     k.band = g->band;
     k.wm0 = g->weights_mul[0], k.wm1 = g->weights_mul[1], k.wm2 = g->weights_mul[2];
     k.wa0 = g->weights_add[0], k.wa1 = g->weights_add[1], k.wa2 = g->weights_add[2];
-    const DtwTiles tiles = dtw_tiles(g->n, g->m);
-    for (int d = 0; d < tiles.diagonals(); ++d) {
-        const int first = d - (tiles.j - 1) > 0 ? d - (tiles.j - 1) : 0, last = d < tiles.i - 1 ? d : tiles.i - 1;
-        k.diagonal = d;
-        k.ti_first = first;
-        hipLaunchKernelGGL(dtw_kernel, dim3((unsigned)(last - first + 1), (unsigned)g->pairs), dim3(kLanes), 0, s, k);
-    }
+    enqueue_diagonals(dtw_kernel, k, dtw_tiles(g->n, g->m), g->pairs, s);
     if (g->path_len || g->total) {
         BacktraceArgs b{};
         b.cost = k.cost;
         b.acc = plane_of<const float>(g->acc, g->acc_pitch, g->acc_pair_pitch, g->pairs);
         b.n = g->n, b.m = g->m, b.subseq = g->subseq;
         b.wm0 = k.wm0, b.wm1 = k.wm1, b.wm2 = k.wm2, b.wa0 = k.wa0, b.wa1 = k.wa1, b.wa2 = k.wa2;
-        b.path_i = g->path_i;
-        b.path_j = g->path_j;
-        b.path_pitch = g->pairs > 1 ? g->path_pitch : 0;
-        b.path_len = g->path_len;
+        b.out = path_out(g, scratch, g->n + g->m - 1);
         b.total = g->total;
-        b.scratch = need > 0 ? static_cast<int*>(scratch) : nullptr;
         hipLaunchKernelGGL(dtw_backtrace_kernel, dim3((unsigned)g->pairs), dim3(kLanes), 0, s, b);
     }
     return finish_launch(who, hipGetLastError());

@@ -12,7 +12,6 @@ namespace {
 using jsg::addr;
 using jsg::i128;
 using jsg::overlap;
-using jsg::span_bytes;
 }  // namespace
 
 int cdist_check(const jsgx_cdist_args* g, const char* who) {
@@ -40,8 +39,8 @@ int dtw_check(const jsgx_dtw_args* g, const char* who) {
     if (!g) return fail(JSGX_ERR_INVALID, who, "null argument");
     if (!g->cost) return fail(JSGX_ERR_INVALID, who, "null cost");
     if (!g->acc) return fail(JSGX_ERR_INVALID, who, "null acc");
-    if (!g->path_i != !g->path_j) return fail(JSGX_ERR_INVALID, who, "path_i and path_j go together");
-    if (g->path_i && !g->path_len) return fail(JSGX_ERR_INVALID, who, "null path_len with paths");
+    int rc = check_path_pointers(g, who);
+    if (rc != JSGX_OK) return rc;
     if (!jsg::aligned4(g->cost, g->acc, g->path_i, g->path_j, g->path_len, g->total))
         return fail(JSGX_ERR_INVALID, who, "pointers must be 4-byte aligned");
     if (g->pairs < 1 || g->pairs > 65535) return fail(JSGX_ERR_INVALID, who, "pairs must be in 1..65535");
@@ -54,14 +53,13 @@ int dtw_check(const jsgx_dtw_args* g, const char* who) {
     if (g->reserved0 != 0) return fail(JSGX_ERR_INVALID, who, "reserved0 must be 0");
     if (g->band != 0 && g->subseq) return fail(JSGX_ERR_INVALID, who, "band and subseq exclude each other");
     const long long N = g->n, M = g->m, P = g->pairs;
-    if (g->path_i && g->max_path < N + M - 1) return fail(JSGX_ERR_INVALID, who, "max_path smaller than n + m - 1");
-    i128 cost_bytes, acc_bytes;
-    int rc = check_plane(who, "cost", "", "m", N, M, g->cost_pitch, g->cost_pair_pitch, P, &cost_bytes);
+    if ((rc = check_max_path(g, who, N + M - 1, "max_path smaller than n + m - 1")) != JSGX_OK) return rc;
+    i128 cost_bytes, acc_bytes, path_bytes;
+    rc = check_plane(who, "cost", "", "m", N, M, g->cost_pitch, g->cost_pair_pitch, P, &cost_bytes);
     if (rc == JSGX_OK) rc = check_plane(who, "acc", "", "m", N, M, g->acc_pitch, g->acc_pair_pitch, P, &acc_bytes);
+    if (rc == JSGX_OK) rc = check_path_pitch(g, who, &path_bytes);
     if (rc != JSGX_OK) return rc;
-    if (P > 1 && g->path_i && g->path_pitch < g->max_path) return fail(JSGX_ERR_INVALID, who, "path_pitch smaller than max_path");
     const i128 cost0 = addr(g->cost), acc0 = addr(g->acc);
-    const i128 path_bytes = g->path_i ? span_bytes(P, g->path_pitch, g->max_path, 4) : 0;
     const i128 out[4] = {addr(g->path_i), addr(g->path_j), addr(g->path_len), addr(g->total)};
     const i128 out_bytes[4] = {path_bytes, path_bytes, 4 * (i128)P, 4 * (i128)P};
     if (overlap(acc0, acc_bytes, cost0, cost_bytes)) return fail(JSGX_ERR_INVALID, who, "acc overlaps cost");
@@ -73,10 +71,6 @@ int dtw_check(const jsgx_dtw_args* g, const char* who) {
 }
 
 int64_t dtw_scratch_bytes(const jsgx_dtw_args* g) { return g->path_i ? 8ll * g->pairs * ((int64_t)g->n + g->m - 1) : 0; }
-
-int dtw_launches(const jsgx_dtw_args* g) {
-    return dtw_tiles(g->n, g->m).diagonals() + ((g->path_len || g->total) ? 1 : 0);
-}
 
 }  // namespace jsgx
 
@@ -107,11 +101,7 @@ int jsgx_dtw_plan(const jsgx_dtw_args* g, char* name, int name_len, int32_t* til
     if (rc == JSGX_OK) rc = dtw_check(g, who);
     if (rc != JSGX_OK) return rc;
     put_name(name, name_len, "dtw_tiles");
-    if (tile_rows) *tile_rows = JSGX_DTW_TILE_ROWS;
-    if (tile_cols) *tile_cols = JSGX_DTW_TILE_COLS;
-    if (n_launches) *n_launches = dtw_launches(g);
-    if (threads) *threads = JSGX_DTW_THREADS;
-    if (lds_bytes) *lds_bytes = JSGX_DTW_LDS_BYTES;
+    put_tiles_plan(tile_rows, tile_cols, n_launches, threads, lds_bytes, tile_launches(g->n, g->m, g->path_len || g->total), JSGX_DTW_THREADS, JSGX_DTW_LDS_BYTES);
     return JSGX_OK;
 }
 

@@ -32,7 +32,6 @@ int64_t beat_scratch_bytes(const jsgx_beat_args* g);
 int cdist_check(const jsgx_cdist_args* g, const char* who);
 int dtw_check(const jsgx_dtw_args* g, const char* who);
 int64_t dtw_scratch_bytes(const jsgx_dtw_args* g);
-int dtw_launches(const jsgx_dtw_args* g);          // the kernels jsgx_dtw_launch enqueues
 // section 4 (jsgx_viterbi_host.cpp): every refusal that does not look at the scratch, in the header's order
 int viterbi_check(const jsgx_viterbi_args* g, const char* who);
 
@@ -89,7 +88,6 @@ struct RqaScratch {
     long long off_paths, bytes;
 };
 RqaScratch rqa_scratch(const jsgx_rqa_args* g);
-int rqa_launches(const jsgx_rqa_args* g);          // the kernels jsgx_rqa_launch enqueues
 
 // The three refusals of a launch's scratch buffer, in this order; `sizer` names the call that states `need`.
 inline int check_scratch(const char* who, const void* scratch, int64_t scratch_bytes, int64_t need, const char* sizer) {
@@ -150,6 +148,38 @@ struct DtwTiles {
     int diagonals() const { return i + j - 1; }
 };
 inline DtwTiles dtw_tiles(int n, int m) { return {(n + JSGX_DTW_TILE_ROWS - 1) / JSGX_DTW_TILE_ROWS, (m + JSGX_DTW_TILE_COLS - 1) / JSGX_DTW_TILE_COLS}; }
+// The tiles (ti, d - ti) of anti-diagonal d: ti in first..last.
+struct TileRange {
+    int first, last;
+};
+inline TileRange tiles_on_diagonal(const DtwTiles& t, int d) { return {d - (t.j - 1) > 0 ? d - (t.j - 1) : 0, d < t.i - 1 ? d : t.i - 1}; }
+// The kernels a launch of section 3 or 9 enqueues: one per tile anti-diagonal, and the backtrace.
+inline int tile_launches(int n, int m, bool backtrace) { return dtw_tiles(n, m).diagonals() + (backtrace ? 1 : 0); }
+// What a ..._plan call of those sections writes, each where asked for.
+inline void put_tiles_plan(int32_t* tile_rows, int32_t* tile_cols, int32_t* n_launches, int32_t* threads, int32_t* lds_bytes, int launches, int lanes, int lds) {
+    if (tile_rows) *tile_rows = JSGX_DTW_TILE_ROWS;
+    if (tile_cols) *tile_cols = JSGX_DTW_TILE_COLS;
+    if (n_launches) *n_launches = launches;
+    if (threads) *threads = lanes;
+    if (lds_bytes) *lds_bytes = lds;
+}
+
+// The path outputs of sections 3 and 9, whose argument blocks name them alike: their refusals, each called at its place in the header's
+// order (`what`: "max_path smaller than" the section's longest path), and the bytes of path_i and of path_j for the overlap refusals.
+template <class Args>
+int check_path_pointers(const Args* g, const char* who) {
+    if (!g->path_i != !g->path_j) return fail(JSGX_ERR_INVALID, who, "path_i and path_j go together");
+    return g->path_i && !g->path_len ? fail(JSGX_ERR_INVALID, who, "null path_len with paths") : JSGX_OK;
+}
+template <class Args>
+int check_max_path(const Args* g, const char* who, long long longest, const char* what) {
+    return g->path_i && g->max_path < longest ? fail(JSGX_ERR_INVALID, who, what) : JSGX_OK;
+}
+template <class Args>
+int check_path_pitch(const Args* g, const char* who, jsg::i128* path_bytes) {
+    *path_bytes = g->path_i ? jsg::span_bytes(g->pairs, g->path_pitch, g->max_path, 4) : 0;
+    return g->pairs > 1 && g->path_i && g->path_pitch < g->max_path ? fail(JSGX_ERR_INVALID, who, "path_pitch smaller than max_path") : JSGX_OK;
+}
 
 #if defined(__HIPCC__)
 // the device a launch goes to

@@ -1,20 +1,19 @@
 // libjsgx.so, recurrence quantification alignment over a similarity plane (include/jsgx.h section 9): the two kernels and their launcher.
-// The refusals, the scratch size and the plan are in jsgx_rqa_host.cpp.
+// The refusals, the scratch size and the plan are in jsgx_rqa_host.cpp; the tiles, their launches, the staging, the lane move and the
+// backtrace's window and path output are jsgx_plane_tiles.h, shared with jsgx_dtw.hip.
 //
-// rqa_kernel.  S is cut into the tiles of section 3 and the launcher enqueues one launch per tile anti-diagonal over pairs x (tiles on it),
-// one wavefront per tile, exactly as jsgx_dtw_launch does.  The three predecessors of a cell, (i-1, j-1), (i-1, j-2) and (i-2, j-1), lie in
-// an earlier row and an earlier column, so a tile depends on the tiles above, left and above-left of it and reads from S in global memory
-// the two rows above it, the two columns left of it and the corner between them, with the same cells of R; it never waits for another
-// workgroup.  Inside the tile the cells of a row are independent: lane l owns column l and the rows are walked top to bottom.  At row i the
+// rqa_kernel.  The three predecessors of a cell, (i-1, j-1), (i-1, j-2) and (i-2, j-1), lie in an earlier row and an earlier column, so a
+// tile reads from S in global memory the two rows above it, the two columns left of it and the corner between them, with the same cells
+// of R.  Inside the tile the cells of a row are independent: lane l owns column l and the rows are walked top to bottom.  At row i the
 // lane holds S(i-1, j) of its own column; its predecessors are
-//     a  (i-1, j-1)   the row above moved up one lane: one DPP wave_shr:1, whose old operand hands lane 0 the left halo
+//     a  (i-1, j-1)   the row above moved up one lane: one lane move, which hands lane 0 the left halo
 //     b  (i-1, j-2)   a moved once more (lane 0: the second halo column)
 //     c  (i-2, j-1)   the a of the step before
 // and what a gap from each of them costs (gap_onset from a link, gap_extend else) travels beside them the same way, so the flags of the
 // predecessors cost three more register moves and no memory access.  A tile takes 64 steps; a step needs the row above, which is the step
 // before, so the steps still form a chain: the move, a subtraction, two compare-and-selects, an addition and the selects of the non-link
 // rule.
-//   tile[64][64]    R on the way in, S on the way out, in place; the global accesses are whole 256-byte lines; lane l reads word r * 64 + l
+//   tile[64][64]    R on the way in, S on the way out; lane l reads word r * 64 + l
 //   left[64]        per row of the tile: S of the two halo columns at the row above, and the two penalties, one 16-byte read per step
 // Both are read two steps ahead, so that only arithmetic is on the chain, and the sweep is written four rows a round so that what was
 // read ahead changes names instead of registers (the compiler does not unroll a loop of wave moves by itself: 16 % at 16384 x 16384,
@@ -24,20 +23,15 @@
 // With a backtrace output the tile also keeps its best (S, i, j) -- the largest S > 0, then the lowest i, then the lowest j -- and writes
 // it to the scratch, 8 bytes a tile.
 //
-// rqa_backtrace_kernel.  One wavefront per pair.  It reduces the tiles' entries by the same key, which is a total order, so the end cell
-// does not depend on the tiling.  The walk is serial: the wavefront fetches the 32 x 32 window of S and R whose last cell is the current
-// one, lane 0 walks inside it while two rows and two columns remain behind the cell (or the matrix ends), at least 15 steps, and the window
-// is fetched again around the cell the walk stands on.  The step of a cell is recomputed by rqa_cell, the forward kernel's own routine.
-// The path is written backwards into the scratch and copied out reversed by all lanes.
+// rqa_backtrace_kernel.  It reduces the tiles' entries by the same key, which is a total order, so the end cell does not depend on the
+// tiling.  The window holds S and R; lane 0 walks inside it while two rows and two columns remain behind the cell (or the matrix ends), at
+// least 15 steps.  The step of a cell is recomputed by rqa_cell, the forward kernel's own routine.
 #include <hip/hip_runtime.h>
 
-#include "jsgx_internal.h"
+#include "jsgx_plane_tiles.h"
 
 namespace jsgx {
 
-constexpr int kRows = JSGX_DTW_TILE_ROWS, kCols = JSGX_DTW_TILE_COLS, kLanes = JSGX_RQA_THREADS;
-constexpr int kWin = JSGX_RQA_WINDOW;
-static_assert(kCols == kLanes && kLanes == 64, "lane l owns column l of a tile: one wavefront");
 static_assert((kRows * kCols + 4 * kRows) * 4 == JSGX_RQA_LDS_BYTES, "include/jsgx.h states the LDS");
 static_assert(JSGX_DTW_MAX_LEN <= 65536, "the key of a cell is i * 65536 + j in 32 bits");
 
@@ -48,7 +42,7 @@ struct RqaTileArgs {
     uint2* best;                    // [pairs][tiles]: the bits of S and i * 65536 + j; null without a backtrace output
     int n, m, tiles, tiles_j;       // tiles: of one pair
     float onset, extend;
-    int diagonal, ti_first;         // this launch: the tiles (ti_first + blockIdx.x, diagonal - ti)
+    TileDiagonal at;
 };
 
 struct RqaBacktraceArgs {
@@ -56,19 +50,10 @@ struct RqaBacktraceArgs {
     const uint2* best;
     int n, m, tiles;
     float onset, extend;
-    int* path_i;
-    int* path_j;
-    long long path_pitch;
-    int* path_len;
+    PathOut out;                    // longest: min(n, m)
     int* end;
     float* total;
-    int* scratch;                   // [pairs][2][min(n, m)], or null without paths
 };
-
-// the value of lane l - 1; lane 0 receives `lane0` (it has no source lane: the DPP move leaves its old value).  The move of jsgx_dtw.hip.
-__device__ __forceinline__ float rqa_lane_below(float v, float lane0) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane0), __float_as_int(v), 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
-}
 
 // S of a cell off the border from its R, S of its predecessors a (k = 0), b (k = 1), c (k = 2) and what a gap from each costs
 // (include/jsgx.h, "Every other cell"); has1, has2: k = 1 and k = 2 are candidates; *k: the step
@@ -115,8 +100,8 @@ __device__ __forceinline__ void rqa_sweep(float* tile, const float4* left, const
             const int ahead = r + 2 < kRows ? r + 2 : kRows - 1;
             const float4 h2 = left[ahead];
             const float r2 = col[ahead * kCols];
-            const float sa = rqa_lane_below(s1, h0.x), pa = rqa_lane_below(p1, h0.z);
-            const float sb = KNIGHT ? rqa_lane_below(sa, h0.y) : 0.f, pb = KNIGHT ? rqa_lane_below(pa, h0.w) : 0.f;
+            const float sa = from_lane_below(s1, h0.x), pa = from_lane_below(p1, h0.z);
+            const float sb = KNIGHT ? from_lane_below(sa, h0.y) : 0.f, pb = KNIGHT ? from_lane_below(pa, h0.w) : 0.f;
             const int i = i0 + r;
             int k;
             float s = rqa_cell<KNIGHT>(r0, sa, sb, c, pa, pb, pc, !BORDER || j >= 2, !BORDER || i >= 2, &k);
@@ -164,15 +149,13 @@ __global__ __launch_bounds__(kLanes) void rqa_kernel(RqaTileArgs a) {
     __shared__ float tile[kRows * kCols];
     __shared__ float4 left[kRows];
     const int l = threadIdx.x;
-    const int ti = a.ti_first + blockIdx.x, tj = a.diagonal - ti;
-    const int i0 = ti * kRows, j0 = tj * kCols;
-    const int rows = a.n - i0 < kRows ? a.n - i0 : kRows, cols = a.m - j0 < kCols ? a.m - j0 : kCols;
+    const auto [ti, tj, i0, j0, rows, cols] = a.at.place(a.n, a.m);
     const float* Rp = a.sim.row(blockIdx.y, 0);                    // the pair's planes
     const float* Sp = a.score.row(blockIdx.y, 0);
     const float* R = a.sim.row(blockIdx.y, i0) + j0;               // the tile
     float* S = a.score.row(blockIdx.y, i0) + j0;
-    // every load below is issued without a branch, from an address kept inside the matrix: the loads are in flight together.  A halo cell
-    // outside the matrix holds a copy of a cell inside; the BORDER form reads none of them.
+    // the halo is loaded as the tile is: without a branch, from addresses kept inside the matrix.  A halo cell outside the matrix holds a
+    // copy of a cell inside; the BORDER form reads none of them.
     const long long rp = a.sim.pitch, sp = a.score.pitch;
     const long long above1 = i0 > 0 ? i0 - 1 : 0, above2 = i0 > 1 ? i0 - 2 : 0, before1 = j0 > 0 ? j0 - 1 : 0, before2 = j0 > 1 ? j0 - 2 : 0;
     const int lc = l < cols ? l : cols - 1;
@@ -180,19 +163,12 @@ __global__ __launch_bounds__(kLanes) void rqa_kernel(RqaTileArgs a) {
     const float top_s1 = Sp[above1 * sp + j0 + lc], top_s2 = Sp[above2 * sp + j0 + lc], top_r1 = Rp[above1 * rp + j0 + lc], top_r2 = Rp[above2 * rp + j0 + lc];
     const float corner_s = Sp[above2 * sp + before1], corner_r = Rp[above2 * rp + before1];
     const float left_s1 = Sp[lrow * sp + before1], left_s2 = Sp[lrow * sp + before2], left_r1 = Rp[lrow * rp + before1], left_r2 = Rp[lrow * rp + before2];
-#pragma unroll
-    for (int r0 = 0; r0 < kRows; r0 += 16) {
-        float v[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) v[q] = R[(long long)(r0 + q < rows ? r0 + q : rows - 1) * rp + lc];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) tile[(r0 + q) * kCols + l] = v[q];
-    }
+    stage_tile(tile, R, rp, rows, cols, l);
     const float on = a.onset, ex = a.extend;
     left[l] = make_float4(left_s1, left_s2, left_r1 > 0.f ? on : ex, left_r2 > 0.f ? on : ex);
     __syncthreads();
     const float p1 = top_r1 > 0.f ? on : ex, p2 = top_r2 > 0.f ? on : ex;
-    const float c = rqa_lane_below(top_s2, corner_s), pc = rqa_lane_below(p2, corner_r > 0.f ? on : ex);          // (i0 - 2, j - 1)
+    const float c = from_lane_below(top_s2, corner_s), pc = from_lane_below(p2, corner_r > 0.f ? on : ex);          // (i0 - 2, j - 1)
     signed char* step_out = STEP ? a.step.row(blockIdx.y, i0) + j0 + l : nullptr;
     float bs;
     int br;
@@ -201,10 +177,7 @@ __global__ __launch_bounds__(kLanes) void rqa_kernel(RqaTileArgs a) {
     else
         rqa_sweep<KNIGHT, STEP, false>(tile, left, a, l, i0, j0, rows, cols, top_s1, p1, c, pc, step_out, &bs, &br);
     __syncthreads();
-    if (l < cols) {
-#pragma unroll 8
-        for (int r = 0; r < rows; ++r) S[(long long)r * sp + l] = tile[r * kCols + l];
-    }
+    store_tile(S, sp, tile, rows, cols, l);
     if (a.best) {
         unsigned key = ((unsigned)(i0 + br) << 16) | (unsigned)(j0 + l);
         if (!(l < cols && bs > 0.f)) {          // a lane right of the matrix, or a column without S > 0: no cell
@@ -220,11 +193,11 @@ template <bool KNIGHT>
 __global__ __launch_bounds__(kLanes) void rqa_backtrace_kernel(RqaBacktraceArgs a) {
 #pragma clang fp contract(off)
     __shared__ float ws[kWin * kWin], wr[kWin * kWin];
-    __shared__ int state[4];            // i, j, the cells recorded, 0 walking / 1 done
+    __shared__ int state[4];            // set_walk(); the status: 0 walking / 1 done
     const int l = threadIdx.x, p = blockIdx.x;
     const float* R = a.sim.row(p, 0);
     const float* S = a.score.row(p, 0);
-    const int longest = a.n < a.m ? a.n : a.m;
+    const int longest = a.out.longest;
     // ---- the end cell: the best of the tiles' best
     float bs = 0.f;
     unsigned key = 0xffffffffu;
@@ -244,7 +217,7 @@ __global__ __launch_bounds__(kLanes) void rqa_backtrace_kernel(RqaBacktraceArgs 
     key = (unsigned)__shfl((int)key, 0);
     if (!(bs > 0.f)) {                  // no cell with S > 0: a result
         if (l == 0) {
-            if (a.path_len) a.path_len[p] = 0;
+            if (a.out.path_len) a.out.path_len[p] = 0;
             if (a.total) a.total[p] = 0.f;
             if (a.end) a.end[2 * p] = a.end[2 * p + 1] = -1;
         }
@@ -255,28 +228,16 @@ __global__ __launch_bounds__(kLanes) void rqa_backtrace_kernel(RqaBacktraceArgs 
         if (a.total) a.total[p] = bs;
         if (a.end) a.end[2 * p] = end_i, a.end[2 * p + 1] = end_j;
     }
-    if (!a.path_len) return;
-    int* rev_i = a.scratch ? a.scratch + (long long)p * 2 * longest : nullptr;
-    int* rev_j = rev_i ? rev_i + longest : nullptr;
-    if (l == 0) {
-        state[0] = end_i;
-        state[1] = end_j;
-        state[2] = 0;
-        state[3] = 0;
-    }
+    if (!a.out.path_len) return;
+    int* rev = a.out.reversed(p);
+    if (l == 0) set_walk(state, end_i, end_j, 0, 0);
     // ---- the walk, window by window: every round records a cell or ends, and a path has at most `longest` cells
     for (int round = 0; round <= longest; ++round) {
         __syncthreads();
         const int i = state[0], j = state[1];
         if (state[3] != 0) break;
-#pragma unroll
-        for (int u = 0; u < kWin * kWin / kLanes; ++u) {    // unconditional loads from addresses kept inside the matrix: all in flight together
-            const int q = u * kLanes + l;
-            const int gi = i - (kWin - 1) + q / kWin, gj = j - (kWin - 1) + q % kWin;       // gi <= i < n and gj <= j < m
-            const long long ri = gi < 0 ? 0 : gi, rj = gj < 0 ? 0 : gj;
-            ws[q] = S[ri * a.score.pitch + rj];
-            wr[q] = R[ri * a.sim.pitch + rj];
-        }
+        fetch_window<false>(ws, S, a.score.pitch, i, j, l);
+        fetch_window<false>(wr, R, a.sim.pitch, i, j, l);
         __syncthreads();
         if (l == 0) {
             int r = kWin - 1, c = kWin - 1, ci = i, cj = j, count = state[2], st = 0;
@@ -296,11 +257,7 @@ __global__ __launch_bounds__(kLanes) void rqa_backtrace_kernel(RqaBacktraceArgs 
                     st = 1;
                     break;
                 }
-                if (rev_i) {
-                    rev_i[count] = ci;
-                    rev_j[count] = cj;
-                }
-                ++count;
+                a.out.record(rev, count++, ci, cj);
                 if (k == -2) {
                     st = 1;
                     break;
@@ -308,33 +265,13 @@ __global__ __launch_bounds__(kLanes) void rqa_backtrace_kernel(RqaBacktraceArgs 
                 const int di = k == 2 ? 2 : 1, dj = k == 1 ? 2 : 1;
                 ci -= di, r -= di, cj -= dj, c -= dj;
             }
-            state[0] = ci;
-            state[1] = cj;
-            state[2] = count;
-            state[3] = st;
+            set_walk(state, ci, cj, count, st);
         }
     }
     __syncthreads();
     const int L = state[2];
-    if (a.path_i) {
-        int* out_i = a.path_i + p * a.path_pitch;
-        int* out_j = a.path_j + p * a.path_pitch;
-        for (int q = l; q < L; q += kLanes) {
-            out_i[q] = rev_i[L - 1 - q];
-            out_j[q] = rev_j[L - 1 - q];
-        }
-    }
-    if (l == 0) a.path_len[p] = L;
-}
-
-template <bool KNIGHT, bool STEP>
-void rqa_enqueue_forward(RqaTileArgs k, const DtwTiles& tiles, int pairs, hipStream_t s) {
-    for (int d = 0; d < tiles.diagonals(); ++d) {
-        const int first = d - (tiles.j - 1) > 0 ? d - (tiles.j - 1) : 0, last = d < tiles.i - 1 ? d : tiles.i - 1;
-        k.diagonal = d;
-        k.ti_first = first;
-        hipLaunchKernelGGL((rqa_kernel<KNIGHT, STEP>), dim3((unsigned)(last - first + 1), (unsigned)pairs), dim3(kLanes), 0, s, k);
-    }
+    a.out.copy_out(rev, p, L, l);
+    if (l == 0) a.out.path_len[p] = L;
 }
 
 }  // namespace jsgx
@@ -360,10 +297,8 @@ extern "C" int jsgx_rqa_launch(const jsgx_rqa_args* g, void* scratch, int64_t sc
     k.best = backtrace ? static_cast<uint2*>(scratch) : nullptr;
     k.n = g->n, k.m = g->m, k.tiles = (int)need.tiles, k.tiles_j = tiles.j;
     k.onset = g->gap_onset, k.extend = g->gap_extend;
-    if (g->knight)
-        g->step ? rqa_enqueue_forward<true, true>(k, tiles, g->pairs, s) : rqa_enqueue_forward<true, false>(k, tiles, g->pairs, s);
-    else
-        g->step ? rqa_enqueue_forward<false, true>(k, tiles, g->pairs, s) : rqa_enqueue_forward<false, false>(k, tiles, g->pairs, s);
+    void (*const forward[2][2])(RqaTileArgs) = {{rqa_kernel<false, false>, rqa_kernel<false, true>}, {rqa_kernel<true, false>, rqa_kernel<true, true>}};
+    enqueue_diagonals(forward[g->knight][g->step != nullptr], k, tiles, g->pairs, s);
     if (backtrace) {
         RqaBacktraceArgs b{};
         b.sim = k.sim;
@@ -371,13 +306,9 @@ extern "C" int jsgx_rqa_launch(const jsgx_rqa_args* g, void* scratch, int64_t sc
         b.best = k.best;
         b.n = g->n, b.m = g->m, b.tiles = (int)need.tiles;
         b.onset = g->gap_onset, b.extend = g->gap_extend;
-        b.path_i = g->path_i;
-        b.path_j = g->path_j;
-        b.path_pitch = g->pairs > 1 ? g->path_pitch : 0;
-        b.path_len = g->path_len;
+        b.out = path_out(g, static_cast<char*>(scratch) + need.off_paths, g->n < g->m ? g->n : g->m);
         b.end = g->end;
         b.total = g->total;
-        b.scratch = g->path_i ? reinterpret_cast<int*>(static_cast<char*>(scratch) + need.off_paths) : nullptr;
         if (g->knight)
             hipLaunchKernelGGL(rqa_backtrace_kernel<true>, dim3((unsigned)g->pairs), dim3(kLanes), 0, s, b);
         else

@@ -11,15 +11,14 @@ namespace {
 using jsg::addr;
 using jsg::i128;
 using jsg::overlap;
-using jsg::span_bytes;
 }  // namespace
 
 int rqa_check(const jsgx_rqa_args* g, const char* who) {
     if (!g) return fail(JSGX_ERR_INVALID, who, "null argument");
     if (!g->sim) return fail(JSGX_ERR_INVALID, who, "null sim");
     if (!g->score) return fail(JSGX_ERR_INVALID, who, "null score");
-    if (!g->path_i != !g->path_j) return fail(JSGX_ERR_INVALID, who, "path_i and path_j go together");
-    if (g->path_i && !g->path_len) return fail(JSGX_ERR_INVALID, who, "null path_len with paths");
+    int rc = check_path_pointers(g, who);
+    if (rc != JSGX_OK) return rc;
     if (!jsg::aligned4(g->sim, g->score, g->path_i, g->path_j, g->path_len, g->end, g->total))
         return fail(JSGX_ERR_INVALID, who, "pointers must be 4-byte aligned");
     if (g->pairs < 1 || g->pairs > 65535) return fail(JSGX_ERR_INVALID, who, "pairs must be in 1..65535");
@@ -30,18 +29,17 @@ int rqa_check(const jsgx_rqa_args* g, const char* who) {
     if (!std::isfinite(g->gap_extend) || !(g->gap_extend >= 0.f)) return fail(JSGX_ERR_INVALID, who, "gap_extend must be finite and >= 0");
     if (g->reserved0 != 0) return fail(JSGX_ERR_INVALID, who, "reserved0 must be 0");
     const long long N = g->n, M = g->m, P = g->pairs;
-    if (g->path_i && g->max_path < (N < M ? N : M)) return fail(JSGX_ERR_INVALID, who, "max_path smaller than min(n, m)");
-    i128 sim_bytes, score_bytes, step_bytes = 0;
-    int rc = check_plane(who, "sim", "", "m", N, M, g->sim_pitch, g->sim_pair_pitch, P, &sim_bytes);
+    if ((rc = check_max_path(g, who, N < M ? N : M, "max_path smaller than min(n, m)")) != JSGX_OK) return rc;
+    i128 sim_bytes, score_bytes, step_bytes = 0, path_bytes;
+    rc = check_plane(who, "sim", "", "m", N, M, g->sim_pitch, g->sim_pair_pitch, P, &sim_bytes);
     if (rc == JSGX_OK) rc = check_plane(who, "score", "", "m", N, M, g->score_pitch, g->score_pair_pitch, P, &score_bytes);
     if (rc == JSGX_OK && g->step) {
         rc = check_plane(who, "step", "", "m", N, M, g->step_pitch, g->step_pair_pitch, P, &step_bytes);
         step_bytes /= 4;            // a plane of bytes
     }
+    if (rc == JSGX_OK) rc = check_path_pitch(g, who, &path_bytes);
     if (rc != JSGX_OK) return rc;
-    if (P > 1 && g->path_i && g->path_pitch < g->max_path) return fail(JSGX_ERR_INVALID, who, "path_pitch smaller than max_path");
     const i128 sim0 = addr(g->sim);
-    const i128 path_bytes = g->path_i ? span_bytes(P, g->path_pitch, g->max_path, 4) : 0;
     const i128 out[7] = {addr(g->score), addr(g->step), addr(g->path_i), addr(g->path_j), addr(g->path_len), addr(g->end), addr(g->total)};
     const i128 out_bytes[7] = {score_bytes, step_bytes, path_bytes, path_bytes, 4 * (i128)P, 8 * (i128)P, 4 * (i128)P};
     if (overlap(out[0], out_bytes[0], sim0, sim_bytes)) return fail(JSGX_ERR_INVALID, who, "score overlaps sim");
@@ -62,10 +60,6 @@ RqaScratch rqa_scratch(const jsgx_rqa_args* g) {
     return s;
 }
 
-int rqa_launches(const jsgx_rqa_args* g) {
-    return dtw_tiles(g->n, g->m).diagonals() + ((g->path_len || g->end || g->total) ? 1 : 0);
-}
-
 }  // namespace jsgx
 
 using namespace jsgx;
@@ -84,11 +78,7 @@ int jsgx_rqa_plan(const jsgx_rqa_args* g, char* name, int name_len, int32_t* til
     if (rc == JSGX_OK) rc = rqa_check(g, who);
     if (rc != JSGX_OK) return rc;
     put_name(name, name_len, "rqa_tiles");
-    if (tile_rows) *tile_rows = JSGX_DTW_TILE_ROWS;
-    if (tile_cols) *tile_cols = JSGX_DTW_TILE_COLS;
-    if (n_launches) *n_launches = rqa_launches(g);
-    if (threads) *threads = JSGX_RQA_THREADS;
-    if (lds_bytes) *lds_bytes = JSGX_RQA_LDS_BYTES;
+    put_tiles_plan(tile_rows, tile_cols, n_launches, threads, lds_bytes, tile_launches(g->n, g->m, g->path_len || g->end || g->total), JSGX_RQA_THREADS, JSGX_RQA_LDS_BYTES);
     return JSGX_OK;
 }
 

@@ -1889,19 +1889,38 @@ def cdist(X, Y, metric: str = "euclidean"):
     return cost
 
 
+def _path_args(d_path_i, d_path_j, P):
+    """(path_pitch, max_path) of the path outputs of a dtw or rqa launch; 0, 0 unless both are given (the library refuses one alone)."""
+    import torch
+    if d_path_i is None or d_path_j is None:
+        return 0, 0
+    pi, pj = (t[None] if t.dim() == 1 else t for t in (d_path_i, d_path_j))
+    for t in (pi, pj):
+        assert t.is_cuda and t.dtype == torch.int32 and t.dim() == 2 and t.shape[0] == P and (t.stride(1) == 1 or t.shape[1] == 1), "d_path_i, d_path_j: int32 CUDA [pairs][max_path]"
+    assert pi.shape == pj.shape and pi.stride(0) == pj.stride(0), "d_path_i and d_path_j: one shape and pitch"
+    return pi.stride(0), pi.shape[1]
+
+
+def _tiles_plan(fn, args):
+    """The tail of dtw_plan and rqa_plan: the call and its six results."""
+    name, out = C.create_string_buffer(32), [C.c_int32() for _ in range(5)]
+    capix.check(fn(C.byref(args), name, 32, *[C.byref(o) for o in out]))
+    return (name.value.decode(),) + tuple(o.value for o in out)
+
+
+def _cut_paths(path, lengths):
+    """path int32 [2][pairs][max_path] and the pairs' lengths -> the list of [L, 2] tensors."""
+    import torch
+    return [torch.stack((path[0, p, :L], path[1, p, :L]), dim=1) for p, L in enumerate(lengths)]
+
+
 def _dtw_args(d_cost, d_acc, weights_mul, weights_add, subseq, band, d_path_i, d_path_j, d_path_len, d_total) -> capix.DtwArgs:
     import torch
     c, d = _planes(d_cost, "d_cost"), _planes(d_acc, "d_acc")
     P, N, M = c.shape
     assert tuple(d.shape) == (P, N, M), "d_acc: the shape of d_cost"
     ptr = lambda t: None if t is None else t.data_ptr()
-    path_pitch = max_path = 0
-    if d_path_i is not None and d_path_j is not None:
-        pi, pj = (t[None] if t.dim() == 1 else t for t in (d_path_i, d_path_j))
-        for t in (pi, pj):
-            assert t.is_cuda and t.dtype == torch.int32 and t.dim() == 2 and t.shape[0] == P and (t.stride(1) == 1 or t.shape[1] == 1), "d_path_i, d_path_j: int32 CUDA [pairs][max_path]"
-        assert pi.shape == pj.shape and pi.stride(0) == pj.stride(0), "d_path_i and d_path_j: one shape and pitch"
-        path_pitch, max_path = pi.stride(0), pi.shape[1]
+    path_pitch, max_path = _path_args(d_path_i, d_path_j, P)
     for t, dtype, what in ((d_path_len, torch.int32, "d_path_len: int32"), (d_total, torch.float32, "d_total: float32")):
         assert t is None or (t.is_cuda and t.dtype == dtype and t.dim() == 1 and t.shape[0] >= P and t.is_contiguous()), f"{what} CUDA [pairs]"
     wm = (1.0, 1.0, 1.0) if weights_mul is None else tuple(float(w) for w in weights_mul)
@@ -1936,9 +1955,7 @@ def dtw_plan(n: int, m: int, pairs: int = 1, backtrack: bool = True):
     shape: one launch per tile anti-diagonal and one for the backtrace.  Needs no device."""
     a = capix.DtwArgs(cost=1 << 44, cost_pitch=int(m), cost_pair_pitch=int(n) * int(m), pairs=int(pairs), n=int(n), m=int(m), weights_mul=(C.c_float * 3)(1, 1, 1),
                       acc=2 << 44, acc_pitch=int(m), acc_pair_pitch=int(n) * int(m), path_len=(3 << 44) if backtrack else None)      # never dereferenced
-    name, out = C.create_string_buffer(32), [C.c_int32() for _ in range(5)]
-    capix.check(capix.lib().jsgx_dtw_plan(C.byref(a), name, 32, *[C.byref(o) for o in out]))
-    return (name.value.decode(),) + tuple(o.value for o in out)
+    return _tiles_plan(capix.lib().jsgx_dtw_plan, a)
 
 
 def dtw(X=None, Y=None, *, C=None, metric="euclidean", weights_mul=None, weights_add=None, subseq=False, band=0, backtrack=True):
@@ -1969,7 +1986,7 @@ def dtw(X=None, Y=None, *, C=None, metric="euclidean", weights_mul=None, weights
     lengths = length.tolist()           # the one host synchronisation
     if min(lengths) < 0:
         raise JsgError(capix.JSGX_ERR_INVALID, f"dtw: no warping path for pair {lengths.index(min(lengths))} (a band too narrow for the shape, or a NaN)")
-    wp = [torch.stack((path[0, p, :L], path[1, p, :L]), dim=1) for p, L in enumerate(lengths)]
+    wp = _cut_paths(path, lengths)
     return (D, wp) if batched else (D[0], wp[0])
 
 
@@ -1987,13 +2004,7 @@ def _rqa_args(d_sim, d_score, gap_onset, gap_extend, knight_moves, d_step, d_pat
         st = _planes(d_step, "d_step", torch.int8)
         assert tuple(st.shape) == (P, N, M), "d_step: int8, the shape of d_sim"
         step_ptr, step_pitch, step_pair_pitch = st.data_ptr(), st.stride(1), st.stride(0)
-    path_pitch = max_path = 0
-    if d_path_i is not None and d_path_j is not None:
-        pi, pj = (t[None] if t.dim() == 1 else t for t in (d_path_i, d_path_j))
-        for t in (pi, pj):
-            assert t.is_cuda and t.dtype == torch.int32 and t.dim() == 2 and t.shape[0] == P and (t.stride(1) == 1 or t.shape[1] == 1), "d_path_i, d_path_j: int32 CUDA [pairs][max_path]"
-        assert pi.shape == pj.shape and pi.stride(0) == pj.stride(0), "d_path_i and d_path_j: one shape and pitch"
-        path_pitch, max_path = pi.stride(0), pi.shape[1]
+    path_pitch, max_path = _path_args(d_path_i, d_path_j, P)
     for t, dtype, count, what in ((d_path_len, torch.int32, P, "d_path_len: int32 CUDA [pairs]"), (d_end, torch.int32, 2 * P, "d_end: int32 CUDA [pairs][2]"),
                                   (d_total, torch.float32, P, "d_total: float32 CUDA [pairs]")):
         assert t is None or (t.is_cuda and t.dtype == dtype and t.numel() >= count and t.is_contiguous()), what
@@ -2028,9 +2039,7 @@ def rqa_plan(n: int, m: int, pairs: int = 1, backtrack: bool = True):
     shape: one launch per tile anti-diagonal and one for the backtrace.  Needs no device."""
     a = capix.RqaArgs(sim=1 << 44, sim_pitch=int(m), sim_pair_pitch=int(n) * int(m), pairs=int(pairs), n=int(n), m=int(m), knight=1, gap_onset=1.0, gap_extend=1.0,
                       score=2 << 44, score_pitch=int(m), score_pair_pitch=int(n) * int(m), path_len=(3 << 44) if backtrack else None)      # never dereferenced
-    name, out = C.create_string_buffer(32), [C.c_int32() for _ in range(5)]
-    capix.check(capix.lib().jsgx_rqa_plan(C.byref(a), name, 32, *[C.byref(o) for o in out]))
-    return (name.value.decode(),) + tuple(o.value for o in out)
+    return _tiles_plan(capix.lib().jsgx_rqa_plan, a)
 
 
 def rqa(sim, gap_onset=1.0, gap_extend=1.0, knight_moves=True, backtrack=True):
@@ -2054,7 +2063,7 @@ def rqa(sim, gap_onset=1.0, gap_extend=1.0, knight_moves=True, backtrack=True):
         path = torch.empty((2, P, min(N, M)), dtype=torch.int32, device=s.device)
         length = torch.empty((P,), dtype=torch.int32, device=s.device)
         rqa_launch(s3, score, gap_onset=gap_onset, gap_extend=gap_extend, knight_moves=knight_moves, d_path_i=path[0], d_path_j=path[1], d_path_len=length)
-    wp = [torch.stack((path[0, p, :L], path[1, p, :L]), dim=1) for p, L in enumerate(length.tolist())]           # the one host synchronisation
+    wp = _cut_paths(path, length.tolist())           # the one host synchronisation
     return (score, wp) if batched else (score[0], wp[0])
 
 

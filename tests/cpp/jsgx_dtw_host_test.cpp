@@ -1,14 +1,14 @@
 // The host entry points of sections 2 and 3 of libjsgx.so (include/jsgx.h) from C++: the plans, the scratch size and the refusals with
 // their texts.  No launch, so no device: built against libjsgx.so (CMake, jsg::jsgx) or, for the sanitizers, together with
 // csrc/jsgx_beat_host.cpp and csrc/jsgx_dtw_host.cpp themselves (tests/test_dtw_host.py: -fsanitize=address,undefined).  Exit code 0 and
-// "ok" on success.
+// "ok" on success.  It also walks the tile anti-diagonals that the launches of sections 3 and 9 take (csrc/jsgx_internal.h, its host part).
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <initializer_list>
 
-#include "jsgx.h"
+#include "../../jadespectrogram_amd/csrc/jsgx_internal.h"
 
 static int failures = 0;
 #define EXPECT(cond)                                                     \
@@ -167,6 +167,27 @@ int main() {
     d = good_dtw(); d.total = d.acc + 90000; EXPECT(jsgx_dtw_scratch_bytes(&d) > 0);
     // one pair: the pair pitches are not looked at
     d = good_dtw(); d.pairs = 1; d.cost_pair_pitch = d.acc_pair_pitch = d.path_pitch = 0; EXPECT(jsgx_dtw_scratch_bytes(&d) == 8 * 399);
+
+    // the launches of a plane: every anti-diagonal of every tile grid takes tiles inside the grid, and together they take each tile once
+    for (int ti = 1; ti <= 6; ++ti)
+        for (int tj = 1; tj <= 6; ++tj) {
+            const jsgx::DtwTiles tiles = jsgx::dtw_tiles(ti * JSGX_DTW_TILE_ROWS, (tj - 1) * JSGX_DTW_TILE_COLS + 1);
+            EXPECT(tiles.i == ti && tiles.j == tj);
+            int visits[6][6] = {};
+            for (int dg = 0; dg < tiles.diagonals(); ++dg) {
+                const jsgx::TileRange on = jsgx::tiles_on_diagonal(tiles, dg);
+                EXPECT(0 <= on.first && on.first <= on.last && on.last < ti);
+                for (int i = on.first; i <= on.last; ++i) {
+                    EXPECT(0 <= dg - i && dg - i < tj);
+                    if (0 <= dg - i && dg - i < tj) ++visits[i][dg - i];
+                }
+            }
+            for (int i = 0; i < 6; ++i)
+                for (int j = 0; j < 6; ++j) EXPECT(visits[i][j] == (i < ti && j < tj ? 1 : 0));
+            // ... and the loop above ran once per launch: no anti-diagonal was empty, so there are ti + tj - 1 of them
+            EXPECT(tiles.diagonals() == ti + tj - 1 && jsgx::tile_launches(ti * JSGX_DTW_TILE_ROWS, (tj - 1) * JSGX_DTW_TILE_COLS + 1, false) == ti + tj - 1);
+            EXPECT(jsgx::tile_launches(ti * JSGX_DTW_TILE_ROWS, (tj - 1) * JSGX_DTW_TILE_COLS + 1, true) == ti + tj);
+        }
 
     if (failures) {
         std::printf("%d failures\n", failures);
