@@ -1002,6 +1002,154 @@ JSGX_API int jsgx_rqa_launch(const jsgx_rqa_args* args, void* scratch, int64_t s
 JSGX_API int jsgx_rqa_plan(const jsgx_rqa_args* args, char* name, int name_len, int32_t* tile_rows, int32_t* tile_cols, int32_t* n_launches,
                            int32_t* threads, int32_t* lds_bytes);
 
+/* Sections 10 and 11 were added to version 1 in the same way: sections 1 to 9, their structs and their constants are as they were. */
+
+/* ------------------------------------------------------------------------------------------------
+ * 10. Path enhancement of a recurrence plane (librosa.segment.path_enhance, the step between sections 7 and 9): a bank of sparse
+ *     two-dimensional filters over the plane and the maximum over the bank.  R[i][j] = r[p*r_pair_pitch + i*r_pitch + j], i < N, j < M,
+ *     float32; Rz is R inside the plane and +0 outside (scipy.ndimage's mode="constant", cval=0).  Pairs are independent.
+ *
+ *     A bank is a tap list in device memory: tap_w[t] float32 weights; tap_at[t] int32 holding two signed 16-bit offsets, di in the high
+ *     half and dj in the low half; filter_first[f], f <= F, int32, ascending, filter_first[F] = n_taps.  For filter f, the taps in list order:
+ *         acc_f = +0
+ *         for t in filter_first[f] .. filter_first[f+1]-1 :   acc_f = fmaf(tap_w[t], Rz[i + di_t][j + dj_t], acc_f)
+ *     Across the filters in ascending f:
+ *         best = acc_0;   later f:  if (acc_f > best || acc_f != acc_f) best = acc_f          (np.maximum: a NaN wins and stays)
+ *     With clip:  out = best < 0 ? +0 : best  (a NaN stays); without:  out = best.
+ *     out[p*out_pair_pitch + i*out_pitch + j]; every element of the plane is written and nothing else.
+ *     A filter with no taps gives acc_f = +0.  A tap with |di| > reach_i or |dj| > reach_j is skipped; reach_i and reach_j are host
+ *     arguments in 0..JSGX_PE_MAX_REACH.  The host cannot see the device table: this rule, and every filter_first entry being clamped into
+ *     0..n_taps, keep a bad table from reading outside the arrays or outside the staged window (a filter_first that descends gives an
+ *     empty filter).
+ *     For finite weights, skipping a tap that falls outside the plane and adding w * (+0) give the same bits: acc starts at +0 and
+ *     x + (+-0) = x for x != 0, (+0) + (+-0) = +0, so acc never becomes -0.  A kernel may therefore zero-fill its halo.  (An infinite or
+ *     NaN weight times the +0 outside the plane is a NaN: stated, not avoided.)
+ *     out[i][j] is a function of the plane and the list alone: it does not depend on tiles, pairs, pitches or how a kernel groups taps.
+ *
+ *     Against scipy.  For a table K of shape (h, w), scipy.ndimage.convolve(R, K, mode="constant")[i][j] = sum K[a][b] * Rz[i + h/2 - a][j +
+ *     w/2 - b] (integer halves; even and odd h, w): the tap of K[a][b] has di = h/2 - a, dj = w/2 - b.  scipy sums in float64 in an order of
+ *     its own; for non-negative planes and weights this chain is within T u / (1 - T u) relative of the exact sum, T the taps of the
+ *     largest filter, u = 2^-24.
+ *
+ *     The builder (host, double precision, no device) restates librosa.segment.path_enhance's bank: slopes 2 ** linspace(log2(min_ratio),
+ *     log2(max_ratio), n_filters); each filter starts as diag(window) (n x n) and stays so where |slope - 1| <= 1e-8 + 1e-5 (numpy's
+ *     isclose); otherwise it is rotated as scipy.ndimage.rotate(win, -(atan(slope) * 180 / pi - 45), order=5, prefilter=False) does: with
+ *     c, s the cosine and sine of that angle, Rm = [[c, s], [-s, c]]; the output shape is int(ptp(Rm @ [[0,0,n,n],[0,n,0,n]], axis=1) +
+ *     0.5); offset = (n-1)/2 - Rm @ ((shape-1)/2); output cell (y, x) maps to p = Rm @ (y, x) + offset; a cell with a coordinate of p < 0
+ *     or > n - 1 is 0, every other is the 6 x 6 sum of B5(p_y - yy) B5(p_x - xx) win[mirror(yy)][mirror(xx)], yy from floor(p_y) - 2, B5
+ *     the centred quintic B-spline and mirror the reflection about the end samples, period 2 (n - 1).  Then the table is clipped at 0 and
+ *     divided by its sum; with zero_mean its mean is subtracted, which makes it dense (every entry a tap: up to 129 x 129 a filter
+ *     instead of a few hundred, and the kernel's time grows with it).  The taps are the non-zero entries in row-major order (a, then b,
+ *     ascending), rounded to float32; an entry whose float32 is zero or subnormal, or below drop_below times the largest magnitude of
+ *     its table, is dropped (drop_below 0, the default in Python: librosa's filters, untrimmed).
+ *
+ *     The kernel ("path_enhance_tiles", vector pipe: the summation order is the contract).  A workgroup of JSGX_PE_THREADS lanes owns a
+ *     JSGX_PE_TILE x JSGX_PE_TILE output tile and stages it with its halo of reach_i rows and reach_j columns once into LDS, zero-filled
+ *     outside the plane: (64 + 2 reach_i) rows of W words, W = 64 + 2 reach_j rounded up to 1 (mod 4), so that the eight rows a
+ *     wavefront reads at once fall on different banks.  A lane holds 4 rows x 4 adjacent columns of outputs in registers.  Weights and
+ *     offsets are the same for every lane: they are fetched by scalar loads, eight taps ahead, and enter v_fma_f32 as scalar operands.
+ *     Row-major order puts horizontal runs of taps next to each other in the list; a uniform branch on the run length (8, 4, 2, 1) lets
+ *     the L taps of a run share L + 3 LDS reads per output row instead of 4 L, and every output still sees its taps in list order.
+ *     LDS: 4 * (64 + 2 reach_i) * W bytes, dynamic: 148224 at the largest reach (inside 160 KiB), 66048 at reach 32 (two workgroups a
+ *     compute unit).
+ * ------------------------------------------------------------------------------------------------ */
+#define JSGX_PE_MAX_REACH 64
+#define JSGX_PE_MAX_FILTERS 32
+#define JSGX_PE_MAX_TAPS 1048576
+#define JSGX_PE_TILE 64
+#define JSGX_PE_THREADS 256
+#define JSGX_PE_LDS_LIMIT 163840
+#define JSGX_PE_MIN_WINDOW 3
+#define JSGX_PE_MAX_WINDOW 101
+
+typedef struct jsgx_path_enhance_args {
+    const float* r;             /* device floats: R */
+    int64_t r_pitch;            /* >= m */
+    int64_t r_pair_pitch;       /* pairs > 1: >= (n - 1) * r_pitch + m */
+    const float* tap_w;         /* device floats [n_taps] */
+    const int32_t* tap_at;      /* device int32 [n_taps]: (di << 16) | (dj & 0xffff) */
+    const int32_t* filter_first;/* device int32 [n_filters + 1] */
+    int32_t pairs;              /* 1..65535 */
+    int32_t n;                  /* N, 1..JSGX_DTW_MAX_LEN */
+    int32_t m;                  /* M, 1..JSGX_DTW_MAX_LEN */
+    int32_t n_filters;          /* F, 1..JSGX_PE_MAX_FILTERS */
+    int32_t n_taps;             /* 1..JSGX_PE_MAX_TAPS */
+    int32_t reach_i;            /* 0..JSGX_PE_MAX_REACH */
+    int32_t reach_j;            /* 0..JSGX_PE_MAX_REACH */
+    int32_t clip;               /* 0 or 1 */
+    float* out;                 /* device floats: [p][i][j] */
+    int64_t out_pitch;          /* >= m */
+    int64_t out_pair_pitch;     /* pairs > 1: >= (n - 1) * out_pitch + m */
+} jsgx_path_enhance_args;       /* 104 bytes, no padding */
+
+/* Enqueue only (one kernel, no scratch): no allocation, no synchronisation; capture works, a first launch included.  Refused
+ * (JSGX_ERR_INVALID, nothing enqueued), in this order and before any device call: null args, a null r, a null tap_w, a null tap_at, a
+ * null filter_first, a null out; a pointer that is not 4-byte aligned; pairs outside 1..65535, n outside 1..65536, m outside 1..65536,
+ * n_filters outside 1..32, n_taps outside 1..2^20, reach_i outside 0..64, reach_j outside 0..64, clip other than 0 or 1; r_pitch below m,
+ * r_pair_pitch that does not cover a plane (pairs > 1), the same for out_pitch and out_pair_pitch; out overlapping r, out overlapping
+ * tap_w, tap_at, filter_first in this order.  Then JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_path_enhance_launch(const jsgx_path_enhance_args* args, void* stream);
+/* The kernel of these arguments, without a device: its name ("path_enhance_tiles"), the rows and columns of a tile, the lanes of a
+ * workgroup and the bytes of LDS it holds for these reaches.  Any output pointer may be NULL (name: else name_len >= 32).  Refused: a
+ * name_len below 32 with a name, then what the launch refuses. */
+JSGX_API int jsgx_path_enhance_plan(const jsgx_path_enhance_args* args, char* name, int name_len, int32_t* tile_rows, int32_t* tile_cols, int32_t* threads,
+                                    int32_t* lds_bytes);
+/* The dense table of one filter of the builder, in double: *rows x *cols, row-major into table where table is not NULL and capacity
+ * (in doubles) holds it; with table NULL only the shape is returned.  JSGX_ERR_INVALID, in this order: a null window, a null rows, a
+ * null cols; n outside 3..101; a slope that is not finite and > 0; zero_mean other than 0 or 1; a window entry that is not finite; a
+ * table whose sum after clipping is not > 0; a capacity below rows * cols (table given). */
+JSGX_API int jsgx_diagonal_filter_table(const double* window, int32_t n, double slope, int32_t zero_mean, int32_t* rows, int32_t* cols, double* table,
+                                        int64_t capacity);
+/* The bank of librosa.segment.path_enhance as a tap list (above).  *n_taps, *reach_i and *reach_j are always written (the size query:
+ * tap_w, tap_at and filter_first all NULL); with the three arrays, tap_w and tap_at take *n_taps entries and filter_first n_filters + 1.
+ * JSGX_ERR_INVALID, in this order: a null window, a null n_taps, a null reach_i, a null reach_j; some but not all of the three arrays;
+ * n outside 3..101; min_ratio or max_ratio not finite and > 0, min_ratio above max_ratio; n_filters outside 1..32; zero_mean other
+ * than 0 or 1; drop_below not in [0, 1); a window entry that is not finite; a table whose sum after clipping is not > 0; a bank with
+ * no tap or with more than JSGX_PE_MAX_TAPS; a reach above JSGX_PE_MAX_REACH; a capacity below *n_taps (arrays given). */
+JSGX_API int jsgx_diagonal_filter_build(const double* window, int32_t n, double min_ratio, double max_ratio, int32_t n_filters, int32_t zero_mean,
+                                        double drop_below, int32_t* n_taps, int32_t* reach_i, int32_t* reach_j, float* tap_w, int32_t* tap_at,
+                                        int32_t* filter_first, int64_t capacity);
+
+/* ------------------------------------------------------------------------------------------------
+ * 11. Time-lag conversion of a square plane (librosa.segment.recurrence_to_lag and lag_to_recurrence) in this library's index order.
+ *     L = 2 N with pad, else N.  Rz is R with +0 for rows (axis 1) or columns (axis 0) >= N.
+ *         axis 1, to lag (inverse 0):     lag[l][j] = Rz[(l + j) mod L][j],  l < L, j < N     (in N x N, out L x N)
+ *         axis 1, from lag (inverse 1):   R[i][j] = lag[(i - j) mod L][j],   i, j < N         (in L x N, out N x N)
+ *         axis 0, to lag:                 lag[i][l] = Rz[i][(l + i) mod L],  i < N, l < L     (in N x N, out N x L)
+ *         axis 0, from lag:               R[i][j] = lag[i][(j - i) mod L]                     (in N x L, out N x N)
+ *     librosa's axis=-1 on a two-dimensional array is axis 1 here.  The output is a pure permutation (and the zeros of the padding):
+ *     every output element is written once, bits unchanged, and nothing else is written.  Planes are [p][row][col] with a pitch and a pair
+ *     pitch as in section 7, whose query-major orientation note holds: lag l of column j (axis 1) is the row distance of a neighbour.
+ *     The kernels: "lag_columns" (axis 1) takes a 64 x 64 output tile per workgroup: its source is a parallelogram of 127 row pieces of
+ *     64 columns, read as whole 256-byte lines into LDS (a source line is read by two tiles) and written out as whole lines; "lag_rows"
+ *     (axis 0) rotates every row: reads and writes run along the row.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSGX_LAG_THREADS 256
+#define JSGX_LAG_TILE 64
+#define JSGX_LAG_LDS_BYTES 32512           /* static, "lag_columns": 127 pieces of 64 words */
+
+typedef struct jsgx_lag_args {
+    const float* in;            /* device floats */
+    int64_t in_pitch;           /* >= the input's columns */
+    int64_t in_pair_pitch;      /* pairs > 1: covers the input plane */
+    int32_t pairs;              /* 1..65535 */
+    int32_t n;                  /* N, 1..JSGX_DTW_MAX_LEN */
+    int32_t pad;                /* 0 or 1 */
+    int32_t axis;               /* 0 or 1 */
+    int32_t inverse;            /* 0: to lag, 1: from lag */
+    int32_t reserved0;          /* 0 */
+    float* out;                 /* device floats */
+    int64_t out_pitch;          /* >= the output's columns */
+    int64_t out_pair_pitch;     /* pairs > 1: covers the output plane */
+} jsgx_lag_args;                /* 72 bytes, no padding */
+
+/* Enqueue only (one kernel, no scratch); capture works, a first launch included.  Refused (JSGX_ERR_INVALID, nothing enqueued), in this
+ * order and before any device call: null args, a null in, a null out; a pointer that is not 4-byte aligned; pairs outside 1..65535, n
+ * outside 1..65536, pad other than 0 or 1, axis other than 0 or 1, inverse other than 0 or 1; a non-zero reserved0; in_pitch below the
+ * input's columns, in_pair_pitch that does not cover a plane (pairs > 1), the same for out_pitch and out_pair_pitch; out overlapping
+ * in.  Then JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_lag_launch(const jsgx_lag_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,21 @@ class RqaArgs(C.Structure):
                 ("end", C.c_void_p), ("total", C.c_void_p)]
 
 
+PE_MAX_REACH, PE_MAX_FILTERS, PE_MAX_TAPS, PE_TILE, PE_THREADS, PE_LDS_LIMIT, PE_MIN_WINDOW, PE_MAX_WINDOW = 64, 32, 1 << 20, 64, 256, 163840, 3, 101
+LAG_THREADS, LAG_TILE, LAG_LDS_BYTES = 256, 64, 32512
+
+
+class PathEnhanceArgs(C.Structure):
+    _fields_ = [("r", C.c_void_p), ("r_pitch", C.c_int64), ("r_pair_pitch", C.c_int64), ("tap_w", C.c_void_p), ("tap_at", C.c_void_p), ("filter_first", C.c_void_p),
+                ("pairs", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("n_filters", C.c_int32), ("n_taps", C.c_int32), ("reach_i", C.c_int32),
+                ("reach_j", C.c_int32), ("clip", C.c_int32), ("out", C.c_void_p), ("out_pitch", C.c_int64), ("out_pair_pitch", C.c_int64)]
+
+
+class LagArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("in_pitch", C.c_int64), ("in_pair_pitch", C.c_int64), ("pairs", C.c_int32), ("n", C.c_int32), ("pad", C.c_int32),
+                ("axis", C.c_int32), ("inverse", C.c_int32), ("reserved0", C.c_int32), ("out", C.c_void_p), ("out_pitch", C.c_int64), ("out_pair_pitch", C.c_int64)]
+
+
 # every symbol include/jsgx.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -154,6 +169,11 @@ SIGNATURES = {
     "jsgx_rqa_scratch_bytes": (C.c_int64, [C.POINTER(RqaArgs)]),
     "jsgx_rqa_launch": (C.c_int, [C.POINTER(RqaArgs), _P, C.c_int64, _P]),
     "jsgx_rqa_plan": (C.c_int, [C.POINTER(RqaArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 5),
+    "jsgx_path_enhance_launch": (C.c_int, [C.POINTER(PathEnhanceArgs), _P]),
+    "jsgx_path_enhance_plan": (C.c_int, [C.POINTER(PathEnhanceArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 4),
+    "jsgx_diagonal_filter_table": (C.c_int, [_P, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, C.c_int64]),
+    "jsgx_diagonal_filter_build": (C.c_int, [_P, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double] + [C.POINTER(C.c_int32)] * 3 + [_P, _P, _P, C.c_int64]),
+    "jsgx_lag_launch": (C.c_int, [C.POINTER(LagArgs), _P]),
 }
 
 _lib = None

@@ -89,6 +89,26 @@ struct RqaScratch {
 };
 RqaScratch rqa_scratch(const jsgx_rqa_args* g);
 
+// sections 10 and 11 (jsgx_path_enhance_host.cpp): every refusal, in the header's order
+int path_enhance_check(const jsgx_path_enhance_args* g, const char* who);
+int lag_check(const jsgx_lag_args* g, const char* who);
+// The staged window of section 10: its rows, and the words of a row (64 + 2 reach_j rounded up to 1 mod 4: eight rows, eight banks apart).
+JSGX_HD int pe_window_rows(int reach_i) { return JSGX_PE_TILE + 2 * reach_i; }
+JSGX_HD int pe_window_pitch(int reach_j) { return ((JSGX_PE_TILE + 2 * reach_j + 3) & ~3) + 1; }
+JSGX_HD int pe_lds_bytes(int reach_i, int reach_j) { return 4 * pe_window_rows(reach_i) * pe_window_pitch(reach_j); }
+// The planes of section 11: rows and columns of the input and of the output.
+struct LagShape {
+    int L, in_rows, in_cols, out_rows, out_cols;
+};
+JSGX_HD LagShape lag_shape(int n, int pad, int axis, int inverse) {
+    LagShape s;
+    s.L = pad ? 2 * n : n;
+    const int lag_rows = axis == 1 ? s.L : n, lag_cols = axis == 1 ? n : s.L;
+    s.in_rows = inverse ? lag_rows : n, s.in_cols = inverse ? lag_cols : n;
+    s.out_rows = inverse ? n : lag_rows, s.out_cols = inverse ? n : lag_cols;
+    return s;
+}
+
 // The three refusals of a launch's scratch buffer, in this order; `sizer` names the call that states `need`.
 inline int check_scratch(const char* who, const void* scratch, int64_t scratch_bytes, int64_t need, const char* sizer) {
     if (!scratch) return fail(JSGX_ERR_INVALID, who, "null scratch");

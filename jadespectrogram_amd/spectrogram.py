@@ -2068,6 +2068,159 @@ def rqa(sim, gap_onset=1.0, gap_extend=1.0, knight_moves=True, backtrack=True):
 
 
 # --------------------------------------------------------------------------------------------------
+# path enhancement and time-lag conversion of a recurrence plane (include/jsgx.h, sections 10 and 11: libjsgx.so)
+# --------------------------------------------------------------------------------------------------
+def _pe_window(window, n: int) -> np.ndarray:
+    """The n window samples in double: "hann" is the symmetric form (scipy's get_window(..., fftbins=False)); an array is taken as given."""
+    n = int(n)
+    if isinstance(window, str):
+        if window != "hann":
+            raise JsgError(capix.JSGX_ERR_INVALID, f"window must be 'hann' or an array of n samples, not {window!r}")
+        return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / max(n - 1, 1))
+    w = np.ascontiguousarray(window, dtype=np.float64)
+    if w.shape != (n,):
+        raise JsgError(capix.JSGX_ERR_INVALID, f"window must be 'hann' or an array of n = {n} samples, not one of shape {w.shape}")
+    return w
+
+
+def diagonal_filter(window, n: int, slope: float = 1.0, zero_mean: bool = False) -> np.ndarray:
+    """librosa.segment.path_enhance's filter of one slope as a dense float64 table (jsgx_diagonal_filter_table): diag(window), rotated as
+    scipy.ndimage.rotate(order=5, prefilter=False) does unless the slope is 1, clipped at 0, normalised to sum 1; zero_mean subtracts the
+    table's mean.  Host only."""
+    w = _pe_window(window, n)
+    rows, cols = C.c_int32(), C.c_int32()
+    capix.check(capix.lib().jsgx_diagonal_filter_table(w.ctypes.data, int(n), float(slope), int(bool(zero_mean)), C.byref(rows), C.byref(cols), None, 0))
+    table = np.zeros((rows.value, cols.value), dtype=np.float64)
+    capix.check(capix.lib().jsgx_diagonal_filter_table(w.ctypes.data, int(n), float(slope), int(bool(zero_mean)), C.byref(rows), C.byref(cols), table.ctypes.data, table.size))
+    return table
+
+
+def path_enhance_filters(n: int, *, window="hann", max_ratio: float = 2.0, min_ratio=None, n_filters: int = 7, zero_mean: bool = False, drop_below: float = 0.0):
+    """The bank of librosa.segment.path_enhance as the tap list of include/jsgx.h section 10 (jsgx_diagonal_filter_build) -> (tap_w
+    float32 [T], tap_at int32 [T] ((di << 16) | (dj & 0xffff)), filter_first int32 [n_filters + 1], reach_i, reach_j) on the host.
+    min_ratio None: 1 / max_ratio.  drop_below: taps below this fraction of their table's largest are dropped (0: librosa's filters)."""
+    w = _pe_window(window, n)
+    lo = 1.0 / float(max_ratio) if min_ratio is None else float(min_ratio)
+    head = (w.ctypes.data, int(n), lo, float(max_ratio), int(n_filters), int(bool(zero_mean)), float(drop_below))
+    count, ri, rj = C.c_int32(), C.c_int32(), C.c_int32()
+    capix.check(capix.lib().jsgx_diagonal_filter_build(*head, C.byref(count), C.byref(ri), C.byref(rj), None, None, None, 0))
+    tap_w, tap_at, first = np.zeros(count.value, np.float32), np.zeros(count.value, np.int32), np.zeros(int(n_filters) + 1, np.int32)
+    capix.check(capix.lib().jsgx_diagonal_filter_build(*head, C.byref(count), C.byref(ri), C.byref(rj), tap_w.ctypes.data, tap_at.ctypes.data, first.ctypes.data, count.value))
+    return tap_w, tap_at, first, ri.value, rj.value
+
+
+def _pe_args(d_r, d_tap_w, d_tap_at, d_filter_first, d_out, reach_i, reach_j, clip) -> capix.PathEnhanceArgs:
+    import torch
+    r, o = _planes(d_r, "d_r"), _planes(d_out, "d_out")
+    P, N, M = r.shape
+    assert tuple(o.shape) == (P, N, M), "d_out: the shape of d_r"
+    for t, dtype, what in ((d_tap_w, torch.float32, "d_tap_w: float32"), (d_tap_at, torch.int32, "d_tap_at: int32"), (d_filter_first, torch.int32, "d_filter_first: int32")):
+        assert t.is_cuda and t.dtype == dtype and t.dim() == 1 and t.is_contiguous(), f"{what} CUDA, contiguous"
+    assert d_tap_at.numel() == d_tap_w.numel() and d_filter_first.numel() >= 2, "d_tap_w and d_tap_at [n_taps], d_filter_first [n_filters + 1]"
+    return capix.PathEnhanceArgs(r.data_ptr(), r.stride(1), r.stride(0), d_tap_w.data_ptr(), d_tap_at.data_ptr(), d_filter_first.data_ptr(), P, N, M,
+                                 d_filter_first.numel() - 1, d_tap_w.numel(), int(reach_i), int(reach_j), int(bool(clip)), o.data_ptr(), o.stride(1), o.stride(0))
+
+
+def path_enhance_launch(d_r, d_tap_w, d_tap_at, d_filter_first, d_out, *, reach_i: int, reach_j: int, clip: bool = True, stream: int | None = None):
+    """jsgx_path_enhance_launch: d_r float32 [n][m] or [pairs][n][m] and a tap list on the device (path_enhance_filters, or the caller's:
+    weights, packed offsets, the first tap of every filter and the end) -> d_out, the same shape: per cell the maximum over the filters
+    of the fmaf chain of its taps in list order, +0 outside the plane; clip: negative results become +0.  A tap further than reach_i
+    rows or reach_j columns is skipped.  Enqueue only."""
+    a = _pe_args(d_r, d_tap_w, d_tap_at, d_filter_first, d_out, reach_i, reach_j, clip)
+    capix.check(capix.lib().jsgx_path_enhance_launch(C.byref(a), _stream_handle(stream, d_out)))
+
+
+def path_enhance_plan(reach_i: int, reach_j: int, n: int = 64, m: int = 64, pairs: int = 1):
+    """jsgx_path_enhance_plan: (kernel name, tile rows, tile columns, lanes per workgroup, bytes of LDS per workgroup) for these reaches.
+    Needs no device."""
+    a = capix.PathEnhanceArgs(r=1 << 44, r_pitch=int(m), r_pair_pitch=int(n) * int(m), tap_w=2 << 44, tap_at=3 << 44, filter_first=4 << 44, pairs=int(pairs), n=int(n),
+                              m=int(m), n_filters=1, n_taps=1, reach_i=int(reach_i), reach_j=int(reach_j), clip=1, out=5 << 44, out_pitch=int(m),
+                              out_pair_pitch=int(n) * int(m))      # never dereferenced
+    name, out = C.create_string_buffer(32), [C.c_int32() for _ in range(4)]
+    capix.check(capix.lib().jsgx_path_enhance_plan(C.byref(a), name, 32, *[C.byref(o) for o in out]))
+    return (name.value.decode(),) + tuple(o.value for o in out)
+
+
+def path_enhance(R, n: int, *, window="hann", max_ratio: float = 2.0, min_ratio=None, n_filters: int = 7, zero_mean: bool = False, drop_below: float = 0.0,
+                 clip: bool = True, out=None):
+    """librosa.segment.path_enhance on the GPU: R float32 CUDA [N][M] or [P][N][M] (recurrence_matrix in affinity mode, cross_similarity)
+    -> the plane smoothed along diagonals of n_filters slopes between min_ratio and max_ratio, the maximum over the slopes, the same
+    shape.  The bank is built once per set of parameters and device (path_enhance_filters) and stays on the device.  out: a tensor of
+    R's shape to write into (it must not overlap R).  Query-major like section 7: row i holds the neighbours of frame i; a bank of
+    slopes min_ratio..max_ratio with min_ratio = 1 / max_ratio is its own transpose, so the orientation does not change the result's
+    meaning.  Every operation is as include/jsgx.h section 10 states it: float32 fmaf chains in list order (scipy sums in float64)."""
+    import torch
+    assert hasattr(R, "is_cuda") and R.is_cuda and R.dtype == torch.float32 and R.dim() in (2, 3), "path_enhance: R float32 CUDA [N][M] or [P][N][M]"
+    r = R if R.stride(-1) == 1 else R.contiguous()
+    key = ("path_enhance", int(n), window if isinstance(window, str) else tuple(float(v) for v in window), float(max_ratio), None if min_ratio is None else float(min_ratio),
+           int(n_filters), bool(zero_mean), float(drop_below))
+    dev_key = (str(r.device),) + key
+    if dev_key not in _beat_cache:
+        tap_w, tap_at, first, ri, rj = path_enhance_filters(n, window=window, max_ratio=max_ratio, min_ratio=min_ratio, n_filters=n_filters, zero_mean=zero_mean,
+                                                            drop_below=drop_below)
+        _beat_cache[dev_key] = (torch.from_numpy(tap_w).to(r.device), torch.from_numpy(tap_at).to(r.device), torch.from_numpy(first).to(r.device), ri, rj)
+    d_w, d_at, d_first, ri, rj = _beat_cache[dev_key]
+    if out is None:
+        out = torch.empty(tuple(r.shape), dtype=torch.float32, device=r.device)
+    assert tuple(out.shape) == tuple(r.shape), "out: the shape of R"
+    with torch.cuda.device(_device_index(r)):
+        path_enhance_launch(r, d_w, d_at, d_first, out, reach_i=ri, reach_j=rj, clip=clip)
+    return out
+
+
+def _lag_axis(axis: int) -> int:
+    if axis not in (-1, 1, 0, -2):
+        raise JsgError(capix.JSGX_ERR_INVALID, f"axis must be -1, 1, 0 or -2 (of the plane's two axes), not {axis!r}")
+    return 1 if axis in (-1, 1) else 0
+
+
+def lag_launch(d_in, d_out, *, pad: bool = True, axis: int = -1, inverse: bool = False, stream: int | None = None):
+    """jsgx_lag_launch: the time-lag conversion of square planes.  To lag (inverse False): d_in float32 [n][n] or [pairs][n][n] -> d_out
+    [L][n] (axis -1 or 1: lag[l][j] = R[(l + j) mod L][j]) or [n][L] (axis 0 or -2), L = 2 n with pad else n; from lag (inverse True) the
+    shapes are exchanged and pad says which L the input has.  A pure permutation; the padding is +0.  Enqueue only."""
+    i, o = _planes(d_in, "d_in"), _planes(d_out, "d_out")
+    ax = _lag_axis(axis)
+    square, lagged = (o, i) if inverse else (i, o)
+    P, N = square.shape[0], square.shape[1]
+    L = 2 * N if pad else N
+    assert square.shape[2] == N and tuple(lagged.shape) == ((P, L, N) if ax == 1 else (P, N, L)), "lag_launch: a square plane and its lag plane for this pad and axis"
+    a = capix.LagArgs(i.data_ptr(), i.stride(1), i.stride(0), P, N, int(bool(pad)), ax, int(bool(inverse)), 0, o.data_ptr(), o.stride(1), o.stride(0))
+    capix.check(capix.lib().jsgx_lag_launch(C.byref(a), _stream_handle(stream, d_out)))
+
+
+def recurrence_to_lag(R, pad: bool = True, axis: int = -1):
+    """librosa.segment.recurrence_to_lag on the GPU: R float32 CUDA [N][N] or [P][N][N] -> the lag plane, [L][N] for axis -1 (lag[l][j] =
+    R[(l + j) mod L][j]) or [N][L] for axis 0 (of the plane's two axes), L = 2 N with pad (the added half is +0) else N.  Query-major as
+    section 7: with axis -1 the lag l of column j is the row distance i - j of a frame i that has j among its neighbours."""
+    import torch
+    assert hasattr(R, "is_cuda") and R.is_cuda and R.dtype == torch.float32 and R.dim() in (2, 3) and R.shape[-1] == R.shape[-2], "recurrence_to_lag: R float32 CUDA, square"
+    r = R if R.stride(-1) == 1 else R.contiguous()
+    N = r.shape[-1]
+    L = 2 * N if pad else N
+    shape = tuple(r.shape[:-2]) + ((L, N) if _lag_axis(axis) == 1 else (N, L))
+    out = torch.empty(shape, dtype=torch.float32, device=r.device)
+    with torch.cuda.device(_device_index(r)):
+        lag_launch(r, out, pad=pad, axis=axis)
+    return out
+
+
+def lag_to_recurrence(lag, axis: int = -1):
+    """librosa.segment.lag_to_recurrence on the GPU: the inverse of recurrence_to_lag; whether the lag plane was padded is read from its
+    shape ([L][N] for axis -1, [N][L] for axis 0, L = N or 2 N)."""
+    import torch
+    assert hasattr(lag, "is_cuda") and lag.is_cuda and lag.dtype == torch.float32 and lag.dim() in (2, 3), "lag_to_recurrence: lag float32 CUDA"
+    g = lag if lag.stride(-1) == 1 else lag.contiguous()
+    ax = _lag_axis(axis)
+    N, L = (g.shape[-1], g.shape[-2]) if ax == 1 else (g.shape[-2], g.shape[-1])
+    if L not in (N, 2 * N):
+        raise JsgError(capix.JSGX_ERR_INVALID, f"lag_to_recurrence: a lag plane of {N} frames has {N} or {2 * N} lags, not {L}")
+    out = torch.empty(tuple(g.shape[:-2]) + (N, N), dtype=torch.float32, device=g.device)
+    with torch.cuda.device(_device_index(g)):
+        lag_launch(g, out, pad=(L == 2 * N and N > 0), axis=axis, inverse=True)
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
 # Viterbi decoding of hidden Markov models (include/jsgx.h, section 4: libjsgx.so)
 # --------------------------------------------------------------------------------------------------
 def _viterbi_args(d_log_emit, d_log_init, d_log_trans, d_states, band_half, d_logp, d_value) -> capix.ViterbiArgs:

@@ -15,7 +15,8 @@ instruction-mix counts from the disassembly.  CPU only (llvm-objcopy / clang-off
                                                                pairwise cost, jsgx_dtw.o the time warping, jsgx_viterbi.o
                                                                the Viterbi kernels, jsgx_pyin.o the pYIN kernels, jsgx_knn.o
                                                                the nearest-frame, recurrence and nn_filter kernels and
-                                                               jsgx_rqa.o the recurrence quantification alignment: name them)
+                                                               jsgx_rqa.o the recurrence quantification alignment, jsgx_path_enhance.o
+                                                               the path enhancement and the lag conversion: name them)
 """
 import os
 import re
@@ -76,7 +77,8 @@ def main():
                                                "pvoc_scan_kernel", "hpss_freq_kernel", "hpss_time_kernel", "resample_kernel", "cqt_kernel", "yin_kernel", "onset_kernel", "tempogram_kernel", "tempo_kernel", "mfcc_kernel", "delta_kernel", "spectral_regs_kernel",
                                                "spectral_stream_kernel", "beat_kernel", "cdist_kernel", "dtw_kernel", "dtw_backtrace_kernel", "viterbi_forward_kernel",
                                                "viterbi_jump_kernel", "viterbi_ends_kernel", "viterbi_trace_kernel", "pyin_observe_kernel", "pyin_forward_kernel",
-                                               "knn_kernel", "knn_merge_kernel", "recurrence_kernel", "nn_filter_kernel", "rqa_kernel", "rqa_backtrace_kernel")):
+                                               "knn_kernel", "knn_merge_kernel", "recurrence_kernel", "nn_filter_kernel", "rqa_kernel", "rqa_backtrace_kernel",
+                                               "path_enhance_kernel", "lag_columns_kernel", "lag_rows_kernel")):
                     continue
                 mx = mix.get(name, {})
                 valu = sum(c for o, c in mx.items() if o.startswith("v_"))
