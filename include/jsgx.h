@@ -1150,6 +1150,124 @@ typedef struct jsgx_lag_args {
  * in.  Then JSGX_ERR_NO_DEVICE without a HIP device. */
 JSGX_API int jsgx_lag_launch(const jsgx_lag_args* args, void* stream);
 
+/* Section 12 was added to version 1 in the same way: sections 1 to 11, their structs and their constants are as they were. */
+
+/* ------------------------------------------------------------------------------------------------
+ * 12. Non-negative matrix factorisation (librosa.decompose.decompose with scikit-learn's NMF, solver="mu", beta_loss="frobenius"):
+ *     a plane V of T frames and K bins is factored into r spectral templates and their activations over time, V ~ A C.
+ *     Planes are frame-major, as everywhere here:
+ *         V[t][k] = v[p*v_problem_pitch + t*v_pitch + k],  t < T, k < K        the input, read only
+ *         A[t][c] = a[p*a_problem_pitch + t*a_pitch + c],  c < r               the activations, [T][r]
+ *         C[c][k] = c[p*c_problem_pitch + c*c_pitch + k]                       the components, [r][K]
+ *     librosa documents the transposes: its `components` is K x r (C transposed) and its `activations` r x T (A transposed); scikit-learn's
+ *     W is A and its H is C for X = V.  The P problems are independent.  A and C hold the start when the launch begins and are
+ *     updated in place, n_iter times.
+ *
+ *     Data: non-negative finite float32.  Negative, NaN or infinite inputs, and values so large that a sum below overflows, are
+ *     outside the contract: the launch still ends and writes nothing outside A and C (and the scratch), as in section 1.  Subnormals
+ *     are kept (the default kernel mode).
+ *
+ *     The chunked sum of n products x_i * y_i with chunk length L, the one rule for every long sum here: chunk q covers i in
+ *     [q L, min(n, q L + L));  p_q is the chain  acc = +0;  acc = fmaf(x_i, y_i, acc)  for i ascending over the chunk;  the sum is
+ *     ((p_0 + p_1) + p_2) + ... with plain adds, q ascending (one chunk: p_0 itself).  L is JSGX_NMF_CHUNK_K for sums over bins and
+ *     JSGX_NMF_CHUNK_T for sums over frames; both are multiples of 64 and depend on nothing: not on the device, the grid, P, the pitches
+ *     or r.  (The unit started from 256 and 1024; frame chunks of 256 measured faster, DESIGN.md 6u, and no other value was tried.)
+ *
+ *     One iteration, in scikit-learn's order: the activations first, then the components from the new activations.
+ *         N[t][c]  = chunked sum over k (CHUNK_K) of V[t][k] * C[c][k]
+ *         G[c][c'] = chunked sum over k (CHUNK_K) of C[c][k] * C[c'][k]
+ *         D[t][c]  = acc = +0;  acc = fmaf(A[t][c'], G[c'][c], acc),  c' = 0..r-1 ascending             (one chain, no chunks)
+ *         Dz = D where D != 0, else 2^-23 (JSGX_NMF_EPSILON)                                             (scikit-learn's EPSILON rule)
+ *         A[t][c]  = fl(A[t][c] * fl(N[t][c] / Dz))                                                      (the divide correctly rounded)
+ *     and, where update_components is 1, with the new A:
+ *         N2[c][k]  = chunked sum over t (CHUNK_T) of A[t][c] * V[t][k]
+ *         G2[c][c'] = chunked sum over t (CHUNK_T) of A[t][c] * A[t][c']
+ *         D2[c][k]  = acc = +0;  acc = fmaf(G2[c][c'], C[c'][k], acc),  c' ascending
+ *         C[c][k]   = fl(C[c][k] * fl(N2[c][k] / D2z))                                                   (D2z from D2 as Dz from D)
+ *     With update_components 0 the components stay as they are (scikit-learn's transform with update_H=False) and G is the same in
+ *     every iteration.
+ *
+ *     Padding.  On non-negative data every acc is +0 or positive, and fmaf(+0, +0, acc) = acc bit for bit; so a chain may be extended
+ *     by operand pairs that are both +0 wherever a kernel likes.  This is why r, K, T and the chunk tails need not be multiples of a
+ *     tile: the kernels zero-fill their panels.  fmaf(x, y, acc) = fmaf(y, x, acc), so G and G2 are symmetric bit for bit.
+ *
+ *     Known answers.  V = A C from small integers (every sum exact in float32) is a fixed point: N = D and N2 = D2, every ratio is
+ *     exactly 1, A and C come back bit-identical.  An all-zero frame of V has N = +0 and zeroes its row of A; an all-zero bin zeroes its
+ *     column of C.  An all-zero row of A has D = +0, takes the 2^-23 rule and stays zero.
+ *
+ *     Deliberate differences from librosa.decompose.decompose / scikit-learn: a fixed iteration count, no `tol` stopping (the launch
+ *     is enqueue-only); no "nndsvd" initialisation (the caller gives the start; Python offers scikit-learn's init="random" rule); the
+ *     Frobenius loss only (`loss` is carried for a later Kullback-Leibler form and any value but JSGX_NMF_FROBENIUS is refused); no
+ *     regularisation.  In float64 this definition equals sklearn.decomposition.non_negative_factorization(init="custom",
+ *     solver="mu", beta_loss="frobenius", tol=0) exactly (tests/test_nmf_ref.py); agreement with librosa itself is not measured.
+ *
+ *     The kernels (the matrix pipe: v_mfma_f32_16x16x4_f32 on float32 inputs is, on gfx950, bit for bit the k-ascending fmaf chain from
+ *     its accumulator input, one rounding a product and no wider accumulator; tests/test_gpu_nmf.py checks that first, and it is the one
+ *     stated exception to this library's vector-pipe rule).  Workgroups of JSGX_NMF_THREADS lanes (four wavefronts) stage 64 x 64
+ *     panels into JSGX_NMF_LDS_BYTES of LDS, zero-filled outside the planes, the next panel on its way from memory into registers while
+ *     the current one is multiplied; a wavefront owns 16 x 16 output tiles, one accumulator each.
+ *         "nmf_gram"      one (chunk, problem): the r x r chain of that chunk of C C^T (or A^T A) into the scratch
+ *         "nmf_chunk_sum" one element a lane: adds the chunks' partials of a Gram matrix, or of N2, in ascending chunk order
+ *         "nmf_update_a"  one strip of 64 frames: sweeps k chunk by chunk (a chain a chunk, then the plain add), then the D chain, the
+ *                         divide and the multiply; it alone reads and writes its rows of A
+ *         "nmf_partial_c" one (tile of 64 bins, frame chunk, problem): the chain of that chunk of N2 into the scratch
+ *         "nmf_update_c"  one tile of 64 bins, every component: the D2 chain, the divide and the multiply; it alone reads and writes its
+ *                         columns of C
+ *     An iteration is 8 launches on the one stream with update_components (gram, chunk_sum, update_a, gram, chunk_sum, partial_c,
+ *     chunk_sum, update_c) and 1 without (update_a; gram and chunk_sum run once in front of the first).  No workgroup waits for another and
+ *     there are no atomics.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSGX_NMF_MAX_COMPONENTS 64
+#define JSGX_NMF_MAX_BINS 16384
+#define JSGX_NMF_MAX_FRAMES 16777216
+#define JSGX_NMF_MAX_ITER 65536
+#define JSGX_NMF_CHUNK_K 256
+#define JSGX_NMF_CHUNK_T 256
+#define JSGX_NMF_FROBENIUS 0
+#define JSGX_NMF_EPSILON 1.1920928955078125e-07f        /* 2^-23 */
+#define JSGX_NMF_THREADS 256
+#define JSGX_NMF_LDS_BYTES 40960           /* static: two panels of 64 rows of 80 words */
+
+typedef struct jsgx_nmf_args {
+    const float* v;             /* device floats: V */
+    int64_t v_pitch;            /* >= n_bins */
+    int64_t v_problem_pitch;    /* problems > 1: >= (n_frames - 1) * v_pitch + n_bins */
+    float* a;                   /* device floats: A, the start on entry */
+    int64_t a_pitch;            /* >= n_components */
+    int64_t a_problem_pitch;    /* problems > 1: >= (n_frames - 1) * a_pitch + n_components */
+    float* c;                   /* device floats: C, the start on entry */
+    int64_t c_pitch;            /* >= n_bins */
+    int64_t c_problem_pitch;    /* problems > 1: >= (n_components - 1) * c_pitch + n_bins */
+    int32_t problems;           /* P, 1..65535 */
+    int32_t n_frames;           /* T, 1..JSGX_NMF_MAX_FRAMES */
+    int32_t n_bins;             /* K, 1..JSGX_NMF_MAX_BINS */
+    int32_t n_components;       /* r, 1..JSGX_NMF_MAX_COMPONENTS */
+    int32_t n_iter;             /* 1..JSGX_NMF_MAX_ITER */
+    int32_t update_components;  /* 0 or 1 */
+    int32_t loss;               /* JSGX_NMF_FROBENIUS */
+    int32_t reserved0;          /* 0 */
+} jsgx_nmf_args;                /* 104 bytes, no padding */
+
+/* The bytes of scratch the launch needs, with cK = ceil(K / CHUNK_K) and cT = ceil(T / CHUNK_T):  4 * P * r * r * (2 + cK)  without
+ * update_components (G, G2 unused, the chunks' partials of G), else  4 * P * r * (r * (2 + max(cK, cT)) + cT * K)  (also the partials
+ * of G2, in the same place, and of N2).  A larger scratch changes nothing.  Refused (a negative jsgx_status): what the launch refuses
+ * before it looks at the scratch. */
+JSGX_API int64_t jsgx_nmf_scratch_bytes(const jsgx_nmf_args* args);
+/* Enqueue only: no allocation, no synchronisation; capture works, a first launch included.  Refused (JSGX_ERR_INVALID, nothing
+ * enqueued), in this order and before any device call: null args, a null v, a null a, a null c; a pointer that is not 4-byte aligned;
+ * problems outside 1..65535, n_frames outside 1..2^24, n_bins outside 1..16384, n_components outside 1..64, n_iter outside 1..65536,
+ * update_components other than 0 or 1, a loss other than JSGX_NMF_FROBENIUS, a non-zero reserved0; v_pitch below n_bins,
+ * v_problem_pitch that does not cover a plane (problems > 1), the same for a_pitch (against n_components) and a_problem_pitch and for
+ * c_pitch (against n_bins) and c_problem_pitch; a overlapping v, c overlapping v, a overlapping c; a null scratch, a scratch that is
+ * not 4-byte aligned, scratch_bytes below the size above; the scratch (the bytes of that size) overlapping v, a, c in this order.
+ * Then JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_nmf_launch(const jsgx_nmf_args* args, void* scratch, int64_t scratch_bytes, void* stream);
+/* What the launch enqueues, without a device: the name of the kernel that sweeps V ("nmf_update_a"), JSGX_NMF_THREADS,
+ * JSGX_NMF_LDS_BYTES, the launches of an iteration (8, or 1 without update_components) and cT, the frame chunks.  Any output pointer may
+ * be NULL (name: else name_len >= 16).  Refused: a name_len below 16 with a name, then what the scratch size refuses. */
+JSGX_API int jsgx_nmf_plan(const jsgx_nmf_args* args, char* name, int name_len, int32_t* threads, int32_t* lds_bytes, int32_t* launches_per_iter,
+                           int32_t* t_chunks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,16 @@ class LagArgs(C.Structure):
                 ("axis", C.c_int32), ("inverse", C.c_int32), ("reserved0", C.c_int32), ("out", C.c_void_p), ("out_pitch", C.c_int64), ("out_pair_pitch", C.c_int64)]
 
 
+NMF_MAX_COMPONENTS, NMF_MAX_BINS, NMF_MAX_FRAMES, NMF_MAX_ITER, NMF_CHUNK_K, NMF_CHUNK_T = 64, 16384, 1 << 24, 65536, 256, 256
+NMF_FROBENIUS, NMF_EPSILON, NMF_THREADS, NMF_LDS_BYTES = 0, 2.0 ** -23, 256, 40960
+
+
+class NmfArgs(C.Structure):
+    _fields_ = [("v", C.c_void_p), ("v_pitch", C.c_int64), ("v_problem_pitch", C.c_int64), ("a", C.c_void_p), ("a_pitch", C.c_int64), ("a_problem_pitch", C.c_int64),
+                ("c", C.c_void_p), ("c_pitch", C.c_int64), ("c_problem_pitch", C.c_int64), ("problems", C.c_int32), ("n_frames", C.c_int32), ("n_bins", C.c_int32),
+                ("n_components", C.c_int32), ("n_iter", C.c_int32), ("update_components", C.c_int32), ("loss", C.c_int32), ("reserved0", C.c_int32)]
+
+
 # every symbol include/jsgx.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -174,6 +184,9 @@ SIGNATURES = {
     "jsgx_diagonal_filter_table": (C.c_int, [_P, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, C.c_int64]),
     "jsgx_diagonal_filter_build": (C.c_int, [_P, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double] + [C.POINTER(C.c_int32)] * 3 + [_P, _P, _P, C.c_int64]),
     "jsgx_lag_launch": (C.c_int, [C.POINTER(LagArgs), _P]),
+    "jsgx_nmf_scratch_bytes": (C.c_int64, [C.POINTER(NmfArgs)]),
+    "jsgx_nmf_launch": (C.c_int, [C.POINTER(NmfArgs), _P, C.c_int64, _P]),
+    "jsgx_nmf_plan": (C.c_int, [C.POINTER(NmfArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 4),
 }
 
 _lib = None

@@ -109,6 +109,32 @@ JSGX_HD LagShape lag_shape(int n, int pad, int axis, int inverse) {
     return s;
 }
 
+// section 12 (jsgx_nmf_host.cpp): every refusal that does not look at the scratch, in the header's order, and the bytes of the planes;
+// then the refusals of the scratch
+struct NmfSpans {
+    jsg::i128 v, a, c;
+};
+int nmf_check(const jsgx_nmf_args* g, const char* who, NmfSpans* spans);
+int nmf_check_scratch(const jsgx_nmf_args* g, const char* who, const NmfSpans& spans, const void* scratch, int64_t scratch_bytes);
+// Where the parts of the scratch of section 12 lie, in floats: G and G2 ([P][r][r] each), the chunks' partials of either Gram matrix
+// ([P][chunks][r][r], the larger chunk count), the chunks' partials of N2 ([P][cT][r][K]).
+struct NmfScratch {
+    long long chunks_k, chunks_t, chunks_g;
+    long long off_g2, off_gpart, off_n2part, bytes;
+};
+inline NmfScratch nmf_scratch(const jsgx_nmf_args* g) {
+    NmfScratch s;
+    const long long P = g->problems, r = g->n_components, K = g->n_bins;
+    s.chunks_k = (K + JSGX_NMF_CHUNK_K - 1) / JSGX_NMF_CHUNK_K;
+    s.chunks_t = ((long long)g->n_frames + JSGX_NMF_CHUNK_T - 1) / JSGX_NMF_CHUNK_T;
+    s.chunks_g = g->update_components && s.chunks_t > s.chunks_k ? s.chunks_t : s.chunks_k;
+    s.off_g2 = P * r * r;
+    s.off_gpart = 2 * s.off_g2;
+    s.off_n2part = s.off_gpart + P * s.chunks_g * r * r;
+    s.bytes = 4 * (s.off_n2part + (g->update_components ? P * s.chunks_t * r * K : 0));
+    return s;
+}
+
 // The three refusals of a launch's scratch buffer, in this order; `sizer` names the call that states `need`.
 inline int check_scratch(const char* who, const void* scratch, int64_t scratch_bytes, int64_t need, const char* sizer) {
     if (!scratch) return fail(JSGX_ERR_INVALID, who, "null scratch");

@@ -2221,6 +2221,92 @@ def lag_to_recurrence(lag, axis: int = -1):
 
 
 # --------------------------------------------------------------------------------------------------
+# Non-negative matrix factorisation (include/jsgx.h, section 12: libjsgx.so)
+# --------------------------------------------------------------------------------------------------
+def _nmf_args(d_v, d_a, d_c, n_iter, update_components) -> capix.NmfArgs:
+    v, a, c = _planes(d_v, "d_v"), _planes(d_a, "d_a"), _planes(d_c, "d_c")
+    P, T, K = v.shape
+    r = c.shape[1]
+    assert tuple(a.shape) == (P, T, r) and tuple(c.shape) == (P, r, K), "nmf: d_v [T][K], d_a [T][r], d_c [r][K], with the same leading problems if any"
+    # a row of one element may carry any stride: the pitch the library sees is then the row length or more
+    pitch = lambda t: t.stride(1) if t.shape[1] > 1 else max(t.shape[2], t.stride(1))
+    return capix.NmfArgs(v.data_ptr(), pitch(v), v.stride(0), a.data_ptr(), pitch(a), a.stride(0), c.data_ptr(), pitch(c), c.stride(0), P, T, K, r, int(n_iter),
+                         int(bool(update_components)), capix.NMF_FROBENIUS, 0)
+
+
+def nmf_scratch_bytes(d_v, d_a, d_c, *, n_iter: int = 1, update_components: bool = True) -> int:
+    """jsgx_nmf_scratch_bytes: the bytes of scratch nmf_launch needs for these arguments."""
+    return int(capix.check(capix.lib().jsgx_nmf_scratch_bytes(C.byref(_nmf_args(d_v, d_a, d_c, n_iter, update_components)))))
+
+
+def nmf_launch(d_v, d_a, d_c, *, n_iter: int, update_components: bool = True, d_scratch=None, stream: int | None = None):
+    """jsgx_nmf_launch: n_iter multiplicative updates (Frobenius loss, scikit-learn's solver="mu" order) of d_a float32 [T][r] and, with
+    update_components, d_c float32 [r][K], in place, for d_v float32 [T][K] ~ d_a d_c; a leading axis of problems is allowed on all three.
+    d_a and d_c hold the start.  d_scratch: a contiguous CUDA tensor of at least nmf_scratch_bytes bytes (None: one is allocated with
+    torch for this call).  Enqueue only."""
+    import torch
+    a = _nmf_args(d_v, d_a, d_c, n_iter, update_components)
+    d_scratch, stream = _scratch_and_stream(d_scratch, stream, d_v, lambda: capix.check(capix.lib().jsgx_nmf_scratch_bytes(C.byref(a))) // 4, torch.float32,
+                                            any_dtype=True)
+    capix.check(capix.lib().jsgx_nmf_launch(C.byref(a), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), stream))
+
+
+def nmf_plan(n_frames: int, n_bins: int, n_components: int, problems: int = 1, update_components: bool = True):
+    """jsgx_nmf_plan: (name of the kernel that sweeps V, lanes per workgroup, bytes of LDS per workgroup, launches per iteration, frame
+    chunks) for this shape.  Needs no device."""
+    T, K, r = int(n_frames), int(n_bins), int(n_components)
+    a = capix.NmfArgs(v=1 << 44, v_pitch=K, v_problem_pitch=T * K, a=2 << 44, a_pitch=r, a_problem_pitch=T * r, c=3 << 44, c_pitch=K, c_problem_pitch=r * K,
+                      problems=int(problems), n_frames=T, n_bins=K, n_components=r, n_iter=1, update_components=int(bool(update_components)),
+                      loss=capix.NMF_FROBENIUS, reserved0=0)      # never dereferenced
+    name, out = C.create_string_buffer(16), [C.c_int32() for _ in range(4)]
+    capix.check(capix.lib().jsgx_nmf_plan(C.byref(a), name, 16, *[C.byref(o) for o in out]))
+    return (name.value.decode(),) + tuple(o.value for o in out)
+
+
+def decompose(S, n_components=None, *, n_iter: int = 200, components=None, activations=None, fit: bool = True, sort: bool = False, seed: int = 0):
+    """librosa.decompose.decompose on the GPU (non-negative matrix factorisation, include/jsgx.h section 12): S float32 CUDA [T][K] or
+    [P][T][K], non-negative, frame-major as stft_fb, cqt and hpss write it -> (components [r][K], activations [T][r]) with S ~
+    activations @ components; librosa documents the transposes.  n_components None: K (at most 64).  The start is the caller's
+    `components` / `activations` (copied, not written) and else scikit-learn's init="random" rule, sqrt(mean(S) / r) * |randn| from a torch
+    generator seeded with `seed` (plumbing: the contract begins at the start).  fit=False needs `components`, keeps them fixed and
+    starts the activations at the constant sqrt(mean(S) / r): scikit-learn's transform.  sort=True orders the components by the bin of
+    their peak, ties to the lower component, and the activations alike (librosa's axis_sort).  A fixed n_iter, no tolerance."""
+    import torch
+    assert hasattr(S, "is_cuda") and S.is_cuda and S.dtype == torch.float32 and S.dim() in (2, 3), "decompose: S float32 CUDA [T][K] or [P][T][K]"
+    v = S if S.stride(-1) == 1 else S.contiguous()
+    lead, (T, K) = tuple(v.shape[:-2]), v.shape[-2:]
+    if components is not None:
+        assert components.is_cuda and components.dtype == torch.float32 and tuple(components.shape[:-2]) == lead and components.shape[-1] == K, \
+            "components: float32 CUDA [r][K], with the problems of S if any"
+        if n_components is None:
+            n_components = components.shape[-2]
+    if not fit and components is None:
+        raise JsgError(capix.JSGX_ERR_INVALID, "decompose: fit=False needs components")
+    r = K if n_components is None else int(n_components)
+    if not 1 <= r <= capix.NMF_MAX_COMPONENTS:
+        raise JsgError(capix.JSGX_ERR_INVALID, f"decompose: n_components must be in 1..{capix.NMF_MAX_COMPONENTS}, not {r}")
+    assert components is None or components.shape[-2] == r, "components: n_components rows"
+    assert activations is None or (activations.is_cuda and activations.dtype == torch.float32 and tuple(activations.shape) == lead + (T, r)), \
+        "activations: float32 CUDA [T][r], with the problems of S if any"
+    with torch.cuda.device(_device_index(v)):
+        scale = torch.sqrt(v.mean(dim=(-2, -1), keepdim=True) / r)
+        gen = torch.Generator(device=v.device)
+        gen.manual_seed(int(seed))
+        rand = lambda *shape: (scale * torch.randn(lead + shape, generator=gen, device=v.device, dtype=torch.float32).abs()).contiguous()
+        c = components.clone().contiguous() if components is not None else rand(r, K)
+        if not fit:
+            a = scale.expand(lead + (T, r)).contiguous()
+        else:
+            a = activations.clone().contiguous() if activations is not None else rand(T, r)
+        nmf_launch(v, a, c, n_iter=n_iter, update_components=fit)
+        if sort:
+            order = torch.argsort(torch.argmax(c, dim=-1), dim=-1, stable=True)
+            c = torch.gather(c, -2, order[..., :, None].expand_as(c))
+            a = torch.gather(a, -1, order[..., None, :].expand_as(a))
+    return c, a
+
+
+# --------------------------------------------------------------------------------------------------
 # Viterbi decoding of hidden Markov models (include/jsgx.h, section 4: libjsgx.so)
 # --------------------------------------------------------------------------------------------------
 def _viterbi_args(d_log_emit, d_log_init, d_log_trans, d_states, band_half, d_logp, d_value) -> capix.ViterbiArgs:
