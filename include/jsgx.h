@@ -1268,6 +1268,112 @@ JSGX_API int jsgx_nmf_launch(const jsgx_nmf_args* args, void* scratch, int64_t s
 JSGX_API int jsgx_nmf_plan(const jsgx_nmf_args* args, char* name, int name_len, int32_t* threads, int32_t* lds_bytes, int32_t* launches_per_iter,
                            int32_t* t_chunks);
 
+/* Section 13 was added to version 1 in the same way: sections 1 to 12, their structs and their constants are as they were. */
+
+/* ------------------------------------------------------------------------------------------------
+ * 13. Per-channel energy normalisation (librosa.pcen; Wang et al. 2017, Lostanlen et al. 2019): an automatic gain control per band
+ *     followed by root compression, the alternative to 10 log10 between a mel plane and whatever reads it.  The plane is
+ *         M[r][t][m] = in[r*row_pitch + t*frame_pitch + m],  r < rows, t < T (n_frames), m < B (n_bands)
+ *     as in jsg.h sections 2j to 2l; out and smooth_out have pitches of their own, state_in and state_out are [rows][B] at a row
+ *     pitch.  Rows and bands are independent.  The scalars b (the smoothing coefficient), gain, bias, power and eps are float32;
+ *     a = fl(1.0f - b).  The chunk length JSGX_PCEN_CHUNK = 256 frames depends on nothing: not on the shape, the device or the launch.
+ *
+ *     Smoother.  q[j] = (float)(a^(j+1)), j = 0..255: the table `decay`, pow in double of the float a, rounded once
+ *     (jsgx_pcen_decay_build).  The state that enters a row is s = state_in[r][m] where state_in is given, else M[r][0][m]: in exact
+ *     arithmetic that is librosa's default zi, which gives S[0] = M[0].  For chunk c over the frames t = 256 c + j, c ascending:
+ *         p = +0;   for j ascending:   p = fmaf(a, p, fl(b * M[t]));   S[t] = fmaf(q[j], s, p)
+ *         s = S[the last frame of the chunk]        (the state that enters chunk c + 1; behind the last chunk: state_out[r][m])
+ *     In exact arithmetic S[t] = a S[t-1] + b M[t].  S goes to smooth_out where that is given.
+ *
+ *     Compression.  Every product and sum is rounded on its own, no contraction:
+ *         g   = E(fl(-gain * L(fl(eps + S[t]))))                      ((eps + S)^-gain)
+ *         y   = fl(bias + fl(M[t] * g))
+ *         out = fl(E(fl(power * L(y))) - d),   d = E(fl(power * L(bias)))  by the same routines        ((M g + bias)^power - bias^power)
+ *     L(x) is the logarithm of section 5, here over every positive float32, subnormals included (against log in double over all of them:
+ *     JSGX_LOG_ABS_BOUND holds, profiles/pcen_accuracy.md).  E(x) is the exponential of section 1 carried to the whole line:
+ *         a NaN: NaN;   x < -87.0f: +0;   x > 88.72f: +inf
+ *         otherwise n, r and the polynomial p of section 1 (n = -126 .. 128), and
+ *         E = fl(fl(p * 2^h) * 2^(n - h)),  h = floor(n / 2), both factors floats built from their exponent bits: the first product is exact
+ *     For -87 <= x <= 0 the bits of E are those of section 1's routine (one routine serves both).  Against exp in double over every
+ *     float32 in [-87, 88.72] the relative error is within JSGX_EXP_REL_BOUND (profiles/pcen_accuracy.md).
+ *
+ *     Known answers.  A silent frame (M[t] = 0, g finite) has y = bias and out = fl(x - x) = +0 exactly, for every bias >= 0; with
+ *     bias = 0, L(0) = -inf and E(-inf) = +0 serve without a special case.  b = 1: a = +0, q = +0, S = M.
+ *
+ *     Consequences.  A NaN at (r, t0, m) makes p, S and every later state NaN: it poisons (r, t >= t0, m) and nothing else.  A
+ *     negative value gives NaN wherever eps + S < 0 or y < 0, in its own (r, m) only.  No output depends on the number of rows, on the
+ *     pitches or on the launch geometry.  A plane processed in two calls, split at a multiple of 256 frames with state_out fed to
+ *     state_in, equals the single call bit for bit; split elsewhere it differs in the last bits (another association of the same sum).
+ *
+ *     Deliberate differences from librosa.pcen: the state is the previous smoothed value, not scipy's filter delay (zi = a * state);
+ *     power > 0 only (the log1p limit at power = 0 is not built); no max_size maximum filter across bands; no axis argument (frames
+ *     are the second-to-last axis); float32 throughout.  Against the float64 route through scipy.signal.lfilter the restatement of
+ *     this definition is within the figures of profiles/pcen_accuracy.md; agreement with librosa itself is not measured.
+ *
+ *     The kernels.  A lane owns one chain: one band of one chunk of one row.  The chains are numbered (row, chunk, band), the band
+ *     fastest, and dealt to workgroups of JSGX_PCEN_THREADS lanes in that order: a wavefront reads neighbouring floats of a frame, and
+ *     with fewer than 64 bands it holds several chunks or rows, so no lane idles but in the last workgroup.  No LDS.
+ *         "pcen_chunked" (T > 256), three launches: "pcen_scan" (p of every chunk but a row's last, into the scratch), "pcen_carry"
+ *                        (one lane a (row, band): s_(c+1) = fmaf(q[255], s_c, p_c), the entering states into the scratch), "pcen_apply"
+ *                        (p again, S, the compression, the stores, state_out: four lanes a chain, each runs p from the chunk's start, the
+                        same chain and the same bits, and compresses 64 frames of its own, since the compression is some 170 vector
+                        operations a value and p is two)
+ *         "pcen_single"  (T <= 256), one launch: "pcen_apply" with the entering state read directly; no scratch
+ *     No workgroup waits for another and there are no atomics.  The plane is read twice and written once.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSGX_PCEN_CHUNK 256
+#define JSGX_PCEN_MAX_BANDS 65536
+#define JSGX_PCEN_MAX_CHAINS 68719476736           /* 2^36: rows * ceil(n_frames / JSGX_PCEN_CHUNK) * n_bands; four lanes a chain at the most */
+#define JSGX_PCEN_THREADS 256
+
+typedef struct jsgx_pcen_args {
+    const float* in;            /* device floats: M */
+    int64_t frame_pitch;        /* >= n_bands */
+    int64_t row_pitch;          /* rows > 1: >= (n_frames - 1) * frame_pitch + n_bands */
+    const float* decay;         /* device floats: q, JSGX_PCEN_CHUNK of them, from jsgx_pcen_decay_build(b) */
+    const float* state_in;      /* device floats [rows][n_bands] or NULL: the first frame is the state */
+    int64_t state_in_pitch;     /* rows > 1: >= n_bands */
+    float* state_out;           /* device floats [rows][n_bands] or NULL */
+    int64_t state_out_pitch;    /* rows > 1: >= n_bands */
+    float* smooth_out;          /* device floats: S, or NULL */
+    int64_t smooth_frame_pitch; /* >= n_bands */
+    int64_t smooth_row_pitch;   /* rows > 1: covers a plane */
+    float* out;                 /* device floats */
+    int64_t out_frame_pitch;    /* >= n_bands */
+    int64_t out_row_pitch;      /* rows > 1: covers a plane */
+    int32_t rows;               /* 1..65535 */
+    int32_t n_bands;            /* B, 1..JSGX_PCEN_MAX_BANDS */
+    int32_t n_frames;           /* T, 1..2^31-1 */
+    float b;                    /* in (0, 1]; decay was built from the same b */
+    float gain;                 /* >= 0 */
+    float bias;                 /* >= 0 */
+    float power;                /* > 0 */
+    float eps;                  /* > 0 */
+} jsgx_pcen_args;               /* 144 bytes, no padding */
+
+/* The table q on the host (no device): out[j] = (float)pow((double)fl(1.0f - b), j + 1), j = 0..JSGX_PCEN_CHUNK-1.
+ * JSGX_ERR_INVALID: a null out; a b that is not finite or lies outside (0, 1]. */
+JSGX_API int jsgx_pcen_decay_build(float b, float* out);
+/* The bytes of scratch the launch needs: 0 where n_frames <= JSGX_PCEN_CHUNK, else 4 * rows * ceil(n_frames / 256) * n_bands.  A larger
+ * scratch changes nothing.  Refused (a negative jsgx_status): what the launch refuses before it looks at the scratch. */
+JSGX_API int64_t jsgx_pcen_scratch_bytes(const jsgx_pcen_args* args);
+/* Enqueue only: no allocation, no synchronisation; capture works, a first launch included.  Refused (JSGX_ERR_INVALID, nothing
+ * enqueued), in this order and before any device call: null args, a null in, a null decay, a null out; a pointer (the optional ones
+ * included) that is not 4-byte aligned; rows outside 1..65535, n_bands outside 1..65536, n_frames below 1, more than
+ * JSGX_PCEN_MAX_CHAINS chains; frame_pitch below n_bands, row_pitch that does not cover a plane (rows > 1); state_in_pitch and then
+ * state_out_pitch below n_bands (where the buffer is given and rows > 1); the same two for smooth_out (where given) and for out; b not
+ * finite or outside (0, 1]; gain, then bias, negative or not finite; power, then eps, not finite or not positive; out, then smooth_out,
+ * then state_out overlapping in, decay, state_in in this order; out overlapping smooth_out, out overlapping state_out, smooth_out
+ * overlapping state_out; and where the scratch size is not 0: a null scratch, a scratch that is not 4-byte aligned, scratch_bytes
+ * below the size, the scratch (the bytes of that size) overlapping in, decay, state_in, out, smooth_out, state_out in this order.
+ * Then JSGX_ERR_NO_DEVICE without a HIP device.  That decay holds the table of b is the caller's to see to. */
+JSGX_API int jsgx_pcen_launch(const jsgx_pcen_args* args, void* scratch, int64_t scratch_bytes, void* stream);
+/* What the launch enqueues, without a device: the form ("pcen_single" or "pcen_chunked"), JSGX_PCEN_THREADS, the bytes of LDS (0), the
+ * launches (1 or 3) and the chunks of a row.  Any output pointer may be NULL (name: else name_len >= 16).  Refused: a name_len below
+ * 16 with a name, then what the scratch size refuses. */
+JSGX_API int jsgx_pcen_plan(const jsgx_pcen_args* args, char* name, int name_len, int32_t* threads, int32_t* lds_bytes, int32_t* n_launches,
+                            int32_t* chunks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,17 @@ class NmfArgs(C.Structure):
                 ("n_components", C.c_int32), ("n_iter", C.c_int32), ("update_components", C.c_int32), ("loss", C.c_int32), ("reserved0", C.c_int32)]
 
 
+PCEN_CHUNK, PCEN_MAX_BANDS, PCEN_MAX_CHAINS, PCEN_THREADS = 256, 65536, 1 << 36, 256
+
+
+class PcenArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("frame_pitch", C.c_int64), ("row_pitch", C.c_int64), ("decay", C.c_void_p), ("state_in", C.c_void_p),
+                ("state_in_pitch", C.c_int64), ("state_out", C.c_void_p), ("state_out_pitch", C.c_int64), ("smooth_out", C.c_void_p),
+                ("smooth_frame_pitch", C.c_int64), ("smooth_row_pitch", C.c_int64), ("out", C.c_void_p), ("out_frame_pitch", C.c_int64),
+                ("out_row_pitch", C.c_int64), ("rows", C.c_int32), ("n_bands", C.c_int32), ("n_frames", C.c_int32), ("b", C.c_float), ("gain", C.c_float),
+                ("bias", C.c_float), ("power", C.c_float), ("eps", C.c_float)]
+
+
 # every symbol include/jsgx.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -187,6 +198,10 @@ SIGNATURES = {
     "jsgx_nmf_scratch_bytes": (C.c_int64, [C.POINTER(NmfArgs)]),
     "jsgx_nmf_launch": (C.c_int, [C.POINTER(NmfArgs), _P, C.c_int64, _P]),
     "jsgx_nmf_plan": (C.c_int, [C.POINTER(NmfArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 4),
+    "jsgx_pcen_decay_build": (C.c_int, [C.c_float, _P]),
+    "jsgx_pcen_scratch_bytes": (C.c_int64, [C.POINTER(PcenArgs)]),
+    "jsgx_pcen_launch": (C.c_int, [C.POINTER(PcenArgs), _P, C.c_int64, _P]),
+    "jsgx_pcen_plan": (C.c_int, [C.POINTER(PcenArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 4),
 }
 
 _lib = None

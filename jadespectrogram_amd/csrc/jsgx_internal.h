@@ -135,6 +135,31 @@ inline NmfScratch nmf_scratch(const jsgx_nmf_args* g) {
     return s;
 }
 
+// section 13 (jsgx_pcen_host.cpp): every refusal that does not look at the scratch, in the header's order, and the bytes of the buffers;
+// then the refusals of the scratch
+struct PcenSpans {
+    jsg::i128 in, decay, state_in, out, smooth, state_out;
+};
+int pcen_check(const jsgx_pcen_args* g, const char* who, PcenSpans* spans);
+int pcen_check_scratch(const jsgx_pcen_args* g, const char* who, const PcenSpans& spans, const void* scratch, int64_t scratch_bytes);
+// How section 13 serves a shape: the chunks of a row, the chains (one lane each: a band of a chunk of a row), the launches and the bytes
+// of the scratch ([rows][chunks][bands] floats: a chunk's last p, then the state that enters it; none where a row is one chunk).
+struct PcenPlan {
+    const char* name;
+    long long chunks, chains;
+    int launches;
+    long long scratch_bytes;
+};
+inline PcenPlan pcen_plan(const jsgx_pcen_args* g) {
+    PcenPlan p;
+    p.chunks = ((long long)g->n_frames + JSGX_PCEN_CHUNK - 1) / JSGX_PCEN_CHUNK;
+    p.chains = (long long)g->rows * p.chunks * g->n_bands;
+    p.name = p.chunks == 1 ? "pcen_single" : "pcen_chunked";
+    p.launches = p.chunks == 1 ? 1 : 3;
+    p.scratch_bytes = p.chunks == 1 ? 0 : 4 * p.chains;
+    return p;
+}
+
 // The three refusals of a launch's scratch buffer, in this order; `sizer` names the call that states `need`.
 inline int check_scratch(const char* who, const void* scratch, int64_t scratch_bytes, int64_t need, const char* sizer) {
     if (!scratch) return fail(JSGX_ERR_INVALID, who, "null scratch");
@@ -289,11 +314,14 @@ JSGX_HD float float_of_bits(unsigned b) {
 #endif
 }
 
-// exp(x) for x <= 0 as include/jsgx.h states it, operation by operation
-JSGX_HD float exp_neg(float x) {
-    if (x < -87.0f) return 0.f;
-    const float n = __builtin_floorf(__builtin_fmaf(x, 1.44269502162933349609375f, 0.5f));
-    float r = __builtin_fmaf(n, -0.693145751953125f, x);
+// E(x), the exponential as include/jsgx.h states it, operation by operation: jsgx_exp of section 1 carried to the whole line (section
+// 13).  The scale 2^n, -126 <= n <= 128, goes on as two exact factors; for -87 <= x <= 0 the bits are those of the one product
+JSGX_HD float exp_any(float x) {
+    // straight-line: the arithmetic runs on an argument inside the range (itself wherever it lies inside), the three special answers
+    // are selected behind it
+    const float v = __builtin_fminf(__builtin_fmaxf(x, -87.0f), 88.72f);
+    const float n = __builtin_floorf(__builtin_fmaf(v, 1.44269502162933349609375f, 0.5f));
+    float r = __builtin_fmaf(n, -0.693145751953125f, v);
     r = __builtin_fmaf(n, -1.42860676533018704503775e-06f, r);
     float p = 1.984127011382952332496643e-04f;
     p = __builtin_fmaf(p, r, 1.388888922519981861114502e-03f);
@@ -303,8 +331,14 @@ JSGX_HD float exp_neg(float x) {
     p = __builtin_fmaf(p, r, 0.5f);
     p = __builtin_fmaf(p, r, 1.0f);
     p = __builtin_fmaf(p, r, 1.0f);
-    return p * float_of_bits((unsigned)((int)n + 127) << 23);
+    const int ni = (int)n, half = ni >> 1;            // floor(n / 2)
+    const float e = (p * float_of_bits((unsigned)(half + 127) << 23)) * float_of_bits((unsigned)(ni - half + 127) << 23);
+    float out = x > 88.72f ? __builtin_inff() : e;          // one select each: no arm is an expression
+    out = x < -87.0f ? 0.f : out;
+    return x != x ? x : out;
 }
+// the name sections 1 and 7 call it by: their arguments are <= 0
+JSGX_HD float exp_neg(float x) { return exp_any(x); }
 
 JSGX_HD unsigned bits_of_float(float v) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -322,13 +356,15 @@ JSGX_HD float log_pos(float x) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-    if (!(x > 0.f)) return x == 0.f ? -__builtin_inff() : __builtin_nanf("");
-    if (x == __builtin_inff()) return x;
-    int k = 0;
-    if (x < 1.1754943508222875e-38f) {           // below 2^-126: scaled by 2^24, exactly
-        x = x * 16777216.0f;
-        k = -24;
-    }
+    // straight-line: the arithmetic runs on a positive finite argument (x itself wherever it is one), the special answers are selected
+    // behind it
+    const float x0 = x;
+    const bool plain = x > 0.f && x < __builtin_inff();
+    x = plain ? x : 1.0f;
+    const bool tiny = x < 1.1754943508222875e-38f;           // below 2^-126: scaled by 2^24, exactly
+    const float scaled = x * 16777216.0f;
+    x = tiny ? scaled : x;
+    int k = tiny ? -24 : 0;
     unsigned ix = bits_of_float(x) + (0x3f800000u - 0x3f3504f3u);
     k += (int)(ix >> 23) - 127;
     const float m = float_of_bits((ix & 0x007fffffu) + 0x3f3504f3u);        // x = m 2^k, sqrt(1/2) <= m < sqrt(2)
@@ -341,7 +377,10 @@ JSGX_HD float log_pos(float x) {
     const float r = t2 + t1;
     const float hfsq = (0.5f * f) * f;
     const float dk = (float)k;
-    return (((s * (hfsq + r) + dk * 9.0580006145e-06f) - hfsq) + f) + dk * 6.9313812256e-01f;
+    const float l = (((s * (hfsq + r) + dk * 9.0580006145e-06f) - hfsq) + f) + dk * 6.9313812256e-01f;
+    float special = x0 == 0.f ? -__builtin_inff() : __builtin_nanf("");          // one select each: no arm is an expression
+    special = x0 == __builtin_inff() ? x0 : special;
+    return plain ? l : special;
 }
 
 }  // namespace jsgx

@@ -742,6 +742,11 @@ def mel_spectrogram_db(x, fs: float, n_fft: int, hop: int, n_mels: int, fmin: fl
     normalisation (librosa.feature.melspectrogram's bank), frames at t * hop (no padding), 10*log10(band power + 1e-11).
     hop must divide n_fft (the kernels' regular framing, hop * feedblocks = n_fft; other hops are refused with JSG_ERR_INVALID).
     Returns a new tensor [frames][n_mels] on x.device.  Plan and Filterbank are cached per geometry."""
+    return _mel_plane(x, fs, n_fft, hop, n_mels, fmin, fmax, window, mix_mode, exact_log, False)
+
+
+def _mel_plane(x, fs, n_fft, hop, n_mels, fmin, fmax, window, mix_mode, exact_log, linear_out):
+    """mel_spectrogram_db, or with linear_out the band power in front of its logarithm."""
     import torch
     if hop <= 0 or hop > n_fft or n_fft % hop:
         raise JsgError(capi.JSG_ERR_INVALID, f"mel_spectrogram_db: hop {hop} must divide n_fft {n_fft} (frames at t * hop)")
@@ -761,7 +766,7 @@ def mel_spectrogram_db(x, fs: float, n_fft: int, hop: int, n_mels: int, fmin: fl
     plan, fb = _mel_cache[key]
     out = torch.empty((frames, n_mels), dtype=torch.float32, device=x.device)
     with torch.cuda.device(dev):
-        stft_fb_db(plan, fb, x, hop, frames, out, feedblocks=n_fft // hop, mix_mode=mix_mode, exact_log=exact_log)
+        stft_fb_db(plan, fb, x, hop, frames, out, feedblocks=n_fft // hop, mix_mode=mix_mode, exact_log=exact_log, linear_out=linear_out)
     return out
 
 
@@ -2304,6 +2309,126 @@ def decompose(S, n_components=None, *, n_iter: int = 200, components=None, activ
             c = torch.gather(c, -2, order[..., :, None].expand_as(c))
             a = torch.gather(a, -1, order[..., None, :].expand_as(a))
     return c, a
+
+
+# --------------------------------------------------------------------------------------------------
+# Per-channel energy normalisation (include/jsgx.h, section 13: libjsgx.so)
+# --------------------------------------------------------------------------------------------------
+_pcen_decay_cache: dict = {}
+
+
+def pcen_coefficient(time_constant: float, sr: float, hop_length: int) -> float:
+    """librosa.pcen's smoothing coefficient b = (sqrt(1 + 4 T^2) - 1) / (2 T^2), T = time_constant * sr / hop_length, in double."""
+    T = float(time_constant) * float(sr) / float(hop_length)
+    return (np.sqrt(1.0 + 4.0 * T * T) - 1.0) / (2.0 * T * T)
+
+
+def pcen_decay(b: float) -> np.ndarray:
+    """jsgx_pcen_decay_build: the table q[j] = (float)((1 - b)^(j + 1)), j = 0..255, of the float32 b.  Needs no device."""
+    out = np.empty(capix.PCEN_CHUNK, np.float32)
+    capix.check(capix.lib().jsgx_pcen_decay_build(float(b), out.ctypes.data))
+    return out
+
+
+def _pcen_states(t, R, B, what: str):
+    """(pointer, row pitch) of an optional float32 CUDA [rows][bands] (or [bands] for one row) with unit band stride."""
+    import torch
+    if t is None:
+        return None, 0
+    t = t[None] if t.dim() == 1 else t
+    assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (R, B) and (t.stride(1) == 1 or B == 1), f"{what}: float32 CUDA [rows][bands]"
+    return t.data_ptr(), t.stride(0)
+
+
+def _pcen_args(d_in, d_decay, d_out, b, gain, bias, power, eps, d_state_in, d_state_out, d_smooth) -> capix.PcenArgs:
+    import torch
+    x, o = _plane(d_in, "d_in"), _plane(d_out, "d_out")
+    R, T, B = x.shape
+    assert tuple(o.shape) == (R, T, B), "d_out: the shape of d_in"
+    assert d_decay.is_cuda and d_decay.dtype == torch.float32 and d_decay.dim() == 1 and d_decay.shape[0] >= capix.PCEN_CHUNK and d_decay.stride(0) == 1, \
+        "d_decay: float32 CUDA [256], pcen_decay(b) on the device"
+    # a plane of one frame may carry any frame stride: the pitch the library sees is then the frame length or more
+    pitch = lambda t: t.stride(1) if T > 1 else max(B, t.stride(1))
+    sm = None if d_smooth is None else _plane(d_smooth, "d_smooth")
+    assert sm is None or tuple(sm.shape) == (R, T, B), "d_smooth: the shape of d_in"
+    si, si_pitch = _pcen_states(d_state_in, R, B, "d_state_in")
+    so, so_pitch = _pcen_states(d_state_out, R, B, "d_state_out")
+    return capix.PcenArgs(x.data_ptr(), pitch(x), x.stride(0), d_decay.data_ptr(), si, si_pitch, so, so_pitch, None if sm is None else sm.data_ptr(),
+                          0 if sm is None else pitch(sm), 0 if sm is None else sm.stride(0), o.data_ptr(), pitch(o), o.stride(0), R, B, T, float(b), float(gain),
+                          float(bias), float(power), float(eps))
+
+
+def pcen_scratch_bytes(d_in, d_decay, d_out, *, b: float, gain: float = 0.98, bias: float = 2.0, power: float = 0.5, eps: float = 1e-6, d_state_in=None,
+                       d_state_out=None, d_smooth=None) -> int:
+    """jsgx_pcen_scratch_bytes: the bytes of scratch pcen_launch needs for these arguments (0 up to 256 frames)."""
+    a = _pcen_args(d_in, d_decay, d_out, b, gain, bias, power, eps, d_state_in, d_state_out, d_smooth)
+    return int(capix.check(capix.lib().jsgx_pcen_scratch_bytes(C.byref(a))))
+
+
+def pcen_launch(d_in, d_decay, d_out, *, b: float, gain: float = 0.98, bias: float = 2.0, power: float = 0.5, eps: float = 1e-6, d_state_in=None,
+                d_state_out=None, d_smooth=None, d_scratch=None, stream: int | None = None):
+    """jsgx_pcen_launch: d_in float32 [rows][frames][bands] (or one [frames][bands] plane; views with pitches) -> d_out of the same shape,
+    (d_in * (eps + S)^-gain + bias)^power - bias^power with S the first-order smoothing of d_in along the frames with coefficient b.
+    d_decay: pcen_decay(b) on the device.  d_state_in float32 [rows][bands]: the smoothed value in front of frame 0 (None: frame 0
+    itself); d_state_out: the one behind the last frame; d_smooth: S.  d_scratch: a contiguous CUDA tensor of at least
+    pcen_scratch_bytes bytes (None: one is allocated with torch for this call).  Enqueue only."""
+    import torch
+    a = _pcen_args(d_in, d_decay, d_out, b, gain, bias, power, eps, d_state_in, d_state_out, d_smooth)
+    d_scratch, stream = _scratch_and_stream(d_scratch, stream, d_in, lambda: capix.check(capix.lib().jsgx_pcen_scratch_bytes(C.byref(a))) // 4, torch.float32,
+                                            any_dtype=True)
+    capix.check(capix.lib().jsgx_pcen_launch(C.byref(a), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), stream))
+
+
+def pcen_plan(n_frames: int, n_bands: int, rows: int = 1):
+    """jsgx_pcen_plan: (form, lanes per workgroup, bytes of LDS per workgroup, launches, chunks of a row) for this shape: "pcen_single" up
+    to 256 frames, else "pcen_chunked".  Needs no device."""
+    T, B, R = int(n_frames), int(n_bands), int(rows)
+    a = capix.PcenArgs(in_=1 << 50, frame_pitch=B, row_pitch=T * B, decay=1 << 40, out=1 << 58, out_frame_pitch=B, out_row_pitch=T * B, rows=R, n_bands=B,
+                       n_frames=T, b=0.5, gain=0.98, bias=2.0, power=0.5, eps=1e-6)      # never dereferenced
+    name, out = C.create_string_buffer(16), [C.c_int32() for _ in range(4)]
+    capix.check(capix.lib().jsgx_pcen_plan(C.byref(a), name, 16, *[C.byref(o) for o in out]))
+    return (name.value.decode(),) + tuple(o.value for o in out)
+
+
+def pcen(plane, *, sr: float = 22050, hop_length: int = 512, gain: float = 0.98, bias: float = 2.0, power: float = 0.5, time_constant: float = 0.4,
+         eps: float = 1e-6, b: float | None = None, state=None, return_state: bool = False, return_smooth: bool = False):
+    """librosa.pcen on the GPU (include/jsgx.h section 13): plane float32 CUDA [..., frames, bands], non-negative (what stft_fb_db writes with
+    linear_out, or a cqt magnitude) -> a new tensor of the same shape.  b None: pcen_coefficient(time_constant, sr, hop_length).  state
+    float32 CUDA [..., bands]: the smoothed value in front of frame 0, as a former call returned it (None: frame 0 itself, librosa's
+    default); return_state adds the value behind the last frame and return_smooth the smoothed plane: (out[, state][, smooth]).  Differs
+    from librosa.pcen on purpose: frames lie along axis -2, the state is the smoothed value itself (not scipy's zi), power > 0 only, no
+    max_size, and the plane is taken as it is (librosa's documentation scales audio by 2^31 first).  A plane cut at a multiple of 256
+    frames and fed block by block with the state equals the whole in every bit.  Agreement with librosa was not measured."""
+    import torch
+    assert hasattr(plane, "is_cuda") and plane.is_cuda and plane.dtype == torch.float32 and plane.dim() >= 2, "pcen: plane float32 CUDA [..., frames, bands]"
+    lead, (T, B) = tuple(plane.shape[:-2]), plane.shape[-2:]
+    x = plane.reshape(-1, T, B)
+    x = x if x.stride(2) == 1 else x.contiguous()
+    R = x.shape[0]
+    b = pcen_coefficient(time_constant, sr, hop_length) if b is None else float(b)
+    s_in = None
+    if state is not None:
+        assert state.is_cuda and state.dtype == torch.float32 and tuple(state.shape) == lead + (B,), "state: float32 CUDA [..., bands]"
+        s_in = state.reshape(R, B).contiguous()
+    with torch.cuda.device(_device_index(x)):
+        key = (_device_index(x), float(np.float32(b)))
+        if key not in _pcen_decay_cache:
+            _pcen_decay_cache[key] = torch.from_numpy(pcen_decay(b)).to(x.device)
+        out = torch.empty((R, T, B), dtype=torch.float32, device=x.device)
+        s_out = torch.empty((R, B), dtype=torch.float32, device=x.device) if return_state else None
+        smooth = torch.empty((R, T, B), dtype=torch.float32, device=x.device) if return_smooth else None
+        pcen_launch(x, _pcen_decay_cache[key], out, b=b, gain=gain, bias=bias, power=power, eps=eps, d_state_in=s_in, d_state_out=s_out, d_smooth=smooth)
+    res = (out.reshape(plane.shape),) + ((s_out.reshape(lead + (B,)),) if return_state else ()) + ((smooth.reshape(plane.shape),) if return_smooth else ())
+    return res[0] if len(res) == 1 else res
+
+
+def pcen_audio(x, sr: float, n_fft: int = 2048, hop: int = 512, n_mels: int = 128, fmin: float = 0.0, fmax: float | None = None, **kw):
+    """PCEN of the mel power plane of audio x ([samples] or [channels][samples], float32 CUDA): the plane of mel_spectrogram_db before its
+    logarithm (stft_fb_db with linear_out) -> pcen with sr and hop_length = hop, nothing returned to the host in between -> float32
+    [frames, n_mels], and what pcen's return_state / return_smooth add.  kw: pcen's gain, bias, power, time_constant, eps, b, state."""
+    import torch
+    with torch.cuda.device(_device_index(x)):
+        return pcen(_mel_plane(x, sr, n_fft, hop, n_mels, fmin, fmax, capi.WIN_HANN, capi.MIX_ABSMEAN, False, True), sr=sr, hop_length=hop, **kw)
 
 
 # --------------------------------------------------------------------------------------------------
