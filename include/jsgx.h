@@ -1374,6 +1374,130 @@ JSGX_API int jsgx_pcen_launch(const jsgx_pcen_args* args, void* scratch, int64_t
 JSGX_API int jsgx_pcen_plan(const jsgx_pcen_args* args, char* name, int name_len, int32_t* threads, int32_t* lds_bytes, int32_t* n_launches,
                             int32_t* chunks);
 
+/* Section 14 was added to version 1 in the same way: sections 1 to 13, their structs and their constants are as they were. */
+
+/* ------------------------------------------------------------------------------------------------
+ * 14. Peak picking and onset backtracking (librosa.util.peak_pick, librosa.onset.onset_detect, librosa.onset.onset_backtrack): at which
+ *     frames of an envelope are the onsets.  The input is what jsg_onset_strength_launch (jsg.h section 2j) writes, taken as it is:
+ *         x[t] = in[r*in_pitch + t],  r < rows, t < T (n_frames)
+ *     and, for backtracking, an optional energy plane e[t] = energy[r*energy_pitch + t].  Rows are independent.  The four reaches
+ *     pre_max, post_max, pre_avg, post_avg (0..JSGX_PEAK_MAX_REACH) and wait (0..JSGX_PEAK_MAX_FRAMES) are integers in frames, delta is
+ *     a finite float32.  All arithmetic is float32, every operation rounded on its own (no contraction), and every result is an
+ *     integer: a restatement on the CPU gives the same integers (tests/peak_ref.py).  No result depends on the number of rows, on the
+ *     pitches, on which optional outputs are NULL or on the form of the kernels.
+ *
+ *     Refused row.  A row with a NaN or an infinity in x, or in e where energy is given, has n_peaks[r] = -1 and nothing else is
+ *     written for it (not its candidates, not its peaks).  The other rows are as if it were not there.
+ *
+ *     Normalise.  normalise = 1: mn and mx are the row's minimum and maximum (they depend on no order), range = fl(mx - mn) and
+ *         y[t] = fl(fl(x[t] - mn) / range)   (the divide correctly rounded);   y = +0 everywhere where range == 0
+ *     normalise = 0: y = x.  The sign of a zero of y is never observable: y is only compared, and summed from +0.  A finite row
+ *     whose mx - mn overflows is outside the contract; the launch still ends and writes only that row's outputs.
+ *
+ *     Candidate.  Two windows, inclusive and clipped to the row (nothing outside the row is read or padded):
+ *         Wm(t) = [max(0, t - pre_max), min(T-1, t + post_max)]      Wa(t) = [max(0, t - pre_avg), min(T-1, t + post_avg)]
+ *         top(t): y[t] >= y[j] for every j in Wm(t)                  (equal neighbours are candidates on both sides)
+ *         acc = +0;  for j ascending over Wa(t): acc = fl(acc + y[j]);   avg = fl(acc / (float)|Wa(t)|);   thr = fl(avg + delta)
+ *         c[t] = top(t) and y[t] >= thr
+ *     c goes to the optional plane candidate[r*candidate_pitch + t] as bytes 0 / 1.
+ *
+ *     Wait rule (greedy, librosa's).  E = 0; for t ascending: if c[t] and t >= E then t is a peak and E = t + wait + 1.  A candidate
+ *     inside a wait is dropped, not deferred.
+ *
+ *     Backtrack (where energy is given).  Frame 0 is a minimum; frame t in 1..T-2 is one iff e[t] <= e[t-1] and e[t] < e[t+1]; frame
+ *     T-1 never is (T = 1 has frame 0).  back(p) is the largest minimum <= p.  Two peaks may share one: duplicates are kept, the list
+ *     is non-decreasing.
+ *
+ *     Outputs.  n_peaks[r] = n, the whole count, which may exceed max_peaks.  peaks[r*peaks_pitch + i], i < min(n, max_peaks),
+ *     ascending: where the list is cut the earliest peaks are kept.  backtracked[r*peaks_pitch + i] = back(peaks[i]) where given;
+ *     it needs energy and energy needs it.  Nothing behind the written entries is touched.
+ *
+ *     Known answers.  An all-zero row with delta <= 0: every frame is a candidate, the peaks are 0, w+1, 2(w+1), ... (w = wait) and
+ *     n = ceil(T / (w+1)).  An all-zero row with delta > 0, or any constant row with normalise = 1 and delta > 0: no candidate,
+ *     n = 0.  Unit impulses every 6 frames from frame 0, reaches (1, 1, 2, 2), delta = 0.07: the peaks are every
+ *     6 * ceil((wait + 1) / 6) frames from 0, which tells wait = 5 (every 6) from wait = 6 (every 12).  T = 1: frame 0 is a candidate
+ *     iff 0 >= delta (normalised) or x[0] >= fl(x[0] + delta) (not normalised).
+ *
+ *     Deliberate differences from librosa: the windows are clipped at both ends of the row (librosa treats frame 0 on its own, and
+ *     older versions padded with the row's minimum); reaches and wait are whole frames with post_max and post_avg inclusive (the
+ *     Python layer converts seconds); normalise divides by mx - mn with no tiny added; float32 throughout.  Agreement with librosa
+ *     itself is not measured.
+ *
+ *     The kernels.  A row is cut into blocks of B = JSGX_PEAK_BLOCK frames; workgroups of JSGX_PEAK_THREADS lanes, no atomics, no
+ *     workgroup waits for another.  The wait rule in parallel: with nxt(t) the first candidate >= t, a chain that enters a block at
+ *     frame E picks nxt(E) first and from there on depends on that pick alone: s(p) = nxt(p + wait + 1) inside the block.  The
+ *     tables s^(2^k), k < log2 B, built in LDS by squaring, give the count and the last pick of the chain from any p in log2 B steps
+ *     and its i-th pick in as many.  A chain enters a block at an offset of at most min(wait, B - 1).
+ *         "peak_blocked" (T > B), five launches: "peak_stats" (minimum, maximum and the non-finite vote of every block), "peak_row"
+ *                        (a workgroup a row: the row's three out of its blocks'), "peak_cand" (a workgroup a block: y with a halo
+ *                        of the largest reach into LDS, the candidates by direct evaluation, the tables, and for every entering
+ *                        offset the count and the last pick; the block's last energy minimum), "peak_carry" (a lane a row walks
+ *                        the blocks: the entering frame, the running count and the last minimum so far of every block; a wait
+ *                        longer than a block is skipped by arithmetic, no table is read for it), "peak_emit" (a workgroup a block:
+ *                        the tables again from the stored candidates, lane i writes the block's i-th pick and its back())
+ *         "peak_single"  (T <= B), one launch, no scratch: a workgroup a row does all of it from LDS; with T <= 64 a wavefront a
+ *                        row, four rows a workgroup
+ *     JSGX_PEAK_BLOCK was chosen among 256, 512, 1024 and 2048 by measurement (profiles/peak_bench.md, tools/peak_bench.py).
+ * ------------------------------------------------------------------------------------------------ */
+#ifndef JSGX_PEAK_BLOCK
+#define JSGX_PEAK_BLOCK 1024               /* a power of two, 256..2048 */
+#endif
+#define JSGX_PEAK_MAX_REACH 256
+#define JSGX_PEAK_MAX_FRAMES 16777216      /* 2^24 */
+#define JSGX_PEAK_THREADS 256
+#define JSGX_PEAK_SHORT 64                 /* up to this many frames a wavefront takes a row of "peak_single" */
+#define JSGX_PEAK_LOG2_BLOCK (JSGX_PEAK_BLOCK == 256 ? 8 : JSGX_PEAK_BLOCK == 512 ? 9 : JSGX_PEAK_BLOCK == 1024 ? 10 : 11)
+/* static, of "peak_cand", "peak_emit" and "peak_single": log2 B tables of B 16-bit offsets (y and its halo lie there first), nxt
+ * (B + 4 of them), the last minimum of every frame (B of them): 24584 bytes at B = 1024, 53256 at B = 2048 */
+#define JSGX_PEAK_LDS_BYTES (2 * JSGX_PEAK_BLOCK * JSGX_PEAK_LOG2_BLOCK + 2 * (JSGX_PEAK_BLOCK + 4) + 2 * JSGX_PEAK_BLOCK)
+#define JSGX_PEAK_LDS_LIMIT 163840
+
+typedef struct jsgx_peak_args {
+    const float* in;            /* device floats: x */
+    int64_t in_pitch;           /* rows > 1: >= n_frames */
+    const float* energy;        /* device floats: e, or NULL (then backtracked is NULL) */
+    int64_t energy_pitch;       /* rows > 1: >= n_frames */
+    uint8_t* candidate;         /* device bytes: c, or NULL */
+    int64_t candidate_pitch;    /* rows > 1: >= n_frames */
+    int32_t* peaks;             /* device int32 [rows][max_peaks] */
+    int32_t* backtracked;       /* device int32 [rows][max_peaks] at peaks_pitch, or NULL (then energy is NULL) */
+    int64_t peaks_pitch;        /* rows > 1: >= max_peaks */
+    int32_t* n_peaks;           /* device int32 [rows] */
+    int32_t rows;               /* 1..65535 */
+    int32_t n_frames;           /* T, 1..JSGX_PEAK_MAX_FRAMES */
+    int32_t pre_max;            /* 0..JSGX_PEAK_MAX_REACH, and so the next three */
+    int32_t post_max;
+    int32_t pre_avg;
+    int32_t post_avg;
+    float delta;                /* finite */
+    int32_t wait;               /* 0..JSGX_PEAK_MAX_FRAMES */
+    int32_t normalise;          /* 0 or 1 */
+    int32_t max_peaks;          /* 1..JSGX_PEAK_MAX_FRAMES */
+} jsgx_peak_args;               /* 120 bytes, no padding */
+
+/* The bytes of scratch the launch needs: 0 where n_frames <= B, else with nb = ceil(n_frames / B)
+ *     rows * nb * (32 + 4 * min(wait + 1, B) + B)
+ * (a record of 32 bytes a block, a word for every entering offset of a block, a byte a frame of whole blocks): below 16 bytes a frame plus
+ * 32 a block a row.  A larger scratch changes nothing.  Refused (a negative jsgx_status): what the launch refuses before it looks at the
+ * scratch. */
+JSGX_API int64_t jsgx_peak_scratch_bytes(const jsgx_peak_args* args);
+/* Enqueue only: no allocation, no synchronisation; capture works, a first launch included.  Refused (JSGX_ERR_INVALID, nothing
+ * enqueued), in this order and before any device call: null args, a null in, a null peaks, a null n_peaks; in, energy, peaks,
+ * backtracked or n_peaks not 4-byte aligned (candidate is bytes); rows outside 1..65535, n_frames outside 1..2^24; pre_max, post_max,
+ * pre_avg, post_avg outside 0..256 in this order; delta not finite; wait outside 0..2^24; normalise not 0 or 1; max_peaks outside
+ * 1..2^24; backtracked without energy or energy without backtracked; with rows > 1: in_pitch, then energy_pitch, then candidate_pitch
+ * below n_frames (where the buffer is given), peaks_pitch below max_peaks; peaks, then backtracked, then n_peaks, then candidate
+ * overlapping in and then energy; peaks overlapping backtracked, n_peaks, candidate; backtracked overlapping n_peaks, candidate; n_peaks
+ * overlapping candidate; and where the scratch size is not 0: a null scratch, a scratch that is not 4-byte aligned, scratch_bytes below
+ * the size, the scratch (the bytes of that size) overlapping in, energy, peaks, backtracked, n_peaks, candidate in this order.  Then
+ * JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_peak_launch(const jsgx_peak_args* args, void* scratch, int64_t scratch_bytes, void* stream);
+/* What the launch enqueues, without a device: the form ("peak_single" or "peak_blocked"), JSGX_PEAK_THREADS, the bytes of LDS
+ * (JSGX_PEAK_LDS_BYTES), the launches (1 or 5) and the blocks of a row.  Any output pointer may be NULL (name: else name_len >= 16).
+ * Refused: a name_len below 16 with a name, then what the scratch size refuses. */
+JSGX_API int jsgx_peak_plan(const jsgx_peak_args* args, char* name, int name_len, int32_t* threads, int32_t* lds_bytes, int32_t* n_launches,
+                            int32_t* blocks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,18 @@ class PcenArgs(C.Structure):
                 ("bias", C.c_float), ("power", C.c_float), ("eps", C.c_float)]
 
 
+PEAK_BLOCK, PEAK_MAX_REACH, PEAK_MAX_FRAMES, PEAK_THREADS, PEAK_SHORT, PEAK_LDS_LIMIT = 1024, 256, 1 << 24, 256, 64, 163840
+PEAK_LOG2_BLOCK = PEAK_BLOCK.bit_length() - 1
+PEAK_LDS_BYTES = 2 * PEAK_BLOCK * PEAK_LOG2_BLOCK + 2 * (PEAK_BLOCK + 4) + 2 * PEAK_BLOCK
+
+
+class PeakArgs(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("in_pitch", C.c_int64), ("energy", C.c_void_p), ("energy_pitch", C.c_int64), ("candidate", C.c_void_p),
+                ("candidate_pitch", C.c_int64), ("peaks", C.c_void_p), ("backtracked", C.c_void_p), ("peaks_pitch", C.c_int64), ("n_peaks", C.c_void_p),
+                ("rows", C.c_int32), ("n_frames", C.c_int32), ("pre_max", C.c_int32), ("post_max", C.c_int32), ("pre_avg", C.c_int32), ("post_avg", C.c_int32),
+                ("delta", C.c_float), ("wait", C.c_int32), ("normalise", C.c_int32), ("max_peaks", C.c_int32)]
+
+
 # every symbol include/jsgx.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -202,6 +214,9 @@ SIGNATURES = {
     "jsgx_pcen_scratch_bytes": (C.c_int64, [C.POINTER(PcenArgs)]),
     "jsgx_pcen_launch": (C.c_int, [C.POINTER(PcenArgs), _P, C.c_int64, _P]),
     "jsgx_pcen_plan": (C.c_int, [C.POINTER(PcenArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 4),
+    "jsgx_peak_scratch_bytes": (C.c_int64, [C.POINTER(PeakArgs)]),
+    "jsgx_peak_launch": (C.c_int, [C.POINTER(PeakArgs), _P, C.c_int64, _P]),
+    "jsgx_peak_plan": (C.c_int, [C.POINTER(PeakArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 4),
 }
 
 _lib = None

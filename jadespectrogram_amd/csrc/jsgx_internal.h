@@ -160,6 +160,45 @@ inline PcenPlan pcen_plan(const jsgx_pcen_args* g) {
     return p;
 }
 
+// section 14 (jsgx_peak_host.cpp): every refusal that does not look at the scratch, in the header's order, and the bytes of the buffers;
+// then the refusals of the scratch
+struct PeakSpans {
+    jsg::i128 in, energy, peaks, backtracked, n_peaks, candidate;
+};
+int peak_check(const jsgx_peak_args* g, const char* who, PeakSpans* spans);
+int peak_check_scratch(const jsgx_peak_args* g, const char* who, const PeakSpans& spans, const void* scratch, int64_t scratch_bytes);
+// What "peak_stats", "peak_row", "peak_cand" and "peak_carry" leave for a block of a row, 32 bytes: the row's minimum, maximum and
+// non-finite vote (the block's own until "peak_row"), the block's last energy minimum (a frame, -1: none); the frame the chain enters
+// the block at (the block's end: it does not), the peaks in front of the block and inside it, the last minimum in front of the block
+struct PeakRecord {
+    float mn, mx;
+    int bad, block_min;
+    int enter, run, count, carried_min;
+};
+static_assert(sizeof(PeakRecord) == 32, "include/jsgx.h states the bytes of a block's record");
+// How section 14 serves a shape: the blocks of a row, the entering offsets of a block, and where the parts of the scratch lie (bytes):
+// the records [rows][blocks] at 0, the words [rows][blocks][offsets] (count << 16 | last pick, as offsets in the block), the
+// candidates [rows][blocks][B] as bytes
+struct PeakPlan {
+    const char* name;
+    long long blocks, offsets;
+    int launches;
+    long long off_words, off_flags, scratch_bytes;
+};
+inline PeakPlan peak_plan(const jsgx_peak_args* g) {
+    PeakPlan p;
+    const long long B = JSGX_PEAK_BLOCK, R = g->rows;
+    p.blocks = (g->n_frames + B - 1) / B;
+    p.offsets = (long long)g->wait + 1 < B ? (long long)g->wait + 1 : B;
+    const bool single = p.blocks == 1;
+    p.name = single ? "peak_single" : "peak_blocked";
+    p.launches = single ? 1 : 5;
+    p.off_words = R * p.blocks * 32;
+    p.off_flags = p.off_words + R * p.blocks * p.offsets * 4;
+    p.scratch_bytes = single ? 0 : p.off_flags + R * p.blocks * B;
+    return p;
+}
+
 // The three refusals of a launch's scratch buffer, in this order; `sizer` names the call that states `need`.
 inline int check_scratch(const char* who, const void* scratch, int64_t scratch_bytes, int64_t need, const char* sizer) {
     if (!scratch) return fail(JSGX_ERR_INVALID, who, "null scratch");

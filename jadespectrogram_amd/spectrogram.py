@@ -2432,6 +2432,192 @@ def pcen_audio(x, sr: float, n_fft: int = 2048, hop: int = 512, n_mels: int = 12
 
 
 # --------------------------------------------------------------------------------------------------
+# Peak picking and onset detection (include/jsgx.h, section 14: libjsgx.so)
+# --------------------------------------------------------------------------------------------------
+def _peak_rows(t, rows, least, dtype, what: str):
+    """(pointer, row pitch) of an optional CUDA [rows][>= least] (or [>= least] for one row) of `dtype` with unit stride."""
+    if t is None:
+        return None, 0
+    t = t[None] if t.dim() == 1 else t
+    assert t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[0] == rows and t.shape[1] >= least and (t.stride(1) == 1 or t.shape[1] == 1), \
+        f"{what}: {dtype} CUDA [rows][>= {least}]"
+    return t.data_ptr(), t.stride(0)
+
+
+def _peak_args(d_in, d_peaks, d_n_peaks, pre_max, post_max, pre_avg, post_avg, delta, wait, normalise, d_energy, d_backtracked, d_candidate) -> capix.PeakArgs:
+    import torch
+    x = d_in[None] if d_in.dim() == 1 else d_in
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and (x.stride(1) == 1 or x.shape[1] == 1), "d_in: float32 CUDA [rows][frames]"
+    R, T = x.shape
+    p = d_peaks[None] if d_peaks.dim() == 1 else d_peaks
+    max_peaks = p.shape[-1]
+    peaks, peaks_pitch = _peak_rows(p, R, 1, torch.int32, "d_peaks")
+    back, back_pitch = _peak_rows(d_backtracked, R, max_peaks, torch.int32, "d_backtracked")
+    assert back is None or R == 1 or back_pitch == peaks_pitch, "d_backtracked: the row pitch of d_peaks"
+    assert d_n_peaks.is_cuda and d_n_peaks.dtype == torch.int32 and d_n_peaks.numel() == R and d_n_peaks.is_contiguous(), "d_n_peaks: int32 CUDA [rows]"
+    energy, energy_pitch = _peak_rows(d_energy, R, T, torch.float32, "d_energy")
+    cand, cand_pitch = _peak_rows(d_candidate, R, T, torch.uint8, "d_candidate")
+    return capix.PeakArgs(x.data_ptr(), x.stride(0), energy, energy_pitch, cand, cand_pitch, peaks, back, peaks_pitch, d_n_peaks.data_ptr(), R, T, int(pre_max),
+                          int(post_max), int(pre_avg), int(post_avg), float(delta), int(wait), int(bool(normalise)), int(max_peaks))
+
+
+def peak_scratch_bytes(d_in, d_peaks, d_n_peaks, *, pre_max: int, post_max: int, pre_avg: int, post_avg: int, delta: float, wait: int, normalise: bool = False,
+                       d_energy=None, d_backtracked=None, d_candidate=None) -> int:
+    """jsgx_peak_scratch_bytes: the bytes of scratch peak_launch needs for these arguments (0 up to capix.PEAK_BLOCK frames)."""
+    a = _peak_args(d_in, d_peaks, d_n_peaks, pre_max, post_max, pre_avg, post_avg, delta, wait, normalise, d_energy, d_backtracked, d_candidate)
+    return int(capix.check(capix.lib().jsgx_peak_scratch_bytes(C.byref(a))))
+
+
+def peak_launch(d_in, d_peaks, d_n_peaks, *, pre_max: int, post_max: int, pre_avg: int, post_avg: int, delta: float, wait: int, normalise: bool = False,
+                d_energy=None, d_backtracked=None, d_candidate=None, d_scratch=None, stream: int | None = None):
+    """jsgx_peak_launch: d_in float32 [rows][frames] (or one [frames] row; views with a row pitch) -> d_n_peaks int32 [rows], the peaks of
+    every row (-1: a row with a NaN or an infinity, nothing else is written for it), and d_peaks int32 [rows][max_peaks], the first
+    max_peaks of them ascending.  A frame is a peak where it is the maximum of [t - pre_max, t + post_max], at least delta above the
+    mean of [t - pre_avg, t + post_avg] (both clipped to the row) and more than wait frames behind the peak before it.  d_energy float32
+    [rows][frames] with d_backtracked int32 like d_peaks: every peak moved back to the last local minimum of the energy at or before
+    it.  d_candidate uint8 [rows][frames]: the frames that pass the two window tests.  d_scratch: a contiguous CUDA tensor of at least
+    peak_scratch_bytes bytes (None: one is allocated with torch for this call).  Enqueue only."""
+    import torch
+    a = _peak_args(d_in, d_peaks, d_n_peaks, pre_max, post_max, pre_avg, post_avg, delta, wait, normalise, d_energy, d_backtracked, d_candidate)
+    d_scratch, stream = _scratch_and_stream(d_scratch, stream, d_in, lambda: max(1, capix.check(capix.lib().jsgx_peak_scratch_bytes(C.byref(a))) // 4), torch.float32,
+                                            any_dtype=True)
+    capix.check(capix.lib().jsgx_peak_launch(C.byref(a), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), stream))
+
+
+def peak_plan(n_frames: int, rows: int = 1, wait: int = 0):
+    """jsgx_peak_plan: (form, lanes per workgroup, bytes of LDS per workgroup, launches, blocks of a row) for this shape: "peak_single" up
+    to capix.PEAK_BLOCK frames, else "peak_blocked".  Needs no device."""
+    T, R = int(n_frames), int(rows)
+    a = capix.PeakArgs(in_=1 << 50, in_pitch=T, peaks=1 << 58, peaks_pitch=1, n_peaks=1 << 40, rows=R, n_frames=T, wait=int(wait), max_peaks=1)      # never dereferenced
+    name, out = C.create_string_buffer(16), [C.c_int32() for _ in range(4)]
+    capix.check(capix.lib().jsgx_peak_plan(C.byref(a), name, 16, *[C.byref(o) for o in out]))
+    return (name.value.decode(),) + tuple(o.value for o in out)
+
+
+def _peak_lists(peaks, n_peaks, one: bool):
+    """The rows' lists cut at their counts (None for a refused row); one synchronising copy of the counts."""
+    counts = n_peaks.cpu().tolist()
+    assert all(n <= peaks.shape[1] for n in counts), "max_peaks cut a list: pass a larger one or use peak_launch"
+    out = [None if n < 0 else peaks[r, :n] for r, n in enumerate(counts)]
+    return out[0] if one else out
+
+
+def peak_pick(x, pre_max: int, post_max: int, pre_avg: int, post_avg: int, delta: float, wait: int, *, normalise: bool = False, max_peaks: int | None = None):
+    """librosa.util.peak_pick on the GPU (include/jsgx.h section 14): x [T] or [rows, T] (numpy array or float32 CUDA tensor) -> the peak
+    frames, an int32 CUDA tensor for [T] or a list of them, one a row; a row with a NaN or an infinity gives None in its place.  The
+    reaches and wait are whole frames; post_max and post_avg are inclusive, where librosa's are exclusive.  max_peaks None: as many as
+    a row can hold.  Differs from librosa on purpose: windows clipped at both ends of the row, no special case at frame 0, float32.  The
+    call waits for the device once, to read the counts.  Agreement with librosa was not measured."""
+    import torch
+    xt, _ = _to_cuda(x)
+    assert xt.dim() in (1, 2), "peak_pick: x is [T] or [rows, T]"
+    xr = (xt[None] if xt.dim() == 1 else xt).contiguous()
+    R, T = xr.shape
+    most = 1 + (T - 1) // (int(wait) + 1) if max_peaks is None else int(max_peaks)
+    with torch.cuda.device(_device_index(xr)):
+        peaks = torch.empty((R, most), dtype=torch.int32, device=xr.device)
+        n_peaks = torch.empty((R,), dtype=torch.int32, device=xr.device)
+        peak_launch(xr, peaks, n_peaks, pre_max=pre_max, post_max=post_max, pre_avg=pre_avg, post_avg=post_avg, delta=delta, wait=wait, normalise=normalise)
+        if max_peaks is not None:
+            n_peaks = torch.where(n_peaks > most, torch.full_like(n_peaks, most), n_peaks)
+        return _peak_lists(peaks, n_peaks, xt.dim() == 1)
+
+
+def onset_backtrack(events, energy):
+    """librosa.onset.onset_backtrack on the GPU: every event frame moved back to the last local minimum of energy [T] at or before it
+    (frame 0 counts as one; t is one where energy[t] <= energy[t-1] and energy[t] < energy[t+1]).  events: ints (a list, a numpy array
+    or a CUDA tensor), in any order, duplicates allowed -> an int32 CUDA tensor of the same length and order.  The events are made the
+    peaks of a launch of their own: a plane that is 2^30 at the events and 0 elsewhere, windows of one frame, delta = 1 and no wait,
+    where x >= fl(x + 1) holds for 2^30 alone."""
+    import torch
+    e, _ = _to_cuda(energy)
+    assert e.dim() == 1, "onset_backtrack: energy is [T]"
+    e = e.contiguous()
+    T = e.shape[0]
+    ev = torch.as_tensor(np.asarray(events.cpu() if hasattr(events, "is_cuda") else events, dtype=np.int64), device=e.device).reshape(-1)
+    if ev.numel() == 0:
+        return torch.empty((0,), dtype=torch.int32, device=e.device)
+    assert int(ev.min()) >= 0 and int(ev.max()) < T, "onset_backtrack: events are frames of energy"
+    with torch.cuda.device(_device_index(e)):
+        marks = torch.zeros((T,), dtype=torch.float32, device=e.device)
+        marks[ev] = 2.0 ** 30
+        distinct = torch.unique(ev)          # ascending: the order of the peaks
+        peaks, back = torch.empty((2, distinct.numel()), dtype=torch.int32, device=e.device)
+        n_peaks = torch.empty((1,), dtype=torch.int32, device=e.device)
+        peak_launch(marks, peaks, n_peaks, pre_max=0, post_max=0, pre_avg=0, post_avg=0, delta=1.0, wait=0, d_energy=e, d_backtracked=back)
+        n = int(n_peaks[0])
+        if n < 0:
+            raise ValueError("onset_backtrack: energy holds a NaN or an infinity")
+        assert n == distinct.numel()
+        return back[torch.searchsorted(distinct, ev)]
+
+
+def _frames_of(seconds: float, sr: float, hop_length: int) -> int:
+    return int(seconds * sr // hop_length)
+
+
+def onset_detect(onset_envelope, *, sr: float = 22050, hop_length: int = 512, backtrack: bool = False, energy=None, normalise: bool = True, units: str = "frames",
+                 pre_max: float = 0.03, post_max: float = 0.0, pre_avg: float = 0.10, post_avg: float = 0.10, wait: float = 0.03, delta: float = 0.07):
+    """librosa.onset.onset_detect on the GPU: onset_envelope [T] or [rows, T] (numpy array or float32 CUDA tensor; what onset_strength
+    returns) -> the onsets of every row: one result for [T], else a list with one a row (None for a row with a NaN or an infinity).  The
+    windows and wait are seconds, converted as int(v * sr // hop_length) frames (at 22050 / 512 the defaults are the reaches (1, 0, 4, 4)
+    and wait = 1); post_max and post_avg are then inclusive.  backtrack: the onsets moved back to the last local minimum of energy (None:
+    the envelope itself) at or before them.  units: "frames" (an int32 CUDA tensor), or converted on the host, "samples" (numpy int64,
+    frame * hop_length) and "time" (numpy float64, frame * hop_length / sr).  Differs from librosa on purpose: windows clipped at both
+    ends of the row, normalise divides by max - min with nothing added, float32.  Agreement with librosa was not measured."""
+    import torch
+    assert units in ("frames", "samples", "time"), 'onset_detect: units is "frames", "samples" or "time"'
+    xt, _ = _to_cuda(onset_envelope)
+    assert xt.dim() in (1, 2), "onset_detect: onset_envelope is [T] or [rows, T]"
+    xr = (xt[None] if xt.dim() == 1 else xt).contiguous()
+    R, T = xr.shape
+    reach = [_frames_of(v, sr, hop_length) for v in (pre_max, post_max, pre_avg, post_avg)]
+    w = _frames_of(wait, sr, hop_length)
+    most = 1 + (T - 1) // (w + 1)
+    d_energy = back = None
+    with torch.cuda.device(_device_index(xr)):
+        if backtrack:
+            d_energy = xr if energy is None else _to_cuda(energy)[0].reshape(R, T).contiguous()
+            back = torch.empty((R, most), dtype=torch.int32, device=xr.device)
+        peaks = torch.empty((R, most), dtype=torch.int32, device=xr.device)
+        n_peaks = torch.empty((R,), dtype=torch.int32, device=xr.device)
+        peak_launch(xr, peaks, n_peaks, pre_max=reach[0], post_max=reach[1], pre_avg=reach[2], post_avg=reach[3], delta=delta, wait=w, normalise=normalise,
+                    d_energy=d_energy, d_backtracked=back)
+        rows = _peak_lists(back if backtrack else peaks, n_peaks, False)
+    rows = [_onset_units(f, units, sr, hop_length) for f in rows]
+    return rows[0] if xt.dim() == 1 else rows
+
+
+def _onset_units(frames, units: str, sr: float, hop_length: int):
+    """Frames (an int32 CUDA tensor, or None) in `units`: as they are, or on the host as samples (int64) or seconds (float64)."""
+    if frames is None or units == "frames":
+        return frames
+    samples = frames.cpu().numpy().astype(np.int64) * int(hop_length)
+    return samples if units == "samples" else samples / float(sr)
+
+
+def onset_detect_audio(x, sr, n_fft=2048, hop=512, n_mels=128, **kw):
+    """The onsets of audio x [samples] (numpy array or float32 CUDA tensor): mel_spectrogram_db -> onset_strength_launch -> onset_detect
+    with sr and hop_length = hop, the envelope never leaving the device.  An onset is reported where its window is centred: frame t of
+    the mel spectrogram covers the samples t * hop .. t * hop + n_fft - 1 (no centring is applied to the audio), so an onset picked at
+    frame t of the envelope is returned as t + n_fft // (2 * hop), and frame * hop (units "samples", "time") is the middle of the window
+    that first heard it, as with librosa's centred frames; without that every onset lay n_fft / 2 samples early.  With backtrack the
+    minimum is shifted alike.  kw: onset_detect's backtrack, energy, normalise, units, pre_max, post_max, pre_avg, post_avg, wait,
+    delta (energy: a row of the envelope's length, in the envelope's own frames)."""
+    import torch
+    xt, _ = _to_cuda(x)
+    assert xt.dim() == 1, "onset_detect_audio: x is one channel [samples]"
+    with torch.cuda.device(_device_index(xt)):
+        S = mel_spectrogram_db(xt, sr, n_fft, hop, n_mels)
+        env = torch.empty((1, S.shape[0]), dtype=torch.float32, device=xt.device)
+        onset_strength_launch(S, env)
+        units = kw.pop("units", "frames")
+        assert units in ("frames", "samples", "time"), 'onset_detect_audio: units is "frames", "samples" or "time"'
+        frames = onset_detect(env[0], sr=sr, hop_length=hop, **kw)
+        return _onset_units(None if frames is None else frames + int(n_fft) // (2 * int(hop)), units, sr, hop)
+
+
+# --------------------------------------------------------------------------------------------------
 # Viterbi decoding of hidden Markov models (include/jsgx.h, section 4: libjsgx.so)
 # --------------------------------------------------------------------------------------------------
 def _viterbi_args(d_log_emit, d_log_init, d_log_trans, d_states, band_half, d_logp, d_value) -> capix.ViterbiArgs:
