@@ -1498,6 +1498,158 @@ JSGX_API int jsgx_peak_launch(const jsgx_peak_args* args, void* scratch, int64_t
 JSGX_API int jsgx_peak_plan(const jsgx_peak_args* args, char* name, int name_len, int32_t* threads, int32_t* lds_bytes, int32_t* n_launches,
                             int32_t* blocks);
 
+/* Sections 15 and 16 were added to version 1 in the same way: sections 1 to 14, their structs and their constants are as they were. */
+
+/* ------------------------------------------------------------------------------------------------
+ * 15. Aggregation of a plane over segments (librosa.util.sync): one row of the output for every stretch of frames between two
+ *     boundaries.  The plane is frame-major, what the feature kernels write,
+ *         X[t][f] = x[p*x_pair_pitch + t*x_frame_pitch + f],  p < pairs, t < N (n_frames), f < F (n_features)
+ *     and the boundaries are frames b[i] = bounds[p*bounds_pitch + i] with a count of their own per pair: the beats / n_beats of
+ *     section 1 or the peaks, backtracked / n_peaks of section 14, taken as they are.  A bounds_pitch of 0 is one list for every pair.
+ *     The count of a pair is m = min(n_bounds[p], max_bounds); with n_bounds NULL, m = bounds_all for every pair.
+ *
+ *     Segments (kernel "sync_segments", a workgroup a pair).
+ *     Refused pair.  n_bounds[p] < 0 (the -1 of a refused row upstream), or b[i] < b[i-1] for some i < m on the raw values:
+ *     n_segments[p] = -1 and nothing else is written for the pair, neither its segments nor its output rows.  Otherwise
+ *         c[i] = min(max(b[i], 0), N)
+ *         s    = (0 where pad = 1), c[0], ..., c[m-1], (N where pad = 1)
+ *         u    = s without every entry that equals its predecessor:  u[0] < u[1] < ... < u[U-1]
+ *         n_segments[p] = max(U - 1, 0)                      the whole count, which may exceed max_segments
+ *         segments[p*segments_pitch + j] = u[j],  j <= min(U - 1, max_segments), where U >= 2; nothing behind these entries is written
+ *     Segment o is the frames u[o] .. u[o+1]-1, cnt = u[o+1] - u[o] >= 1 of them.  segments holds max_segments + 1 entries a pair.
+ *
+ *     Aggregate (kernel "sync_aggregate"), for o < min(n_segments[p], max_segments) and every f:
+ *     out[p*out_pair_pitch + o*out_frame_pitch + f] is
+ *         JSGX_SYNC_MEAN    the segment is cut from its start into chunks of JSGX_SYNC_CHUNK frames; part_j is the chain
+ *                           acc = fl(acc + X[t][f]) from +0 over the frames of chunk j ascending, tot the chain fl(tot + part_j) from
+ *                           +0 over j ascending, the value fl(tot / (float)cnt), the divide correctly rounded.  The order depends on
+ *                           nothing but cnt.
+ *         JSGX_SYNC_MIN,    the least and the greatest under the order of key(v): the bits of v, all of them flipped where the sign
+ *         JSGX_SYNC_MAX     is set, else the sign alone (-0 < +0, the infinities at the ends).  No order of evaluation shows.
+ *         JSGX_SYNC_MEDIAN  with v[0..cnt-1] the segment's values sorted by key: v[(cnt-1)/2] for an odd cnt, else
+ *                           0.5f * fl(v[cnt/2 - 1] + v[cnt/2]), the formula of section 7's bandwidth.  A sum that overflows gives the
+ *                           infinity: stated, not avoided.
+ *     NaN.  Min, max and median of a segment with a NaN at feature f are the bits JSGX_SYNC_NAN_BITS there; a mean that is a NaN, and
+ *     an even median whose two middle values are the two infinities, is written as those bits.  Every output is comparable bit for
+ *     bit (tests/sync_ref.py restates both kernels in numpy).  Nothing depends on pairs, on the pitches or on the form of the kernel.
+ *
+ *     Deliberate differences from librosa.util.sync: frame-major planes; boundaries are clipped to 0..N, where librosa raises on a
+ *     negative one; a non-decreasing list is required, where librosa sorts; these four aggregates only; float32.  Agreement with
+ *     librosa itself is not measured.
+ *
+ *     The kernel.  Workgroups of JSGX_SYNC_THREADS lanes, lane = feature (64 features a workgroup, reads coalesced along f), four
+ *     segments a workgroup; no atomics, no workgroup waits for another; a workgroup whose first segment is behind the pair's count
+ *     leaves after one uniform read.  Where none of its segments is longer than JSGX_SYNC_WAVE_MAX frames (median) or JSGX_SYNC_CHUNK
+ *     (the other three), a wavefront takes a segment on its own.  Otherwise the four wavefronts take the segments one after the other
+ *     together: for the mean wavefront w takes the chunks j = w (mod 4) and the partials are added in ascending order from LDS, for the
+ *     others it takes the frames t = w (mod 4).  The median is a bitwise selection, no sort: 32 counting passes over the keys, most
+ *     significant bit first, find the k-th smallest, and for an even cnt one more pass finds its successor.  A segment of up to
+ *     JSGX_SYNC_WAVE_MAX frames (a wavefront alone) or JSGX_SYNC_STAGE frames (the four together) is staged in LDS as keys, a longer
+ *     one is read again through the caches.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSGX_SYNC_MEAN 0
+#define JSGX_SYNC_MIN 1
+#define JSGX_SYNC_MAX 2
+#define JSGX_SYNC_MEDIAN 3
+#define JSGX_SYNC_CHUNK 256                /* frames of a partial sum of the mean; the longest segment a wavefront takes alone */
+#ifndef JSGX_SYNC_WAVE_MAX                 /* the two thresholds of the median can be set at build time, for tools/sync_bench.py */
+#define JSGX_SYNC_WAVE_MAX 64              /* median: the longest segment a wavefront takes alone, staged in its quarter of the tile */
+#endif
+#ifndef JSGX_SYNC_STAGE
+#define JSGX_SYNC_STAGE 256                /* median: the longest segment the four wavefronts stage in LDS; at least 4 JSGX_SYNC_WAVE_MAX */
+#endif
+#define JSGX_SYNC_THREADS 256
+#define JSGX_SYNC_MAX_FRAMES 16777216      /* 2^24 */
+#define JSGX_SYNC_MAX_FEATURES 65536
+#define JSGX_SYNC_MAX_BOUNDS 1048576       /* 2^20 */
+#define JSGX_SYNC_MAX_SEGMENTS 1048577     /* 2^20 + 1 */
+#define JSGX_SYNC_NAN_BITS 0x7FC00000u
+#define JSGX_SYNC_LDS_BYTES 4096           /* static, of "sync_aggregate": what the four wavefronts hand each other, two rounds */
+#define JSGX_SYNC_LDS_TILE 65536           /* dynamic, median only: JSGX_SYNC_STAGE = 256 frames of 64 keys */
+
+typedef struct jsgx_sync_args {
+    const float* x;             /* device floats: X */
+    int64_t x_frame_pitch;      /* >= n_features */
+    int64_t x_pair_pitch;       /* pairs > 1: covers a plane */
+    const int32_t* bounds;      /* device int32 [pairs][max_bounds]; may be NULL where max_bounds == 0 */
+    int64_t bounds_pitch;       /* pairs > 1: 0 (one list for every pair) or >= max_bounds */
+    const int32_t* n_bounds;    /* device int32 [pairs], or NULL: bounds_all for every pair */
+    int32_t* segments;          /* device int32 [pairs][max_segments + 1]: u */
+    int64_t segments_pitch;     /* pairs > 1: >= max_segments + 1 */
+    int32_t* n_segments;        /* device int32 [pairs] */
+    float* out;                 /* device floats [pairs][max_segments][n_features] */
+    int64_t out_frame_pitch;    /* >= n_features */
+    int64_t out_pair_pitch;     /* pairs > 1: covers max_segments rows */
+    int32_t pairs;              /* 1..65535 */
+    int32_t n_frames;           /* N, 1..JSGX_SYNC_MAX_FRAMES */
+    int32_t n_features;         /* F, 1..JSGX_SYNC_MAX_FEATURES */
+    int32_t max_bounds;         /* 0..JSGX_SYNC_MAX_BOUNDS */
+    int32_t bounds_all;         /* n_bounds NULL: 0..max_bounds; else not looked at */
+    int32_t max_segments;       /* 1..JSGX_SYNC_MAX_SEGMENTS */
+    int32_t aggregate;          /* JSGX_SYNC_MEAN .. JSGX_SYNC_MEDIAN */
+    int32_t pad;                /* 0 or 1 */
+    int32_t reserved0;          /* 0 */
+    int32_t reserved1;          /* 0 */
+} jsgx_sync_args;               /* 136 bytes, no padding beyond the two reserved words */
+
+/* Enqueue only, two kernels and no scratch: segments and n_segments are required outputs and hand the segments from "sync_segments"
+ * to "sync_aggregate" (which is not launched where no segment can exist: max_bounds, or bounds_all with n_bounds NULL, + 2 pad < 2).
+ * No allocation, no synchronisation; capture works, a first launch included.  Refused (JSGX_ERR_INVALID, nothing enqueued), in this order and before any device call:
+ * null args, a null x, a null out, a null segments, a null n_segments; a null bounds with max_bounds > 0; a pointer (n_bounds
+ * included) that is not 4-byte aligned; pairs outside 1..65535, n_frames outside 1..2^24, n_features outside 1..65536; max_bounds
+ * outside 0..2^20; with n_bounds NULL, bounds_all outside 0..max_bounds; max_segments outside 1..2^20+1; aggregate outside 0..3; pad not
+ * 0 or 1; reserved0 or reserved1 not 0; x_frame_pitch below n_features, x_pair_pitch that does not cover a plane (pairs > 1); the
+ * same two for out (a plane of max_segments rows); with pairs > 1: bounds_pitch neither 0 nor >= max_bounds (where bounds is given),
+ * segments_pitch below max_segments + 1; out, then segments, then n_segments overlapping x, bounds, n_bounds in this order; out
+ * overlapping segments, out overlapping n_segments, segments overlapping n_segments.  Then JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_sync_launch(const jsgx_sync_args* args, void* stream);
+/* What the launch enqueues, without a device: the aggregate's kernel ("sync_mean", "sync_min", "sync_max" or "sync_median"),
+ * JSGX_SYNC_THREADS, the bytes of LDS of a workgroup (JSGX_SYNC_LDS_BYTES, with the median JSGX_SYNC_LDS_TILE more) and the launches (2,
+ * or 1).  Any output pointer may be NULL (name: else name_len >= 16).  Refused: a name_len below 16 with a name, then what the launch
+ * refuses. */
+JSGX_API int jsgx_sync_plan(const jsgx_sync_args* args, char* name, int name_len, int32_t* threads, int32_t* lds_bytes, int32_t* n_launches);
+
+/* ------------------------------------------------------------------------------------------------
+ * 16. Time-delay embedding (librosa.feature.stack_memory): n_steps copies of a frame-major plane side by side, each delayed further,
+ *         out[p*out_pair_pitch + t*out_frame_pitch + s*F + f] = X[t - s*delay][f],   s < n_steps, t < N, f < F
+ *     the link between section 15 and the recurrence plane of section 7.  A negative delay stacks the future, as librosa does.  Where
+ *     t - s*delay is outside 0..N-1, JSGX_STACK_CONSTANT writes fill and JSGX_STACK_EDGE writes X[clamp(t - s*delay, 0, N-1)][f].  A
+ *     pure permutation: bits are copied unchanged, NaN payloads included, fill's too.  Kernel "stack_memory": one launch, workgroups of
+ *     JSGX_STACK_THREADS lanes, each a run of whole frames of the output, lanes along the row; no LDS.  Frame-major, where librosa
+ *     stacks along the first axis of a feature-major plane; float32.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSGX_STACK_CONSTANT 0
+#define JSGX_STACK_EDGE 1
+#define JSGX_STACK_MAX_STEPS 256
+#define JSGX_STACK_MAX_DELAY 16777216      /* 2^24 */
+#define JSGX_STACK_MAX_WIDTH 1048576       /* 2^20: n_steps * n_features */
+#define JSGX_STACK_THREADS 256
+
+typedef struct jsgx_stack_memory_args {
+    const float* x;             /* device floats: X */
+    int64_t x_frame_pitch;      /* >= n_features */
+    int64_t x_pair_pitch;       /* pairs > 1: covers a plane */
+    float* out;                 /* device floats [pairs][n_frames][n_steps * n_features] */
+    int64_t out_frame_pitch;    /* >= n_steps * n_features */
+    int64_t out_pair_pitch;     /* pairs > 1: covers a plane */
+    int32_t pairs;              /* 1..65535 */
+    int32_t n_frames;           /* N, 1..2^24 */
+    int32_t n_features;         /* F, 1..65536 */
+    int32_t n_steps;            /* 1..JSGX_STACK_MAX_STEPS, n_steps * n_features <= JSGX_STACK_MAX_WIDTH */
+    int32_t delay;              /* not 0, |delay| <= JSGX_STACK_MAX_DELAY */
+    int32_t mode;               /* JSGX_STACK_CONSTANT or JSGX_STACK_EDGE */
+    float fill;                 /* JSGX_STACK_CONSTANT: the value outside, any bits */
+    int32_t reserved0;          /* 0 */
+} jsgx_stack_memory_args;       /* 80 bytes, no padding */
+
+/* Enqueue only, one kernel and no scratch; capture works, a first launch included.  Refused (JSGX_ERR_INVALID, nothing enqueued), in
+ * this order and before any device call: null args, a null x, a null out; a pointer that is not 4-byte aligned; pairs outside
+ * 1..65535, n_frames outside 1..2^24, n_features outside 1..65536; n_steps outside 1..256, n_steps * n_features above 2^20; delay 0 or
+ * |delay| above 2^24; mode not 0 or 1; reserved0 not 0; x_frame_pitch below n_features, x_pair_pitch that does not cover a plane
+ * (pairs > 1); out_frame_pitch below n_steps * n_features, out_pair_pitch that does not cover a plane; out overlapping x.  Then
+ * JSGX_ERR_NO_DEVICE without a HIP device. */
+JSGX_API int jsgx_stack_memory_launch(const jsgx_stack_memory_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ from .spectrogram import (CColorPalette, Filterbank, FreqAxis, Plan, Spectrogram
                           decompose, nmf_launch, nmf_plan, nmf_scratch_bytes,
                           pcen, pcen_audio, pcen_coefficient, pcen_decay, pcen_launch, pcen_plan, pcen_scratch_bytes,
                           onset_backtrack, onset_detect, onset_detect_audio, peak_launch, peak_pick, peak_plan, peak_scratch_bytes,
+                          beat_sync_audio, stack_memory, stack_memory_launch, sync, sync_launch, sync_plan,
                           delta, delta_launch, delta_weights, mfcc, mfcc_audio, mfcc_kernel_name, mfcc_launch, mfcc_plan, mfcc_table, mfcc_to_mel_db,
                           fft_frequencies, spectral_bandwidth, spectral_centroid, spectral_crest, spectral_flatness, spectral_rolloff, spectral_shape,
                           spectral_shape_audio, spectral_shape_kernel_name, spectral_shape_launch, spectral_shape_plan)
@@ -51,6 +52,7 @@ __all__ = ["Spectrogram", "SpectrogramDisplay", "CColorPalette", "Plan", "stft_d
            "decompose", "nmf_launch", "nmf_scratch_bytes", "nmf_plan",
            "pcen", "pcen_audio", "pcen_coefficient", "pcen_decay", "pcen_launch", "pcen_scratch_bytes", "pcen_plan",
            "peak_launch", "peak_scratch_bytes", "peak_plan", "peak_pick", "onset_backtrack", "onset_detect", "onset_detect_audio",
+           "sync", "sync_launch", "sync_plan", "stack_memory", "stack_memory_launch", "beat_sync_audio",
            "mfcc_table", "mfcc_launch", "mfcc_plan", "mfcc_kernel_name", "delta_weights", "delta_launch", "mfcc", "mfcc_to_mel_db", "delta", "mfcc_audio",
            "spectral_shape_launch", "spectral_shape_plan", "spectral_shape_kernel_name", "fft_frequencies", "spectral_shape", "spectral_centroid",
            "spectral_bandwidth", "spectral_rolloff", "spectral_flatness", "spectral_crest", "spectral_shape_audio"]

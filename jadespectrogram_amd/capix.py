@@ -167,6 +167,27 @@ class PeakArgs(C.Structure):
                 ("delta", C.c_float), ("wait", C.c_int32), ("normalise", C.c_int32), ("max_peaks", C.c_int32)]
 
 
+SYNC_MEAN, SYNC_MIN, SYNC_MAX, SYNC_MEDIAN = 0, 1, 2, 3
+SYNC_CHUNK, SYNC_WAVE_MAX, SYNC_STAGE, SYNC_THREADS = 256, 64, 256, 256
+SYNC_MAX_FRAMES, SYNC_MAX_FEATURES, SYNC_MAX_BOUNDS, SYNC_MAX_SEGMENTS = 1 << 24, 65536, 1 << 20, (1 << 20) + 1
+SYNC_NAN_BITS, SYNC_LDS_BYTES, SYNC_LDS_TILE = 0x7FC00000, 4096, 65536
+STACK_CONSTANT, STACK_EDGE, STACK_MAX_STEPS, STACK_MAX_DELAY, STACK_MAX_WIDTH, STACK_THREADS = 0, 1, 256, 1 << 24, 1 << 20, 256
+
+
+class SyncArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_frame_pitch", C.c_int64), ("x_pair_pitch", C.c_int64), ("bounds", C.c_void_p), ("bounds_pitch", C.c_int64),
+                ("n_bounds", C.c_void_p), ("segments", C.c_void_p), ("segments_pitch", C.c_int64), ("n_segments", C.c_void_p), ("out", C.c_void_p),
+                ("out_frame_pitch", C.c_int64), ("out_pair_pitch", C.c_int64), ("pairs", C.c_int32), ("n_frames", C.c_int32), ("n_features", C.c_int32),
+                ("max_bounds", C.c_int32), ("bounds_all", C.c_int32), ("max_segments", C.c_int32), ("aggregate", C.c_int32), ("pad", C.c_int32),
+                ("reserved0", C.c_int32), ("reserved1", C.c_int32)]
+
+
+class StackMemoryArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_frame_pitch", C.c_int64), ("x_pair_pitch", C.c_int64), ("out", C.c_void_p), ("out_frame_pitch", C.c_int64),
+                ("out_pair_pitch", C.c_int64), ("pairs", C.c_int32), ("n_frames", C.c_int32), ("n_features", C.c_int32), ("n_steps", C.c_int32),
+                ("delay", C.c_int32), ("mode", C.c_int32), ("fill", C.c_float), ("reserved0", C.c_int32)]
+
+
 # every symbol include/jsgx.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -217,6 +238,9 @@ SIGNATURES = {
     "jsgx_peak_scratch_bytes": (C.c_int64, [C.POINTER(PeakArgs)]),
     "jsgx_peak_launch": (C.c_int, [C.POINTER(PeakArgs), _P, C.c_int64, _P]),
     "jsgx_peak_plan": (C.c_int, [C.POINTER(PeakArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 4),
+    "jsgx_sync_launch": (C.c_int, [C.POINTER(SyncArgs), _P]),
+    "jsgx_sync_plan": (C.c_int, [C.POINTER(SyncArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 3),
+    "jsgx_stack_memory_launch": (C.c_int, [C.POINTER(StackMemoryArgs), _P]),
 }
 
 _lib = None

@@ -199,6 +199,35 @@ inline PeakPlan peak_plan(const jsgx_peak_args* g) {
     return p;
 }
 
+// sections 15 and 16 (jsgx_sync_host.cpp): every refusal, in the header's order
+int sync_check(const jsgx_sync_args* g, const char* who);
+int stack_memory_check(const jsgx_stack_memory_args* g, const char* who);
+// How section 15 serves a call: the aggregate's kernel, the most segments a pair can have (what the grid of "sync_aggregate" covers:
+// strictly rising frames in 0..N, one fewer than the entries of s, and no more than the caller takes), the dynamic LDS and the launches
+struct SyncPlan {
+    const char* name;
+    long long segments;
+    int lds_dynamic, launches;
+};
+inline SyncPlan sync_plan(const jsgx_sync_args* g) {
+    static const char* const names[4] = {"sync_mean", "sync_min", "sync_max", "sync_median"};
+    SyncPlan p;
+    p.name = names[g->aggregate];
+    const long long entries = (long long)(g->n_bounds ? g->max_bounds : g->bounds_all) + 2 * g->pad;
+    p.segments = entries - 1 < g->n_frames ? entries - 1 : g->n_frames;
+    if (p.segments > g->max_segments) p.segments = g->max_segments;
+    if (p.segments < 0) p.segments = 0;
+    p.lds_dynamic = g->aggregate == JSGX_SYNC_MEDIAN ? JSGX_SYNC_LDS_TILE : 0;
+    p.launches = p.segments > 0 ? 2 : 1;
+    return p;
+}
+// The frames of the output a workgroup of section 16 takes: about 4096 elements, and few enough workgroups for one grid axis
+inline int stack_frames_per_group(long long n_frames, long long width) {
+    long long G = (4096 + width - 1) / width;
+    const long long least = (n_frames + (1 << 23) - 1) >> 23;
+    return (int)(G < least ? least : G);
+}
+
 // The three refusals of a launch's scratch buffer, in this order; `sizer` names the call that states `need`.
 inline int check_scratch(const char* who, const void* scratch, int64_t scratch_bytes, int64_t need, const char* sizer) {
     if (!scratch) return fail(JSGX_ERR_INVALID, who, "null scratch");

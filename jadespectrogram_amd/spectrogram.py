@@ -2618,6 +2618,170 @@ def onset_detect_audio(x, sr, n_fft=2048, hop=512, n_mels=128, **kw):
 
 
 # --------------------------------------------------------------------------------------------------
+# Aggregation over segments and time-delay embedding (include/jsgx.h, sections 15 and 16: libjsgx.so)
+# --------------------------------------------------------------------------------------------------
+_SYNC_AGGREGATES = {"mean": capix.SYNC_MEAN, "min": capix.SYNC_MIN, "max": capix.SYNC_MAX, "median": capix.SYNC_MEDIAN}
+_STACK_MODES = {"constant": capix.STACK_CONSTANT, "edge": capix.STACK_EDGE}
+
+
+def _sync_args(d_x, d_bounds, d_n_bounds, d_segments, d_n_segments, d_out, aggregate, pad, bounds_all) -> capix.SyncArgs:
+    import torch
+    x, o = _planes(d_x, "d_x"), _planes(d_out, "d_out")
+    P, N, F = x.shape
+    S = o.shape[1]
+    assert o.shape[0] == P and o.shape[2] == F and S >= 1, "d_out: float32 CUDA [pairs][max_segments][features]"
+    bounds, bounds_pitch, max_bounds = None, 0, 0
+    if d_bounds is not None and d_bounds.shape[-1] > 0:
+        b = d_bounds[None] if d_bounds.dim() == 1 else d_bounds          # one list: every pair's
+        assert b.is_cuda and b.dtype == torch.int32 and b.dim() == 2 and b.shape[0] in (1, P) and (b.stride(1) == 1 or b.shape[1] == 1), "d_bounds: int32 CUDA [max_bounds] or [pairs][max_bounds]"
+        bounds, bounds_pitch, max_bounds = b.data_ptr(), 0 if b.shape[0] == 1 else b.stride(0), b.shape[1]
+    n_bounds = None
+    if d_n_bounds is not None:
+        assert d_n_bounds.is_cuda and d_n_bounds.dtype == torch.int32 and d_n_bounds.numel() == P and d_n_bounds.is_contiguous(), "d_n_bounds: int32 CUDA [pairs]"
+        n_bounds = d_n_bounds.data_ptr()
+    seg = d_segments[None] if d_segments.dim() == 1 else d_segments
+    assert seg.is_cuda and seg.dtype == torch.int32 and seg.dim() == 2 and seg.shape[0] == P and seg.shape[1] >= S + 1 and (seg.stride(1) == 1 or seg.shape[1] == 1), \
+        "d_segments: int32 CUDA [pairs][>= max_segments + 1]"
+    assert d_n_segments.is_cuda and d_n_segments.dtype == torch.int32 and d_n_segments.numel() == P and d_n_segments.is_contiguous(), "d_n_segments: int32 CUDA [pairs]"
+    return capix.SyncArgs(x.data_ptr(), x.stride(1), x.stride(0), bounds, bounds_pitch, n_bounds, seg.data_ptr(), seg.stride(0), d_n_segments.data_ptr(), o.data_ptr(),
+                          o.stride(1), o.stride(0), P, N, F, max_bounds, max_bounds if bounds_all is None else int(bounds_all), S,
+                          _named(_SYNC_AGGREGATES, aggregate, "aggregate"), int(bool(pad)), 0, 0)
+
+
+def sync_launch(d_x, d_bounds, d_n_bounds, d_segments, d_n_segments, d_out, *, aggregate: str = "mean", pad: bool = True, bounds_all: int | None = None,
+                stream: int | None = None):
+    """jsgx_sync_launch: d_x float32 [frames][features] or [pairs][frames][features] (frame-major; views with pitches) aggregated over the
+    segments between the frames d_bounds int32 [max_bounds] (one list for every pair) or [pairs][max_bounds] (None: no boundary), of
+    which pair p takes the first min(d_n_bounds[p], max_bounds) (d_n_bounds int32 [pairs]; None: bounds_all of them, None: all) -> d_out
+    float32 [pairs][max_segments][features], one row a segment, d_segments int32 [pairs][>= max_segments + 1], the frames where the
+    segments begin and the last one ends, and d_n_segments int32 [pairs], the whole count (-1: a pair whose count is negative or whose
+    list decreases; nothing else is written for it).  aggregate: "mean", "min", "max" or "median".  pad: frames 0 and N are boundaries
+    too.  Enqueue only."""
+    a = _sync_args(d_x, d_bounds, d_n_bounds, d_segments, d_n_segments, d_out, aggregate, pad, bounds_all)
+    capix.check(capix.lib().jsgx_sync_launch(C.byref(a), _stream_handle(stream, d_out)))
+
+
+def sync_plan(n_frames: int, n_features: int, aggregate: str = "mean", pairs: int = 1, max_bounds: int = 1, pad: bool = True):
+    """jsgx_sync_plan: (the aggregate's kernel, lanes per workgroup, bytes of LDS per workgroup, launches) for this shape.  Needs no
+    device."""
+    N, F, P, M = int(n_frames), int(n_features), int(pairs), int(max_bounds)
+    S = max(1, min(N, M + 2 * int(bool(pad)) - 1))
+    a = capix.SyncArgs(x=1 << 40, x_frame_pitch=F, x_pair_pitch=N * F, bounds=(1 << 44) if M else None, bounds_pitch=M, n_bounds=1 << 42, segments=5 << 60,
+                       segments_pitch=S + 1, n_segments=6 << 60, out=1 << 62, out_frame_pitch=F, out_pair_pitch=S * F, pairs=P, n_frames=N, n_features=F,
+                       max_bounds=M, max_segments=S, aggregate=_named(_SYNC_AGGREGATES, aggregate, "aggregate"), pad=int(bool(pad)))      # never dereferenced
+    name, out = C.create_string_buffer(16), [C.c_int32() for _ in range(3)]
+    capix.check(capix.lib().jsgx_sync_plan(C.byref(a), name, 16, *[C.byref(o) for o in out]))
+    return (name.value.decode(),) + tuple(o.value for o in out)
+
+
+def _host_segments(idx, n_frames: int, pad: bool):
+    """The rule of include/jsgx.h section 15 on the host: the frames u of a non-decreasing list of boundaries."""
+    b = np.asarray(idx, dtype=np.int64).reshape(-1)
+    if b.size > capix.SYNC_MAX_BOUNDS:
+        raise JsgError(capix.JSGX_ERR_INVALID, f"sync: at most {capix.SYNC_MAX_BOUNDS} boundaries")
+    if (np.diff(b) < 0).any():
+        raise JsgError(capix.JSGX_ERR_INVALID, "sync: idx must be non-decreasing (it is not sorted here)")
+    c = np.clip(b, 0, n_frames)
+    s = np.concatenate(([0], c, [n_frames])) if pad else c
+    u = s[np.concatenate(([True], s[1:] != s[:-1]))] if s.size else s
+    return c.astype(np.int32), u.astype(np.int32)
+
+
+def sync(data, idx, aggregate: str = "mean", pad: bool = True, n_idx=None, max_segments: int | None = None):
+    """librosa.util.sync on the GPU (include/jsgx.h section 15): data [N, F] or [P, N, F] (numpy array or float32 CUDA tensor) aggregated
+    between the frames idx -> (out float32 [..., segments, F], segments int32 [..., segments + 1], n_segments int32 [...]) as CUDA
+    tensors: row o of out is the aggregate of the frames segments[o] .. segments[o+1]-1.
+
+    idx on the host (a list or numpy array of ints, one list for every plane): the count follows on the host by the same rule, the three
+    results are returned trimmed to it, and nothing waits for the device.  idx on the device, an int32 CUDA tensor [max] or [P, max]
+    with n_idx the int32 CUDA count(s), exactly what beat_track, peak_pick's launch or onset_detect leave there: the results have
+    max_segments rows (None: as many as the list and the plane allow), of which the first n_segments are written; n_segments is -1 for
+    a plane whose count is negative (a refused row upstream) or whose list decreases, and nothing waits for the device.
+
+    Differs from librosa on purpose: the planes are frame-major ([frames][features], what the feature kernels write; librosa aggregates
+    along the last axis of a feature-major plane); boundaries are clipped to 0..N, where librosa raises on a negative one; the list must be
+    non-decreasing, where librosa sorts it; aggregate is one of "mean", "min", "max", "median", not a callable; float32 throughout, the
+    mean summed in chunks of 256 frames.  Agreement with librosa itself was not measured: librosa is not among the test dependencies."""
+    import torch
+    x, _ = _to_cuda(data)
+    assert x.dim() in (2, 3), "sync: data is [N, F] or [P, N, F]"
+    one = x.dim() == 2
+    xp = x[None] if one else x
+    xp = xp if xp.stride(2) == 1 or xp.shape[2] == 1 else xp.contiguous()
+    P, N, F = xp.shape
+    dev = xp.device
+    with torch.cuda.device(_device_index(xp)):
+        on_device = hasattr(idx, "is_cuda")
+        if on_device:
+            assert idx.is_cuda and idx.dtype == torch.int32 and idx.dim() in (1, 2), "sync: idx on the device is int32 [max] or [P, max]"
+            bounds = idx if idx.stride(-1) == 1 or idx.shape[-1] == 1 else idx.contiguous()
+            n_bounds = None if n_idx is None else n_idx.reshape(-1).contiguous()
+            if n_bounds is not None and n_bounds.numel() == 1 and P > 1:
+                n_bounds = n_bounds.expand(P).contiguous()
+            most = min(N, bounds.shape[-1] + 2 * int(bool(pad)) - 1)
+            S = max(1, most) if max_segments is None else int(max_segments)
+            keep = S
+        else:
+            assert n_idx is None, "sync: n_idx goes with idx on the device"
+            c, u = _host_segments(idx, N, pad)
+            bounds = torch.from_numpy(c).to(dev) if c.size else None
+            n_bounds = None
+            keep = max(0, u.size - 1) if max_segments is None else min(max(0, u.size - 1), int(max_segments))
+            S = max(1, keep)
+        out = torch.empty((P, S, F), dtype=torch.float32, device=dev)
+        segments = torch.empty((P, S + 1), dtype=torch.int32, device=dev)
+        n_segments = torch.empty((P,), dtype=torch.int32, device=dev)
+        sync_launch(xp, bounds, n_bounds, segments, n_segments, out, aggregate=aggregate, pad=pad)
+        out, segments = out[:, :keep], segments[:, :keep + 1 if keep else 0]
+    return (out[0], segments[0], n_segments[0]) if one else (out, segments, n_segments)
+
+
+def stack_memory_launch(d_x, d_out, *, n_steps: int = 2, delay: int = 1, mode: str = "constant", constant_values: float = 0.0, stream: int | None = None):
+    """jsgx_stack_memory_launch: d_x float32 [frames][features] or [pairs][frames][features] -> d_out [pairs][frames][n_steps * features],
+    d_out[t][s * features + f] = d_x[t - s * delay][f]; outside the plane constant_values ("constant") or the nearest frame ("edge").
+    A negative delay stacks the future.  Bits are copied unchanged.  d_out must not overlap d_x.  Enqueue only."""
+    x, o = _planes(d_x, "d_x"), _planes(d_out, "d_out")
+    P, N, F = x.shape
+    assert tuple(o.shape) == (P, N, int(n_steps) * F), "d_out: float32 CUDA [pairs][frames][n_steps * features]"
+    a = capix.StackMemoryArgs(x.data_ptr(), x.stride(1), x.stride(0), o.data_ptr(), o.stride(1), o.stride(0), P, N, F, int(n_steps), int(delay),
+                              _named(_STACK_MODES, mode, "mode"), 0.0, 0)
+    C.memmove(C.byref(a, capix.StackMemoryArgs.fill.offset), np.float32(constant_values).tobytes(), 4)          # the bits, a NaN's payload included
+    capix.check(capix.lib().jsgx_stack_memory_launch(C.byref(a), _stream_handle(stream, d_out)))
+
+
+def stack_memory(data, n_steps: int = 2, delay: int = 1, mode: str = "constant", constant_values: float = 0.0):
+    """librosa.feature.stack_memory on the GPU (include/jsgx.h section 16): data [N, F] or [P, N, F] (numpy array or float32 CUDA tensor) ->
+    float32 CUDA [..., N, n_steps * F]: every frame with its n_steps - 1 predecessors delay, 2 delay, ... frames back side by side (a
+    negative delay: its successors).  mode "constant" fills what lies outside the plane with constant_values, "edge" with the nearest
+    frame.  Differs from librosa on purpose: frame-major planes (librosa stacks along the first axis of a feature-major one), these two
+    modes of np.pad only, float32.  Agreement with librosa itself was not measured."""
+    import torch
+    x, _ = _to_cuda(data)
+    assert x.dim() in (2, 3), "stack_memory: data is [N, F] or [P, N, F]"
+    xp = x if x.stride(-1) == 1 or x.shape[-1] == 1 else x.contiguous()
+    out = torch.empty(tuple(xp.shape[:-1]) + (int(n_steps) * xp.shape[-1],), dtype=torch.float32, device=xp.device)
+    with torch.cuda.device(_device_index(xp)):
+        stack_memory_launch(xp, out, n_steps=n_steps, delay=delay, mode=mode, constant_values=constant_values)
+    return out
+
+
+def beat_sync_audio(x, sr, n_fft=2048, hop=512, n_mels=128, aggregate: str = "median", pad: bool = True, **kw):
+    """Beat-synchronous mel features of audio x [samples] (numpy array or float32 CUDA tensor): beat_track_audio and mel_spectrogram_db,
+    then sync of the mel plane over the beat frames with the device's own count, enqueued one after the other with no host
+    synchronisation between them.  Returns (bpm float32 [], out float32 [max_segments, n_mels], segments int32 [max_segments + 1],
+    n_segments int32 []) as CUDA tensors: the first n_segments rows of out are written.  kw: beat_track_audio's win_length, start_bpm,
+    std_bpm, max_bpm, tightness, smooth, normalise, max_beats.  The differences from librosa are sync's."""
+    import torch
+    xt, _ = _to_cuda(x)
+    assert xt.dim() == 1, "beat_sync_audio: x is one channel [samples]"
+    with torch.cuda.device(_device_index(xt)):
+        bpm, beats, n_beats = beat_track_audio(xt, sr, n_fft, hop, n_mels, **kw)
+        S = mel_spectrogram_db(xt, sr, n_fft, hop, n_mels)
+        out, segments, n_segments = sync(S, beats, aggregate=aggregate, pad=pad, n_idx=n_beats)
+    return bpm, out, segments, n_segments
+
+
+# --------------------------------------------------------------------------------------------------
 # Viterbi decoding of hidden Markov models (include/jsgx.h, section 4: libjsgx.so)
 # --------------------------------------------------------------------------------------------------
 def _viterbi_args(d_log_emit, d_log_init, d_log_trans, d_states, band_half, d_logp, d_value) -> capix.ViterbiArgs:

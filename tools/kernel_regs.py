@@ -18,7 +18,8 @@ instruction-mix counts from the disassembly.  CPU only (llvm-objcopy / clang-off
                                                                jsgx_rqa.o the recurrence quantification alignment, jsgx_path_enhance.o
                                                                the path enhancement and the lag conversion, jsgx_nmf.o the
                                                                non-negative matrix factorisation, jsgx_pcen.o the per-channel
-                                                               energy normalisation, jsgx_peak.o the peak picking: name them)
+                                                               energy normalisation, jsgx_peak.o the peak picking, jsgx_sync.o the
+                                                               segment aggregation and the time-delay embedding: name them)
 """
 import os
 import re
@@ -82,7 +83,8 @@ def main():
                                                "knn_kernel", "knn_merge_kernel", "recurrence_kernel", "nn_filter_kernel", "rqa_kernel", "rqa_backtrace_kernel",
                                                "path_enhance_kernel", "lag_columns_kernel", "lag_rows_kernel", "nmf_gram_kernel", "nmf_chunk_sum_kernel",
                                                "nmf_update_a_kernel", "nmf_partial_c_kernel", "nmf_update_c_kernel", "pcen_scan_kernel", "pcen_carry_kernel", "pcen_apply_kernel",
-                                               "peak_single_kernel", "peak_stats_kernel", "peak_row_kernel", "peak_cand_kernel", "peak_carry_kernel", "peak_emit_kernel")):
+                                               "peak_single_kernel", "peak_stats_kernel", "peak_row_kernel", "peak_cand_kernel", "peak_carry_kernel", "peak_emit_kernel",
+                                               "sync_segments_kernel", "sync_aggregate_kernel", "stack_memory_kernel")):
                     continue
                 mx = mix.get(name, {})
                 valu = sum(c for o, c in mx.items() if o.startswith("v_"))
