@@ -78,3 +78,60 @@ def test_phase_vocoder_launch(jsg, torch_cuda):
     jsg.phase_vocoder_launch(X, rate, hop, n, got, chunk_frames=chunk, stream=st.cuda_stream)
     torch.cuda.synchronize()
     assert want.abs().max() > 0 and torch.equal(bits(torch, got), bits(torch, want))
+
+
+def both_ways(jsg, torch, name):
+    """A case of tests/test_gpu_scratch_contents.py (its shapes, inputs, sentinel-filled outputs and reference) launched with the caller's
+    own scratch on the current stream and without a scratch tensor on a side stream: the same bytes in every output, and the reference's."""
+    import test_gpu_scratch_contents as sc
+    work, _ = sc.built(jsg, torch, name)
+    want, got = work.alloc(), work.alloc()
+    args, kw = work.bind(want)
+    work.launch(*args, d_scratch=torch.empty(work.need, dtype=torch.uint8, device="cuda"), **kw)
+    st = side_stream(torch)
+    args, kw = work.bind(got)
+    work.launch(*args, stream=st.cuda_stream, **kw)
+    torch.cuda.synchronize()
+    work.check(tuple(t.cpu().numpy() for t in want))
+    for g, w in zip(got, want):
+        assert g.cpu().numpy().tobytes() == w.cpu().numpy().tobytes()
+
+
+def test_hpss_launch(jsg, torch_cuda):
+    both_ways(jsg, torch_cuda, "hpss-K65-complex-windows1x63")
+
+
+def test_beat_launch(jsg, torch_cuda):
+    both_ways(jsg, torch_cuda, "beat-period33-smooth1")
+
+
+def test_dtw_launch(jsg, torch_cuda):
+    both_ways(jsg, torch_cuda, "dtw-subseq")
+
+
+def test_viterbi_launch(jsg, torch_cuda):
+    both_ways(jsg, torch_cuda, "viterbi-band-65-states-half-30")
+
+
+def test_pyin_decode_launch(jsg, torch_cuda):
+    both_ways(jsg, torch_cuda, "pyin_decode-129-bins-half-50")
+
+
+def test_knn_launch(jsg, torch_cuda):
+    both_ways(jsg, torch_cuda, "knn-k65-split3-width2")
+
+
+def test_rqa_launch(jsg, torch_cuda):
+    both_ways(jsg, torch_cuda, "rqa-knight-moves")
+
+
+def test_nmf_launch(jsg, torch_cuda):
+    both_ways(jsg, torch_cuda, "nmf-257-frames-257-bins-5-components")
+
+
+def test_pcen_launch(jsg, torch_cuda):
+    both_ways(jsg, torch_cuda, "pcen-513-frames-state-in")
+
+
+def test_peak_launch(jsg, torch_cuda):
+    both_ways(jsg, torch_cuda, "peak-two-blocks-and-five-frames-long-wait-backtracking")
