@@ -1650,6 +1650,128 @@ typedef struct jsgx_stack_memory_args {
  * JSGX_ERR_NO_DEVICE without a HIP device. */
 JSGX_API int jsgx_stack_memory_launch(const jsgx_stack_memory_args* args, void* stream);
 
+/* Section 17 was added to version 1 in the same way: sections 1 to 16, their structs and their constants are as they were. */
+
+/* ------------------------------------------------------------------------------------------------
+ * 17. Temporally constrained agglomerative segmentation (librosa.segment.agglomerative and librosa.segment.subsegment): Ward clustering
+ *     of the frames of a plane in which a cluster is a run of consecutive frames and every step merges two neighbours.  The plane is
+ *     section 15's, frame-major, X[t][f] = x[p*x_pair_pitch + t*x_frame_pitch + f], and so are the boundary inputs, with the same names
+ *     and meanings: bounds, bounds_pitch (0: one list for every pair), n_bounds, max_bounds, bounds_all, pad.  The list u[0] < ... <
+ *     u[U-1] is built by section 15's rule (one copy of it serves both sections) and goes to segments / n_segments as there.  Each
+ *     stretch o, the frames u[o] .. u[o+1]-1 (len of them), is clustered on its own into min(k, len) clusters, k = n_clusters >= 1.
+ *     max_bounds = 0 with pad = 1 is the one stretch 0..N: librosa.segment.agglomerative.  A list of beats: librosa.segment.subsegment.
+ *     max_segments must cover every stretch the list can give: min(n_frames, entries - 1) with entries = max_bounds (bounds_all where
+ *     n_bounds is NULL) + 2 pad, so that every stretch is handed on through segments.
+ *
+ *     Definition.  A cluster C has a start frame, a count m_C and float32 sums S_C[f].  A frame alone: S = X[t][f], m = 1.  Merging the
+ *     left cluster A with its right neighbour B: S[f] = fl(S_A[f] + S_B[f]), m = m_A + m_B.  The mean is M_C[f] = fl(S_C[f] / (float)m_C),
+ *     the divide correctly rounded.  The cost of a pair of neighbours A (left), B (right):
+ *         d_f  = fl(M_A[f] - M_B[f])
+ *         q_l  = fmaf(d_f, d_f, q_l) from +0 over f = l, l + 64, ... ascending, for each lane l < 64 (a lane with no feature: +0)
+ *         q_l  = fl(q_l + q_{l xor s}) for s = 32, 16, 8, 4, 2, 1: the same value Q in every lane
+ *         w    = fl(fl((float)m_A * (float)m_B) / (float)(m_A + m_B)),  cost = fl(w * Q);  a cost that is a NaN is JSGX_SYNC_NAN_BITS
+ *     The order depends on F alone.  A step: among the pairs of neighbours take the least under section 15's key() of the cost bits (a
+ *     total order on every bit pattern: an overflowed sum that makes a cost an infinity or the NaN still sorts, the NaN last), a tie to
+ *     the lower start frame; merge the pair; recompute the costs to its two neighbours.  Stop at min(k, len) clusters.  All of this is
+ *     float32 with every operation rounded on its own; tests/agglo_ref.py restates it in numpy and every output is compared as bits.
+ *     Nothing depends on pairs, on the pitches, on the form of the kernel or on how the minimum is searched.
+ *
+ *     Outputs.  out_bounds[p*out_pitch + i], int32: the start frames of the final clusters of all stretches of the pair, ascending, the
+ *     stretches one behind the other: stretch o begins at index sum over o' < o of min(k, len_o') with the entry u[o].  Entries at or
+ *     beyond max_out are not written.  n_out[p]: the whole count.  segments, n_segments: as in section 15 (required).  order (int32)
+ *     and height (float32), [pairs][n_frames] at tree_pitch, both or neither: step j of stretch o writes the boundary it removes (the
+ *     start of B) and its cost at index u[o] + j; no other entry is touched.  With k = 1 that is the whole dendrogram of a stretch: the
+ *     clusters for any k' are u[o] and the boundaries removed by its last k' - 1 steps.
+ *
+ *     Refused pair: n_out[p] = -1 and nothing else is written for the pair except n_segments, where n_bounds[p] < 0 or the list
+ *     decreases (n_segments[p] = -1, as in section 15); where a value in the frames u[0] .. u[U-1]-1 of the pair is a NaN or an
+ *     infinity; where a stretch is longer than JSGX_AGGLO_MAX_STRETCH.  In the last two cases segments and n_segments are written.
+ *
+ *     Deliberate differences from librosa / scikit-learn: frame-major planes; a tie goes to the lower frame (sklearn: its heap's
+ *     order); float32 (sklearn: float64); boundaries are clipped and a non-decreasing list is required, as in section 15; Ward linkage
+ *     on a chain only: no other linkage, no distance threshold in place of k, no other connectivity.  The greedy merge of neighbours
+ *     gave scikit-learn's boundaries on every plane of tests/test_agglo_ref.py.  Agreement with librosa itself is not measured.
+ *
+ *     The kernels.  No atomics, no workgroup waits for another; a stretch is served by one wavefront, so no barrier stands in a step.
+ *         "agglo_segments"  a workgroup a pair: section 15's rule
+ *         "agglo_copy"      a wavefront a frame, lane = feature, JSGX_AGGLO_COPY_FRAMES frames a workgroup: X into the plane of sums in
+ *                           the scratch, the cost of every frame with its successor, and the workgroup's non-finite vote
+ *         "agglo_offsets"   a workgroup a pair: the votes, the over-long stretches, the prefix sums of min(k, len), n_out
+ *         "agglo_wave"      stretches of up to JSGX_AGGLO_SHORT frames, four to a workgroup of 256 lanes, a wavefront each: the costs (as
+ *                           keys) and 16-bit left / right links one per lane in LDS, the minimum one reduction over (key, frame)
+ *         "agglo_group"     longer stretches, a workgroup of one wavefront each: keys and links of every frame in LDS (8 bytes a frame)
+ *                           and a minimum (key, frame) for every block of 64 frames.  A merge dirties at most three blocks: a step is a
+ *                           reduction over the block minima and one over each dirty block, not a sweep.  Launched where n_frames >
+ *                           JSGX_AGGLO_SHORT; a workgroup whose stretch is short leaves at once, as "agglo_wave" leaves the long ones.
+ *     The sums of the touched clusters are read and written through the caches, lane = feature; a step reads four rows and writes one.
+ *     A launch is len - k dependent steps a stretch and is bound by their latency.  Measured on one MI355X (profiles/agglo_bench.md,
+ *     tools/agglo_bench.py): a step of "agglo_wave" takes 1.2 to 1.3 microseconds, a step of "agglo_group" 1.8 to 2.1 (20 to 128
+ *     features); 24448 stretches of 43 frames to four clusters each (64 x 16384 x 128) take 0.86 ms.
+ * ------------------------------------------------------------------------------------------------ */
+#define JSGX_AGGLO_MAX_STRETCH 16384       /* the longest stretch: 8 bytes of LDS a frame and 8 a block of 64 are 133120 bytes */
+#define JSGX_AGGLO_SHORT 64                /* up to this many frames a stretch is one of four in a workgroup of "agglo_wave" */
+#define JSGX_AGGLO_THREADS 256             /* all kernels but "agglo_group" */
+#define JSGX_AGGLO_GROUP_THREADS 64        /* "agglo_group" */
+#define JSGX_AGGLO_COPY_FRAMES 64          /* frames of a workgroup of "agglo_copy": one vote each */
+#define JSGX_AGGLO_MAX_OUT 16777216        /* 2^24 */
+#define JSGX_AGGLO_LDS_BYTES 2048          /* static, of "agglo_wave": 8 bytes a frame, four stretches */
+#define JSGX_AGGLO_LDS_LIMIT 133120        /* dynamic, of "agglo_group", at most: 8 L + 8 ceil(L / 64) for L = min(n_frames, JSGX_AGGLO_MAX_STRETCH) */
+
+typedef struct jsgx_agglomerative_args {
+    const float* x;             /* device floats: X */
+    int64_t x_frame_pitch;      /* >= n_features */
+    int64_t x_pair_pitch;       /* pairs > 1: covers a plane */
+    const int32_t* bounds;      /* device int32 [pairs][max_bounds]; may be NULL where max_bounds == 0 */
+    int64_t bounds_pitch;       /* pairs > 1: 0 (one list for every pair) or >= max_bounds */
+    const int32_t* n_bounds;    /* device int32 [pairs], or NULL: bounds_all for every pair */
+    int32_t* segments;          /* device int32 [pairs][max_segments + 1]: u */
+    int64_t segments_pitch;     /* pairs > 1: >= max_segments + 1 */
+    int32_t* n_segments;        /* device int32 [pairs] */
+    int32_t* out_bounds;        /* device int32 [pairs][max_out] */
+    int64_t out_pitch;          /* pairs > 1: >= max_out */
+    int32_t* n_out;             /* device int32 [pairs] */
+    int32_t* order;             /* device int32 [pairs][n_frames], or NULL (then height is NULL) */
+    float* height;              /* device floats [pairs][n_frames], or NULL (then order is NULL) */
+    int64_t tree_pitch;         /* pairs > 1 and order given: >= n_frames */
+    int32_t pairs;              /* 1..65535 */
+    int32_t n_frames;           /* N, 1..2^24 */
+    int32_t n_features;         /* F, 1..65536 */
+    int32_t max_bounds;         /* 0..JSGX_SYNC_MAX_BOUNDS */
+    int32_t bounds_all;         /* n_bounds NULL: 0..max_bounds; else not looked at */
+    int32_t max_segments;       /* 1..JSGX_SYNC_MAX_SEGMENTS, and every stretch the list can give */
+    int32_t max_out;            /* 1..JSGX_AGGLO_MAX_OUT */
+    int32_t n_clusters;         /* k >= 1 */
+    int32_t pad;                /* 0 or 1 */
+    int32_t reserved0;          /* 0 */
+} jsgx_agglomerative_args;      /* 160 bytes, no padding beyond the reserved word */
+
+/* The bytes of scratch the launch needs, with S the stretches max_segments must cover and V = ceil(n_frames / JSGX_AGGLO_COPY_FRAMES):
+ *     4 * pairs * (n_frames * n_features + n_frames + V + S + 1)
+ * (the plane of sums, a cost a frame, a vote a workgroup of "agglo_copy", an offset a stretch, a verdict a pair).  The layout is private,
+ * the contents on entry are undefined, a larger scratch changes nothing.  Refused (a negative jsgx_status): what the launch refuses
+ * before it looks at the scratch. */
+JSGX_API int64_t jsgx_agglomerative_scratch_bytes(const jsgx_agglomerative_args* args);
+/* Enqueue only: no allocation, no synchronisation; capture works, a first launch included.  Refused (JSGX_ERR_INVALID, nothing
+ * enqueued), in this order and before any device call: null args, a null x, a null segments, a null n_segments, a null out_bounds, a
+ * null n_out; a null bounds with max_bounds > 0; order without height or height without order; a pointer that is not 4-byte aligned;
+ * pairs outside 1..65535, n_frames outside 1..2^24, n_features outside 1..65536; max_bounds outside 0..2^20; with n_bounds NULL,
+ * bounds_all outside 0..max_bounds; max_segments outside 1..2^20+1; max_out outside 1..2^24; n_clusters below 1; pad not 0 or 1;
+ * reserved0 not 0; max_segments below the stretches the list can give; n_frames above JSGX_AGGLO_MAX_STRETCH where no boundary can
+ * come (max_bounds, or bounds_all with n_bounds NULL, is 0) and pad = 1; x_frame_pitch below n_features, x_pair_pitch that does not
+ * cover a plane (pairs > 1); with pairs > 1: bounds_pitch neither 0 nor >= max_bounds (where bounds is given), segments_pitch below
+ * max_segments + 1, out_pitch below max_out, tree_pitch below n_frames (where order is given); out_bounds, then n_out, segments,
+ * n_segments, order, height overlapping x, bounds, n_bounds in this order; any two of those six outputs overlapping, in that order;
+ * a null scratch, a scratch that is not 4-byte aligned, scratch_bytes below the size, the scratch (the bytes of that size)
+ * overlapping x, bounds, n_bounds, out_bounds, n_out, segments, n_segments, order, height in this order.  Then JSGX_ERR_NO_DEVICE
+ * without a HIP device. */
+JSGX_API int jsgx_agglomerative_launch(const jsgx_agglomerative_args* args, void* scratch, int64_t scratch_bytes, void* stream);
+/* What the launch enqueues, without a device: the form of the merge that takes the longest stretch the shape allows ("agglo_wave" where
+ * n_frames <= JSGX_AGGLO_SHORT, else "agglo_group"), its lanes per workgroup (256 or 64), its bytes of LDS (JSGX_AGGLO_LDS_BYTES, or 8 L +
+ * 8 ceil(L / 64)) and the launches (5 with "agglo_group", else 4; 2 where the list can give no stretch).  Any output pointer may be NULL
+ * (name: else name_len >= 16).  Refused: a name_len below 16 with a name, then what the scratch size refuses. */
+JSGX_API int jsgx_agglomerative_plan(const jsgx_agglomerative_args* args, char* name, int name_len, int32_t* threads, int32_t* lds_bytes,
+                                     int32_t* n_launches);
+
 #ifdef __cplusplus
 }
 #endif

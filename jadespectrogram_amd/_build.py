@@ -29,9 +29,9 @@ ARCH = "gfx950"
 # the companion library (include/jsgx.h): its own units, the same flags; of libjsg.so it takes two headers without state (jsg_spans.h,
 # jsg_launch.h), no object code
 LIBX = os.path.join(PKG, "libjsgx.so")
-SOURCES_X = ["jsgx_beat.hip", "jsgx_cdist.hip", "jsgx_dtw.hip", "jsgx_viterbi.hip", "jsgx_pyin.hip", "jsgx_knn.hip", "jsgx_rqa.hip", "jsgx_path_enhance.hip", "jsgx_nmf.hip", "jsgx_pcen.hip", "jsgx_peak.hip", "jsgx_sync.hip", "jsgx_beat_host.cpp", "jsgx_dtw_host.cpp", "jsgx_viterbi_host.cpp",
-             "jsgx_pyin_host.cpp", "jsgx_knn_host.cpp", "jsgx_rqa_host.cpp", "jsgx_path_enhance_host.cpp", "jsgx_nmf_host.cpp", "jsgx_pcen_host.cpp", "jsgx_peak_host.cpp", "jsgx_sync_host.cpp"]
-HEADERS_X = ["jsgx_internal.h", "jsgx_cost_tile.h", "jsgx_plane_tiles.h", "jsg_spans.h", "jsg_launch.h", os.path.join(ROOT, "include", "jsgx.h")]
+SOURCES_X = ["jsgx_beat.hip", "jsgx_cdist.hip", "jsgx_dtw.hip", "jsgx_viterbi.hip", "jsgx_pyin.hip", "jsgx_knn.hip", "jsgx_rqa.hip", "jsgx_path_enhance.hip", "jsgx_nmf.hip", "jsgx_pcen.hip", "jsgx_peak.hip", "jsgx_sync.hip", "jsgx_agglo.hip", "jsgx_beat_host.cpp", "jsgx_dtw_host.cpp", "jsgx_viterbi_host.cpp",
+             "jsgx_pyin_host.cpp", "jsgx_knn_host.cpp", "jsgx_rqa_host.cpp", "jsgx_path_enhance_host.cpp", "jsgx_nmf_host.cpp", "jsgx_pcen_host.cpp", "jsgx_peak_host.cpp", "jsgx_sync_host.cpp", "jsgx_agglo_host.cpp"]
+HEADERS_X = ["jsgx_internal.h", "jsgx_cost_tile.h", "jsgx_plane_tiles.h", "jsgx_segments.h", "jsg_spans.h", "jsg_launch.h", os.path.join(ROOT, "include", "jsgx.h")]
 
 
 def _hipcc() -> str:

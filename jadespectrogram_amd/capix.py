@@ -188,6 +188,18 @@ class StackMemoryArgs(C.Structure):
                 ("delay", C.c_int32), ("mode", C.c_int32), ("fill", C.c_float), ("reserved0", C.c_int32)]
 
 
+AGGLO_MAX_STRETCH, AGGLO_SHORT, AGGLO_THREADS, AGGLO_GROUP_THREADS, AGGLO_COPY_FRAMES, AGGLO_MAX_OUT = 16384, 64, 256, 64, 64, 1 << 24
+AGGLO_LDS_BYTES, AGGLO_LDS_LIMIT = 2048, 133120
+
+
+class AgglomerativeArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("x_frame_pitch", C.c_int64), ("x_pair_pitch", C.c_int64), ("bounds", C.c_void_p), ("bounds_pitch", C.c_int64),
+                ("n_bounds", C.c_void_p), ("segments", C.c_void_p), ("segments_pitch", C.c_int64), ("n_segments", C.c_void_p), ("out_bounds", C.c_void_p),
+                ("out_pitch", C.c_int64), ("n_out", C.c_void_p), ("order", C.c_void_p), ("height", C.c_void_p), ("tree_pitch", C.c_int64), ("pairs", C.c_int32),
+                ("n_frames", C.c_int32), ("n_features", C.c_int32), ("max_bounds", C.c_int32), ("bounds_all", C.c_int32), ("max_segments", C.c_int32),
+                ("max_out", C.c_int32), ("n_clusters", C.c_int32), ("pad", C.c_int32), ("reserved0", C.c_int32)]
+
+
 # every symbol include/jsgx.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -241,6 +253,9 @@ SIGNATURES = {
     "jsgx_sync_launch": (C.c_int, [C.POINTER(SyncArgs), _P]),
     "jsgx_sync_plan": (C.c_int, [C.POINTER(SyncArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 3),
     "jsgx_stack_memory_launch": (C.c_int, [C.POINTER(StackMemoryArgs), _P]),
+    "jsgx_agglomerative_scratch_bytes": (C.c_int64, [C.POINTER(AgglomerativeArgs)]),
+    "jsgx_agglomerative_launch": (C.c_int, [C.POINTER(AgglomerativeArgs), _P, C.c_int64, _P]),
+    "jsgx_agglomerative_plan": (C.c_int, [C.POINTER(AgglomerativeArgs), C.c_char_p, C.c_int] + [C.POINTER(C.c_int32)] * 3),
 }
 
 _lib = None

@@ -228,6 +228,44 @@ inline int stack_frames_per_group(long long n_frames, long long width) {
     return (int)(G < least ? least : G);
 }
 
+// section 17 (jsgx_agglo_host.cpp): every refusal that does not look at the scratch, in the header's order, and the bytes of the
+// buffers; then the refusals of the scratch
+struct AggloSpans {
+    jsg::i128 x, bounds, n_bounds, out_bounds, n_out, segments, n_segments, order, height;
+};
+int agglo_check(const jsgx_agglomerative_args* g, const char* who, AggloSpans* spans);
+int agglo_check_scratch(const jsgx_agglomerative_args* g, const char* who, const AggloSpans& spans, const void* scratch, int64_t scratch_bytes);
+// How section 17 serves a call: the stretches a pair can have (what the grids of the merge kernels cover, and what max_segments must
+// cover), the longest of them, the form that takes it, and where the parts of the scratch lie (in 4-byte words): the plane of sums
+// [pairs][N][F] at 0, the first costs as keys [pairs][N], the votes [pairs][votes], the offsets [pairs][stretches], the verdicts [pairs]
+struct AggloPlan {
+    const char* name;
+    long long stretches, longest, votes;
+    int threads, lds_bytes, launches;
+    long long off_cost, off_votes, off_offsets, off_verdict, scratch_bytes;
+};
+JSGX_HD int agglo_group_lds(long long longest) { return (int)(8 * longest + 8 * ((longest + 63) / 64)); }
+inline AggloPlan agglo_plan(const jsgx_agglomerative_args* g) {
+    AggloPlan p;
+    const long long P = g->pairs, N = g->n_frames, F = g->n_features;
+    const long long entries = (long long)(g->n_bounds ? g->max_bounds : g->bounds_all) + 2 * g->pad;
+    p.stretches = entries - 1 < N ? entries - 1 : N;
+    if (p.stretches < 0) p.stretches = 0;
+    p.longest = N < JSGX_AGGLO_MAX_STRETCH ? N : JSGX_AGGLO_MAX_STRETCH;
+    const bool group = N > JSGX_AGGLO_SHORT;
+    p.name = group ? "agglo_group" : "agglo_wave";
+    p.threads = group ? JSGX_AGGLO_GROUP_THREADS : JSGX_AGGLO_THREADS;
+    p.lds_bytes = group ? agglo_group_lds(p.longest) : JSGX_AGGLO_LDS_BYTES;
+    p.launches = p.stretches == 0 ? 2 : group ? 5 : 4;
+    p.votes = (N + JSGX_AGGLO_COPY_FRAMES - 1) / JSGX_AGGLO_COPY_FRAMES;
+    p.off_cost = P * N * F;
+    p.off_votes = p.off_cost + P * N;
+    p.off_offsets = p.off_votes + P * p.votes;
+    p.off_verdict = p.off_offsets + P * p.stretches;
+    p.scratch_bytes = 4 * (p.off_verdict + P);
+    return p;
+}
+
 // The three refusals of a launch's scratch buffer, in this order; `sizer` names the call that states `need`.
 inline int check_scratch(const char* who, const void* scratch, int64_t scratch_bytes, int64_t need, const char* sizer) {
     if (!scratch) return fail(JSGX_ERR_INVALID, who, "null scratch");

@@ -1,13 +1,14 @@
 // libjsgx.so, aggregation of a plane over segments and time-delay embedding (include/jsgx.h sections 15 and 16): the kernels and the
 // launchers.
 //   "sync_segments"   a workgroup a pair: the boundaries are checked (one pass), then clipped, padded and freed of repeats by a prefix
-//                     count over 256 entries a step (ballots inside a wavefront, four totals through LDS)
+//                     count over 256 entries a step (ballots inside a wavefront, four totals through LDS): jsgx_segments.h
 //   "sync_aggregate"  lane = feature; a workgroup owns four segments and 64 features.  A team is one wavefront (a segment each) or the
 //                     four of the workgroup (the segments one after the other); every aggregate is written once for a team of
 //                     either size, so no result depends on which one served it.  The median selects the k-th smallest key bit by bit.
 //   "stack_memory"    a workgroup a run of whole output frames, lanes along the row; the row index advances by addition, the step of
 //                     a column is one float multiply and a correction
 #include "jsgx_internal.h"
+#include "jsgx_segments.h"
 
 namespace jsgx {
 
@@ -20,7 +21,7 @@ constexpr int kWaveMax = JSGX_SYNC_WAVE_MAX;
 constexpr int kStage = JSGX_SYNC_STAGE;
 static_assert(kWaves == 4 && kWaves * kWaveMax <= kStage && 4 * 64 * kStage <= JSGX_SYNC_LDS_TILE, "the tile holds a staged segment, or one a wavefront");
 static_assert(2 * 2 * kWaves * 64 * 4 == JSGX_SYNC_LDS_BYTES, "include/jsgx.h");
-static_assert(JSGX_STACK_THREADS == 256, "include/jsgx.h");
+static_assert(JSGX_STACK_THREADS == 256 && kThreads == kSegThreads, "include/jsgx.h");
 
 struct SyncK {
     const float* x;
@@ -36,63 +37,10 @@ struct SyncK {
     int N, F, max_bounds, bounds_all, max_segments, pad;
 };
 
-// HPSS's hp_key: unsigned order = the order of the floats, -0 below +0, the infinities at the ends (a NaN beyond them)
-__device__ __forceinline__ unsigned key_of(float v) {
-    const unsigned b = __float_as_uint(v);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float unkey(unsigned k) { return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k); }
-
 __global__ __launch_bounds__(kThreads) void sync_segments_kernel(const SyncK g) {
     __shared__ int wave_total[2][kWaves], wave_bad[kWaves];
-    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int n = g.n_bounds ? g.n_bounds[p] : g.bounds_all;
-    const int m = n < g.max_bounds ? n : g.max_bounds;
-    const long long b0 = p * g.bounds_pitch;          // bounds may be NULL with max_bounds == 0: then m <= 0 and nothing is read
-    int bad = n < 0;
-    for (int i = 1 + tid; i < m; i += kThreads) bad |= g.bounds[b0 + i] < g.bounds[b0 + i - 1];
-    const bool some = __ballot(bad) != 0;
-    if (lane == 0) wave_bad[w] = some;
-    __syncthreads();
-    if (wave_bad[0] | wave_bad[1] | wave_bad[2] | wave_bad[3]) {
-        if (tid == 0) g.n_segments[p] = -1;
-        return;
-    }
-    const int L = m + 2 * g.pad, N = g.N;
-    // s[i], 0 <= i < L
-    auto entry = [&](int i) {
-        if (g.pad && i == 0) return 0;
-        if (g.pad && i == L - 1) return N;
-        const int v = g.bounds[b0 + i - g.pad];
-        return v < 0 ? 0 : v > N ? N : v;
-    };
-    int* seg = g.segments + p * g.segments_pitch;
-    int kept = 0;          // the entries of u in front of this step
-    for (int i0 = 0, step = 0; i0 < L; i0 += kThreads, ++step) {
-        const int i = i0 + tid;
-        int v = 0;
-        bool keep = false;
-        if (i < L) {
-            v = entry(i);
-            keep = i == 0 || v != entry(i - 1);
-        }
-        const unsigned long long votes = __ballot(keep);
-        if (lane == 0) wave_total[step & 1][w] = __popcll(votes);
-        __syncthreads();          // the other buffer is the one the step before read
-        int at = kept + __popcll(votes & ((1ull << lane) - 1)), all = 0;
-#pragma unroll
-        for (int q = 0; q < kWaves; ++q) {
-            const int c = wave_total[step & 1][q];
-            at += q < w ? c : 0;
-            all += c;
-        }
-        if (keep && at >= 1 && at <= g.max_segments) {
-            seg[at] = v;
-            if (at == 1) seg[0] = entry(0);          // u[0] is written only where there is a u[1]
-        }
-        kept += all;
-    }
-    if (tid == 0) g.n_segments[p] = kept > 0 ? kept - 1 : 0;
+    const SegmentsK s{g.bounds, g.bounds_pitch, g.n_bounds, g.segments, g.segments_pitch, g.n_segments, g.N, g.max_bounds, g.bounds_all, g.max_segments, g.pad};
+    segments_of_pair(s, blockIdx.x, wave_total, wave_bad);          // jsgx_segments.h: the rule, shared with section 17
 }
 
 // What the wavefronts of a team hand each other: two values a lane, in two buffers that alternate, so that one barrier a round is

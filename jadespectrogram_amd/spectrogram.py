@@ -2674,13 +2674,14 @@ def sync_plan(n_frames: int, n_features: int, aggregate: str = "mean", pairs: in
     return (name.value.decode(),) + tuple(o.value for o in out)
 
 
-def _host_segments(idx, n_frames: int, pad: bool):
-    """The rule of include/jsgx.h section 15 on the host: the frames u of a non-decreasing list of boundaries."""
+def _host_segments(idx, n_frames: int, pad: bool, who: str = "sync", what: str = "idx"):
+    """The rule of include/jsgx.h section 15 on the host: the frames u of a non-decreasing list of boundaries (who, what: the caller and
+    its name for the list, for the error text)."""
     b = np.asarray(idx, dtype=np.int64).reshape(-1)
     if b.size > capix.SYNC_MAX_BOUNDS:
-        raise JsgError(capix.JSGX_ERR_INVALID, f"sync: at most {capix.SYNC_MAX_BOUNDS} boundaries")
+        raise JsgError(capix.JSGX_ERR_INVALID, f"{who}: at most {capix.SYNC_MAX_BOUNDS} boundaries")
     if (np.diff(b) < 0).any():
-        raise JsgError(capix.JSGX_ERR_INVALID, "sync: idx must be non-decreasing (it is not sorted here)")
+        raise JsgError(capix.JSGX_ERR_INVALID, f"{who}: {what} must be non-decreasing (it is not sorted here)")
     c = np.clip(b, 0, n_frames)
     s = np.concatenate(([0], c, [n_frames])) if pad else c
     u = s[np.concatenate(([True], s[1:] != s[:-1]))] if s.size else s
@@ -2779,6 +2780,166 @@ def beat_sync_audio(x, sr, n_fft=2048, hop=512, n_mels=128, aggregate: str = "me
         S = mel_spectrogram_db(xt, sr, n_fft, hop, n_mels)
         out, segments, n_segments = sync(S, beats, aggregate=aggregate, pad=pad, n_idx=n_beats)
     return bpm, out, segments, n_segments
+
+
+# --------------------------------------------------------------------------------------------------
+# Temporally constrained agglomerative segmentation (include/jsgx.h, section 17: libjsgx.so)
+# --------------------------------------------------------------------------------------------------
+def _agglo_args(d_x, d_bounds, d_n_bounds, d_segments, d_n_segments, d_out_bounds, d_n_out, n_clusters, pad, bounds_all, d_order, d_height) -> capix.AgglomerativeArgs:
+    import torch
+    x = _planes(d_x, "d_x")
+    P, N, F = x.shape
+    bounds, bounds_pitch, max_bounds = None, 0, 0
+    if d_bounds is not None and d_bounds.shape[-1] > 0:
+        b = d_bounds[None] if d_bounds.dim() == 1 else d_bounds          # one list: every pair's
+        assert b.is_cuda and b.dtype == torch.int32 and b.dim() == 2 and b.shape[0] in (1, P) and (b.stride(1) == 1 or b.shape[1] == 1), "d_bounds: int32 CUDA [max_bounds] or [pairs][max_bounds]"
+        bounds, bounds_pitch, max_bounds = b.data_ptr(), 0 if b.shape[0] == 1 else b.stride(0), b.shape[1]
+    n_bounds = None
+    if d_n_bounds is not None:
+        assert d_n_bounds.is_cuda and d_n_bounds.dtype == torch.int32 and d_n_bounds.numel() == P and d_n_bounds.is_contiguous(), "d_n_bounds: int32 CUDA [pairs]"
+        n_bounds = d_n_bounds.data_ptr()
+
+    def rows(t, what, dtype=torch.int32):
+        t = t[None] if t.dim() == 1 else t
+        assert t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[0] == P and t.shape[1] >= 1 and (t.stride(1) == 1 or t.shape[1] == 1), f"{what}: {dtype} CUDA [pairs][...]"
+        return t
+    seg, out = rows(d_segments, "d_segments"), rows(d_out_bounds, "d_out_bounds")
+    assert seg.shape[1] >= 2, "d_segments: int32 CUDA [pairs][>= max_segments + 1]"
+    for t, what in ((d_n_segments, "d_n_segments"), (d_n_out, "d_n_out")):
+        assert t.is_cuda and t.dtype == torch.int32 and t.numel() == P and t.is_contiguous(), f"{what}: int32 CUDA [pairs]"
+    assert (d_order is None) == (d_height is None), "d_order and d_height go together"
+    order = height = None
+    tree_pitch = 0
+    if d_order is not None:
+        o, h = rows(d_order, "d_order"), rows(d_height, "d_height", torch.float32)
+        assert o.shape[1] >= N and h.shape[1] >= N and (P == 1 or o.stride(0) == h.stride(0)), "d_order, d_height: [pairs][>= frames] at one row pitch"
+        order, height, tree_pitch = o.data_ptr(), h.data_ptr(), o.stride(0)
+    return capix.AgglomerativeArgs(x.data_ptr(), x.stride(1), x.stride(0), bounds, bounds_pitch, n_bounds, seg.data_ptr(), seg.stride(0), d_n_segments.data_ptr(),
+                                   out.data_ptr(), out.stride(0), d_n_out.data_ptr(), order, height, tree_pitch, P, N, F, max_bounds,
+                                   max_bounds if bounds_all is None else int(bounds_all), seg.shape[1] - 1, out.shape[1], int(n_clusters), int(bool(pad)), 0)
+
+
+def agglomerative_scratch_bytes(d_x, d_bounds, d_n_bounds, d_segments, d_n_segments, d_out_bounds, d_n_out, *, n_clusters: int, pad: bool = True,
+                                bounds_all: int | None = None, d_order=None, d_height=None) -> int:
+    """jsgx_agglomerative_scratch_bytes: the bytes of scratch agglomerative_launch needs for these arguments (the plane once more, and a
+    few words a frame)."""
+    a = _agglo_args(d_x, d_bounds, d_n_bounds, d_segments, d_n_segments, d_out_bounds, d_n_out, n_clusters, pad, bounds_all, d_order, d_height)
+    return int(capix.check(capix.lib().jsgx_agglomerative_scratch_bytes(C.byref(a))))
+
+
+def agglomerative_launch(d_x, d_bounds, d_n_bounds, d_segments, d_n_segments, d_out_bounds, d_n_out, *, n_clusters: int, pad: bool = True,
+                         bounds_all: int | None = None, d_order=None, d_height=None, d_scratch=None, stream: int | None = None):
+    """jsgx_agglomerative_launch: every stretch of d_x float32 [frames][features] or [pairs][frames][features] (frame-major; views with
+    pitches) between two boundaries clustered into min(n_clusters, its frames) runs of frames by Ward's criterion.  d_bounds, d_n_bounds,
+    bounds_all, pad, d_segments int32 [pairs][>= stretches + 1] and d_n_segments int32 [pairs]: as in sync_launch (d_bounds None with
+    pad: the whole plane is one stretch) -> d_out_bounds int32 [pairs][max_out], the first frames of the clusters of all stretches,
+    ascending, and d_n_out int32 [pairs], their whole count (-1: a refused pair, nothing else is written for it: a negative count or a
+    decreasing list, a NaN or an infinity between the first and the last boundary, a stretch of more than capix.AGGLO_MAX_STRETCH
+    frames).  d_order int32 and d_height float32 [pairs][>= frames], both or neither: step j of the stretch that begins at frame u
+    writes the boundary it removes and its cost at index u + j.  d_scratch: a contiguous CUDA tensor of at least
+    agglomerative_scratch_bytes bytes (None: one is allocated with torch for this call).  Enqueue only."""
+    import torch
+    a = _agglo_args(d_x, d_bounds, d_n_bounds, d_segments, d_n_segments, d_out_bounds, d_n_out, n_clusters, pad, bounds_all, d_order, d_height)
+    d_scratch, stream = _scratch_and_stream(d_scratch, stream, d_x, lambda: capix.check(capix.lib().jsgx_agglomerative_scratch_bytes(C.byref(a))) // 4, torch.int32,
+                                            any_dtype=True)
+    capix.check(capix.lib().jsgx_agglomerative_launch(C.byref(a), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), stream))
+
+
+def agglomerative_plan(n_frames: int, n_features: int, pairs: int = 1, max_bounds: int = 0, pad: bool = True):
+    """jsgx_agglomerative_plan: (the merge kernel that takes the longest stretch the shape allows, its lanes per workgroup, its bytes of LDS
+    per workgroup, launches): "agglo_wave" up to capix.AGGLO_SHORT frames, else "agglo_group".  Needs no device."""
+    N, F, P, M = int(n_frames), int(n_features), int(pairs), int(max_bounds)
+    S = max(1, min(N, M + 2 * int(bool(pad)) - 1))
+    a = capix.AgglomerativeArgs(x=1 << 40, x_frame_pitch=F, x_pair_pitch=N * F, bounds=(1 << 44) if M else None, bounds_pitch=M, n_bounds=(1 << 42) if M else None,
+                                segments=5 << 60, segments_pitch=S + 1, n_segments=6 << 60, out_bounds=1 << 62, out_pitch=1, n_out=7 << 60, pairs=P, n_frames=N,
+                                n_features=F, max_bounds=M, max_segments=S, max_out=1, n_clusters=1, pad=int(bool(pad)))      # never dereferenced
+    name, out = C.create_string_buffer(16), [C.c_int32() for _ in range(3)]
+    capix.check(capix.lib().jsgx_agglomerative_plan(C.byref(a), name, 16, *[C.byref(o) for o in out]))
+    return (name.value.decode(),) + tuple(o.value for o in out)
+
+
+def agglomerative(data, k: int, return_tree: bool = False):
+    """librosa.segment.agglomerative on the GPU (include/jsgx.h section 17): data [N, F] or [P, N, F] (numpy array or float32 CUDA tensor)
+    cut into min(k, N) runs of consecutive frames by temporally constrained Ward clustering -> (bounds int32 [..., min(k, N)], the
+    first frame of every run, ascending, and n_bounds int32 [...], their count, -1 for a plane with a NaN or an infinity) as CUDA
+    tensors; with return_tree also (order int32 [..., N], height float32 [..., N]): entry j < N - min(k, N) is the boundary step j
+    removed and the cost of that step, the other entries are 0.  With k = 1 that is the whole tree: the boundaries for any k' are frame
+    0 and those of the last k' - 1 steps.  At most capix.AGGLO_MAX_STRETCH frames.  Nothing waits for the device.
+
+    Differs from librosa (which calls scikit-learn's AgglomerativeClustering) on purpose: the planes are frame-major ([frames][features];
+    librosa clusters along the last axis of a feature-major plane); where two merges cost the same the one at the lower frame is
+    taken, where sklearn's heap order decides; float32 throughout, where sklearn computes in float64; Ward linkage on the chain of
+    frames only.  The float64 form of the same definition gave scikit-learn's boundaries on every plane of tests/test_agglo_ref.py.
+    Agreement with librosa itself was not measured: librosa is not among the test dependencies."""
+    import torch
+    x, _ = _to_cuda(data)
+    assert x.dim() in (2, 3), "agglomerative: data is [N, F] or [P, N, F]"
+    one = x.dim() == 2
+    xp = x[None] if one else x
+    xp = xp if xp.stride(2) == 1 or xp.shape[2] == 1 else xp.contiguous()
+    P, N, _ = xp.shape
+    dev = xp.device
+    with torch.cuda.device(_device_index(xp)):
+        bounds = torch.empty((P, min(int(k), N) if int(k) >= 1 else 1), dtype=torch.int32, device=dev)
+        segments = torch.empty((P, 2), dtype=torch.int32, device=dev)
+        n_segments, n_out = torch.empty((2, P), dtype=torch.int32, device=dev)
+        order = torch.zeros((P, N), dtype=torch.int32, device=dev) if return_tree else None
+        height = torch.zeros((P, N), dtype=torch.float32, device=dev) if return_tree else None
+        agglomerative_launch(xp, None, None, segments, n_segments, bounds, n_out, n_clusters=k, pad=True, d_order=order, d_height=height)
+    res = (bounds, n_out) + ((order, height) if return_tree else ())
+    return tuple(r[0] for r in res) if one else res
+
+
+def subsegment(data, frames, n_segments: int = 4, pad: bool = True, n_frames=None, max_bounds: int | None = None):
+    """librosa.segment.subsegment on the GPU (include/jsgx.h section 17): every stretch of data [N, F] or [P, N, F] (numpy array or
+    float32 CUDA tensor) between two of the boundaries `frames` cut into min(n_segments, its frames) runs by temporally constrained Ward
+    clustering -> (bounds int32 [..., max_bounds], the first frames of all runs, ascending: the boundaries among them, and n_bounds
+    int32 [...], their count) as CUDA tensors.
+
+    frames on the host (a list or numpy array of ints, one list for every plane): the count follows on the host, bounds is returned
+    trimmed to it (max_bounds cuts it), and nothing waits for the device.  frames on the device, an int32 CUDA tensor [max] or [P, max]
+    with n_frames the int32 CUDA count(s) of the boundaries in it (the name is librosa's word for the list; it is not the number of
+    frames of the plane, which is N = data.shape[-2]), exactly what beat_track, peak_pick's launch or onset_detect leave there: bounds has
+    max_bounds entries a plane (None: as many as the list and the plane allow), of which the first n_bounds are written, and nothing
+    waits for the device.  n_bounds is -1 for a plane whose count is negative (a refused row upstream) or whose list decreases, that
+    holds a NaN or an infinity between its first and its last boundary, or that has a stretch of more than capix.AGGLO_MAX_STRETCH frames.
+
+    Differs from librosa on purpose: the planes are frame-major; the boundaries are clipped to 0..N and the list must be non-decreasing,
+    as in sync (librosa sorts, and raises on a boundary outside the plane); pad adds both frame 0 and frame N; where two merges cost the
+    same the one at the lower frame is taken, where sklearn's heap order decides; float32 throughout.  Agreement with librosa itself
+    was not measured: librosa is not among the test dependencies."""
+    import torch
+    x, _ = _to_cuda(data)
+    assert x.dim() in (2, 3), "subsegment: data is [N, F] or [P, N, F]"
+    one = x.dim() == 2
+    xp = x[None] if one else x
+    xp = xp if xp.stride(2) == 1 or xp.shape[2] == 1 else xp.contiguous()
+    P, N, _ = xp.shape
+    dev = xp.device
+    k = int(n_segments)
+    with torch.cuda.device(_device_index(xp)):
+        if hasattr(frames, "is_cuda"):
+            assert frames.is_cuda and frames.dtype == torch.int32 and frames.dim() in (1, 2), "subsegment: frames on the device is int32 [max] or [P, max]"
+            bounds = frames if frames.stride(-1) == 1 or frames.shape[-1] == 1 else frames.contiguous()
+            n_bounds = None if n_frames is None else n_frames.reshape(-1).contiguous()
+            if n_bounds is not None and n_bounds.numel() == 1 and P > 1:
+                n_bounds = n_bounds.expand(P).contiguous()
+            S = max(1, min(N, bounds.shape[-1] + 2 * int(bool(pad)) - 1))
+            keep = max(1, min(N, S * max(k, 1))) if max_bounds is None else int(max_bounds)
+        else:
+            assert n_frames is None, "subsegment: n_frames goes with frames on the device"
+            c, u = _host_segments(frames, N, pad, "subsegment", "frames")
+            bounds = torch.from_numpy(c).to(dev) if c.size else None
+            n_bounds = None
+            S = max(1, min(N, c.size + 2 * int(bool(pad)) - 1))          # what the list could give before its repeats are dropped
+            keep = int(np.minimum(np.diff(u), max(k, 1)).sum()) if u.size > 1 else 0
+            keep = keep if max_bounds is None else min(keep, int(max_bounds))
+        out = torch.empty((P, max(1, keep)), dtype=torch.int32, device=dev)
+        segments = torch.empty((P, S + 1), dtype=torch.int32, device=dev)
+        n_seg, n_out = torch.empty((2, P), dtype=torch.int32, device=dev)
+        agglomerative_launch(xp, bounds, n_bounds, segments, n_seg, out, n_out, n_clusters=k, pad=pad)
+        out = out[:, :keep]
+    return (out[0], n_out[0]) if one else (out, n_out)
 
 
 # --------------------------------------------------------------------------------------------------

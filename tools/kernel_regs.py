@@ -19,7 +19,8 @@ instruction-mix counts from the disassembly.  CPU only (llvm-objcopy / clang-off
                                                                the path enhancement and the lag conversion, jsgx_nmf.o the
                                                                non-negative matrix factorisation, jsgx_pcen.o the per-channel
                                                                energy normalisation, jsgx_peak.o the peak picking, jsgx_sync.o the
-                                                               segment aggregation and the time-delay embedding: name them)
+                                                               segment aggregation and the time-delay embedding, jsgx_agglo.o the
+                                                               agglomerative segmentation: name them)
 """
 import os
 import re
@@ -84,7 +85,8 @@ def main():
                                                "path_enhance_kernel", "lag_columns_kernel", "lag_rows_kernel", "nmf_gram_kernel", "nmf_chunk_sum_kernel",
                                                "nmf_update_a_kernel", "nmf_partial_c_kernel", "nmf_update_c_kernel", "pcen_scan_kernel", "pcen_carry_kernel", "pcen_apply_kernel",
                                                "peak_single_kernel", "peak_stats_kernel", "peak_row_kernel", "peak_cand_kernel", "peak_carry_kernel", "peak_emit_kernel",
-                                               "sync_segments_kernel", "sync_aggregate_kernel", "stack_memory_kernel")):
+                                               "sync_segments_kernel", "sync_aggregate_kernel", "stack_memory_kernel",
+                                               "agglo_segments_kernel", "agglo_copy_kernel", "agglo_offsets_kernel", "agglo_wave_kernel", "agglo_group_kernel")):
                     continue
                 mx = mix.get(name, {})
                 valu = sum(c for o, c in mx.items() if o.startswith("v_"))
